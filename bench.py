@@ -2,6 +2,9 @@
 
     python bench.py --gpus N --steps K --warmup W          (N > 1: launched by torch.distributed.run, one rank per GPU;
                                                             without RANK in the environment it starts its N ranks itself)
+        [--full]                 everything else the benchmark measures (see below); a plain run only sets up, warms up,
+                                 times the K steps and prints the headline line
+        [--dump-outputs DIR]     after the timed steps: the waveform the last timed step returned, DIR/waveform.npy (float32)
 
 One *step* = one cold conversion per rank on synthetic inputs already resident in HBM:
 WavLM-Large (6 layers) encode of a 10-minute target pool shard (20 x 30 s) and a 30 s source,
@@ -11,7 +14,11 @@ HiFi-GAN generator ('mix', post_opt_0.2).  Weights are seeded random tensors of 
 architectures (no network for the released checkpoints).  value = source seconds converted by all
 ranks / wall time of the slowest rank.
 
-Extra objects on the JSON line:
+Extra objects on the JSON line, with --full only (each takes passes of its own after the timed steps):
+  config.sequential_ms_per_step — the same K steps again with conversions one after the other (latency);
+  value_long_adam — the same K steps with both Adam smoothness loops forced to 2000 iterations;
+  knn          — the kNN stage's rate and roofline, from the eager pass below;
+  other_configs — BASELINE cfg 5 (one GPU's share) and cfg 3 through the product entry points (rank 0, N = 1 only);
   roofline     — the dominant kernel (conv_gemm2quad_kernel<Gemm2QuadS>: implicit GEMM, 256x256 block tiles of
                  v_mfma_f32_16x16x32_f16, fp32 emulated as three fp16 MFMAs per product): algorithmic fp32 FLOP
                  (2*M*N*K per launch) / HIP-event time of those launches, against the dense fp16 matrix peak / 3
@@ -421,15 +428,30 @@ def other_configs(enc, voc, dev):
     return out
 
 
+def dump_outputs(out_dir, y, rank):
+    """--dump-outputs: what the timed path handed its caller in its last step, the converted waveform (float32, 30 s at 16 kHz),
+    as DIR/waveform.npy (rank r > 0: DIR/waveform_rank<r>.npy).  Inputs and weights are seeded, so two builds run with the same
+    arguments can be compared output for output.  Copied to the host at once: later passes (--full) replay the same graphs."""
+    if y is None:                      # --scaling strong: this rank owned no conversion of the timed steps
+        return
+    os.makedirs(out_dir, exist_ok=True)
+    name = "waveform" if rank == 0 else f"waveform_rank{rank}"
+    np.save(os.path.join(out_dir, name + ".npy"), y.detach().float().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--max-batch", type=int, default=32, help="30 s chunks per WavLM batch")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the cfg 3 / cfg 5-share figures (rank 0, N = 1; ~20 s)")
-    ap.add_argument("--stages", action="store_true", help="print per-stage ms to stderr")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-other-configs", action="store_true", help="with --full: skip the cfg 3 / cfg 5-share figures (rank 0, N = 1; ~20 s)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: latency and long-Adam passes, the eager roofline / kNN pass, "
+                         "the CPU baseline and the cfg 3 / cfg 5-share figures")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's waveform to DIR/waveform.npy (float32)")
+    ap.add_argument("--stages", action="store_true", help="print per-stage ms to stderr (implies --full)")
     ap.add_argument("--timed-only", action="store_true", help="tracing aid: stop after the timed region (no latency / roofline passes, no JSON line)")
     ap.add_argument("--scaling", choices=("weak", "strong"), default="weak",
                     help="weak (default): one 30 s source + one 10-min pool shard PER RANK (pool and kNN work grow with N); "
@@ -438,6 +460,9 @@ def main():
     ap.add_argument("--pipeline-depth", type=int, default=2, choices=(1, 2),
                     help="2 = overlap match+vocoder of conversion i with the encoder of conversion i+1 (default); 1 = sequential")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    a.full = a.full or a.stages        # the stage table comes from the eager pass
 
     ws = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -476,7 +501,8 @@ def main():
     voc = Vocoder(S.seeded_state(S.generator_param_spec(C.HIFIGAN_V1, "mix"), seed=2), C.HIFIGAN_V1, "mix", dev)
     src, sf0, pool_w, pool_f0 = make_inputs(rank, dev)
     timer = GemmTimer()
-    timer.install()
+    if a.full:
+        timer.install()
     timer.all_variants = a.stages
 
     def barrier():
@@ -496,47 +522,50 @@ def main():
         y = run_steps(a.steps, a.pipeline_depth, *args)
         barrier()
         dt = time.perf_counter() - t0
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, y, rank)
         if a.timed_only:
             if rank == 0:
                 print(f"timed region only: {dt / a.steps * 1e3:.3f} ms/step", file=sys.stderr)
             if dist.is_initialized():
                 dist.destroy_process_group()
             return
-        # latency of ONE conversion with nothing overlapped (reported next to the throughput figure)
-        t1 = time.perf_counter()
-        run_steps(a.steps, 1, *args)
-        barrier()
-        dt_seq = time.perf_counter() - t1
-        # Sensitivity of the headline figure to the length of the two Adam smoothness loops: on these synthetic features
-        # they stop at the earliest plateau exit (~200 / ~400 iterations); the reference's cap is 100 000 and real data can
-        # run thousands (ddsp_prematch_dataset.py:613-680).  Same pipelined K steps with both loops forced to 2000 iterations.
-        ops.ADAM_FORCED_ITERS = LONG_ADAM_ITERS
-        run_steps(1, a.pipeline_depth, *args)
-        barrier()
-        t2 = time.perf_counter()
-        run_steps(a.steps, a.pipeline_depth, *args)
-        barrier()
-        dt_long = time.perf_counter() - t2
-        ops.ADAM_FORCED_ITERS = None
-        # Roofline pass: the timed region replays hipGraphs (encoder, vocoder), and HIP events cannot be
-        # recorded around individual launches inside a replayed graph.  The same K steps are therefore run
-        # once more eagerly with an event pair around every launch of the dominant kernel, on its own stream.
-        # (only the encoder goes eager: its launches are the ones timed.  The generator keeps replaying its graph — run eagerly,
-        #  its ~110 launches on three streams left the HOST behind the GPU, and every timing of the following conversion then
-        #  included launch gaps: dominant-kernel fraction 0.47 instead of 0.51, kNN stage 0.86 instead of 0.46 ms)
-        # (and the encoder's launch sequence comes from the host in this pass — KNNSVC_WAVLM_HOST_SEQ: since round 5 the product path
-        #  enqueues it inside ONE C call, knnsvc_wavlm_encode, where no event can be recorded between two launches; same kernels,
-        #  same arguments, same bits: tests/test_gpu_models.py::test_wavlm_one_call_equals_the_host_sequenced_forward)
-        enc.use_graphs = False
-        os.environ["KNNSVC_WAVLM_HOST_SEQ"] = "1"
-        timer.enabled = True
-        stage.on = True                     # five event pairs per step; the table is printed only with --stages
-        for _ in range(a.steps):
-            step(enc, voc, src, sf0, pool_w, pool_f0, a.max_batch)
-        barrier()
-        timer.enabled = False
-        os.environ.pop("KNNSVC_WAVLM_HOST_SEQ", None)
-        enc.use_graphs = True
+        if a.full:
+            # latency of ONE conversion with nothing overlapped (reported next to the throughput figure)
+            t1 = time.perf_counter()
+            run_steps(a.steps, 1, *args)
+            barrier()
+            dt_seq = time.perf_counter() - t1
+            # Sensitivity of the headline figure to the length of the two Adam smoothness loops: on these synthetic features
+            # they stop at the earliest plateau exit (~200 / ~400 iterations); the reference's cap is 100 000 and real data can
+            # run thousands (ddsp_prematch_dataset.py:613-680).  Same pipelined K steps with both loops forced to 2000 iterations.
+            ops.ADAM_FORCED_ITERS = LONG_ADAM_ITERS
+            run_steps(1, a.pipeline_depth, *args)
+            barrier()
+            t2 = time.perf_counter()
+            run_steps(a.steps, a.pipeline_depth, *args)
+            barrier()
+            dt_long = time.perf_counter() - t2
+            ops.ADAM_FORCED_ITERS = None
+            # Roofline pass: the timed region replays hipGraphs (encoder, vocoder), and HIP events cannot be
+            # recorded around individual launches inside a replayed graph.  The same K steps are therefore run
+            # once more eagerly with an event pair around every launch of the dominant kernel, on its own stream.
+            # (only the encoder goes eager: its launches are the ones timed.  The generator keeps replaying its graph — run eagerly,
+            #  its ~110 launches on three streams left the HOST behind the GPU, and every timing of the following conversion then
+            #  included launch gaps: dominant-kernel fraction 0.47 instead of 0.51, kNN stage 0.86 instead of 0.46 ms)
+            # (and the encoder's launch sequence comes from the host in this pass — KNNSVC_WAVLM_HOST_SEQ: since round 5 the product path
+            #  enqueues it inside ONE C call, knnsvc_wavlm_encode, where no event can be recorded between two launches; same kernels,
+            #  same arguments, same bits: tests/test_gpu_models.py::test_wavlm_one_call_equals_the_host_sequenced_forward)
+            enc.use_graphs = False
+            os.environ["KNNSVC_WAVLM_HOST_SEQ"] = "1"
+            timer.enabled = True
+            stage.on = True                     # five event pairs per step; the table is printed only with --stages
+            for _ in range(a.steps):
+                step(enc, voc, src, sf0, pool_w, pool_f0, a.max_batch)
+            barrier()
+            timer.enabled = False
+            os.environ.pop("KNNSVC_WAVLM_HOST_SEQ", None)
+            enc.use_graphs = True
     kdist.raise_if_any_nan()                                            # the deferred NaN flags of every sharded search of this run
     if y is not None:                                                   # strong scaling with fewer steps than ranks: not every rank owned one
         assert y.numel() == SRC_SECONDS * C.SAMPLE_RATE, y.numel()      # 1500 frames x 320
@@ -598,30 +627,31 @@ def main():
                        "pipeline_depth": a.pipeline_depth,
                        "pipeline": ("match + vocoder of conversion i run on a second stream under the encoder of conversion i+1; the pipeline's "
                                     "streams are chosen by measured contention (pipeline.new_stream), not by creation order"
-                                    if a.pipeline_depth > 1 else "none: conversions run one after the other"),
-                       "sequential_ms_per_step": round(dt_seq / a.steps * 1e3, 3)},
-            "roofline": {"bound": "mfma", "achieved": round(achieved, 2), "peak": round(peak, 1), "unit": "TFLOP/s",
-                         "frac": round(achieved / peak, 4), "traffic": None,
-                         "kernel": kernel_name,
-                         "note": f"achieved = algorithmic fp32 FLOP (2*M*N*K per launch) / HIP-event time; peak = dense 16-bit "
-                                 f"MFMA peak 2500 TFLOP/s / {mfmas} MFMAs per product; executed MFMA rate = {mfmas} x achieved",
-                         "frac_of_fp32_mfma_peak_157.3": round(achieved / FP32_MFMA_PEAK_TFLOPS, 4),
-                         "timing": "HIP events around each launch in an eager, host-sequenced re-run of the same K steps right after the "
-                                   "timed region (which replays hipGraphs of the one-call encoder)",
-                         "launches": n_launch, "avg_launch_ms": round(gemm_ms / max(1, n_launch), 4),
-                         "kernel_ms_per_step": round(gemm_ms / a.steps, 3),
-                         "secondary": [{"kernel": "+".join(f), "launches": nl, "kernel_ms_per_step": round(ms / a.steps, 3),
-                                        "achieved": round(fl / (ms * 1e-3) / 1e12, 2) if ms > 0 else 0.0,
-                                        "frac": round(fl / (ms * 1e-3) / 1e12 / peak, 4) if ms > 0 else 0.0}
-                                       for f, nl, ms, fl, _b in fams[1:]]},
+                                    if a.pipeline_depth > 1 else "none: conversions run one after the other")},
         }
         line["config"]["adam_iterations"] = [int(step.last["iters_wavlm"]), int(step.last["iters_harm"])]
-        tl = torch.tensor([dt_long], device=dev, dtype=torch.float64)
-        line["value_long_adam"] = {"value": round((1 if STRONG else ws) * SRC_SECONDS * a.steps / float(tl.item()), 3),
-                                   "adam_iterations": [LONG_ADAM_ITERS, LONG_ADAM_ITERS],
-                                   "ms_per_step": round(float(tl.item()) / a.steps * 1e3, 3),
-                                   "note": "same pipelined steps with both smoothness loops forced to 2000 iterations (stopping rules "
-                                           "off): the headline value's sensitivity to data on which the loops run long; rank 0's clock"}
+        if a.full:
+            line["config"]["sequential_ms_per_step"] = round(dt_seq / a.steps * 1e3, 3)
+            line["roofline"] = {"bound": "mfma", "achieved": round(achieved, 2), "peak": round(peak, 1), "unit": "TFLOP/s",
+                                "frac": round(achieved / peak, 4), "traffic": None,
+                                "kernel": kernel_name,
+                                "note": f"achieved = algorithmic fp32 FLOP (2*M*N*K per launch) / HIP-event time; peak = dense 16-bit "
+                                        f"MFMA peak 2500 TFLOP/s / {mfmas} MFMAs per product; executed MFMA rate = {mfmas} x achieved",
+                                "frac_of_fp32_mfma_peak_157.3": round(achieved / FP32_MFMA_PEAK_TFLOPS, 4),
+                                "timing": "HIP events around each launch in an eager, host-sequenced re-run of the same K steps right after the "
+                                          "timed region (which replays hipGraphs of the one-call encoder)",
+                                "launches": n_launch, "avg_launch_ms": round(gemm_ms / max(1, n_launch), 4),
+                                "kernel_ms_per_step": round(gemm_ms / a.steps, 3),
+                                "secondary": [{"kernel": "+".join(f), "launches": nl, "kernel_ms_per_step": round(ms / a.steps, 3),
+                                               "achieved": round(fl / (ms * 1e-3) / 1e12, 2) if ms > 0 else 0.0,
+                                               "frac": round(fl / (ms * 1e-3) / 1e12 / peak, 4) if ms > 0 else 0.0}
+                                              for f, nl, ms, fl, _b in fams[1:]]}
+            tl = torch.tensor([dt_long], device=dev, dtype=torch.float64)
+            line["value_long_adam"] = {"value": round((1 if STRONG else ws) * SRC_SECONDS * a.steps / float(tl.item()), 3),
+                                       "adam_iterations": [LONG_ADAM_ITERS, LONG_ADAM_ITERS],
+                                       "ms_per_step": round(float(tl.item()) / a.steps * 1e3, 3),
+                                       "note": "same pipelined steps with both smoothness loops forced to 2000 iterations (stopping rules "
+                                               "off): the headline value's sensitivity to data on which the loops run long; rank 0's clock"}
         # BASELINE.json's second metric: kNN query frames/s and its roofline (MFMA-bound once Nq >= ~64).
         # One kNN stage = every rank's 1500 query frames against the whole pool (each rank searches all ws*1500 queries in
         # its own 30 000-row shard: row norms, f16x2 split of the shard and the queries, q.p^T GEMM, distance formula +
@@ -656,23 +686,24 @@ def main():
                     break
         # measured offline with rocprofv3 --pmc (tools/pmc_traffic.py, tools/refresh_profiles.sh); bench.py cannot read PMCs itself.
         # Newest round's file whose kernel is the one reported above.
-        want = {"Q256S": "Gemm2QuadS", "Q256": "Gemm2QuadR"}.get(dom_tags[0], "Gemm2Tile<128, 128" if dom_tags[0].startswith("F128") else None)
-        for pmc in sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_pmc_traffic.json")), reverse=True):
-            t = json.load(open(pmc))
-            if want and want in t.get("kernel", ""):
-                line["roofline"]["traffic"] = t["hbm_bytes_per_launch"]
-                line["roofline"]["traffic_source"] = (f"profiles/{os.path.basename(pmc)}: 2*FETCH_SIZE + WRITE_SIZE per launch, "
-                                                      "separate rocprofv3 --pmc passes")
-                line["roofline"]["algorithmic_bytes_per_launch"] = int(4 * dom_floats / max(1, n_launch))
-                break
-        if ws == 1 and not a.no_cpu_baseline:
+        if a.full:
+            want = {"Q256S": "Gemm2QuadS", "Q256": "Gemm2QuadR"}.get(dom_tags[0], "Gemm2Tile<128, 128" if dom_tags[0].startswith("F128") else None)
+            for pmc in sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_pmc_traffic.json")), reverse=True):
+                t = json.load(open(pmc))
+                if want and want in t.get("kernel", ""):
+                    line["roofline"]["traffic"] = t["hbm_bytes_per_launch"]
+                    line["roofline"]["traffic_source"] = (f"profiles/{os.path.basename(pmc)}: 2*FETCH_SIZE + WRITE_SIZE per launch, "
+                                                          "separate rocprofv3 --pmc passes")
+                    line["roofline"]["algorithmic_bytes_per_launch"] = int(4 * dom_floats / max(1, n_launch))
+                    break
+        if a.full and ws == 1 and not a.no_cpu_baseline:
             L = step.last
             c = lambda x: x.detach().cpu()
             snap = dict(src=c(src), q=c(L["q"]), qf0=c(L["qf0"]), P=c(L["P"]), Pf0=c(L["Pf0"]), Ph=c(L["Ph"]), nn32=c(L["nn32"]),
                         idx_wavlm=c(L["idx_wavlm"]), idx_harm=c(L["idx_harm"]), of=c(L["of"]), hw=c(L["hw"]), s0=c(L["s0"]),
                         iters_wavlm=int(L["iters_wavlm"]), iters_harm=int(L["iters_harm"]))
             line["cpu_baseline"] = cpu_baseline(snap)
-        if ws == 1 and not a.no_other_configs and not a.stages:
+        if a.full and ws == 1 and not a.no_other_configs and not a.stages:
             import contextlib
             with contextlib.redirect_stdout(sys.stderr):        # bulk_match prints its progress like the reference: keep stdout ONE line
                 line["other_configs"] = other_configs(enc, voc, dev)

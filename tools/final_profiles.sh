@@ -1,6 +1,6 @@
 cd $GRAFT_REPO_ROOT
 O=gpurun_out/final; mkdir -p $O
-python bench.py > $O/r03_bench_default_line.json 2> /dev/null
+python bench.py --full > $O/r03_bench_default_line.json 2> /dev/null
 python3 tools/cfg5_product_bench.py 2>/dev/null | tail -1 > $O/r03_cfg5_share_product_entry_1gpu.json
 python3 tools/cfg5_bench.py --sources 32 --pool-minutes 60 --reps 3 2>/dev/null | tail -1 > $O/r03_cfg5_share_1gpu.json
 timeout 600 python3 tools/cfg3_bench.py --speakers 4 --utts 80 2>/dev/null | tail -1 > $O/r03_cfg3_1gpu.json

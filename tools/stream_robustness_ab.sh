@@ -3,7 +3,7 @@
 # of every N > 1 run): VERDICT r4 #3 asks that the figure does not depend on either.  tools/stream_robustness_ab.sh [tree]
 T=${1:-.}
 cd $GRAFT_REPO_ROOT/$T
-B="--no-cpu-baseline --no-other-configs"
+B="--full --no-cpu-baseline --no-other-configs"
 P='import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); print("%-44s %8.1f xRT  %7.2f ms/step  sequential %6.2f" % (sys.argv[2], d["value"], d["ms_per_step"], d["config"]["sequential_ms_per_step"]))'
 O=$GRAFT_REPO_ROOT/gpurun_out/robust_$(echo $T | tr -c 'A-Za-z0-9' '_'); mkdir -p $O
 for n in 0 1 2 3 4 7; do
