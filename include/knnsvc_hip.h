@@ -349,9 +349,12 @@ size_t knnsvc_knn_workspace_bytes(int64_t nq, int64_t np, int32_t k);
  * (lib_ongaku_test.py:162-165) evaluated on ITS matrix product; whatever product a GPU kernel forms (here: fp16-split MFMAs with 96
  * fp32 roundings along K, or fp32 MFMAs) differs from it in the last bits, and neighbours closer together than those bits swap.
  * The selection kernels below therefore only PICK candidates: each keeps, per query row, a WIDE list of up to 64 keys
- * (uint64: order-preserving bits of the screening distance << 32 | pool row) — the k best and every pair within 4e-6 of the
- * k-th — and knnsvc_knn_rescore recomputes q.p for exactly those pairs in fp64 from the fp32 operands, rounds once to fp32,
- * replays the reference's formula and sorts by (distance bits, lower index first).  What is left between this order and the
+ * (uint64: order-preserving bits of the screening distance << 32 | pool row) — the k best and every pair within the guard band
+ * of the k-th (4e-6 on the f16x2 routes; 5e-7 sqrt(dim), at least 4e-6, on knnsvc_knn_topk's fp32-MFMA tile) — and
+ * knnsvc_knn_rescore recomputes q.p for exactly those pairs in fp64 from the fp32 operands, rounds once to fp32,
+ * replays the reference's formula and sorts by (distance bits, lower index first).  A CROWDED row — all 64 places filled, the
+ * 64th key still inside the band: exact top-k members may have been cut — is re-scored against every one of the np pool rows
+ * instead, so the result is the exact top-k either way.  What is left between this order and the
  * reference's is the reference's own BLAS rounding.  exact = 0 passes the screening order through (A/B aid).
  * wide: [nq][64] keys ascending, unused places 0xFFFF...F; out_idx / out_dist: [nq][k], indices + idx_offset; a row with fewer
  * than k finite distances (a NaN row) is filled with VALID row indices and NaN distances.  [mask_lo, mask_hi) as below. */

@@ -71,14 +71,19 @@ __device__ __forceinline__ void list_insert(unsigned long long& mine, unsigned l
 // ---- wide lists: 64 keys in ascending order, one per lane (unused lanes: KEY_INF).  The k-th key + KNN_GUARD bounds what a list
 // keeps; when more than 64 keys lie inside the guard band (thousands of identical pool rows) the 64 best by (distance, index) stay.
 constexpr int KW = 64;
-constexpr float KNN_GUARD = 4.0e-6f;      // > 3 x the largest |screening distance - exact distance| measured (1.22e-6, g3c): 2 x is the least that keeps every exact top-k member listed
-__device__ __forceinline__ unsigned long long guard_key(unsigned long long kth) {
+// The band has to be at least twice the largest |screening distance - exact distance|.  Measured against the exact oracle
+// (tests/test_gpu_kernels.py, adversarial families at dim 256 .. 2048): the f16x2 screening products stay below 1.7e-6, so the f16x2
+// routes keep 4e-6; the fp32-MFMA tile's sequential fp32 sums grow with dim (1.3e-6 at 256, 4.9e-6 at 2048 with outlier channels),
+// so its band is 5e-7 sqrt(dim), at least 4e-6 (knn_guard_fp32; ops.knn_guard mirrors both).
+constexpr float KNN_GUARD = 4.0e-6f;
+__host__ __device__ inline float knn_guard_fp32(int dim) { const float g = 5.0e-7f * sqrtf((float)dim); return g > KNN_GUARD ? g : KNN_GUARD; }
+__device__ __forceinline__ unsigned long long guard_key(unsigned long long kth, float guard) {
     if (kth == KEY_INF) return KEY_INF;
-    const float d = unsortable((unsigned)(kth >> 32)) + KNN_GUARD;
+    const float d = unsortable((unsigned)(kth >> 32)) + guard;
     return ((unsigned long long)sortable(d) << 32) | 0xFFFFFFFFull;
 }
-__device__ __forceinline__ unsigned long long wide_thr(unsigned long long mine, int k) {       // a candidate can matter iff key <= this
-    const unsigned long long g = guard_key(readlane64(mine, k - 1)), w = readlane64(mine, KW - 1);
+__device__ __forceinline__ unsigned long long wide_thr(unsigned long long mine, int k, float guard = KNN_GUARD) {       // a candidate can matter iff key <= this
+    const unsigned long long g = guard_key(readlane64(mine, k - 1), guard), w = readlane64(mine, KW - 1);
     return g < w ? g : w;
 }
 // mine (ascending) U c (ascending) -> the 64 smallest, ascending: min(a_i, c_{63-i}) is bitonic and holds them; six
@@ -130,7 +135,7 @@ constexpr int KNN_LDS_BYTES = LDS_STAGE * 4 + 128 * KW * 8 /*wide lists*/ + 128 
 __global__ __launch_bounds__(512) void knn_tile_kernel(
     const float* __restrict__ q, const float* __restrict__ qn, const float* __restrict__ qsq, long nq,
     const float* __restrict__ pool, const float* __restrict__ pn, const float* __restrict__ psq, long np,
-    int dim, int k, long rows_per_split, long mask_lo, long mask_hi, unsigned long long* __restrict__ part, int* nan_flag) {
+    int dim, int k, long rows_per_split, long mask_lo, long mask_hi, unsigned long long* __restrict__ part, int* nan_flag, float guard) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float* dist = lds;                                                       // [128][LDD] (aliases staging)
     unsigned long long* lists = (unsigned long long*)(lds + LDS_STAGE);      // [128][KW]: wide lists
@@ -190,7 +195,7 @@ __global__ __launch_bounds__(512) void knn_tile_kernel(
             if (q0 + row >= nq) break;
             unsigned long long* lst = lists + row * KW;
             unsigned long long mine = lst[lane];
-            const unsigned long long thr = wide_thr(mine, k);
+            const unsigned long long thr = wide_thr(mine, k, guard);
             const float d0 = dist[row * LDD + lane], d1 = dist[row * LDD + 64 + lane];
             // NaN / +inf never enter: their sortable bits are >= those of +inf
             const unsigned long long k0 = ((unsigned long long)sortable(d0) << 32) | (unsigned)(p0 + lane);
@@ -315,13 +320,13 @@ __global__ __launch_bounds__(256) void knn_select_kernel(
 
 // one wave per query row: fold `parts` wide lists into one
 __global__ __launch_bounds__(256) void knn_merge_keys_kernel(const unsigned long long* __restrict__ part,
-                                                            int parts, long nq, int k, unsigned long long* __restrict__ wide_out) {
+                                                            int parts, long nq, int k, unsigned long long* __restrict__ wide_out, float guard) {
     const int lane = threadIdx.x & 63;
     const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= nq) return;
     unsigned long long best = part[row * KW + lane];
     for (int s = 1; s < parts; ++s) wide_merge_sorted(best, part[((long)s * nq + row) * KW + lane], lane);
-    if (best > wide_thr(best, k)) best = KEY_INF;
+    if (best > wide_thr(best, k, guard)) best = KEY_INF;
     wide_out[row * KW + lane] = best;
 }
 
@@ -332,15 +337,44 @@ __global__ __launch_bounds__(256) void knn_merge_keys_kernel(const unsigned long
 // A/B aid) passes the screening distances through.  The pass is a gather of ~33 rows of 4 KB per query row (200 MB at the
 // north-star point): eight waves share the row's entries, four entries per wave in flight (DIM = 1024: every load of a
 // group is issued before the first is used).
+// A CROWDED row — its list holds all 64 keys, the 64th still inside the guard band of the k-th — may have lost exact top-k members
+// to the cut at 64 (more near-ties than a list holds; the screening order among them is not the exact one).  Such a row is
+// re-scored against EVERY pool row of the chunk instead: the same fp64 dots, the same keys, so the result is the exact top-k.
 constexpr int RS_WAVES = 8, RS_FLIGHT = 4;
+template <int DIM>
+__device__ __forceinline__ void rs_dots(const float* __restrict__ qr, const float* const (&rp)[RS_FLIGHT], int dim, int lane,
+                                        double (&dots)[RS_FLIGHT]) {
+    double acc[RS_FLIGHT][4];
+#pragma unroll
+    for (int f = 0; f < RS_FLIGHT; ++f)
+#pragma unroll
+        for (int t = 0; t < 4; ++t) acc[f][t] = 0.0;
+#pragma unroll
+    for (int c0 = 0; c0 < (DIM ? DIM : 1 << 30); c0 += 256) {
+        const int c = c0 + lane * 4;
+        if (!DIM && c0 >= dim) break;
+        const bool in = DIM ? true : c < dim;
+        const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+        const f32x4 vq = in ? *(const f32x4*)(qr + c) : z;
+        f32x4 vp[RS_FLIGHT];
+#pragma unroll
+        for (int f = 0; f < RS_FLIGHT; ++f) vp[f] = in ? *(const f32x4*)(rp[f] + c) : z;
+#pragma unroll
+        for (int f = 0; f < RS_FLIGHT; ++f)
+#pragma unroll
+            for (int t = 0; t < 4; ++t) acc[f][t] = fma((double)vq[t], (double)vp[f][t], acc[f][t]);
+    }
+#pragma unroll
+    for (int f = 0; f < RS_FLIGHT; ++f) dots[f] = wave_sum_d((acc[f][0] + acc[f][1]) + (acc[f][2] + acc[f][3]));
+}
 template <int DIM>
 __global__ __launch_bounds__(RS_WAVES * 64) void knn_rescore_kernel(const unsigned long long* __restrict__ wide, long nq, int k,
                                                          const float* __restrict__ q, const float* __restrict__ qn,
                                                          const float* __restrict__ qsq, const float* __restrict__ pool,
-                                                         const float* __restrict__ pn, const float* __restrict__ psq, int dim_rt,
+                                                         const float* __restrict__ pn, const float* __restrict__ psq, long np, int dim_rt,
                                                          long idx_offset, long mask_lo, long mask_hi, int exact,
                                                          long* __restrict__ out_idx, float* __restrict__ out_dist) {
-    __shared__ unsigned long long s_keys[KW];
+    __shared__ unsigned long long s_keys[RS_WAVES][KW];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int dim = DIM ? DIM : dim_rt;
     // workgroup b runs on XCD b % 8: each XCD takes one contiguous eighth of the query rows, so the rows in flight on one L2 are
@@ -350,40 +384,59 @@ __global__ __launch_bounds__(RS_WAVES * 64) void knn_rescore_kernel(const unsign
     if ((blockIdx.x >> 3) >= rpx || row >= nq) return;
     const unsigned long long key = wide[row * KW + lane];
     const int n = __popcll(__ballot(key != KEY_INF));            // a sorted list: its entries are the first n lanes
+    const float* qr = q + row * (long)dim;
+    if (exact && n == KW) {
+        // crowded row: every wave keeps the k best keys of its share of the chunk's rows (sorted, one per lane), wave 0 merges them
+        const float v_qn = qn[row], v_qsq = qsq[row];
+        unsigned long long mine = KEY_INF;
+        for (long e0 = wave; e0 < np; e0 += RS_WAVES * RS_FLIGHT) {
+            long pp[RS_FLIGHT];
+            const float* rp[RS_FLIGHT];
+#pragma unroll
+            for (int f = 0; f < RS_FLIGHT; ++f) {
+                const long e = e0 + f * RS_WAVES;
+                pp[f] = e < np ? e : e0;                             // (past the chunk: the group's first row again)
+                rp[f] = pool + pp[f] * dim;
+            }
+            double dots[RS_FLIGHT];
+            rs_dots<DIM>(qr, rp, dim, lane, dots);
+#pragma unroll
+            for (int f = 0; f < RS_FLIGHT; ++f) {
+                if (e0 + f * RS_WAVES >= np) break;                      // (wave-uniform)
+                float d = ref_distance((float)dots[f], v_qsq, psq[pp[f]], v_qn, pn[pp[f]]);
+                if (pp[f] >= mask_lo && pp[f] < mask_hi) d = 1.f;
+                if (!(d < __builtin_inff())) continue;                  // (a NaN was reported by the screen; it never enters a list)
+                const unsigned long long kf = readlane64(((unsigned long long)sortable(d) << 32) | (unsigned)pp[f], 0);
+                if (kf < readlane64(mine, k - 1)) list_insert(mine, kf, lane, k);
+            }
+        }
+        s_keys[wave][lane] = mine;
+        __syncthreads();
+        if (wave == 0) {
+            unsigned long long best = s_keys[0][lane];
+#pragma unroll
+            for (int w = 1; w < RS_WAVES; ++w) wide_merge_sorted(best, s_keys[w][lane], lane);
+            if (lane < k) {
+                out_idx[row * k + lane] = (best == KEY_INF ? 0l : (long)(unsigned)(best & 0xFFFFFFFFull)) + idx_offset;
+                out_dist[row * k + lane] = unsortable((unsigned)(best >> 32));
+            }
+        }
+        return;
+    }
     if (exact) {
-        const float* qr = q + row * (long)dim;
         const float v_qn = qn[row], v_qsq = qsq[row];
         const int idx = (int)(unsigned)(key & 0xFFFFFFFFull);
         for (int e0 = wave; e0 < n; e0 += RS_WAVES * RS_FLIGHT) {
             long pp[RS_FLIGHT];
             const float* rp[RS_FLIGHT];
-            double acc[RS_FLIGHT][4];
 #pragma unroll
             for (int f = 0; f < RS_FLIGHT; ++f) {
                 const int e = e0 + f * RS_WAVES;
                 pp[f] = (long)(unsigned)__builtin_amdgcn_readlane(idx, e < n ? e : e0);      // (past the list: the group's first row again)
                 rp[f] = pool + pp[f] * dim;
-#pragma unroll
-                for (int t = 0; t < 4; ++t) acc[f][t] = 0.0;
-            }
-#pragma unroll
-            for (int c0 = 0; c0 < (DIM ? DIM : 1 << 30); c0 += 256) {
-                const int c = c0 + lane * 4;
-                if (!DIM && c0 >= dim) break;
-                const bool in = DIM ? true : c < dim;
-                const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-                const f32x4 vq = in ? *(const f32x4*)(qr + c) : z;
-                f32x4 vp[RS_FLIGHT];
-#pragma unroll
-                for (int f = 0; f < RS_FLIGHT; ++f) vp[f] = in ? *(const f32x4*)(rp[f] + c) : z;
-#pragma unroll
-                for (int f = 0; f < RS_FLIGHT; ++f)
-#pragma unroll
-                    for (int t = 0; t < 4; ++t) acc[f][t] = fma((double)vq[t], (double)vp[f][t], acc[f][t]);
             }
             double dots[RS_FLIGHT];
-#pragma unroll
-            for (int f = 0; f < RS_FLIGHT; ++f) dots[f] = wave_sum_d((acc[f][0] + acc[f][1]) + (acc[f][2] + acc[f][3]));
+            rs_dots<DIM>(qr, rp, dim, lane, dots);
 #pragma unroll
             for (int f = 0; f < RS_FLIGHT; ++f) {
                 const int e = e0 + f * RS_WAVES;
@@ -394,7 +447,7 @@ __global__ __launch_bounds__(RS_WAVES * 64) void knn_rescore_kernel(const unsign
                     if (pp[f] >= mask_lo && pp[f] < mask_hi) d = 1.f;
                     // (a listed pair has a finite screening distance; should the exact one not be finite — it cannot, from the same
                     //  finite operands — the pair keeps its screening key)
-                    s_keys[e] = d < __builtin_inff() ? (((unsigned long long)sortable(d) << 32) | (unsigned)pp[f]) : old;
+                    s_keys[0][e] = d < __builtin_inff() ? (((unsigned long long)sortable(d) << 32) | (unsigned)pp[f]) : old;
                 }
             }
         }
@@ -402,7 +455,7 @@ __global__ __launch_bounds__(RS_WAVES * 64) void knn_rescore_kernel(const unsign
     }
     if (wave == 0) {
         unsigned long long best = key;
-        if (exact) best = wave_sort64(lane < n ? s_keys[lane] : KEY_INF, lane);
+        if (exact) best = wave_sort64(lane < n ? s_keys[0][lane] : KEY_INF, lane);
         if (lane < k) {
             out_idx[row * k + lane] = (best == KEY_INF ? 0l : (long)(unsigned)(best & 0xFFFFFFFFull)) + idx_offset;      // unfilled (NaN row): a valid row, NaN distance
             out_dist[row * k + lane] = unsortable((unsigned)(best >> 32));
@@ -410,14 +463,14 @@ __global__ __launch_bounds__(RS_WAVES * 64) void knn_rescore_kernel(const unsign
     }
 }
 static void launch_rescore(const unsigned long long* wide, long nq, int k, const float* q, const float* qn, const float* qsq, const float* pool,
-                           const float* pn, const float* psq, int dim, long idx_offset, long mask_lo, long mask_hi, int exact, long* out_idx,
+                           const float* pn, const float* psq, long np, int dim, long idx_offset, long mask_lo, long mask_hi, int exact, long* out_idx,
                            float* out_dist, hipStream_t st) {
     if (dim == 1024)
-        hipLaunchKernelGGL(knn_rescore_kernel<1024>, dim3((unsigned)(8 * ((nq + 7) / 8))), dim3(RS_WAVES * 64), 0, st, wide, nq, k, q, qn, qsq, pool, pn, psq, dim,
-                           idx_offset, mask_lo, mask_hi, exact, out_idx, out_dist);
+        hipLaunchKernelGGL(knn_rescore_kernel<1024>, dim3((unsigned)(8 * ((nq + 7) / 8))), dim3(RS_WAVES * 64), 0, st, wide, nq, k, q, qn, qsq, pool, pn, psq, np,
+                           dim, idx_offset, mask_lo, mask_hi, exact, out_idx, out_dist);
     else
-        hipLaunchKernelGGL(knn_rescore_kernel<0>, dim3((unsigned)(8 * ((nq + 7) / 8))), dim3(RS_WAVES * 64), 0, st, wide, nq, k, q, qn, qsq, pool, pn, psq, dim,
-                           idx_offset, mask_lo, mask_hi, exact, out_idx, out_dist);
+        hipLaunchKernelGGL(knn_rescore_kernel<0>, dim3((unsigned)(8 * ((nq + 7) / 8))), dim3(RS_WAVES * 64), 0, st, wide, nq, k, q, qn, qsq, pool, pn, psq, np,
+                           dim, idx_offset, mask_lo, mask_hi, exact, out_idx, out_dist);
 }
 
 // merge of (dist, global idx) lists coming from other devices
@@ -1087,15 +1140,15 @@ extern "C" int knnsvc_knn_topk(const float* q, const float* q_norm, const float*
     hipStream_t st = (hipStream_t)stream;
     dim3 grid((unsigned)cdiv64(nq, 128), (unsigned)S);
     hipLaunchKernelGGL(knn_tile_kernel, grid, dim3(NT), KNN_LDS_BYTES, st, q, q_norm, q_sq, (long)nq, pool, p_norm,
-                       p_sq, (long)np, dim, k, rows_per_split, (long)mask_lo, (long)mask_hi, (unsigned long long*)workspace, nan_flag);
+                       p_sq, (long)np, dim, k, rows_per_split, (long)mask_lo, (long)mask_hi, (unsigned long long*)workspace, nan_flag, knn_guard_fp32(dim));
     int rc = knnsvc_check_launch("knn_tile");
     if (rc) return rc;
     unsigned long long* wide = (unsigned long long*)workspace + (size_t)S * nq * KW;
     hipLaunchKernelGGL(knn_merge_keys_kernel, dim3((unsigned)cdiv64(nq, 4)), dim3(256), 0, st,
-                       (const unsigned long long*)workspace, S, (long)nq, k, wide);
+                       (const unsigned long long*)workspace, S, (long)nq, k, wide, knn_guard_fp32(dim));
     rc = knnsvc_check_launch("knn_merge_keys");
     if (rc) return rc;
-    launch_rescore((const unsigned long long*)wide, (long)nq, k, q, q_norm, q_sq, pool, p_norm, p_sq, dim, (long)idx_offset, (long)mask_lo,
+    launch_rescore((const unsigned long long*)wide, (long)nq, k, q, q_norm, q_sq, pool, p_norm, p_sq, (long)np, dim, (long)idx_offset, (long)mask_lo,
                    (long)mask_hi, rescore ? 1 : 0, (long*)out_idx, out_dist, st);
     return knnsvc_check_launch("knn_rescore");
 }
@@ -1110,7 +1163,7 @@ extern "C" int knnsvc_knn_rescore(const void* wide, int64_t nq, int32_t k, const
         KN_REQUIRE(q && q_norm && q_sq && pool && p_norm && p_sq && np > 0, "knn_rescore: the exact pass needs the fp32 operands and their norms");
         KN_REQUIRE(dim > 0 && dim % 4 == 0 && ((uintptr_t)q & 15) == 0 && ((uintptr_t)pool & 15) == 0, "knn_rescore: dim % 4 == 0 and 16-byte aligned rows");
     }
-    launch_rescore((const unsigned long long*)wide, (long)nq, k, q, q_norm, q_sq, pool, p_norm, p_sq, dim, (long)idx_offset, (long)mask_lo,
+    launch_rescore((const unsigned long long*)wide, (long)nq, k, q, q_norm, q_sq, pool, p_norm, p_sq, (long)np, dim, (long)idx_offset, (long)mask_lo,
                    (long)mask_hi, exact ? 1 : 0, (long*)out_idx, out_dist, (hipStream_t)stream);
     return knnsvc_check_launch("knn_rescore");
 }

@@ -449,6 +449,15 @@ def knn_mode() -> str:
     return mode
 
 
+def knn_pool_chunks(npool: int, dim: int):
+    """The f16x2 routes' pool chunk plan: [(first row, end row), ...] — balanced chunks (no tail shorter than k) of at most
+    p_cap rows, so that every buffer resource of a chunk (fp32 rows, split image) stays below 1 GiB."""
+    p_cap = ((1 << 30) - 1) // (dim * 4) // 128 * 128
+    n_chunks = max(1, -(-npool // p_cap))
+    p_rows = -(-npool // n_chunks)
+    return [(p0, min(npool, p0 + p_rows)) for p0 in range(0, npool, p_rows)]
+
+
 def prepare_knn_pool(pool, k=32, p_stats=None):
     """Pre-split image of a pool for the two-kernel kNN route, reusable across searches against the same pool
     (dataset mode and prematch search one pool once per utterance): list of (first row, rows view, f16x2 image, range
@@ -461,12 +470,9 @@ def prepare_knn_pool(pool, k=32, p_stats=None):
     if not (knn_mode() == "f16x2" and dim % 32 == 0 and npool >= k and pool.is_contiguous()):
         return None
     lib = _lib.load()
-    p_cap = ((1 << 30) - 1) // (dim * 4) // 128 * 128
-    n_chunks = -(-npool // p_cap)
-    p_rows = -(-npool // n_chunks)                    # balanced chunks: no tail shorter than k
     chunks = []
-    for p0 in range(0, npool, p_rows):
-        pc = pool[p0:p0 + p_rows]
+    for p0, p1 in knn_pool_chunks(npool, dim):
+        pc = pool[p0:p1]
         npc = pc.shape[0]
         if npc < k:
             raise KnnSvcError("knn_topk: pool chunk smaller than k")
@@ -492,6 +498,13 @@ def knn_rescore_on() -> bool:
 
 
 KNN_WIDE = 64                     # keys per row of a wide list (include/knnsvc_hip.h, knnsvc_knn_rescore)
+KNN_GUARD = 4.0e-6                # the wide lists keep everything within this of the k-th screening distance (csrc/knn.hip)
+
+
+def knn_guard(dim: int, mode: str = "f16x2") -> float:
+    """Guard band of a search's wide lists (csrc/knn.hip: KNN_GUARD, knn_guard_fp32): the f16x2 routes keep KNN_GUARD, the
+    fp32-MFMA tile route (KNNSVC_KNN=fp32), whose screening error grows with dim, 5e-7 sqrt(dim) and at least KNN_GUARD."""
+    return KNN_GUARD if mode != "fp32" else max(KNN_GUARD, 5.0e-7 * math.sqrt(dim))
 
 
 def _knn_rescore(wide, q, qn, qs, pc, pn, ps, k, idx_offset, mask, idx_out, dist_out):
@@ -645,6 +658,17 @@ def _knn_fused_chunk(q, q2, q_slot, qn, qs, pc, p2, p_slot, pn, ps, k, idx_offse
         _knn_rescore(wide, q[q0:q0 + m], qn[q0:], qs[q0:], pc, pn, ps, k, idx_offset, mask, idx_out[q0:], dist_out[q0:])
 
 
+def knn_search_fill(nq: int, npool: int, dim: int, max_blocks: int = 0) -> int:
+    """int32 words of the fused route's first-epoch workspace that knn_topk folds into its one fill (0: none) — only where the
+    search is one fused launch sequence over ONE pool chunk and one query chunk: a second chunk must not inherit the first one's
+    row bounds and arrival counters."""
+    if not (knn_fused_on() and nq >= KNN_FUSED_MIN_Q and npool >= KNN_FUSED_MIN_P and len(knn_pool_chunks(npool, dim)) == 1 and
+            nq * dim < (1 << 28) and nq * KNN_FUSED_CAP * 8 <= (1 << 30)):
+        return 0
+    ep = knn_epochs(nq, npool, int(max_blocks) if max_blocks else 256)
+    return nq * (2 + 2 * (ep[0][1] - ep[0][0])) + 32 * -(-nq // 256)
+
+
 def knn_topk(q, pool, k=32, idx_offset=0, q_stats=None, p_stats=None, check_nan=True, return_flag=False, mask=None,
              prepared=None, max_blocks=0):
     """Ascending cosine-distance top-k of each q row among pool rows -> (idx int64 [nq,k], dist f32 [nq,k]).
@@ -666,11 +690,7 @@ def knn_topk(q, pool, k=32, idx_offset=0, q_stats=None, p_stats=None, check_nan=
     # candidate counts + first-epoch workspace: four tiny fill launches were ~5 us each in front of a 0.4 ms search
     flag = zeros = None
     if f16:
-        nz = 0
-        if (prepared is None and knn_fused_on() and nq >= KNN_FUSED_MIN_Q and npool >= KNN_FUSED_MIN_P and
-                npool * dim * 4 < (1 << 30) and nq * dim < (1 << 28) and nq * KNN_FUSED_CAP * 8 <= (1 << 30)):
-            ep = knn_epochs(nq, npool, int(max_blocks) if max_blocks else 256)
-            nz = nq * (2 + 2 * (ep[0][1] - ep[0][0])) + 32 * -(-nq // 256)
+        nz = knn_search_fill(nq, npool, dim, max_blocks) if prepared is None else 0
         zbuf = torch.zeros(64 + 2 * SLOT_W + nz, device=q.device, dtype=torch.int32)
         flag = zbuf[:1]
         sl_q, sl_p = zbuf[64:64 + SLOT_W].view(torch.float32), zbuf[64 + SLOT_W:64 + 2 * SLOT_W].view(torch.float32)

@@ -75,16 +75,24 @@ def test_knn_north_star_size_against_the_reference_fixture(golden, monkeypatch, 
     # between two swapped neighbours is 2.9e-7 (r04: 1.03e-6): what is left is decided by the reference's own BLAS rounding
     assert err_gpu <= 0.5 * err_ref, (err_gpu, err_ref)
     assert st["top4"] >= 0.9993 and st["sets"] == 1.0 and st["allk"] >= 0.968 and st["max_gap"] <= 3.5e-7, st
-    TestKnnModesAgree.lists[mode] = (idx, dist)
-    if len(TestKnnModesAgree.lists) == 2:          # both screening routes end in the same exact re-score: identical lists, bit for bit
-        (ia, da_), (ib, db_) = TestKnnModesAgree.lists["f16x2"], TestKnnModesAgree.lists["fp32"]
-        same = float((ia == ib).all(1).float().mean())
-        print(f"f16x2-screened vs fp32-screened lists after the exact re-score: {same:.5f} of the rows identical")
-        assert same == 1.0 and torch.equal(da_, db_)
 
 
-class TestKnnModesAgree:
+def test_knn_north_star_size_f16x2_and_fp32_screening_give_the_same_lists(golden, monkeypatch):
+    """Both screening routes (f16x2 matrix cores, fp32-MFMA tile) end in the same exact re-score: at the G3c size their lists are
+    identical, bit for bit — both searches run here, whatever ran before."""
+    from knn_svc_amd import ops
+    g = golden("g3c_knn_north_star")
+    q = S.clustered_features(int(g["nq"]), 1024, int(g["q_seed"])).to(DEV)
+    p = S.clustered_features(int(g["np_"]), 1024, int(g["p_seed"])).to(DEV)
+    monkeypatch.setenv("KNNSVC_KNN_RESCORE", "1")
     lists = {}
+    for mode in ("f16x2", "fp32"):
+        monkeypatch.setenv("KNNSVC_KNN", mode)
+        lists[mode] = [t.cpu() for t in ops.knn_topk(q, p, 32)]
+    (ia, da_), (ib, db_) = lists["f16x2"], lists["fp32"]
+    same = float((ia == ib).all(1).float().mean())
+    print(f"f16x2-screened vs fp32-screened lists after the exact re-score: {same:.5f} of the rows identical")
+    assert same == 1.0 and torch.equal(da_, db_)
 
 
 def test_selection_chain_north_star_size_against_the_reference_fixture(golden):
@@ -315,6 +323,45 @@ def test_knn_multi_chunk_pool_and_mask_across_chunks():
     assert bool((md2[inside] == 1.0).all())
     assert not bool(((mi2[:, 0] >= lo) & (mi2[:, 0] < hi)).any())                # themselves no longer first
     del pd
+    torch.cuda.empty_cache()
+
+
+def test_knn_two_chunk_pool_just_above_the_chunk_size_equals_the_exact_oracle(monkeypatch):
+    """262 100 x 1024 sits between prepare_knn_pool's chunk size (262 016 rows) and 2^30 / 4096 rows — two chunks,
+    both on the fused route, and each must get a zeroed first-epoch workspace of its own (knn_topk's one fill may only serve a
+    one-chunk search).  Two fused launches and no retry; the lists equal the exact oracle and explicit shards merged."""
+    from knn_svc_amd import ops
+    from oracle import knn_ref
+    monkeypatch.setenv("KNNSVC_KNN", "f16x2")
+    monkeypatch.setenv("KNNSVC_KNN_FUSED", "1")
+    monkeypatch.setenv("KNNSVC_KNN_RESCORE", "1")
+    np_rows, nq = 262_100, 300
+    base = _smooth(S.clustered_features(26_210, 1024, 15, n_centres=120))
+    g = torch.Generator().manual_seed(16)
+    p = torch.cat([base * (1.0 + 0.01 * i) + 0.02 * torch.randn(26_210, 1024, generator=g) for i in range(10)], 0)
+    q = _smooth(S.clustered_features(nq, 1024, 17, n_centres=120))
+    pd, qd = p.to(DEV), q.to(DEV)
+    del p, base
+    chunks = ops.knn_pool_chunks(np_rows, 1024)
+    assert len(chunks) == 2 and len(ops.prepare_knn_pool(pd, 32)) == 2
+    c0 = dict(ops.KNN_ROUTE_COUNTS)
+    idx, dist, flag = ops.knn_topk(qd, pd, 32, check_nan=False, return_flag=True)
+    fl = int(flag.item())
+    ran = {r: ops.KNN_ROUTE_COUNTS[r] - c0[r] for r in ("chunks", "fused", "dot")}
+    print(f"262 100-row pool: flag {fl}, routes {ran}")
+    assert fl == 0 and ran == {"chunks": 2, "fused": 2, "dot": 0}, (fl, ran)
+    qn, qs = ops.row_norms(qd)
+    pn, ps = ops.row_norms(pd)
+    D = knn_ref.exact_distance_matrix(qd, pd, qn, qs, pn, ps)
+    st = knn_ref.compare_to_exact(idx, dist, D, 32)
+    del D
+    print("262 100-row pool vs exact oracle:", st)
+    assert st["bad_lists"] == 0 and st["unexplained"] == 0 and st["left_out"] == 0, st
+    assert int((idx >= chunks[1][0]).sum()) > 0 and int((idx < chunks[1][0]).sum()) > 0       # neighbours come from both chunks
+    parts = [ops.knn_topk(qd, pd[a:b].contiguous(), 32, idx_offset=a) for a, b in chunks]
+    mi, md = ops.knn_merge(torch.stack([d for _, d in parts]), torch.stack([i for i, _ in parts]))
+    assert torch.equal(mi, idx) and torch.equal(md, dist)
+    del pd, parts
     torch.cuda.empty_cache()
 
 

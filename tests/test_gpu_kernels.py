@@ -1147,3 +1147,129 @@ def test_branches_in_one_grid_equal_one_launch_per_branch(C_, T):
     n_valid = 8 * (Tb // 8 - 3)
     for j in range(3):
         assert torch.equal(a[j][:n_valid], b[j][:n_valid])
+
+
+# ------------------------------------------------------------------ kNN against the exact oracle (oracle/knn_ref.py: exact_*)
+# Every route only PICKS candidates (a wide list: the k best plus everything within ops.KNN_GUARD of the k-th); knnsvc_knn_rescore
+# recomputes those dots in fp64, rounds once to fp32 and replays the reference's formula.  So a returned list must be exactly the
+# top-k over the WHOLE pool of that formula on correctly rounded dots, ordered by (distance bits, lower index).
+_KNN_ROUTES = {"fused": dict(KNNSVC_KNN="f16x2", KNNSVC_KNN_FUSED="1"), "dot": dict(KNNSVC_KNN="f16x2", KNNSVC_KNN_FUSED="0"),
+               "fp32": dict(KNNSVC_KNN="fp32", KNNSVC_KNN_FUSED="1")}
+
+
+def _knn_family(name, dim, nq=256, npool=20000):
+    """Seeded adversarial feature families, built on the host -> (q [nq, dim], p [npool, dim]).
+    F1 clustered (control); F2 near-collinear non-negative rows (nearest distances ~1e-5 .. 1e-3); F3 six outlier channels at
+    100-1000x the rest in q and p (WavLM-like); F4 rows scaled by logspace(0, -5) in blocks with their own clusters, so quiet
+    queries have quiet neighbours (one power-of-two scale per operand: the quiet rows' low fp16 halves go subnormal)."""
+    g = torch.Generator().manual_seed(1000 + dim + 17 * int(name[1]))
+    if name == "F1":
+        return S.clustered_features(nq, dim, 101, n_centres=60), S.clustered_features(npool, dim, 102, n_centres=60)
+    if name == "F2":
+        base = 0.5 + torch.randn(64, dim, generator=g).abs()
+
+        def rows(n, lo, hi):
+            s = 10.0 ** (lo + (hi - lo) * torch.rand(n, 1, generator=g))
+            return (base[torch.randint(0, 64, (n,), generator=g)] * (1 + s * torch.randn(n, dim, generator=g))).clamp_min(0).contiguous()
+        return rows(nq, -2.5, -1.5), rows(npool, -2.2, -1.3)
+    if name == "F3":
+        q = S.clustered_features(nq, dim, 103, n_centres=60)
+        p = S.clustered_features(npool, dim, 104, n_centres=60)
+        ch = torch.randperm(dim, generator=g)[:6]
+        f = 10.0 ** (2 + torch.rand(6, generator=g))
+        q[:, ch] *= f; p[:, ch] *= f
+        return q, p
+    assert name == "F4"
+    blocks = 6
+    scale = torch.logspace(0, -5, blocks)
+    qs = [S.clustered_features(len(c), dim, 300 + b, n_centres=20, centre_seed=500 + b) * scale[b]
+          for b, c in enumerate(np.array_split(np.arange(nq), blocks))]
+    ps = [S.clustered_features(len(c), dim, 400 + b, n_centres=20, centre_seed=500 + b) * scale[b]
+          for b, c in enumerate(np.array_split(np.arange(npool), blocks))]
+    return torch.cat(qs).contiguous(), torch.cat(ps).contiguous()
+
+
+def _knn_exact_check(ops, knn_ref, qd, pd, D, k, route, monkeypatch, tag, mask=None):
+    """One search on one route, its route counters and the comparator against the exact oracle D."""
+    for name, v in _KNN_ROUTES[route].items():
+        monkeypatch.setenv(name, v)
+    c0 = dict(ops.KNN_ROUTE_COUNTS)
+    idx, dist, flag = ops.knn_topk(qd, pd, k, mask=mask, idx_offset=3, check_nan=False, return_flag=True)
+    ran = {r: ops.KNN_ROUTE_COUNTS[r] - c0[r] for r in ("fused", "dot")}
+    assert ran == {"fused": int(route == "fused"), "dot": int(route == "dot")}, (tag, route, ran)        # the route under test ran
+    fl = int(flag.item())
+    assert fl & 1 == 0 and (fl == 0 or route == "fused"), (tag, route, fl)
+    retry = ""
+    if fl & ops.KNN_OVERFLOW:        # the fused route's documented fallback (flagged, then repeated on the dot-matrix route)
+        idx, dist = ops.knn_topk(qd, pd, k, mask=mask, idx_offset=3)
+        retry = " (fused route flagged: repeated on the dot-matrix route)"
+    st = knn_ref.compare_to_exact(idx, dist, D, k, idx_offset=3)
+    print(f"kNN vs exact oracle [{tag} {route} k={k}]: {st}{retry}")
+    assert st["bad_lists"] == 0 and st["unexplained"] == 0 and st["left_out"] == 0, (tag, route, k, st)
+    return idx, dist
+
+
+@pytest.mark.parametrize("dim", [256, 768, 1024, 2048])
+@pytest.mark.parametrize("family", ["F1", "F2", "F3", "F4"])
+def test_knn_every_route_equals_the_exact_oracle_on_adversarial_features(family, dim, monkeypatch):
+    """F1-F4 x dim x {fused, dot matrix, fp32 tile} x k in {32, 5}: indices and distance bits equal the exact oracle (a mismatch
+    only inside a double-rounding tie of 1 ulp), nothing closer is left out.  Then the screening error itself (KNNSVC_KNN_RESCORE=0
+    passes the screening distances through): against the oracle at the same indices it must stay below half the route's guard
+    band (ops.knn_guard) — the least that keeps every exact top-k member inside the band."""
+    from oracle import knn_ref
+    ops = _ops()
+    q, p = _knn_family(family, dim)
+    nq, npool = q.shape[0], p.shape[0]
+    assert nq >= ops.KNN_FUSED_MIN_Q and npool >= ops.KNN_FUSED_MIN_P and len(ops.knn_epochs(nq, npool)) > 1
+    qd, pd = q.to(DEV), p.to(DEV)
+    qn, qs = ops.row_norms(qd)
+    pn, ps = ops.row_norms(pd)
+    D = knn_ref.exact_distance_matrix(qd, pd, qn, qs, pn, ps)
+    near = np.sort(D, axis=1)[:, 0]
+    print(f"{family} dim {dim}: nearest exact distance {near.min():.2e} .. {near.max():.2e}")
+    for route in _KNN_ROUTES:
+        for k in (32, 5):
+            _knn_exact_check(ops, knn_ref, qd, pd, D, k, route, monkeypatch, f"{family} dim {dim}")
+    monkeypatch.setenv("KNNSVC_KNN_RESCORE", "0")
+    for route in ("fused", "fp32"):
+        for name, v in _KNN_ROUTES[route].items():
+            monkeypatch.setenv(name, v)
+        idx, dist = ops.knn_topk(qd, pd, 32)
+        ia = idx.cpu().numpy()
+        err = float(np.abs(dist.cpu().numpy().astype(np.float64) - np.take_along_axis(D, ia, axis=1).astype(np.float64)).max())
+        band = ops.knn_guard(dim, "fp32" if route == "fp32" else "f16x2")
+        print(f"screening error [{family} dim {dim} {route}]: {err:.3e} (band {band:.2e})")
+        assert err < band / 2, (family, dim, route, err, band)
+
+
+@pytest.mark.parametrize("spread", [1e-3, 1e-4])
+@pytest.mark.parametrize("dim", [256, 1024])
+def test_knn_crowded_guard_band_is_still_exact(dim, spread, monkeypatch):
+    """F5: 256 pool rows around one point (relative spread 1e-3 / 1e-4), 40 queries near it — more than 64 keys lie inside the
+    guard band of the k-th, more than a wide list holds, and the screening order among them is not the exact one.  The lists must
+    still be the exact top-k on every route (knnsvc_knn_rescore re-scores such a crowded row against the whole pool chunk)."""
+    from oracle import knn_ref
+    ops = _ops()
+    g = torch.Generator().manual_seed(77 + dim)
+    nq, npool, crowd = 256, 20000, 256
+    q = S.clustered_features(nq, dim, 105, n_centres=60)
+    p = S.clustered_features(npool, dim, 106, n_centres=60)
+    x0 = p[123].clone()
+    at = torch.randperm(npool, generator=g)[:crowd]
+    rel = x0.norm() / dim ** 0.5
+    p[at] = x0 + spread * rel * torch.randn(crowd, dim, generator=g)
+    q[:40] = x0 + 0.03 * rel * torch.randn(40, dim, generator=g)
+    qd, pd = q.to(DEV), p.to(DEV)
+    qn, qs = ops.row_norms(qd)
+    pn, ps = ops.row_norms(pd)
+    D = knn_ref.exact_distance_matrix(qd, pd, qn, qs, pn, ps)
+    srt = np.sort(D[:40], axis=1)
+    in_band = int(np.min(np.sum(D[:40] <= srt[:, 31:32] + ops.KNN_GUARD, axis=1)))
+    print(f"F5 dim {dim} spread {spread}: at least {in_band} pool rows inside the band of each crowd query")
+    assert in_band > ops.KNN_WIDE
+    for route in _KNN_ROUTES:
+        for k in (32, 5):
+            _knn_exact_check(ops, knn_ref, qd, pd, D, k, route, monkeypatch, f"F5 dim {dim} spread {spread}")
+    mask = (int(at.min()), int(at.min()) + 500)                # a self-mask over part of the crowd
+    Dm = knn_ref.exact_distance_matrix(qd, pd, qn, qs, pn, ps, mask=mask)
+    _knn_exact_check(ops, knn_ref, qd, pd, Dm, 32, "fused", monkeypatch, f"F5 dim {dim} spread {spread} masked", mask=mask)

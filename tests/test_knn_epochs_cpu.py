@@ -21,3 +21,30 @@ def test_epochs_cover_every_column_tile_once_in_growing_steps(nq, npc, blocks):
 
 def test_north_star_point_is_one_cold_round_and_one_warm_epoch():
     assert ops.knn_epochs(1500, 30000, 256) == [(0, 42), (42, 118)]       # 6 x 42 = 252 workgroups, then 6 x 76 = 456
+
+
+def _window_points(dim):
+    p_cap = ((1 << 30) - 1) // (dim * 4) // 128 * 128
+    top = ((1 << 30) - 1) // (dim * 4)                          # the largest pool whose fp32 rows stay below 1 GiB
+    return p_cap, top, [p_cap - 1, p_cap, p_cap + 1, top, (1 << 30) // (4 * dim)]
+
+
+@pytest.mark.parametrize("dim", [256, 512, 768, 1024, 2048])
+def test_pool_chunk_plan_and_the_one_fill_agree_at_the_chunk_boundary(dim, monkeypatch):
+    """ADVICE r5: the search's one pre-zeroed first-epoch workspace may only go to a search of ONE pool chunk (ops.knn_search_fill);
+    between p_cap (prepare_knn_pool's chunk size) and 2^30 / (4 dim) the pool splits into two chunks, which must each get
+    their own.  The plan: balanced chunks of at least k rows that cover [0, npool) once."""
+    monkeypatch.delenv("KNNSVC_KNN_FUSED", raising=False)
+    p_cap, top, points = _window_points(dim)
+    assert p_cap < top
+    for npool in points:
+        chunks = ops.knn_pool_chunks(npool, dim)
+        assert chunks[0][0] == 0 and chunks[-1][1] == npool
+        assert all(a1 == b0 for (_, a1), (b0, _) in zip(chunks, chunks[1:]))
+        sizes = [b - a for a, b in chunks]
+        assert max(sizes) - min(sizes) <= 1 and min(sizes) >= 32 and max(sizes) <= p_cap
+        assert len(chunks) == (1 if npool <= p_cap else 2), (npool, chunks)
+        nq = 300
+        assert nq >= ops.KNN_FUSED_MIN_Q and npool >= ops.KNN_FUSED_MIN_P
+        fill = ops.knn_search_fill(nq, npool, dim)
+        assert (fill > 0) == (len(chunks) == 1), (dim, npool, fill, chunks)
