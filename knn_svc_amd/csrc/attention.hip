@@ -1154,12 +1154,7 @@ extern "C" int knnsvc_wavlm_attention(const float* qkv, const float* gate, const
     if (mode == 2) {
         const size_t l2 = (size_t)KT * KP2 + (size_t)KT * VP2 + (size_t)(2 * T - 1 + 64) * 4;
         KN_REQUIRE(l2 <= 160 * 1024, "wavlm_attention: T too long for the LDS bias table (T <= ~16000)");
-        static size_t attr2 = 0;
-        if (l2 > attr2) {
-            if (hipFuncSetAttribute((const void*)attention2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l2) != hipSuccess)
-                return knnsvc_fail(KNNSVC_EHIP, "wavlm_attention: hipFuncSetAttribute failed");
-            attr2 = l2;
-        }
+        if (const int rc = kn_lds_optin<attention2_kernel>((int)l2, "wavlm_attention")) return rc;
         // 64 queries per wave once the 128-query grid is at least two rounds of the 768 resident workgroups (bench batch, 21 x 1500:
         // 0.86 -> 0.78 ms); below that the larger workgroups leave CUs idle (3 x 777: 0.054 vs 0.063 ms).  Same results either
         // way, bit for bit.  KNNSVC_ATT_QB=1 / 2 forces one of them.
@@ -1173,22 +1168,12 @@ extern "C" int knnsvc_wavlm_attention(const float* qkv, const float* gate, const
             const long blocks512 = (long)((T + 511) / 512) * heads * batches;
             const size_t l2w = (size_t)3 * (KT * KP2 + KT * VP2) + (size_t)(2 * T - 1 + 64) * 4;
             if ((ew ? ew[0] == '8' : blocks512 >= 512) && l2w <= 160 * 1024) {
-                static size_t attr2w = 0;
-                if (l2w > attr2w) {
-                    if (hipFuncSetAttribute((const void*)attention2w_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l2w) != hipSuccess)
-                        return knnsvc_fail(KNNSVC_EHIP, "wavlm_attention: hipFuncSetAttribute failed");
-                    attr2w = l2w;
-                }
+                if (const int rc = kn_lds_optin<attention2w_kernel<2>>((int)l2w, "wavlm_attention")) return rc;
                 dim3 gridw((unsigned)((T + 511) / 512), (unsigned)heads, (unsigned)batches);
                 hipLaunchKernelGGL(attention2w_kernel<2>, gridw, dim3(512), l2w, (hipStream_t)stream, qkv, gate, table, kv_len, T, heads, out, out_f16x2, kv_f16x2);
                 return knnsvc_check_launch("wavlm_attention2w");
             }
-            static size_t attr2q = 0;
-            if (l2 > attr2q) {
-                if (hipFuncSetAttribute((const void*)attention2q_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l2) != hipSuccess)
-                    return knnsvc_fail(KNNSVC_EHIP, "wavlm_attention: hipFuncSetAttribute failed");
-                attr2q = l2;
-            }
+            if (const int rc = kn_lds_optin<attention2q_kernel<2>>((int)l2, "wavlm_attention")) return rc;
             dim3 gridq((unsigned)((T + 255) / 256), (unsigned)heads, (unsigned)batches);
             hipLaunchKernelGGL(attention2q_kernel<2>, gridq, dim3(256), l2, (hipStream_t)stream, qkv, gate, table, kv_len, T, heads, out, out_f16x2, kv_f16x2);
             return knnsvc_check_launch("wavlm_attention2q");
@@ -1201,25 +1186,14 @@ extern "C" int knnsvc_wavlm_attention(const float* qkv, const float* gate, const
     if (mode == 3) {
         const size_t l3 = (size_t)KT * KP3 + (size_t)HD * VP3 + (size_t)(2 * T - 1 + 64) * 4;
         KN_REQUIRE(l3 <= 160 * 1024, "wavlm_attention: T too long for the LDS bias table (T <= ~13000)");
-        static size_t attr3 = 0;
-        if (l3 > attr3) {
-            if (hipFuncSetAttribute((const void*)attention3_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l3) != hipSuccess)
-                return knnsvc_fail(KNNSVC_EHIP, "wavlm_attention: hipFuncSetAttribute failed");
-            attr3 = l3;
-        }
+        if (const int rc = kn_lds_optin<attention3_kernel>((int)l3, "wavlm_attention")) return rc;
         dim3 grid3((unsigned)((T + 127) / 128), (unsigned)heads, (unsigned)batches);
         hipLaunchKernelGGL(attention3_kernel, grid3, dim3(256), l3, (hipStream_t)stream, qkv, gate, table, kv_len, T, heads, out);
         return knnsvc_check_launch("wavlm_attention3");
     }
     const size_t lds = (size_t)(KT * LDKK + KT * LDV + 2 * T - 1) * 4;
     KN_REQUIRE(lds <= 160 * 1024, "wavlm_attention: T too long for the LDS bias table (T <= ~16000)");
-    static size_t attr = 0;
-    if (lds > attr) {
-        if (hipFuncSetAttribute((const void*)attention_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
-            hipSuccess)
-            return knnsvc_fail(KNNSVC_EHIP, "wavlm_attention: hipFuncSetAttribute failed");
-        attr = lds;
-    }
+    if (const int rc = kn_lds_optin<attention_kernel>((int)lds, "wavlm_attention")) return rc;
     dim3 grid((unsigned)((T + 127) / 128), (unsigned)heads, (unsigned)batches);
     hipLaunchKernelGGL(attention_kernel, grid, dim3(256), lds, (hipStream_t)stream, qkv, gate, table, kv_len, T, heads, out);
     return knnsvc_check_launch("wavlm_attention");

@@ -29,6 +29,37 @@ static inline int knnsvc_check_launch(const char* what) {
 
 static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// Opt-in of KERNEL to `bytes` of dynamic LDS (a launch with more than 64 KiB fails without it).  The attribute is set once per
+// kernel instantiation and process, and again only when a later call needs more.  `entry`: the API entry point, for the message.
+template <auto KERNEL>
+static inline int kn_lds_optin(int bytes, const char* entry) {
+    static int granted = 0;
+    if (bytes <= granted) return KNNSVC_OK;
+    if (hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess)
+        return knnsvc_fail(KNNSVC_EHIP, "%s: hipFuncSetAttribute failed", entry);
+    granted = bytes;
+    return KNNSVC_OK;
+}
+
+// A wave's TM x TN accumulator tiles of 32x32 (v_mfma_f32_32x32x*) in a block of (4 or 8 / WN) x WN waves
+template <int WN, int TM, int TN>
+struct Acc32 {
+    // accumulator element (tile i,j; register r) of this lane -> (row, col) inside the block tile
+    __device__ __forceinline__ static int acc_row(int wave, int lane, int i, int r) {
+        return (wave / WN) * TM * 32 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+    }
+    __device__ __forceinline__ static int acc_col(int wave, int lane, int j) {
+        return (wave % WN) * TN * 32 + j * 32 + (lane & 31);
+    }
+};
+
+// acc[TM][TN] = 0 for a wave's accumulator tiles of NR floats.  A macro on purpose: the same loops behind a function call (or
+// `= {}`) reach the optimiser in another order and reshuffle the scalar prologue of every kernel (tools/isa_diff.py).
+#define KN_ZERO_ACC(ACC, TM, TN, NR)                                                                            \
+    _Pragma("unroll") for (int i = 0; i < (TM); ++i)                                                           \
+        _Pragma("unroll") for (int j = 0; j < (TN); ++j)                                                       \
+            _Pragma("unroll") for (int r = 0; r < (NR); ++r) ACC[i][j][r] = 0.f;
+
 // Zero-fill as an ORDINARY KERNEL on the caller's stream (bytes % 4 == 0).  Not hipMemsetAsync: with several generators in flight on
 // several streams its fills were not ordered with the kernels that follow them on the same stream the way a kernel is (round 5:
 // csrc/models.hip, zero_slots — run-to-run different samples in the dataset-mode pipeline until the memset became a kernel).

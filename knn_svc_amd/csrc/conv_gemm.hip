@@ -30,7 +30,7 @@ struct ConvArgs {
     float a_scale;              // f16x2 path: power-of-two factor applied to activations before the split
     int lin;                    // plain output below 2 GiB: the buffer-addressed epilogue applies (conv_epilogue_lin)
     int wide;                   // ... and bias (+ residual) (+ range slot) is all there is, 16-byte rows: conv_epilogue_wide32 (windowed kernels)
-    int plain;                  // set by the launcher: one column tile and a row-tile count that is no multiple of 8 -> blockIdx.x IS the row tile
+    int plain;                  // set by the launcher: patch_order_plain (gemm2_core.h), blockIdx.x IS the row tile
     // dynamic range of the f16x2 path (include/knnsvc_hip.h, "Range"): device slots holding an upper bound of |x| / |w|;
     // when set, the kernel derives the power-of-two operand scale from the slot (kn_pick_scale) instead of a_scale / w_scale
     const float* x_absmax; const float* w_absmax;
@@ -364,11 +364,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, typename G::acc
                 if (a.accumulate) v += av[r];
                 if (a.div != 1.0f) v = v / a.div;
                 if (a.out_absmax) { const unsigned ab = abs_bits(v); amax = ab > amax ? ab : amax; }
-#ifdef KN_WHATIF_NOSTORE
-                if (v == 123456.789f) oz[orow * a.ldo + col] = v;      // timing-only build: keeps the value live, stores nothing
-#else
                 oz[orow * a.ldo + col] = v;
-#endif
             }
         }
     }
@@ -562,11 +558,7 @@ __device__ __forceinline__ void conv_epilogue_wide(const ConvArgs& a, typename G
 #pragma unroll
                 for (int e = 0; e < 4; ++e) { const unsigned ab = abs_bits(v[e]); amax = ab > amax ? ab : amax; }
             }
-#ifdef KN_T_NOSTORE       // timing aid: everything but the global store
-            if (v[0] == 123456.789f) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), o_rsrc, off, 0, 0);
-#else
             __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), o_rsrc, off, 0, 0);
-#endif
         }
     }
     if (a.out_absmax) publish_absmax(a.out_absmax, amax);
@@ -696,12 +688,7 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(ConvArgs a) {
     const float* wz = a.w + g * a.w_gstride;
 
     f32x16 acc[G::TM][G::TN];
-#pragma unroll
-    for (int i = 0; i < G::TM; ++i)
-#pragma unroll
-        for (int j = 0; j < G::TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    KN_ZERO_ACC(acc, G::TM, G::TN, G::NR)
 
     if constexpr (VEC == 8) {
         FastALoader<G::A_F4> al(a, m0, threadIdx.x);
@@ -728,12 +715,7 @@ __global__ __launch_bounds__(256, 3) void conv_gemm3_kernel(ConvArgs a) {
     const unsigned short* wz = a.w3 + (long)g * a.n * (a.K / 32) * 96;      // 96 ushorts = 192 B per (row, slab)
 
     f32x16 acc[G::TM][G::TN];
-#pragma unroll
-    for (int i = 0; i < G::TM; ++i)
-#pragma unroll
-        for (int j = 0; j < G::TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    KN_ZERO_ACC(acc, G::TM, G::TN, G::NR)
     FastALoader<G::A_F4> al(a, m0, threadIdx.x);
     Split3BLoader<G::B_P, G::B_PIECES> bl(a.n, a.K, n0, threadIdx.x);
     G::mainloop(lds, a.K / 32, al, bl, acc, FastALoader<G::A_F4>::desc(a, xz), Split3BLoader<G::B_P, G::B_PIECES>::desc(wz, a.n, a.K));
@@ -749,37 +731,13 @@ __global__ __launch_bounds__(256, 3) void conv_gemm2_kernel(ConvArgs a) {
     // resident on an XCD spanned all 16 groups of the positional conv — 32 MB of weights against 4 MB of L2)
     const int nbz = (int)gridDim.z / a.groups;
     const int g = z / nbz, b = z - g * nbz;
-    // XCD-aware tile order (see conv_gemm2big_kernel): ids congruent mod 8 share an L2; a group is 8 row tiles x all
-    // column tiles, so the column tiles of one row tile run on one XCD, next to each other in time
-    // and the columns are walked in patches of CW tiles, so an XCD's ~96 resident blocks form a (12 x 8)-ish patch
-    // that shares both A and B panels through its L2.
-    const int gy = (a.n + G::BN - 1) / G::BN;
-    const int gx8 = (int)gridDim.x / gy;                      // row tiles padded to a multiple of 8
-    constexpr int CW = 8;
-    int L = blockIdx.x;
-    const int full = (gy / CW) * CW * gx8;                    // ids covered by full-width column patches
-    int c0, cw;
-    if (L < full) { c0 = (L / (CW * gx8)) * CW; cw = CW; L -= (c0 / CW) * CW * gx8; }
-    else { c0 = (gy / CW) * CW; cw = gy - c0; L -= full; }
-    const int grp = L / (8 * cw), rem = L - grp * 8 * cw;
-    // (rem + z) & 7: which XCD gets which row tile of a group of 8 rotates with the batch / group index.  The padding rows are the
-    // same in every slice of a batched launch: unrotated, the positional conv's 6 row tiles per (chunk, group) — 336 slices — left
-    // XCDs 6 and 7 nothing but padding ids, a quarter of the chip idle for the whole launch (1.76 ms against 1.37 for the same work
-    // as one long sequence); gemm2_core.h's quad_order_decode rotates for the same reason.
-    // a.plain: a single column tile has no operand panel to share between column tiles, so padding the row tiles to groups of 8
-    // buys nothing and the padding ids still queue for LDS before they can exit (6 row tiles: a quarter of all ids)
-    const int m0 = a.plain ? (int)blockIdx.x * G::BM : (grp * 8 + ((rem + (int)blockIdx.z) & 7)) * G::BM, n0 = a.plain ? 0 : (c0 + (rem >> 3)) * G::BN;
-    if (m0 >= a.m) return;                                    // padding of the last group
+    int m0, n0;
+    if (!patch_order_decode<G::BM, G::BN>(a.plain, a.m, a.n, m0, n0)) return;      // XCD-aware tile order (gemm2_core.h)
     const float* xz = a.x + b * a.x_bstride + g * a.x_gstride;
     const unsigned short* wz = a.w2 + (long)g * a.n * (a.K / 32) * 64;      // 64 halves = 128 B per (row, slab)
 
     typename G::acc_t acc[G::TM][G::TN];
-#pragma unroll
-    for (int i = 0; i < G::TM; ++i)
-#pragma unroll
-        for (int j = 0; j < G::TN; ++j)
-#pragma unroll
-            for (int r = 0; r < G::NR; ++r) acc[i][j][r] = 0.f;
+    KN_ZERO_ACC(acc, G::TM, G::TN, G::NR)
     FastALoader<G::A_F4> al(a, m0, threadIdx.x);
     Split2BLoader<G::B_P, G::B_PIECES> bl(a.n, a.K, n0, threadIdx.x);
     G::template mainloop<A2>(lds, a.K / 32, al, bl, acc, FastALoader<G::A_F4>::desc(a, xz), Split2BLoader<G::B_P, G::B_PIECES>::desc(wz, a.n, a.K), a.a_scale);
@@ -876,33 +834,13 @@ __device__ __forceinline__ void conv_gemm2win_body(ConvArgs& a, float* lds) {
     // resident on an XCD spanned all 16 groups of the positional conv — 32 MB of weights against 4 MB of L2)
     const int nbz = (int)gridDim.z / a.groups;
     const int g = z / nbz, b = z - g * nbz;
-    const int gy = (a.n + G::BN - 1) / G::BN;                 // same XCD-aware column-patch order as conv_gemm2_kernel
-    const int gx8 = (int)gridDim.x / gy;
-    constexpr int CW = 8;
-    int L = blockIdx.x;
-    const int full = (gy / CW) * CW * gx8;
-    int c0, cw;
-    if (L < full) { c0 = (L / (CW * gx8)) * CW; cw = CW; L -= (c0 / CW) * CW * gx8; }
-    else { c0 = (gy / CW) * CW; cw = gy - c0; L -= full; }
-    const int grp = L / (8 * cw), rem = L - grp * 8 * cw;
-    // (rem + z) & 7: which XCD gets which row tile of a group of 8 rotates with the batch / group index.  The padding rows are the
-    // same in every slice of a batched launch: unrotated, the positional conv's 6 row tiles per (chunk, group) — 336 slices — left
-    // XCDs 6 and 7 nothing but padding ids, a quarter of the chip idle for the whole launch (1.76 ms against 1.37 for the same work
-    // as one long sequence); gemm2_core.h's quad_order_decode rotates for the same reason.
-    // a.plain: a single column tile has no operand panel to share between column tiles, so padding the row tiles to groups of 8
-    // buys nothing and the padding ids still queue for LDS before they can exit (6 row tiles: a quarter of all ids)
-    const int m0 = a.plain ? (int)blockIdx.x * G::BM : (grp * 8 + ((rem + (int)blockIdx.z) & 7)) * G::BM, n0 = a.plain ? 0 : (c0 + (rem >> 3)) * G::BN;
-    if (m0 >= a.m) return;
+    int m0, n0;
+    if (!patch_order_decode<G::BM, G::BN>(a.plain, a.m, a.n, m0, n0)) return;      // XCD-aware tile order (gemm2_core.h)
     const float* xz = a.x + b * a.x_bstride + g * a.x_gstride;
     const unsigned short* wz = a.w2 + (long)g * a.n * (a.K / 32) * 64;
 
     typename G::acc_t acc[G::TM][G::TN];
-#pragma unroll
-    for (int i = 0; i < G::TM; ++i)
-#pragma unroll
-        for (int j = 0; j < G::TN; ++j)
-#pragma unroll
-            for (int r = 0; r < G::NR; ++r) acc[i][j][r] = 0.f;
+    KN_ZERO_ACC(acc, G::TM, G::TN, G::NR)
     Split2BLoader<G::B_P, G::B_PIECES> bl(a.n, a.K, n0, threadIdx.x);
     const int tid = threadIdx.x;
     const int w_off0 = ((m0 - a.pad + (tid >> 3)) * a.ldx + (tid & 7) * 4) * 4;
@@ -940,40 +878,21 @@ __global__ __launch_bounds__(256, MINB) void conv_gemm2win_multi_kernel(ConvArgs
     conv_gemm2win_body<G>(a, lds);
 }
 
+// `count` convolutions of one output shape: one descriptor is a launch of conv_gemm2win_kernel over its batches and groups,
+// several (batches == groups == 1) are one grid of conv_gemm2win_multi_kernel
 template <class G, int MINB>
-int launch2win(const ConvArgs& a, int batches, hipStream_t st) {
-    static bool attr = false;
-    if (!attr) {
-        if (hipFuncSetAttribute((const void*)conv_gemm2win_kernel<G, MINB>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                G::LDS_BYTES) != hipSuccess)
-            return knnsvc_fail(KNNSVC_EHIP, "conv_gemm: hipFuncSetAttribute failed");
-        attr = true;
-    }
+int launch2win(const ConvArgs* args, int count, int batches, hipStream_t st) {
+    const ConvArgs& a = args[0];
     const long gx = cdiv64(a.m, G::BM), gy = cdiv64(a.n, G::BN);
-    ConvArgs ap = a;
-    ap.plain = gy == 1 && gx % 8 != 0;
-    const long gx8 = ap.plain ? gx : cdiv64(gx, 8) * 8;
-    dim3 grid((unsigned)(gx8 * gy), 1, (unsigned)(batches * a.groups));
-    hipLaunchKernelGGL((conv_gemm2win_kernel<G, MINB>), grid, dim3(256), G::LDS_BYTES, st, ap);
-    return knnsvc_check_launch("conv_gemm2win");
-}
-
-template <class G, int MINB>
-int launch2win_multi(const ConvArgsN& an, int count, hipStream_t st) {
-    static bool attr = false;
-    if (!attr) {
-        if (hipFuncSetAttribute((const void*)conv_gemm2win_multi_kernel<G, MINB>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                G::LDS_BYTES) != hipSuccess)
-            return knnsvc_fail(KNNSVC_EHIP, "conv_gemm_multi: hipFuncSetAttribute failed");
-        attr = true;
+    ConvArgsN ap;
+    for (int i = 0; i < KN_MAX_MULTI; ++i) { ap.b[i] = args[i < count ? i : 0]; ap.b[i].plain = patch_order_plain(gx, gy); }
+    dim3 grid((unsigned)patch_order_ids(gx, gy), (unsigned)count, (unsigned)(batches * a.groups));
+    if (count == 1) {
+        if (const int rc = kn_lds_optin<conv_gemm2win_kernel<G, MINB>>(G::LDS_BYTES, "conv_gemm")) return rc;
+        hipLaunchKernelGGL((conv_gemm2win_kernel<G, MINB>), grid, dim3(256), G::LDS_BYTES, st, ap.b[0]);
+        return knnsvc_check_launch("conv_gemm2win");
     }
-    const ConvArgs& a = an.b[0];
-    const long gx = cdiv64(a.m, G::BM), gy = cdiv64(a.n, G::BN);
-    ConvArgsN ap = an;
-    const int plain = gy == 1 && gx % 8 != 0;
-    for (int i = 0; i < KN_MAX_MULTI; ++i) ap.b[i].plain = plain;
-    const long gx8 = plain ? gx : cdiv64(gx, 8) * 8;
-    dim3 grid((unsigned)(gx8 * gy), (unsigned)count, 1);
+    if (const int rc = kn_lds_optin<conv_gemm2win_multi_kernel<G, MINB>>(G::LDS_BYTES, "conv_gemm_multi")) return rc;
     hipLaunchKernelGGL((conv_gemm2win_multi_kernel<G, MINB>), grid, dim3(256), G::LDS_BYTES, st, ap);
     return knnsvc_check_launch("conv_gemm2win_multi");
 }
@@ -997,12 +916,7 @@ __global__ __launch_bounds__(256, 1) void conv_gemm2quad_kernel(ConvArgs a) {
     const unsigned short* wz = a.w2 + (long)g * a.n * (a.K / 32) * 64;
 
     typename G::acc_t acc[G::TM][G::TN];
-#pragma unroll
-    for (int i = 0; i < G::TM; ++i)
-#pragma unroll
-        for (int j = 0; j < G::TN; ++j)
-#pragma unroll
-            for (int r = 0; r < G::NR; ++r) acc[i][j][r] = 0.f;
+    KN_ZERO_ACC(acc, G::TM, G::TN, G::NR)
     const int M = a.m, row_step = a.stride * a.ldx * 4, row_pad = a.pad * a.ldx * 4;
     auto row_off = [&](int m) -> int { return m < M ? m * row_step - row_pad : G::OOB_OFF; };
     int c_in_tap = 0, uoff = 0;
@@ -1023,9 +937,6 @@ __global__ __launch_bounds__(256, 1) void conv_gemm2quad_kernel(ConvArgs a) {
               for (int r = 0; r < G::NR; ++r) sink += acc[i][j][r];
       if (sink == 123456.789f) a.out[threadIdx.x] = sink; }
 #else
-#ifdef KN_T_LINEPI         // timing aid: the column-per-lane epilogue instead of the LDS-transposed one
-    conv_epilogue_lin<G>(a, acc, m0, n0, b, g);
-#else
     __syncthreads();                                  // every wave is done with the ring: its stages become the epilogue patches
 #ifdef KN_QUAD_PROF
     if (threadIdx.x == 0 && blockIdx.x < 8192) kn_quad_prof_buf[blockIdx.x * 4 + 2] = (long long)__builtin_amdgcn_s_memrealtime();
@@ -1040,18 +951,11 @@ __global__ __launch_bounds__(256, 1) void conv_gemm2quad_kernel(ConvArgs a) {
     if (threadIdx.x == 0 && blockIdx.x < 8192) kn_quad_prof_buf[blockIdx.x * 4 + 3] = (long long)__builtin_amdgcn_s_memrealtime();
 #endif
 #endif
-#endif
 }
 
 template <class G, int EPI = 0>
 int launch2quad(const ConvArgs& a, int batches, hipStream_t st) {
-    static bool attr = false;
-    if (!attr) {
-        if (hipFuncSetAttribute((const void*)conv_gemm2quad_kernel<G, EPI>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                G::LDS_BYTES) != hipSuccess)
-            return knnsvc_fail(KNNSVC_EHIP, "conv_gemm: hipFuncSetAttribute failed");
-        attr = true;
-    }
+    if (const int rc = kn_lds_optin<conv_gemm2quad_kernel<G, EPI>>(G::LDS_BYTES, "conv_gemm")) return rc;
     dim3 grid((unsigned)quad_order_ids(cdiv64(a.m, G::BM), cdiv64(a.n, G::BN)), 1, (unsigned)(batches * a.groups));
     hipLaunchKernelGGL((conv_gemm2quad_kernel<G, EPI>), grid, dim3(256), G::LDS_BYTES, st, a);
     return knnsvc_check_launch("conv_gemm2quad");
@@ -1059,18 +963,11 @@ int launch2quad(const ConvArgs& a, int batches, hipStream_t st) {
 
 template <class G, bool A2>
 int launch2v(const ConvArgs& a, int batches, hipStream_t st) {
-    static bool attr = false;
-    if (!attr) {
-        if (hipFuncSetAttribute((const void*)conv_gemm2_kernel<G, A2>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                G::LDS_BYTES) != hipSuccess)
-            return knnsvc_fail(KNNSVC_EHIP, "conv_gemm: hipFuncSetAttribute failed");
-        attr = true;
-    }
+    if (const int rc = kn_lds_optin<conv_gemm2_kernel<G, A2>>(G::LDS_BYTES, "conv_gemm")) return rc;
     const long gx = cdiv64(a.m, G::BM), gy = cdiv64(a.n, G::BN);
     ConvArgs ap = a;
-    ap.plain = gy == 1 && gx % 8 != 0;
-    const long gx8 = ap.plain ? gx : cdiv64(gx, 8) * 8;          // row tiles padded to whole groups of 8 (one per XCD)
-    dim3 grid((unsigned)(gx8 * gy), 1, (unsigned)(batches * a.groups));
+    ap.plain = patch_order_plain(gx, gy);
+    dim3 grid((unsigned)patch_order_ids(gx, gy), 1, (unsigned)(batches * a.groups));
     hipLaunchKernelGGL((conv_gemm2_kernel<G, A2>), grid, dim3(256), G::LDS_BYTES, st, ap);
     return knnsvc_check_launch("conv_gemm2");
 }
@@ -1096,13 +993,7 @@ __global__ void split_weight2_kernel(const float* __restrict__ w, long n, int K,
 
 template <class G>
 int launch3(const ConvArgs& a, int batches, hipStream_t st) {
-    static bool attr = false;
-    if (!attr) {
-        if (hipFuncSetAttribute((const void*)conv_gemm3_kernel<G>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                G::LDS_BYTES) != hipSuccess)
-            return knnsvc_fail(KNNSVC_EHIP, "conv_gemm: hipFuncSetAttribute failed");
-        attr = true;
-    }
+    if (const int rc = kn_lds_optin<conv_gemm3_kernel<G>>(G::LDS_BYTES, "conv_gemm")) return rc;
     dim3 grid((unsigned)cdiv64(a.m, G::BM), (unsigned)cdiv64(a.n, G::BN), (unsigned)(batches * a.groups));
     hipLaunchKernelGGL((conv_gemm3_kernel<G>), grid, dim3(256), G::LDS_BYTES, st, a);
     return knnsvc_check_launch("conv_gemm3");
@@ -1154,26 +1045,12 @@ using W64 = Gemm2Win<256, 64, 4, 1, 2, 2, 64>;        // 320 rows (45 KB) + 9 KB
 using W32 = Gemm2Win<256, 32, 4, 1, 2, 1, 64>;        // 320 rows + 4.5 KB
 using W64P = Gemm2Win<256, 64, 4, 1, 2, 2, 128>;      // k = 128 positional conv: 384 rows (54 KB) + 9 KB
 
-
 template <class G>
-int prepare() {   // opt in to > 64 KiB of dynamic LDS once per kernel
-    static bool done4 = false, done1 = false, done8 = false;
-    if (!done8) {
-        if (hipFuncSetAttribute((const void*)conv_gemm_kernel<G, 8>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                G::LDS_BYTES) != hipSuccess) return 1;
-        done8 = true;
-    }
-    if (!done4) {
-        if (hipFuncSetAttribute((const void*)conv_gemm_kernel<G, 4>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                G::LDS_BYTES) != hipSuccess) return 1;
-        done4 = true;
-    }
-    if (!done1) {
-        if (hipFuncSetAttribute((const void*)conv_gemm_kernel<G, 1>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                G::LDS_BYTES) != hipSuccess) return 1;
-        done1 = true;
-    }
-    return 0;
+int prepare() {   // the fp32 kernels' dynamic LDS, all three loader forms, on the first call
+    int rc = kn_lds_optin<conv_gemm_kernel<G, 8>>(G::LDS_BYTES, "conv_gemm");
+    if (!rc) rc = kn_lds_optin<conv_gemm_kernel<G, 4>>(G::LDS_BYTES, "conv_gemm");
+    if (!rc) rc = kn_lds_optin<conv_gemm_kernel<G, 1>>(G::LDS_BYTES, "conv_gemm");
+    return rc;
 }
 
 // A/B switches of the dispatcher, read from the environment ONCE (first launch) into this struct; knnsvc_reload_knobs() re-reads
@@ -1258,8 +1135,9 @@ static int conv_prep(const knnsvc_conv_desc* d, ConvArgs& a, bool& fast, bool& v
     vec4 = (d->cin % 4 == 0) && (d->ldx % 4 == 0) && (((uintptr_t)d->x & 15) == 0) &&
                       (((uintptr_t)d->w & 15) == 0) && (d->x_bstride % 4 == 0) && (d->x_gstride % 4 == 0) &&
                       (d->w_gstride % 4 == 0);
-    if (prepare<G128>() || prepare<G64>() || prepare<G32>())
-        return knnsvc_fail(KNNSVC_EHIP, "conv_gemm: hipFuncSetAttribute failed");
+    if (const int rc = prepare<G128>()) return rc;
+    if (const int rc = prepare<G64>()) return rc;
+    if (const int rc = prepare<G32>()) return rc;
     // buffer-load fast path: every slab inside one tap, resources below 1 GiB
     fast = vec4 && (d->cin % 32 == 0) && ((long)d->t_in * d->ldx * 4 < (1L << 30)) &&
                       ((long)d->n * a.K * 4 < (1L << 30)) && ((long)d->m * d->stride * d->ldx * 4 < (1L << 30));
@@ -1326,6 +1204,22 @@ static WinShape win_shape(const knnsvc_conv_desc* d, const ConvArgs& a, long z) 
     return WS_NONE;
 }
 
+// the windowed kernel of shape `ws` for one descriptor (over its batches and groups) or for `count` of them in one grid
+static int launch_win(WinShape ws, const ConvArgs* args, int count, int batches, hipStream_t st) {
+    const bool x = count > 1;
+    switch (ws) {
+        case WS_128D: g_last_kernel = x ? "W128Dx" : "W128D"; return launch2win<W128D, 4>(args, count, batches, st);
+        case WS_128S: g_last_kernel = x ? "W128Sx" : "W128S"; return launch2win<W128S, 4>(args, count, batches, st);
+        case WS_160: g_last_kernel = x ? "W160x" : "W160"; return launch2win<W160, 3>(args, count, batches, st);
+        case WS_128: g_last_kernel = x ? "W128x" : "W128"; return launch2win<W128, 3>(args, count, batches, st);
+        case WS_64: g_last_kernel = x ? "W64x" : "W64"; return launch2win<W64, 2>(args, count, batches, st);
+        case WS_32: g_last_kernel = x ? "W32x" : "W32"; return launch2win<W32, 3>(args, count, batches, st);
+        case WS_64P: g_last_kernel = x ? "W64Px" : "W64P"; return launch2win<W64P, 2>(args, count, batches, st);
+        case WS_NONE: break;
+    }
+    return knnsvc_fail(KNNSVC_EINVAL, "conv_gemm: no windowed kernel for this shape");
+}
+
 extern "C" int knnsvc_conv_gemm(const knnsvc_conv_desc* d, void* stream) {
     ConvArgs a;
     bool fast = false, vec4 = false, quad_ok = false;
@@ -1357,16 +1251,8 @@ extern "C" int knnsvc_conv_gemm(const knnsvc_conv_desc* d, void* stream) {
         }
         g_last_epilogue = a.wide ? "patch" : "lane";      // the windowed and tap-major f16x2 kernels below
         // stride-1 multi-tap convolutions on fp32 input: windowed kernel (A staged once per channel slab, not once per tap)
-        switch (win_shape(d, a, (long)d->batches * d->groups)) {
-            case WS_128D: g_last_kernel = "W128D"; return launch2win<W128D, 4>(a, d->batches, st);
-            case WS_128S: g_last_kernel = "W128S"; return launch2win<W128S, 4>(a, d->batches, st);
-            case WS_160: g_last_kernel = "W160"; return launch2win<W160, 3>(a, d->batches, st);
-            case WS_128: g_last_kernel = "W128"; return launch2win<W128, 3>(a, d->batches, st);
-            case WS_64: g_last_kernel = "W64"; return launch2win<W64, 2>(a, d->batches, st);
-            case WS_32: g_last_kernel = "W32"; return launch2win<W32, 3>(a, d->batches, st);
-            case WS_64P: g_last_kernel = "W64P"; return launch2win<W64P, 2>(a, d->batches, st);
-            case WS_NONE: break;
-        }
+        const WinShape ws = win_shape(d, a, (long)d->batches * d->groups);
+        if (ws != WS_NONE) return launch_win(ws, &a, 1, d->batches, st);
         if (d->n > 64 && cdiv64(d->m, 128) * cdiv64(d->n, 128) * d->batches * d->groups < 256) {
             if (knobs().gemm_small) { g_last_kernel = "F64S"; return launch2<F64S>(a, d->batches, st); }
         }
@@ -1407,19 +1293,7 @@ extern "C" int knnsvc_conv_gemm_multi(const knnsvc_conv_desc* descs, int32_t cou
         for (int i = 0; i < count; ++i) { const int rc = knnsvc_conv_gemm(&descs[i], stream); if (rc) return rc; }
         return KNNSVC_OK;
     }
-    for (int i = count; i < KN_MAX_MULTI; ++i) an.b[i] = an.b[0];
-    hipStream_t st = (hipStream_t)stream;
-    switch (win_shape(&descs[0], an.b[0], count)) {
-        case WS_128D: g_last_kernel = "W128Dx"; return launch2win_multi<W128D, 4>(an, count, st);
-        case WS_128S: g_last_kernel = "W128Sx"; return launch2win_multi<W128S, 4>(an, count, st);
-        case WS_160: g_last_kernel = "W160x"; return launch2win_multi<W160, 3>(an, count, st);
-        case WS_128: g_last_kernel = "W128x"; return launch2win_multi<W128, 3>(an, count, st);
-        case WS_64: g_last_kernel = "W64x"; return launch2win_multi<W64, 2>(an, count, st);
-        case WS_32: g_last_kernel = "W32x"; return launch2win_multi<W32, 3>(an, count, st);
-        case WS_64P: g_last_kernel = "W64Px"; return launch2win_multi<W64P, 2>(an, count, st);
-        case WS_NONE: break;
-    }
-    return knnsvc_fail(KNNSVC_EINVAL, "conv_gemm_multi: no windowed kernel for this shape");
+    return launch_win(win_shape(&descs[0], an.b[0], count), an.b, count, 1, (hipStream_t)stream);      // (not WS_NONE: one_grid)
 }
 
 extern "C" int knnsvc_split_weight_bf16x3(const float* w, int64_t rows, int32_t K, void* out, void* stream) {
@@ -1534,12 +1408,7 @@ __device__ __forceinline__ void conv_pair_body(const PairArgs& a, float* lds) {
 
     // ---- phase 1: t1 rows [t0 - h2, t0 - h2 + BM)
     typename G::acc_t acc[G::TM][G::TN];
-#pragma unroll
-    for (int i = 0; i < G::TM; ++i)
-#pragma unroll
-        for (int j = 0; j < G::TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    KN_ZERO_ACC(acc, G::TM, G::TN, G::NR)
     const __amdgpu_buffer_rsrc_t x_rsrc = uniform_rsrc(a.x, ((T - 1) * a.ldx + C) * 4);
     {
         Split2BLoader<G::B_P, G::B_PIECES> bl(C, K, 0, tid);
@@ -1573,12 +1442,7 @@ __device__ __forceinline__ void conv_pair_body(const PairArgs& a, float* lds) {
     __syncthreads();
 
     // ---- phase 2: out rows [t0, t0 + BMo)
-#pragma unroll
-    for (int i = 0; i < G::TM; ++i)
-#pragma unroll
-        for (int j = 0; j < G::TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    KN_ZERO_ACC(acc, G::TM, G::TN, G::NR)
     {
         Split2BLoader<G::B_P, G::B_PIECES> bl(C, K, 0, tid);
         G::mainloop_resident(lds, ncs, taps, img_slab, ncs * img_slab, bl, acc, Split2BLoader<G::B_P, G::B_PIECES>::desc(a.w2, C, K));
@@ -1628,44 +1492,38 @@ __global__ __launch_bounds__(256, MINB) void conv_pair_multi_kernel(PairArgsN ar
     conv_pair_body<G>(a, lds);
 }
 
+// `count` pairs on inputs of one shape: one is a launch of conv_pair_kernel, several are one grid of conv_pair_multi_kernel
 template <class G, int MINB>
-int launch_pair_multi(const PairArgsN& an, int count, hipStream_t st) {
+int launch_pair(const PairArgs* args, int count, hipStream_t st) {
     constexpr int IR = G::BM + 16;
-    const int ncs = an.b[0].C / 32;
+    const int ncs = args[0].C / 32;
     const int lds_bytes = G::LDS_BYTES > (ncs * IR + G::BN) * G::PITCH ? G::LDS_BYTES : (ncs * IR + G::BN) * G::PITCH;
-    static int attr = 0;
-    if (attr < lds_bytes) {
-        if (hipFuncSetAttribute((const void*)conv_pair_multi_kernel<G, MINB>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes) != hipSuccess)
-            return knnsvc_fail(KNNSVC_EHIP, "resblock_pair_multi: hipFuncSetAttribute failed");
-        attr = lds_bytes;
-    }
     int taps_max = 1;
-    for (int i = 0; i < count; ++i) taps_max = an.b[i].taps > taps_max ? an.b[i].taps : taps_max;
+    for (int i = 0; i < count; ++i) taps_max = args[i].taps > taps_max ? args[i].taps : taps_max;
     // a branch with fewer taps yields more rows per workgroup and needs fewer of them: its surplus workgroups leave at once (t0 >= T)
     const int BMo = G::BM - (taps_max - 1);
-    hipLaunchKernelGGL((conv_pair_multi_kernel<G, MINB>), dim3((unsigned)cdiv64(an.b[0].T, BMo), (unsigned)count), dim3(256), lds_bytes, st, an);
-    return knnsvc_check_launch("resblock_pair_multi");
-}
-
-template <class G, int MINB>
-int launch_pair(const PairArgs& a, hipStream_t st) {
-    constexpr int IR = G::BM + 16;
-    const int ncs = a.C / 32;
-    const int lds_bytes = G::LDS_BYTES > (ncs * IR + G::BN) * G::PITCH ? G::LDS_BYTES : (ncs * IR + G::BN) * G::PITCH;
-    static int attr = 0;
-    if (attr < lds_bytes) {
-        if (hipFuncSetAttribute((const void*)conv_pair_kernel<G, MINB>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes) != hipSuccess)
-            return knnsvc_fail(KNNSVC_EHIP, "resblock_pair: hipFuncSetAttribute failed");
-        attr = lds_bytes;
+    dim3 grid((unsigned)cdiv64(args[0].T, BMo), (unsigned)count);
+    if (count == 1) {
+        if (const int rc = kn_lds_optin<conv_pair_kernel<G, MINB>>(lds_bytes, "resblock_pair")) return rc;
+        hipLaunchKernelGGL((conv_pair_kernel<G, MINB>), grid, dim3(256), lds_bytes, st, args[0]);
+        return knnsvc_check_launch("resblock_pair");
     }
-    const int BMo = G::BM - (a.taps - 1);
-    hipLaunchKernelGGL((conv_pair_kernel<G, MINB>), dim3((unsigned)cdiv64(a.T, BMo)), dim3(256), lds_bytes, st, a);
-    return knnsvc_check_launch("resblock_pair");
+    if (const int rc = kn_lds_optin<conv_pair_multi_kernel<G, MINB>>(lds_bytes, "resblock_pair_multi")) return rc;
+    PairArgsN an;
+    for (int i = 0; i < KN_MAX_MULTI; ++i) an.b[i] = args[i < count ? i : 0];
+    hipLaunchKernelGGL((conv_pair_multi_kernel<G, MINB>), grid, dim3(256), lds_bytes, st, an);
+    return knnsvc_check_launch("resblock_pair_multi");
 }
 
 using P64 = Gemm2Win<128, 64, 4, 1, 1, 2, 64>;        // C = 64: window 27.6 KB / image 41.5 KB + weights 9.2 KB: 3 blocks / CU
 using P32 = Gemm2Win<256, 32, 4, 1, 2, 1, 64>;        // C = 32: window 46 KB + 4.6 KB / image 39 KB: 3 blocks / CU
 using P128 = Gemm2Win<64, 128, 2, 2, 1, 2, 64>;       // C = 128: 64-row tiles (image 4 x 80 rows = 46 KB + weights 18.4 KB): 2 blocks / CU
+
+int launch_pair_c(const PairArgs* args, int count, hipStream_t st) {      // the tile by channel count
+    if (args[0].C == 128) return launch_pair<P128, 2>(args, count, st);
+    if (args[0].C == 64) return launch_pair<P64, 3>(args, count, st);
+    return launch_pair<P32, 3>(args, count, st);
+}
 }  // namespace
 
 static int pair_prep(const knnsvc_pair_desc* d, PairArgs& a) {
@@ -1690,9 +1548,7 @@ extern "C" int knnsvc_resblock_pair(const knnsvc_pair_desc* d, void* stream) {
     const int rc = pair_prep(d, a);
     if (rc) return rc;
     if (d->t == 0) return KNNSVC_OK;
-    if (d->channels == 128) return launch_pair<P128, 2>(a, (hipStream_t)stream);
-    if (d->channels == 64) return launch_pair<P64, 3>(a, (hipStream_t)stream);
-    return launch_pair<P32, 3>(a, (hipStream_t)stream);
+    return launch_pair_c(&a, 1, (hipStream_t)stream);
 }
 
 extern "C" int knnsvc_resblock_pair_multi(const knnsvc_pair_desc* descs, int32_t count, void* stream) {
@@ -1709,10 +1565,7 @@ extern "C" int knnsvc_resblock_pair_multi(const knnsvc_pair_desc* descs, int32_t
         for (int i = 0; i < count; ++i) { const int rc = knnsvc_resblock_pair(&descs[i], stream); if (rc) return rc; }
         return KNNSVC_OK;
     }
-    for (int i = count; i < KN_MAX_MULTI; ++i) an.b[i] = an.b[0];
-    if (descs[0].channels == 128) return launch_pair_multi<P128, 2>(an, count, (hipStream_t)stream);
-    if (descs[0].channels == 64) return launch_pair_multi<P64, 3>(an, count, (hipStream_t)stream);
-    return launch_pair_multi<P32, 3>(an, count, (hipStream_t)stream);
+    return launch_pair_c(an.b, count, (hipStream_t)stream);
 }
 
 namespace {

@@ -41,6 +41,57 @@ __device__ __forceinline__ void f16x2_split4(f32x4 v, float scale, g2_u32x2& hi,
     lo = (g2_u32x2){__builtin_bit_cast(unsigned, la), __builtin_bit_cast(unsigned, lb)};
 }
 
+typedef __attribute__((address_space(3))) char g2_lds_c;
+typedef __attribute__((address_space(3))) g2_u32x4 g2_lds_u4;
+typedef __attribute__((address_space(3))) g2_u32x2 g2_lds_u2;
+
+// -------------------------------------------------------------------------------------------------
+// The pieces every f16x2 main loop on 32x32 tiles is made of (Gemm2Tile::mainloop, Gemm2Win::mainloop / _deep / _resident),
+// each written ONCE.  They are function-like macros on purpose: as inline functions taking acc / rb / rw by reference the same
+// statements reach the optimiser in another order, and the windowed kernels sit right at their register budgets — measured on
+// the device assembly (tools/isa_diff.py): W160 (168 VGPRs allowed) and W128D (128) began to spill, 64 and 12 bytes of scratch,
+// and W64P went from 164 to 196 VGPRs (240, and no unswitching of its tap loop on `a_slope != 1`, with only the slab step and
+// the weight pieces as functions).  Expanded in place they
+// compile to the instruction streams of the hand-copied loops they replace.  They use the enclosing loop's names: lds, tid,
+// acc, TM, TN, PITCH, B_P, B_PIECES, bload, rb_desc.
+// -------------------------------------------------------------------------------------------------
+// One K slab (32 k = two MFMA steps of 16) of a wave's TM x TN tiles: A / B point at the lane's first fragments (image base +
+// a_frag / b_frag), tile i sits 32 rows further, the lo plane 64 bytes behind the hi plane.
+#ifdef KN_WHATIF_NOMFMA         // timing aid (tools/win_whatif.sh): everything but the matrix pipe
+#define KN_F16X2_MMA3(C, FA, FB) C[0] += (float)FA[1][0] * (float)FB[0][0] + (float)FA[0][1] * (float)FB[1][1];
+#else
+#define KN_F16X2_MMA3(C, FA, FB)                                                                               \
+    C = __builtin_amdgcn_mfma_f32_32x32x16_f16(FA[1], FB[0], C, 0, 0, 0);   /* small terms first */            \
+    C = __builtin_amdgcn_mfma_f32_32x32x16_f16(FA[0], FB[1], C, 0, 0, 0);                                      \
+    C = __builtin_amdgcn_mfma_f32_32x32x16_f16(FA[0], FB[0], C, 0, 0, 0);
+#endif
+#define KN_F16X2_SLAB_MMA(A, B)                                                                                \
+    _Pragma("unroll") for (int ks = 0; ks < 2; ++ks) {                                                        \
+        f16x8 fa[TM][2], fb[TN][2];                                                                            \
+        _Pragma("unroll") for (int i = 0; i < TM; ++i)                                                        \
+            _Pragma("unroll") for (int p = 0; p < 2; ++p)                                                     \
+                fa[i][p] = __builtin_bit_cast(f16x8, *(const g2_lds_u4*)(A + i * 32 * PITCH + p * 64 + ks * 32)); \
+        _Pragma("unroll") for (int j = 0; j < TN; ++j)                                                        \
+            _Pragma("unroll") for (int p = 0; p < 2; ++p)                                                     \
+                fb[j][p] = __builtin_bit_cast(f16x8, *(const g2_lds_u4*)(B + j * 32 * PITCH + p * 64 + ks * 32)); \
+        _Pragma("unroll") for (int i = 0; i < TM; ++i)                                                        \
+            _Pragma("unroll") for (int j = 0; j < TN; ++j) {                                                  \
+                f32x16 c = acc[i][j];                                                                          \
+                KN_F16X2_MMA3(c, fa[i], fb[j])                                                                 \
+                acc[i][j] = c;                                                                                 \
+            }                                                                                                  \
+    }
+// Split weights ([n][K/32][2 planes][32] fp16) travel as 16-byte pieces, B_P per thread and slab: piece q = tid + 256 j is
+// piece q % 8 of row q / 8 (Split2BLoader).  Request slab SLAB into the registers RB ...
+#define KN_SPLIT_B_LOAD(RB, SLAB)                                                                              \
+    { const int sl_ = SLAB; bload.begin(sl_); _Pragma("unroll") for (int j = 0; j < B_P; ++j) RB[j] = bload(sl_, j, rb_desc); }
+// ... and write them to the B stage at byte BOFF of the LDS image
+#define KN_SPLIT_B_STAGE(RB, BOFF)                                                                             \
+    _Pragma("unroll") for (int j = 0; j < B_P; ++j) {                                                         \
+        const int q = tid + 256 * j;                                                                          \
+        if (B_PIECES % 256 == 0 || q < B_PIECES) *(g2_lds_u4*)(lds + BOFF + (q >> 3) * PITCH + (q & 7) * 16) = RB[j]; \
+    }
+
 // XCD-aware tile order of the 256x256-tile kernels.  Workgroup ids go round-robin over the 8 XCDs (each with its own L2), so one
 // tile dimension is dealt over the XCDs in groups of 8 (padded: ids whose tile falls into the padding exit at once) and the other
 // is walked in patches of CW = 4: an XCD's resident blocks then share operand panels through its L2.  Which dimension is padded
@@ -87,12 +138,45 @@ __device__ __forceinline__ bool quad_order_decode(int L, int gx, int gy, int& mt
     return at < ga;
 }
 
+// XCD-aware column-patch tile order of the 32x32-tile f16x2 kernels (conv_gemm2_kernel, the windowed kernels): ids congruent
+// mod 8 share an L2; a group is 8 row tiles x all column tiles, so the column tiles of one row tile run on one XCD, next to
+// each other in time, and the columns are walked in patches of CW tiles, so an XCD's ~96 resident blocks form a (12 x 8)-ish
+// patch that shares both A and B panels through its L2.  The row tiles are padded to whole groups of 8 (one per XCD); the
+// padding ids exit at once.
+// plain: a single column tile has no operand panel to share between column tiles, so padding the row tiles to groups of 8
+// buys nothing and the padding ids still queue for LDS before they can exit (6 row tiles: a quarter of all ids) — blockIdx.x
+// IS the row tile.  The host decides (patch_order_plain, handed to the kernel) and sizes grid.x with patch_order_ids.
+__host__ __device__ __forceinline__ bool patch_order_plain(long gx, long gy) { return gy == 1 && gx % 8 != 0; }
+__host__ __device__ __forceinline__ long patch_order_ids(long gx, long gy) {
+    return (patch_order_plain(gx, gy) ? gx : (gx + 7) / 8 * 8) * gy;
+}
+// blockIdx.x -> (m0, n0) of a BM x BN tile of an [m, n] output; false: a padding id.
+// (rem + z) & 7: which XCD gets which row tile of a group of 8 rotates with the batch / group index.  The padding rows are the
+// same in every slice of a batched launch: unrotated, the positional conv's 6 row tiles per (chunk, group) — 336 slices — left
+// XCDs 6 and 7 nothing but padding ids, a quarter of the chip idle for the whole launch (1.76 ms against 1.37 for the same work
+// as one long sequence); quad_order_decode rotates for the same reason.
+template <int BM, int BN>
+__device__ __forceinline__ bool patch_order_decode(int plain, int m, int n, int& m0, int& n0) {
+    const int gy = (n + BN - 1) / BN;
+    const int gx8 = (int)gridDim.x / gy;                      // row tiles padded to a multiple of 8
+    constexpr int CW = 8;
+    int L = blockIdx.x;
+    const int full = (gy / CW) * CW * gx8;                    // ids covered by full-width column patches
+    int c0, cw;
+    if (L < full) { c0 = (L / (CW * gx8)) * CW; cw = CW; L -= (c0 / CW) * CW * gx8; }
+    else { c0 = (gy / CW) * CW; cw = gy - c0; L -= full; }
+    const int grp = L / (8 * cw), rem = L - grp * 8 * cw;
+    m0 = plain ? (int)blockIdx.x * BM : (grp * 8 + ((rem + (int)blockIdx.z) & 7)) * BM;
+    n0 = plain ? 0 : (c0 + (rem >> 3)) * BN;
+    return m0 < m;                                            // padding of the last group
+}
+
 #ifdef KN_QUAD_PROF      // timing aid (tools/quad_prof.py): per block start / prologue done / main loop done / epilogue done, 10 ns ticks
 __device__ long long kn_quad_prof_buf[8192 * 4];
 #endif
 
 template <int BM_, int BN_, int WM_, int WN_, int TM_, int TN_>
-struct Gemm2Tile {
+struct Gemm2Tile : Acc32<WN_, TM_, TN_> {
     typedef f32x16 acc_t;
     static constexpr int NR = 16;               // accumulator elements per MFMA tile and lane
     static constexpr int BM = BM_, BN = BN_, WM = WM_, WN = WN_, TM = TM_, TN = TN_;
@@ -103,14 +187,11 @@ struct Gemm2Tile {
     static constexpr int B_P = (B_PIECES + 255) / 256;         // per thread
     static constexpr int LDS_BYTES = (BM + BN) * PITCH;
 
-    typedef __attribute__((address_space(3))) char lds_c;
-
-    __device__ __forceinline__ static void split_store(lds_c* dst, f32x4 v, float a_scale) {
+    __device__ __forceinline__ static void split_store(g2_lds_c* dst, f32x4 v, float a_scale) {
         g2_u32x2 hi, lo;
         f16x2_split4(v, a_scale, hi, lo);
-        typedef __attribute__((address_space(3))) g2_u32x2 lds_u2;
-        *(lds_u2*)(dst) = hi;
-        *(lds_u2*)(dst + 64) = lo;
+        *(g2_lds_u2*)(dst) = hi;
+        *(g2_lds_u2*)(dst + 64) = lo;
     }
 
     // aload: fp32 A loader (begin(kt), operator()(kt, j) -> f32x4 for row (tid>>3)+32j, k = (tid&7)*4, finish())
@@ -121,37 +202,25 @@ struct Gemm2Tile {
     template <bool A2 = false, class ALoad, class BLoad, class RA, class RB>
     __device__ __forceinline__ static void mainloop(float* lds_generic, int nk, ALoad& aload, BLoad& bload,
                                                     f32x16 (&acc)[TM][TN], RA ra_desc, RB rb_desc, float a_scale) {
-        lds_c* lds = (lds_c*)lds_generic;
-        typedef __attribute__((address_space(3))) g2_u32x4 lds_u4;
-        const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-        const int wm = wave / WN, wn = wave % WN;
+        g2_lds_c* lds = (g2_lds_c*)lds_generic;
+        const int tid = threadIdx.x;
         const int a_st = (tid >> 3) * PITCH + (tid & 7) * (A2 ? 16 : 8);   // staging address of piece j = 0
+        const int lane = tid & 63, wave = tid >> 6;
+        const int wm = wave / WN, wn = wave % WN;
         const int li = lane & 31, lh = lane >> 5;
         const int a_frag = (wm * TM * 32 + li) * PITCH + lh * 16;
         const int b_frag = BM * PITCH + (wn * TN * 32 + li) * PITCH + lh * 16;
 
         f32x4 ra[A_F4];
         g2_u32x4 rb[B_P];
-#ifdef KN_T_NOSTAGE_A
-#define KN_STAGE2_A() _Pragma("unroll") for (int j = 0; j < A_F4; ++j) asm volatile("" ::"v"(ra[j][0]), "v"(ra[j][1]), "v"(ra[j][2]), "v"(ra[j][3]));
-#else
-#define KN_STAGE2_A()                                                                                         \
-        _Pragma("unroll") for (int j = 0; j < A_F4; ++j) {                                                   \
-            if constexpr (A2) *(lds_u4*)(lds + a_st + 32 * j * PITCH) = __builtin_bit_cast(g2_u32x4, ra[j]); \
-            else split_store(lds + a_st + 32 * j * PITCH, aload.finish(ra[j]), a_scale);                     \
-        }
-#endif
-#ifdef KN_T_NOSTAGE_B
-#define KN_STAGE2_B() _Pragma("unroll") for (int j = 0; j < B_P; ++j) asm volatile("" ::"v"(rb[j][0]), "v"(rb[j][1]), "v"(rb[j][2]), "v"(rb[j][3]));
-#else
-#define KN_STAGE2_B()                                                                                         \
-        _Pragma("unroll") for (int j = 0; j < B_P; ++j) {                                                    \
-            const int q = tid + 256 * j;                                                                     \
-            if (B_PIECES % 256 == 0 || q < B_PIECES)                                                         \
-                *(lds_u4*)(lds + BM * PITCH + (q >> 3) * PITCH + (q & 7) * 16) = rb[j];                       \
-        }
-#endif
-#define KN_STAGE2() { KN_STAGE2_A() KN_STAGE2_B() }
+#define KN_STAGE2()                                                                                               \
+    {                                                                                                            \
+        _Pragma("unroll") for (int j = 0; j < A_F4; ++j) {                                                       \
+            if constexpr (A2) *(g2_lds_u4*)(lds + a_st + 32 * j * PITCH) = __builtin_bit_cast(g2_u32x4, ra[j]);   \
+            else split_store(lds + a_st + 32 * j * PITCH, aload.finish(ra[j]), a_scale);                         \
+        }                                                                                                        \
+        KN_SPLIT_B_STAGE(rb, BM * PITCH)                                                                         \
+    }
         aload.begin(0); bload.begin(0);
 #pragma unroll
         for (int j = 0; j < A_F4; ++j) ra[j] = aload(0, j, ra_desc);
@@ -164,60 +233,24 @@ struct Gemm2Tile {
             const bool more = (kt + 1 < nk);
             if (more) {
                 aload.begin(kt + 1); bload.begin(kt + 1);
-#ifndef KN_T_NOLOAD_A
 #pragma unroll
                 for (int j = 0; j < A_F4; ++j) ra[j] = aload(kt + 1, j, ra_desc);
-#endif
-#ifndef KN_T_NOLOAD_B
 #pragma unroll
                 for (int j = 0; j < B_P; ++j) rb[j] = bload(kt + 1, j, rb_desc);
-#endif
             }
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
-                f16x8 fa[TM][2], fb[TN][2];
-#pragma unroll
-                for (int i = 0; i < TM; ++i)
-#pragma unroll
-                    for (int p = 0; p < 2; ++p)
-                        fa[i][p] = __builtin_bit_cast(f16x8, *(const lds_u4*)(lds + a_frag + i * 32 * PITCH + p * 64 + ks * 32));
-#pragma unroll
-                for (int i = 0; i < TN; ++i)
-#pragma unroll
-                    for (int p = 0; p < 2; ++p)
-                        fb[i][p] = __builtin_bit_cast(f16x8, *(const lds_u4*)(lds + b_frag + i * 32 * PITCH + p * 64 + ks * 32));
-#pragma unroll
-                for (int i = 0; i < TM; ++i)
-#pragma unroll
-                    for (int j = 0; j < TN; ++j) {
-                        f32x16 c = acc[i][j];
-                        c = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[i][1], fb[j][0], c, 0, 0, 0);   // small terms first
-                        c = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[i][0], fb[j][1], c, 0, 0, 0);
-                        c = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[i][0], fb[j][0], c, 0, 0, 0);
-                        acc[i][j] = c;
-                    }
-            }
+            KN_F16X2_SLAB_MMA(lds + a_frag, lds + b_frag)
             __syncthreads();                 // every wave is done reading this slab
             if (more) KN_STAGE2();
             __syncthreads();
         }
-    }
-
 #undef KN_STAGE2
-#undef KN_STAGE2_A
-#undef KN_STAGE2_B
-    __device__ __forceinline__ static int acc_row(int wave, int lane, int i, int r) {
-        return (wave / WN) * TM * 32 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-    }
-    __device__ __forceinline__ static int acc_col(int wave, int lane, int j) {
-        return (wave % WN) * TN * 32 + j * 32 + (lane & 31);
     }
 };
 
 // -------------------------------------------------------------------------------------------------
 // Gemm2QuadS: the same 256x256 block / 128x128 wave tile on v_mfma_f32_16x16x32_f16 (the hardware guide measures 1.12-1.15x
-// the FLOP/s of 32x32x16 at equal cycles on random data: the gain is clock, i.e. energy per product — exactly what bounds
-// Gemm2QuadR).  A k slab is 32 wide (one MFMA deep): LDS row = 128 B (hi 64 | lo 64) in 16-byte chunks, chunk' = chunk ^ (row & 7)
+// the FLOP/s of 32x32x16 at equal cycles on random data: the gain is clock, i.e. energy per product — exactly what bounded
+// the 32x32x16 form this kernel replaced).  A k slab is 32 wide (one MFMA deep): LDS row = 128 B (hi 64 | lo 64) in 16-byte chunks, chunk' = chunk ^ (row & 7)
 // (conflict-free for the 16-row x 4-chunk fragment reads and for the 8-row x 8-chunk staging writes); two 64 KB stages.
 // The 8 x 8 tiles of a wave are walked in four 4 x 4 quadrants per slab; fragments live in two A sets and two B sets (32 VGPRs
 // each).  Slab order alternates (I0,J0)(I0,J1)(I1,J1)(I1,J0) / (I0,J1)(I0,J0)(I1,J0)(I1,J1): the A set and the B set a slab
@@ -317,7 +350,7 @@ struct Gemm2QuadS {
         for (int j = 0; j < 4; ++j) KN_S_READ_B(0, 0, 0, j)
 
         // FB: the B set (= column half) this slab starts with.  HN: slab S + 1 exists.  ML: slab S + 2 exists.  All literals
-        // (see Gemm2QuadR: a run-time test inside the slab costs a vmcnt(0) before every ds_write).
+        // (a run-time test inside the slab costs a vmcnt(0) before every ds_write).
 #define KN_S_SLAB(FB, HN, ML)                                                                                             \
     {                                                                                                                     \
         constexpr int cstg = (FB) * STAGE, nstg = (1 - (FB)) * STAGE;       /* even slabs start with column half 0 */       \
@@ -398,7 +431,7 @@ struct Gemm2QuadS {
 // a different order than in Gemm2Tile (slab-major instead of tap-major): equal up to fp32 rounding of the accumulation.
 // -------------------------------------------------------------------------------------------------
 template <int BM_, int BN_, int WM_, int WN_, int TM_, int TN_, int HALO_, int DEEP_ = 0>
-struct Gemm2Win {
+struct Gemm2Win : Acc32<WN_, TM_, TN_> {
     static constexpr int DEEP = DEEP_;          // 1: weight slabs requested two steps ahead (mainloop_deep)
     typedef f32x16 acc_t;
     static constexpr int NR = 16;
@@ -412,21 +445,33 @@ struct Gemm2Win {
     static constexpr int BOFF = WR * PITCH;
     static constexpr int LDS_BYTES = (WR + BN) * PITCH;
 
-    typedef __attribute__((address_space(3))) char lds_c;
-    typedef __attribute__((address_space(3))) g2_u32x4 lds_u4;
-    typedef __attribute__((address_space(3))) g2_u32x2 lds_u2;
+    // The window of channel slab CS into the registers rw, and from there into LDS: prologue activation (leaky ReLU unless
+    // a_slope is 1), f16x2 split.  w_off0: this thread's byte offset of (window row tid>>3, channel (tid&7)*4) in the A buffer
+    // resource (may be "negative": conv padding rows fall outside the resource and read as zeros); row_bytes = ldx * 4;
+    // w_st = (tid >> 3) * PITCH + (tid & 7) * 8.
+#define KN_WIN_LOAD(CS)                                                                                        \
+    _Pragma("unroll") for (int j = 0; j < W_F4; ++j)                                                          \
+        rw[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(ra_desc, w_off0 + j * 32 * row_bytes + (CS) * 128, 0, 0));
+#define KN_WIN_STAGE()                                                                                         \
+    _Pragma("unroll") for (int j = 0; j < W_F4; ++j) {                                                        \
+        f32x4 v = rw[j];                                                                                      \
+        if (a_slope != 1.0f) { _Pragma("unroll") for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.f ? v[e] : v[e] * a_slope; } \
+        g2_u32x2 hi, lo;                                                                                      \
+        f16x2_split4(v, a_scale, hi, lo);                                                                     \
+        *(g2_lds_u2*)(lds + w_st + 32 * j * PITCH) = hi;                                                      \
+        *(g2_lds_u2*)(lds + w_st + 32 * j * PITCH + 64) = lo;                                                 \
+    }
 
-    // w_off0: this thread's byte offset of (window row tid>>3, channel (tid&7)*4) in the A buffer resource (may be
-    // "negative": conv padding rows fall outside the resource and read as zeros); row_bytes = ldx * 4.
     // bload: Split2BLoader; slab index of (tap, cs) in the tap-major weight image = tap * ncs + cs.
     template <class BLoad, class RA, class RB>
     __device__ __forceinline__ static void mainloop(float* lds_generic, int ncs, int taps, int dil, int w_off0, int row_bytes,
                                                     BLoad& bload, f32x16 (&acc)[TM][TN], RA ra_desc, RB rb_desc,
                                                     float a_scale, float a_slope) {
-        lds_c* lds = (lds_c*)lds_generic;
-        const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-        const int wm = wave / WN, wn = wave % WN;
+        g2_lds_c* lds = (g2_lds_c*)lds_generic;
+        const int tid = threadIdx.x;
         const int w_st = (tid >> 3) * PITCH + (tid & 7) * 8;
+        const int lane = tid & 63, wave = tid >> 6;
+        const int wm = wave / WN, wn = wave % WN;
         const int li = lane & 31, lh = lane >> 5;
         const int a_frag = (wm * TM * 32 + li) * PITCH + lh * 16;
         const int b_frag = BOFF + (wn * TN * 32 + li) * PITCH + lh * 16;
@@ -434,95 +479,37 @@ struct Gemm2Win {
 
         f32x4 rw[W_F4];
         g2_u32x4 rb[B_P];
-#define KN_LOAD_W(CS)                                                                                          \
-    _Pragma("unroll") for (int j = 0; j < W_F4; ++j)                                                          \
-        rw[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(ra_desc, w_off0 + j * 32 * row_bytes + (CS) * 128, 0, 0));
-#define KN_STAGE_W()                                                                                           \
-    _Pragma("unroll") for (int j = 0; j < W_F4; ++j) {                                                        \
-        f32x4 v = rw[j];                                                                                      \
-        if (a_slope != 1.0f) { _Pragma("unroll") for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.f ? v[e] : v[e] * a_slope; } \
-        g2_u32x2 hi, lo;                                                                                      \
-        f16x2_split4(v, a_scale, hi, lo);                                                                     \
-        *(lds_u2*)(lds + w_st + 32 * j * PITCH) = hi;                                                         \
-        *(lds_u2*)(lds + w_st + 32 * j * PITCH + 64) = lo;                                                    \
-    }
-#define KN_LOAD_B(SLAB)                                                                                        \
-    { bload.begin(SLAB); _Pragma("unroll") for (int j = 0; j < B_P; ++j) rb[j] = bload(SLAB, j, rb_desc); }
-#define KN_STAGE_B()                                                                                           \
-    _Pragma("unroll") for (int j = 0; j < B_P; ++j) {                                                         \
-        const int q = tid + 256 * j;                                                                          \
-        if (B_PIECES % 256 == 0 || q < B_PIECES) *(lds_u4*)(lds + BOFF + (q >> 3) * PITCH + (q & 7) * 16) = rb[j]; \
-    }
-#ifdef KN_WIN_ROT
-        const int rot = (int)(blockIdx.x % (unsigned)ncs);
-#define KN_CS(I) (((I) + rot) % ncs)
-#else
-#define KN_CS(I) (I)
-#endif
-        KN_LOAD_W(KN_CS(0))
-        KN_LOAD_B(KN_CS(0))
-        KN_STAGE_W()
-        KN_STAGE_B()
+        KN_WIN_LOAD(0)
+        KN_SPLIT_B_LOAD(rb, 0)
+        KN_WIN_STAGE()
+        KN_SPLIT_B_STAGE(rb, BOFF)
         __syncthreads();
-        for (int ci = 0; ci < ncs; ++ci) {
-            const bool more_cs = ci + 1 < ncs;
-            const int cs = KN_CS(ci);
-            if (more_cs) { KN_LOAD_W(KN_CS(ci + 1)) }
+        for (int cs = 0; cs < ncs; ++cs) {
+            const bool more_cs = cs + 1 < ncs;
+            if (more_cs) { KN_WIN_LOAD(cs + 1) }
             int tap_off = 0;
             for (int tap = 0; tap < taps; ++tap, tap_off += tap_step) {
                 const bool last_tap = tap + 1 == taps;
                 const bool more = !last_tap || more_cs;
 #ifndef KN_WIN_NOBLOAD          // timing aid: the first weight slab serves every step
                 if (more) {
-                    const int slab = last_tap ? KN_CS(ci + 1) : ((tap + 1) * ncs + cs);
-                    KN_LOAD_B(slab)
+                    const int slab = last_tap ? (cs + 1) : ((tap + 1) * ncs + cs);
+                    KN_SPLIT_B_LOAD(rb, slab)
                 }
 #endif
-#pragma unroll
-                for (int ks = 0; ks < 2; ++ks) {
-                    f16x8 fa[TM][2], fb[TN][2];
-#pragma unroll
-                    for (int i = 0; i < TM; ++i)
-#pragma unroll
-                        for (int p = 0; p < 2; ++p)
-                            fa[i][p] = __builtin_bit_cast(f16x8, *(const lds_u4*)(lds + a_frag + tap_off + i * 32 * PITCH + p * 64 + ks * 32));
-#pragma unroll
-                    for (int j = 0; j < TN; ++j)
-#pragma unroll
-                        for (int p = 0; p < 2; ++p)
-                            fb[j][p] = __builtin_bit_cast(f16x8, *(const lds_u4*)(lds + b_frag + j * 32 * PITCH + p * 64 + ks * 32));
-#pragma unroll
-                    for (int i = 0; i < TM; ++i)
-#pragma unroll
-                        for (int j = 0; j < TN; ++j) {
-                            f32x16 c = acc[i][j];
-#ifdef KN_WHATIF_NOMFMA
-                            c[0] += (float)fa[i][1][0] * (float)fb[j][0][0] + (float)fa[i][0][1] * (float)fb[j][1][1];
-#else
-                            c = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[i][1], fb[j][0], c, 0, 0, 0);   // small terms first
-                            c = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[i][0], fb[j][1], c, 0, 0, 0);
-                            c = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[i][0], fb[j][0], c, 0, 0, 0);
-#endif
-                            acc[i][j] = c;
-                        }
-                }
+                KN_F16X2_SLAB_MMA(lds + a_frag + tap_off, lds + b_frag)
 #ifndef KN_WIN_NOBAR            // timing aid: no barriers inside the loop
                 __syncthreads();                 // every wave is done with this weight slab (and, on the last tap, the window)
 #endif
 #ifndef KN_WIN_NOBLOAD
-                if (more) { KN_STAGE_B() }
+                if (more) { KN_SPLIT_B_STAGE(rb, BOFF) }
 #endif
-                if (last_tap && more_cs) { KN_STAGE_W() }
+                if (last_tap && more_cs) { KN_WIN_STAGE() }
 #ifndef KN_WIN_NOBAR
                 __syncthreads();
 #endif
             }
         }
-#undef KN_CS
-#undef KN_LOAD_W
-#undef KN_STAGE_W
-#undef KN_LOAD_B
-#undef KN_STAGE_B
     }
 
     // The same loop with the weight slabs requested TWO steps ahead (DEEP = 1: the 64-row tiles of under-filled launches).  In
@@ -536,10 +523,11 @@ struct Gemm2Win {
     __device__ __forceinline__ static void mainloop_deep(float* lds_generic, int ncs, int taps, int dil, int w_off0, int row_bytes,
                                                          BLoad& bload, f32x16 (&acc)[TM][TN], RA ra_desc, RB rb_desc,
                                                          float a_scale, float a_slope) {
-        lds_c* lds = (lds_c*)lds_generic;
-        const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-        const int wm = wave / WN, wn = wave % WN;
+        g2_lds_c* lds = (g2_lds_c*)lds_generic;
+        const int tid = threadIdx.x;
         const int w_st = (tid >> 3) * PITCH + (tid & 7) * 8;
+        const int lane = tid & 63, wave = tid >> 6;
+        const int wm = wave / WN, wn = wave % WN;
         const int li = lane & 31, lh = lane >> 5;
         const int a_frag = (wm * TM * 32 + li) * PITCH + lh * 16;
         const int b_frag = BOFF + (wn * TN * 32 + li) * PITCH + lh * 16;
@@ -549,60 +537,26 @@ struct Gemm2Win {
         g2_u32x4 rb[2][B_P];
         // slab of flat step s in the tap-major weight image: tap * ncs + cs, with s = cs * taps + tap
         auto slab_of = [&](int s) { const int c = s / taps; return (s - c * taps) * ncs + c; };
-#define KN_D_LOAD_W(CS)                                                                                        \
-    _Pragma("unroll") for (int j = 0; j < W_F4; ++j)                                                          \
-        rw[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(ra_desc, w_off0 + j * 32 * row_bytes + (CS) * 128, 0, 0));
-#define KN_D_STAGE_W()                                                                                         \
-    _Pragma("unroll") for (int j = 0; j < W_F4; ++j) {                                                        \
-        f32x4 v = rw[j];                                                                                      \
-        if (a_slope != 1.0f) { _Pragma("unroll") for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.f ? v[e] : v[e] * a_slope; } \
-        g2_u32x2 hi, lo;                                                                                      \
-        f16x2_split4(v, a_scale, hi, lo);                                                                     \
-        *(lds_u2*)(lds + w_st + 32 * j * PITCH) = hi;                                                         \
-        *(lds_u2*)(lds + w_st + 32 * j * PITCH + 64) = lo;                                                    \
-    }
-#define KN_D_LOAD_B(SET, S)                                                                                    \
-    { const int sl_ = slab_of(S); bload.begin(sl_); _Pragma("unroll") for (int j = 0; j < B_P; ++j) rb[SET][j] = bload(sl_, j, rb_desc); }
-#define KN_D_STAGE_B(SET)                                                                                      \
-    _Pragma("unroll") for (int j = 0; j < B_P; ++j) {                                                         \
-        const int q = tid + 256 * j;                                                                          \
-        if (B_PIECES % 256 == 0 || q < B_PIECES) *(lds_u4*)(lds + BOFF + (q >> 3) * PITCH + (q & 7) * 16) = rb[SET][j]; \
-    }
-        KN_D_LOAD_W(0)
-        KN_D_LOAD_B(0, 0)
-        KN_D_STAGE_W()
-        KN_D_STAGE_B(0)
-        if (nsteps > 1) KN_D_LOAD_B(1, 1)              // step s lives in set s & 1
-        if (nsteps > 2) KN_D_LOAD_B(0, 2)
+        KN_WIN_LOAD(0)
+        KN_SPLIT_B_LOAD(rb[0], slab_of(0))
+        KN_WIN_STAGE()
+        KN_SPLIT_B_STAGE(rb[0], BOFF)
+        if (nsteps > 1) KN_SPLIT_B_LOAD(rb[1], slab_of(1))              // step s lives in set s & 1
+        if (nsteps > 2) KN_SPLIT_B_LOAD(rb[0], slab_of(2))
         __syncthreads();
         int cs = 0, tap = 0, tap_off = 0;
         // one step; SET = parity of step s + 1, whose slab is staged at the end of step s and whose set is reloaded with step s + 3
+        // (a literal: the register sets are never indexed at run time)
 #define KN_D_STEP(SET)                                                                                         \
     {                                                                                                          \
         const bool last_tap = tap + 1 == taps;                                                                 \
         const bool more_cs = cs + 1 < ncs;                                                                     \
-        if (tap == 0 && more_cs) { KN_D_LOAD_W(cs + 1) }                                                       \
-        _Pragma("unroll") for (int ks = 0; ks < 2; ++ks) {                                                    \
-            f16x8 fa[TM][2], fb[TN][2];                                                                        \
-            _Pragma("unroll") for (int i = 0; i < TM; ++i)                                                    \
-                _Pragma("unroll") for (int p = 0; p < 2; ++p)                                                 \
-                    fa[i][p] = __builtin_bit_cast(f16x8, *(const lds_u4*)(lds + a_frag + tap_off + i * 32 * PITCH + p * 64 + ks * 32)); \
-            _Pragma("unroll") for (int j = 0; j < TN; ++j)                                                    \
-                _Pragma("unroll") for (int p = 0; p < 2; ++p)                                                 \
-                    fb[j][p] = __builtin_bit_cast(f16x8, *(const lds_u4*)(lds + b_frag + j * 32 * PITCH + p * 64 + ks * 32)); \
-            _Pragma("unroll") for (int i = 0; i < TM; ++i)                                                    \
-                _Pragma("unroll") for (int j = 0; j < TN; ++j) {                                              \
-                    f32x16 c = acc[i][j];                                                                      \
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[i][1], fb[j][0], c, 0, 0, 0);               \
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[i][0], fb[j][1], c, 0, 0, 0);               \
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[i][0], fb[j][0], c, 0, 0, 0);               \
-                    acc[i][j] = c;                                                                             \
-                }                                                                                              \
-        }                                                                                                      \
+        if (tap == 0 && more_cs) { KN_WIN_LOAD(cs + 1) }                                                       \
+        KN_F16X2_SLAB_MMA(lds + a_frag + tap_off, lds + b_frag)                                                \
         __syncthreads();                                                                                       \
-        if (s + 1 < nsteps) { KN_D_STAGE_B(SET) }                                                              \
-        if (s + 3 < nsteps) { KN_D_LOAD_B(SET, s + 3) }                                                        \
-        if (last_tap && more_cs) { KN_D_STAGE_W() }                                                            \
+        if (s + 1 < nsteps) { KN_SPLIT_B_STAGE(rb[SET], BOFF) }                                                \
+        if (s + 3 < nsteps) { KN_SPLIT_B_LOAD(rb[SET], slab_of(s + 3)) }                                       \
+        if (last_tap && more_cs) { KN_WIN_STAGE() }                                                            \
         __syncthreads();                                                                                       \
         if (last_tap) { tap = 0; tap_off = 0; ++cs; } else { ++tap; tap_off += tap_step; }                     \
     }
@@ -615,11 +569,9 @@ struct Gemm2Win {
         }
         if (s < nsteps) { KN_D_STEP(1) }
 #undef KN_D_STEP
-#undef KN_D_LOAD_W
-#undef KN_D_STAGE_W
-#undef KN_D_LOAD_B
-#undef KN_D_STAGE_B
     }
+#undef KN_WIN_LOAD
+#undef KN_WIN_STAGE
 
     // Phase 2 of the fused ResBlock pair (conv_pair_kernel): the same tap loop with the A operand ALREADY resident in LDS for
     // every channel slab — the split image of the pair's inner activation, [slab][IR rows][PITCH] from byte 0, written by the
@@ -628,22 +580,16 @@ struct Gemm2Win {
     template <class BLoad, class RB>
     __device__ __forceinline__ static void mainloop_resident(float* lds_generic, int ncs, int taps, int img_slab_bytes, int boff,
                                                              BLoad& bload, f32x16 (&acc)[TM][TN], RB rb_desc) {
-        lds_c* lds = (lds_c*)lds_generic;
-        const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+        g2_lds_c* lds = (g2_lds_c*)lds_generic;
+        const int tid = threadIdx.x;
+        const int lane = tid & 63, wave = tid >> 6;
         const int wm = wave / WN, wn = wave % WN;
         const int li = lane & 31, lh = lane >> 5;
         const int a_frag = (wm * TM * 32 + li) * PITCH + lh * 16;
         const int b_frag = boff + (wn * TN * 32 + li) * PITCH + lh * 16;
         g2_u32x4 rb[B_P];
-#define KN_LOAD_B(SLAB)                                                                                        \
-    { bload.begin(SLAB); _Pragma("unroll") for (int j = 0; j < B_P; ++j) rb[j] = bload(SLAB, j, rb_desc); }
-#define KN_STAGE_B()                                                                                           \
-    _Pragma("unroll") for (int j = 0; j < B_P; ++j) {                                                         \
-        const int q = tid + 256 * j;                                                                          \
-        if (B_PIECES % 256 == 0 || q < B_PIECES) *(lds_u4*)(lds + boff + (q >> 3) * PITCH + (q & 7) * 16) = rb[j]; \
-    }
-        KN_LOAD_B(0)
-        KN_STAGE_B()
+        KN_SPLIT_B_LOAD(rb, 0)
+        KN_SPLIT_B_STAGE(rb, boff)
         __syncthreads();
         for (int cs = 0; cs < ncs; ++cs) {
             const bool more_cs = cs + 1 < ncs;
@@ -653,45 +599,13 @@ struct Gemm2Win {
                 const bool more = !last_tap || more_cs;
                 if (more) {
                     const int slab = last_tap ? (cs + 1) : ((tap + 1) * ncs + cs);
-                    KN_LOAD_B(slab)
+                    KN_SPLIT_B_LOAD(rb, slab)
                 }
-#pragma unroll
-                for (int ks = 0; ks < 2; ++ks) {
-                    f16x8 fa[TM][2], fb[TN][2];
-#pragma unroll
-                    for (int i = 0; i < TM; ++i)
-#pragma unroll
-                        for (int p = 0; p < 2; ++p)
-                            fa[i][p] = __builtin_bit_cast(f16x8, *(const lds_u4*)(lds + a_cs + tap * PITCH + i * 32 * PITCH + p * 64 + ks * 32));
-#pragma unroll
-                    for (int j = 0; j < TN; ++j)
-#pragma unroll
-                        for (int p = 0; p < 2; ++p)
-                            fb[j][p] = __builtin_bit_cast(f16x8, *(const lds_u4*)(lds + b_frag + j * 32 * PITCH + p * 64 + ks * 32));
-#pragma unroll
-                    for (int i = 0; i < TM; ++i)
-#pragma unroll
-                        for (int j = 0; j < TN; ++j) {
-                            f32x16 c = acc[i][j];
-                            c = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[i][1], fb[j][0], c, 0, 0, 0);   // small terms first
-                            c = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[i][0], fb[j][1], c, 0, 0, 0);
-                            c = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[i][0], fb[j][0], c, 0, 0, 0);
-                            acc[i][j] = c;
-                        }
-                }
+                KN_F16X2_SLAB_MMA(lds + a_cs + tap * PITCH, lds + b_frag)
                 __syncthreads();                 // every wave is done with this weight slab
-                if (more) { KN_STAGE_B() }
+                if (more) { KN_SPLIT_B_STAGE(rb, boff) }
                 __syncthreads();
             }
         }
-#undef KN_LOAD_B
-#undef KN_STAGE_B
-    }
-
-    __device__ __forceinline__ static int acc_row(int wave, int lane, int i, int r) {
-        return (wave / WN) * TM * 32 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-    }
-    __device__ __forceinline__ static int acc_col(int wave, int lane, int j) {
-        return (wave % WN) * TN * 32 + j * 32 + (lane & 31);
     }
 };

@@ -21,7 +21,7 @@ typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
 
 template <int BM_, int BN_, int WM_, int WN_, int TM_, int TN_>
-struct Gemm3Tile {
+struct Gemm3Tile : Acc32<WN_, TM_, TN_> {
     typedef f32x16 acc_t;
     static constexpr int NR = 16;
     static constexpr int BM = BM_, BN = BN_, WM = WM_, WN = WN_, TM = TM_, TN = TN_;
@@ -130,12 +130,5 @@ struct Gemm3Tile {
             __syncthreads();
         }
     }
-
 #undef KN_STAGE3
-    __device__ __forceinline__ static int acc_row(int wave, int lane, int i, int r) {
-        return (wave / WN) * TM * 32 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-    }
-    __device__ __forceinline__ static int acc_col(int wave, int lane, int j) {
-        return (wave % WN) * TN * 32 + j * 32 + (lane & 31);
-    }
 };

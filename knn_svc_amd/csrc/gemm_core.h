@@ -18,7 +18,7 @@
 #include "common.h"
 
 template <int BM_, int BN_, int WM_, int WN_, int TM_, int TN_, int NT_ = 256>
-struct GemmTile {
+struct GemmTile : Acc32<WN_, TM_, TN_> {
     typedef f32x16 acc_t;
     static constexpr int NR = 16;
     static constexpr int BM = BM_, BN = BN_, WM = WM_, WN = WN_, TM = TM_, TN = TN_;
@@ -31,11 +31,9 @@ struct GemmTile {
     static constexpr int LDS_FLOATS = 2 * (BM + BN) * LDK;
     static constexpr int LDS_BYTES = LDS_FLOATS * 4;
 
-    // aload.begin(kt) once per slab (uniform bookkeeping), then
-    // aload(kt, j) -> f32x4 for row (tid>>3) + 32*j, k = kt*32 + (tid&7)*4 ; same for bload.
     // LDS pointers are kept in address space 3 explicitly: through generic pointers hipcc emits
     // flat_load/flat_store for the staging buffers and then waits vmcnt(0) in front of every MFMA
-    // group, which also drains the NEXT slab's global prefetch (measured: 82 -> see DESIGN.md).
+    // group, which also drains the NEXT slab's global prefetch.
     typedef __attribute__((address_space(3))) float lds_f;
     typedef __attribute__((address_space(3))) f32x4 lds_f4;
 
@@ -105,13 +103,5 @@ struct GemmTile {
             }
             __syncthreads();
         }
-    }
-
-    // accumulator element (tile i,j; register r) of this lane -> (row, col) inside the block tile
-    __device__ __forceinline__ static int acc_row(int wave, int lane, int i, int r) {
-        return (wave / WN) * TM * 32 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-    }
-    __device__ __forceinline__ static int acc_col(int wave, int lane, int j) {
-        return (wave % WN) * TN * 32 + j * 32 + (lane & 31);
     }
 };

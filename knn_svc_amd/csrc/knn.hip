@@ -159,12 +159,7 @@ __global__ __launch_bounds__(512) void knn_tile_kernel(
     bool saw_nan = false;
     for (long p0 = p_begin; p0 < p_end; p0 += 128) {
         f32x16 acc[G::TM][G::TN];
-#pragma unroll
-        for (int i = 0; i < G::TM; ++i)
-#pragma unroll
-            for (int j = 0; j < G::TN; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+        KN_ZERO_ACC(acc, G::TM, G::TN, 16)
         RowLoader al{q, nq, dim, q0};
         RowLoader bl{pool, p_end, dim, p0};
         G::mainloop(lds, nk, al, bl, acc, 0, 0);            // ends with __syncthreads(): staging LDS is free
@@ -634,12 +629,7 @@ __global__ __launch_bounds__(256, 1) void knn_screen_kernel(
     KN_KP_T(0)
 
     typename QG::acc_t acc[QG::TM][QG::TN];
-#pragma unroll
-    for (int i = 0; i < QG::TM; ++i)
-#pragma unroll
-        for (int j = 0; j < QG::TN; ++j)
-#pragma unroll
-            for (int r = 0; r < QG::NR; ++r) acc[i][j][r] = 0.f;
+    KN_ZERO_ACC(acc, QG::TM, QG::TN, QG::NR)
     const int M = (int)nq, row_bytes = dim * 4;
     auto row_off = [&](int m) -> int { return m < M ? m * row_bytes : QG::OOB_OFF; };
     auto step = [&](int kt) -> int { return kt * 128; };
@@ -1128,13 +1118,7 @@ extern "C" int knnsvc_knn_topk(const float* q, const float* q_norm, const float*
     const size_t need = ((size_t)S + 1) * nq * KW * 8;
     if (workspace_bytes < need || !workspace)
         return knnsvc_fail(KNNSVC_EWORKSPACE, "knn_topk: workspace %zu < %zu bytes", workspace_bytes, need);
-    static bool attr = false;
-    if (!attr) {
-        if (hipFuncSetAttribute((const void*)knn_tile_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                KNN_LDS_BYTES) != hipSuccess)
-            return knnsvc_fail(KNNSVC_EHIP, "knn_topk: hipFuncSetAttribute failed");
-        attr = true;
-    }
+    if (const int rc = kn_lds_optin<knn_tile_kernel>(KNN_LDS_BYTES, "knn_topk")) return rc;
     const long ptiles = cdiv64(np, 128);
     const long rows_per_split = cdiv64(ptiles, S) * 128;
     hipStream_t st = (hipStream_t)stream;
@@ -1214,16 +1198,13 @@ extern "C" int knnsvc_knn_screen(const void* q_f16x2, const float* q_absmax, con
     static_assert(QG::LDS_BYTES >= (256 * 10 + 4) * 4 + SCR_LIST * 12 + SCR_QD * 256 * 8, "epilogue state fits the operand stages");
     static_assert(SCR_QD > QG::TM * QG::NR, "a lane queue holds more than one column's elements");
     static_assert(SCR_QD * 256 * 8 >= (520 + 512) * 4, "the cold pass's per-half bounds fit the (empty) queue area");
-    static bool attr = false;
+    if (const int rc = kn_lds_optin<knn_screen_kernel<false, false>>(QG::LDS_BYTES, "knn_screen")) return rc;
+    if (const int rc = kn_lds_optin<knn_screen_kernel<true, false>>(QG::LDS_BYTES, "knn_screen")) return rc;
+    if (const int rc = kn_lds_optin<knn_screen_kernel<true, true>>(QG::LDS_BYTES, "knn_screen")) return rc;
     static int cus = 0;
-    if (!attr) {
-        if (hipFuncSetAttribute((const void*)knn_screen_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, QG::LDS_BYTES) != hipSuccess ||
-            hipFuncSetAttribute((const void*)knn_screen_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, QG::LDS_BYTES) != hipSuccess ||
-            hipFuncSetAttribute((const void*)knn_screen_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, QG::LDS_BYTES) != hipSuccess)
-            return knnsvc_fail(KNNSVC_EHIP, "knn_screen: hipFuncSetAttribute failed");
+    if (!cus) {
         int dev = 0;
         if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-        attr = true;
     }
     const long ntiles = quad_order_ids(cdiv64(nq, 256), cdiv64(np, 256));
     KN_REQUIRE(ntiles < (1L << 31), "knn_screen: too many tiles (chunk the call)");

@@ -614,13 +614,9 @@ extern "C" int knnsvc_concat_reselect(const int64_t* idx_in, const float* q, con
         // before the cause was found).
         size_t pl = (size_t)26 * dim * 4;
         { const char* e = getenv("KNNSVC_CONCAT_OWN_CU"); if (e && e[0] == '1' && pl < (size_t)158 * 1024) pl = (size_t)158 * 1024; }
-        static size_t pattr[2] = {0, 0};
-        if (pl > pattr[use_f0 ? 1 : 0]) {
-            const void* fn = use_f0 ? (const void*)concat_reselect_pipe_kernel<true> : (const void*)concat_reselect_pipe_kernel<false>;
-            if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl) != hipSuccess)
-                return knnsvc_fail(KNNSVC_EHIP, "concat_reselect: hipFuncSetAttribute failed");
-            pattr[use_f0 ? 1 : 0] = pl;
-        }
+        if (const int rc = use_f0 ? kn_lds_optin<concat_reselect_pipe_kernel<true>>((int)pl, "concat_reselect")
+                                  : kn_lds_optin<concat_reselect_pipe_kernel<false>>((int)pl, "concat_reselect"))
+            return rc;
         if (use_f0)
             hipLaunchKernelGGL(concat_reselect_pipe_kernel<true>, dim3(1), dim3(LT), pl, (hipStream_t)stream, (const long*)idx_in, q, q_norm,
                                (long)nq, pool, p_norm, (long)np, dim, shifted_f0, pool_f0, concat_weight, (long*)idx_out);
@@ -631,13 +627,7 @@ extern "C" int knnsvc_concat_reselect(const int64_t* idx_in, const float* q, con
     }
     const size_t lds = (size_t)(2 * NC + 2) * dim * 4;
     KN_REQUIRE(lds <= 150 * 1024, "concat_reselect: feature dim too large for LDS");
-    static size_t attr = 0;
-    if (lds > attr) {
-        if (hipFuncSetAttribute((const void*)concat_reselect_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)lds) != hipSuccess)
-            return knnsvc_fail(KNNSVC_EHIP, "concat_reselect: hipFuncSetAttribute failed");
-        attr = lds;
-    }
+    if (const int rc = kn_lds_optin<concat_reselect_kernel>((int)lds, "concat_reselect")) return rc;
     hipLaunchKernelGGL(concat_reselect_kernel, dim3(1), dim3(256), lds, (hipStream_t)stream, (const long*)idx_in, q,
                        q_norm, (long)nq, pool, p_norm, (long)np, dim, shifted_f0, pool_f0, use_f0, concat_weight,
                        (long*)idx_out);

@@ -372,43 +372,26 @@ extern "C" int knnsvc_smooth_weights(const int64_t* idx, int64_t nq, const float
     float* xch = state + (size_t)6 * 4 * nq;            // [2][nq][4] when LDS is too small
     const size_t gl = (size_t)8 * dim * 4;
     KN_REQUIRE(gl <= 150 * 1024, "smooth_weights: feature dim too large for LDS");
-    static size_t gattr = 0, aattr = 0;
-    if (gl > gattr) {
-        if (hipFuncSetAttribute((const void*)gram_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gl) != hipSuccess)
-            return knnsvc_fail(KNNSVC_EHIP, "smooth_weights: hipFuncSetAttribute failed");
-        gattr = gl;
-    }
+    if (const int rc = kn_lds_optin<gram_kernel>((int)gl, "smooth_weights")) return rc;
     hipLaunchKernelGGL(gram_kernel, dim3((unsigned)(nq - 1)), dim3(256), gl, st, (const long*)idx, (long)nq, pool, (long)np,
                        dim, ld, row_scale, gram);
     int rc = knnsvc_check_launch("gram");
     if (rc) return rc;
     if (nq <= 1536) {            // register-resident loop
         const size_t rl = (size_t)nq * 2 * KW * 4;
-        static size_t rattr = 0;
+        if ((rc = kn_lds_optin<adam_reg_kernel<1>>(65536, "smooth_weights")) || (rc = kn_lds_optin<adam_reg_kernel<2>>(65536, "smooth_weights")) ||
+            (rc = kn_lds_optin<adam_reg_kernel<3>>(65536, "smooth_weights")))
+            return rc;
 #define KN_ADAM(F)                                                                                                     \
-    {                                                                                                                  \
-        if (rl > rattr) {                                                                                              \
-            if (hipFuncSetAttribute((const void*)adam_reg_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536) != hipSuccess || \
-                hipFuncSetAttribute((const void*)adam_reg_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536) != hipSuccess || \
-                hipFuncSetAttribute((const void*)adam_reg_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536) != hipSuccess)   \
-                return knnsvc_fail(KNNSVC_EHIP, "smooth_weights: hipFuncSetAttribute failed");                         \
-            rattr = 65536;                                                                                             \
-        }                                                                                                              \
-        hipLaunchKernelGGL(adam_reg_kernel<F>, dim3(1), dim3(512), rl, st, (long)nq, dim, scale, max_iter,              \
-                           (const float*)gram, out_w, out_iters);                                                      \
-    }
-        if (nq <= 512) KN_ADAM(1) else if (nq <= 1024) KN_ADAM(2) else KN_ADAM(3)
+    hipLaunchKernelGGL(adam_reg_kernel<F>, dim3(1), dim3(512), rl, st, (long)nq, dim, scale, max_iter, (const float*)gram, out_w, out_iters);
+        if (nq <= 512) { KN_ADAM(1) } else if (nq <= 1024) { KN_ADAM(2) } else { KN_ADAM(3) }
 #undef KN_ADAM
         return knnsvc_check_launch("adam_reg");
     }
     size_t al = (size_t)nq * 2 * KW * 4;
     int use_lds = al <= 144 * 1024;
     if (!use_lds) al = 0;
-    if (al > aattr) {
-        if (hipFuncSetAttribute((const void*)adam_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)al) != hipSuccess)
-            return knnsvc_fail(KNNSVC_EHIP, "smooth_weights: hipFuncSetAttribute failed");
-        aattr = al;
-    }
+    if ((rc = kn_lds_optin<adam_kernel>((int)al, "smooth_weights"))) return rc;
     hipLaunchKernelGGL(adam_kernel, dim3(1), dim3(1024), al, st, (long)nq, dim, scale, max_iter, (const float*)gram, state,
                        xch, use_lds, out_w, out_iters);
     return knnsvc_check_launch("adam");
