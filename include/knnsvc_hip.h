@@ -31,7 +31,7 @@ extern "C" {
 #define KNNSVC_EHIP      3   /* a HIP runtime call failed                  */
 #define KNNSVC_ENAN      4   /* NaN distance (the reference sys.exit()s)   */
 
-#define KNNSVC_ABI_VERSION 17
+#define KNNSVC_ABI_VERSION 18
 
 int knnsvc_abi_version(void);
 const char* knnsvc_last_error(void);
@@ -463,6 +463,41 @@ size_t knnsvc_smooth_workspace_bytes(int64_t nq);
 int knnsvc_smooth_weights(const int64_t* idx, int64_t nq, const float* pool, int64_t np, int32_t dim,
                           int32_t ld, float scale, const float* row_scale, int32_t max_iter, float* out_w,
                           int32_t* out_iters, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The match stage for n_seg independent sequences in one launch sequence.  Every per-row array is the
+ * sequences' arrays stacked in order; host_seg is a HOST array int64 [n_seg + 1] of row offsets: host_seg[0] == 0,
+ * strictly ascending (no empty segment), host_seg[n_seg] = total rows, 1 <= n_seg <= KNNSVC_MAX_SEGMENTS.  It is
+ * validated on the host, sizes the grids and reaches the kernels by value as a kernel argument: no device-side
+ * table, no allocation, no synchronisation; the calls stay hipGraph-capturable.  One workgroup per segment runs
+ * the code of the single-sequence entry point: every output row of segment s, and its result / out_iters
+ * entry, is bit-identical to that entry point called on the segment's rows alone.  All argument checks run
+ * before the first HIP call.
+ * ------------------------------------------------------------------------------------------ */
+#define KNNSVC_MAX_SEGMENTS 64
+/* knnsvc_log_f0_median per segment (ddsp_prematch_dataset.py:1224-1225).  result [n_seg][2]: (lower median of
+ * log f0 over voiced rows — NaN if there is none —, voiced count); workspace: total floats. */
+int knnsvc_log_f0_median_seg(const float* f0, const int64_t* host_seg, int32_t n_seg, float* result, float* workspace, void* stream);
+
+/* knnsvc_shift_f0 per segment (:1232-1233).  query_median [n_seg][2] (the above), pool_median [2]. */
+int knnsvc_shift_f0_seg(const float* f0, const int64_t* host_seg, int32_t n_seg, const float* query_median,
+                        const float* pool_median, float* shifted, void* stream);
+
+/* knnsvc_concat_reselect per segment (lib_ongaku_test.py:270-369): every segment is a sequence of its own — its
+ * frame 0 keeps its neighbours, the walk never looks across a boundary.  idx_in/out [total, 4]. */
+int knnsvc_concat_reselect_seg(const int64_t* idx_in, const float* q, const float* q_norm, const int64_t* host_seg, int32_t n_seg,
+                               const float* pool, const float* p_norm, int64_t np, int32_t dim, const float* shifted_f0,
+                               const float* pool_f0, int32_t use_f0, float concat_weight, int64_t* idx_out, void* stream);
+
+/* knnsvc_smooth_weights per segment (ddsp_prematch_dataset.py:574-680, 807-924): one Gram launch over the adjacent
+ * pairs of all segments (a pair never spans a boundary), then one launch per loop variant present, each segment on the
+ * variant it would get alone.  out_w [total][4]; out_iters [n_seg] (may be NULL); row_scale (may be NULL) [total][4].
+ * A segment of one row gets 0.25 and 0 iterations.  The workspace is the sum of the per-segment needs
+ * (knnsvc_smooth_workspace_bytes), each rounded up to 64 bytes; 0 for an invalid table. */
+size_t knnsvc_smooth_seg_workspace_bytes(const int64_t* host_seg, int32_t n_seg);
+int knnsvc_smooth_weights_seg(const int64_t* idx, const int64_t* host_seg, int32_t n_seg, const float* pool, int64_t np,
+                              int32_t dim, int32_t ld, float scale, const float* row_scale, int32_t max_iter, float* out_w,
+                              int32_t* out_iters, void* workspace, size_t workspace_bytes, void* stream);
 
 /* out[i,:] = sum_k w[i,k] * pool[idx[i,k], :]   (ddsp_prematch_dataset.py:1358, 1444; w NULL = mean of 4
  * for harmonics :1446 / softmax(ones) :1361-1364) */

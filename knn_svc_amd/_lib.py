@@ -11,7 +11,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("KNNSVC_LIB") or os.path.join(_HERE, "libknnsvc_hip.so")      # KNNSVC_LIB: an A/B build (csrc/Makefile)
-ABI_VERSION = 17
+ABI_VERSION = 18
 
 vp, i32, i64, f32, sz = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_size_t
 
@@ -153,6 +153,11 @@ SIGNATURES = {
     "knnsvc_concat_reselect": (i32, [vp, vp, vp, i64, vp, vp, i64, i32, vp, vp, i32, f32, vp, vp]),
     "knnsvc_smooth_workspace_bytes": (sz, [i64]),
     "knnsvc_smooth_weights": (i32, [vp, i64, vp, i64, i32, i32, f32, vp, i32, vp, vp, vp, sz, vp]),
+    "knnsvc_log_f0_median_seg": (i32, [vp, vp, i32, vp, vp, vp]),
+    "knnsvc_shift_f0_seg": (i32, [vp, vp, i32, vp, vp, vp, vp]),
+    "knnsvc_concat_reselect_seg": (i32, [vp, vp, vp, vp, i32, vp, vp, i64, i32, vp, vp, i32, f32, vp, vp]),
+    "knnsvc_smooth_seg_workspace_bytes": (sz, [vp, i32]),
+    "knnsvc_smooth_weights_seg": (i32, [vp, vp, i32, vp, i64, i32, i32, f32, vp, i32, vp, vp, vp, sz, vp]),
     "knnsvc_weighted_gather": (i32, [vp, vp, i64, i32, vp, i32, i32, i32, vp, vp]),
     "knnsvc_round_f16": (i32, [vp, i64, vp, vp]),
     "knnsvc_amp_ratio": (i32, [vp, i32, vp, i32, i64, vp, i64, i32, i32, vp, vp]),

@@ -29,6 +29,24 @@ static inline int knnsvc_check_launch(const char* what) {
 
 static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// Segment table of the *_seg entry points (n independent sequences stacked row-wise): validated on the host, then handed to the
+// kernels BY VALUE as a kernel argument (528 bytes) — no device-side table, no allocation, no copy to wait for.
+struct KnSegTable { int n; long off[KNNSVC_MAX_SEGMENTS + 1]; };
+
+static inline int kn_seg_table(const int64_t* host_seg, int32_t n_seg, const char* entry, KnSegTable* out) {
+    if (!host_seg) return knnsvc_fail(KNNSVC_EINVAL, "%s: null segment table", entry);
+    if (n_seg < 1 || n_seg > KNNSVC_MAX_SEGMENTS)
+        return knnsvc_fail(KNNSVC_EINVAL, "%s: n_seg %d outside 1..%d", entry, (int)n_seg, KNNSVC_MAX_SEGMENTS);
+    if (host_seg[0] != 0) return knnsvc_fail(KNNSVC_EINVAL, "%s: segment table must start at 0 (got %lld)", entry, (long long)host_seg[0]);
+    for (int s = 0; s < n_seg; ++s)
+        if (host_seg[s + 1] <= host_seg[s])
+            return knnsvc_fail(KNNSVC_EINVAL, "%s: segment table must be strictly ascending (entry %d: %lld after %lld)", entry, s + 1,
+                               (long long)host_seg[s + 1], (long long)host_seg[s]);
+    out->n = n_seg;
+    for (int s = 0; s <= KNNSVC_MAX_SEGMENTS; ++s) out->off[s] = host_seg[s < n_seg ? s : n_seg];
+    return KNNSVC_OK;
+}
+
 // Opt-in of KERNEL to `bytes` of dynamic LDS (a launch with more than 64 KiB fails without it).  The attribute is set once per
 // kernel instantiation and process, and again only when a later call needs more.  `entry`: the API entry point, for the message.
 template <auto KERNEL>

@@ -28,11 +28,12 @@ __device__ __forceinline__ int tri(int i, int j) { return i < j ? i * 7 - i * (i
 // row_scale (optional) [nq][4]: candidate k of frame t and its +-1 neighbours are multiplied by row_scale[t][k]
 // (compute_weight_with_amp, ddsp_prematch_dataset.py:684-713); the centring argument is unchanged because the
 // coefficient vector still sums to zero.
-__global__ __launch_bounds__(256) void gram_kernel(const long* __restrict__ idx, long nq, const float* __restrict__ pool,
-                                                  long np, int dim, int ld, const float* __restrict__ row_scale,
-                                                  float* __restrict__ gram) {
+// The body of gram_kernel (one sequence, block t = pair t) and gram_seg_kernel (all pairs of all segments): idx, row_scale and
+// gram already at the sequence, nq its length.
+__device__ __forceinline__ void gram_body(const long* __restrict__ idx, long nq, const float* __restrict__ pool,
+                                          long np, int dim, int ld, const float* __restrict__ row_scale,
+                                          float* __restrict__ gram, const long t) {
     extern __shared__ float sm[];           // [8][dim] centred vectors of the current term
-    const long t = blockIdx.x;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     double acc[GE / 4];
 #pragma unroll
@@ -76,6 +77,32 @@ __global__ __launch_bounds__(256) void gram_kernel(const long* __restrict__ idx,
     }
 }
 
+__global__ __launch_bounds__(256) void gram_kernel(const long* __restrict__ idx, long nq, const float* __restrict__ pool,
+                                                  long np, int dim, int ld, const float* __restrict__ row_scale,
+                                                  float* __restrict__ gram) {
+    gram_body(idx, nq, pool, np, dim, ld, row_scale, gram, blockIdx.x);
+}
+
+// Segments of knnsvc_smooth_weights_seg: row offsets, and where each segment's workspace (Gram | state | exchange, the layout of
+// the single-sequence call) starts, in units of 64 bytes from the aligned workspace base.  By value, like KnSegTable.
+struct SmoothSegs { int n; long off[KNNSVC_MAX_SEGMENTS + 1]; unsigned ws64[KNNSVC_MAX_SEGMENTS]; };
+// the segments one launch works on: block b -> segment id[b]
+struct SegList { int n; unsigned char id[KNNSVC_MAX_SEGMENTS]; };
+
+__device__ __forceinline__ float* seg_ws(float* base, const SmoothSegs& sg, int s) { return base + (size_t)sg.ws64[s] * 16; }
+
+// one launch over the adjacent pairs of all segments: segment s has len - 1 of them, pair numbers start at off[s] - s
+__global__ __launch_bounds__(256) void gram_seg_kernel(const long* __restrict__ idx, const SmoothSegs sg, const float* __restrict__ pool,
+                                                      long np, int dim, int ld, const float* __restrict__ row_scale,
+                                                      float* __restrict__ ws) {
+    const long b = blockIdx.x;
+    int s = 0;
+    for (int j = 1; j < sg.n; ++j) if (sg.off[j] - j <= b) s = j;       // the last segment whose first pair is <= b (uniform)
+    const long o = sg.off[s];
+    gram_body(idx + o * KW, sg.off[s + 1] - o, pool, np, dim, ld, row_scale ? row_scale + o * KW : row_scale, seg_ws(ws, sg, s),
+              b - (o - s));
+}
+
 struct LoopState { double min_loss, conv_min; int since; };
 
 // The two per-element pieces of an iteration that were IEEE divides, square roots and expf: 250 of the 410 VALU instructions a
@@ -101,10 +128,10 @@ __device__ __forceinline__ float loop_step(float th, float m, float vmax, float 
 }
 
 
-__global__ __launch_bounds__(1024) void adam_kernel(long nq, int dim, float scale, int max_iter,
-                                                   const float* __restrict__ gram, float* __restrict__ state,
-                                                   float* __restrict__ xch_global, int use_lds,
-                                                   float* __restrict__ out_w, int* __restrict__ out_iters) {
+__device__ __forceinline__ void adam_body(long nq, int dim, float scale, int max_iter,
+                                          const float* __restrict__ gram, float* __restrict__ state,
+                                          float* __restrict__ xch_global, int use_lds,
+                                          float* __restrict__ out_w, int* __restrict__ out_iters) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     __shared__ double red[2][16];
     float* xw = use_lds ? sm : xch_global;                 // [nq][4] softmax weights
@@ -212,14 +239,36 @@ __global__ __launch_bounds__(1024) void adam_kernel(long nq, int dim, float scal
     if (tid == 0 && out_iters) out_iters[0] = it;
 }
 
+inline size_t ws_floats(long nq) { return (size_t)GE * nq + (size_t)6 * 4 * nq + (size_t)2 * 4 * nq; }
+constexpr long ADAM_LDS_ROWS = 144 * 1024 / (2 * KW * 4);     // longest sequence whose weight / gradient exchange fits LDS (adam_kernel)
+
+__global__ __launch_bounds__(1024) void adam_kernel(long nq, int dim, float scale, int max_iter,
+                                                   const float* __restrict__ gram, float* __restrict__ state,
+                                                   float* __restrict__ xch_global, int use_lds,
+                                                   float* __restrict__ out_w, int* __restrict__ out_iters) {
+    adam_body(nq, dim, scale, max_iter, gram, state, xch_global, use_lds, out_w, out_iters);
+}
+
+// block b runs the loop of segment list.id[b] in that segment's own workspace; LDS or the global exchange buffer as the segment
+// would get alone
+__global__ __launch_bounds__(1024) void adam_seg_kernel(const SmoothSegs sg, const SegList list, int dim, float scale, int max_iter,
+                                                       float* __restrict__ ws, float* __restrict__ out_w, int* __restrict__ out_iters) {
+    const int s = list.id[blockIdx.x];
+    const long o = sg.off[s], nq = sg.off[s + 1] - o;
+    float* gram = seg_ws(ws, sg, s);
+    float* state = gram + (size_t)GE * nq;
+    adam_body(nq, dim, scale, max_iter, gram, state, state + (size_t)6 * 4 * nq, nq <= ADAM_LDS_ROWS, out_w + o * KW,
+              out_iters ? out_iters + s : out_iters);
+}
+
 // Same loop with everything a thread needs for its (up to FPT) frames in registers: the 36-entry Gram of
 // each frame pair, theta, Adam moments, amsgrad maximum and the best iterate.  Only the softmax weights and
 // the gradient contribution of the left neighbour travel through LDS; an iteration costs three barriers and
 // no global memory traffic (the global-state variant streams ~150 KB of Gram data per iteration through one CU).
 template <int FPT>
-__global__ __launch_bounds__(512) void adam_reg_kernel(long nq, int dim, float scale, int max_iter,
-                                                      const float* __restrict__ gram, float* __restrict__ out_w,
-                                                      int* __restrict__ out_iters) {
+__device__ __forceinline__ void adam_reg_body(long nq, int dim, float scale, int max_iter,
+                                              const float* __restrict__ gram, float* __restrict__ out_w,
+                                              int* __restrict__ out_iters) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     __shared__ double red[2][8];      // by iteration parity: a fast wave may write its next sum while a slow one still reads
     float* xw = sm;                       // [nq][4]
@@ -340,12 +389,35 @@ __global__ __launch_bounds__(512) void adam_reg_kernel(long nq, int dim, float s
     if (tid == 0 && out_iters) out_iters[0] = it;
 }
 
+template <int FPT>
+__global__ __launch_bounds__(512) void adam_reg_kernel(long nq, int dim, float scale, int max_iter,
+                                                      const float* __restrict__ gram, float* __restrict__ out_w,
+                                                      int* __restrict__ out_iters) {
+    adam_reg_body<FPT>(nq, dim, scale, max_iter, gram, out_w, out_iters);
+}
+
+template <int FPT>
+__global__ __launch_bounds__(512) void adam_reg_seg_kernel(const SmoothSegs sg, const SegList list, int dim, float scale, int max_iter,
+                                                          float* __restrict__ ws, float* __restrict__ out_w, int* __restrict__ out_iters) {
+    const int s = list.id[blockIdx.x];
+    const long o = sg.off[s];
+    adam_reg_body<FPT>(sg.off[s + 1] - o, dim, scale, max_iter, seg_ws(ws, sg, s), out_w + o * KW, out_iters ? out_iters + s : out_iters);
+}
+
 __global__ void fill_quarter_kernel(float* w, long n) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) w[i] = 0.25f;
 }
 
-inline size_t ws_floats(long nq) { return (size_t)GE * nq + (size_t)6 * 4 * nq + (size_t)2 * 4 * nq; }
+// segments of one row (no adjacent pair): softmax(0) and zero iterations, as knnsvc_smooth_weights answers them
+__global__ void fill_quarter_seg_kernel(const SmoothSegs sg, const SegList list, float* __restrict__ out_w, int* __restrict__ out_iters) {
+    const int s = list.id[blockIdx.x];
+    if (threadIdx.x < KW) out_w[sg.off[s] * KW + threadIdx.x] = 0.25f;
+    if (threadIdx.x == 0 && out_iters) out_iters[s] = 0;
+}
+
+// bytes of segment workspace: what the segment needs alone, rounded up to 64
+inline size_t seg_ws_bytes(long nq) { return (ws_floats(nq) * 4 + 64 + 63) & ~(size_t)63; }
 
 }  // namespace
 
@@ -389,10 +461,83 @@ extern "C" int knnsvc_smooth_weights(const int64_t* idx, int64_t nq, const float
         return knnsvc_check_launch("adam_reg");
     }
     size_t al = (size_t)nq * 2 * KW * 4;
-    int use_lds = al <= 144 * 1024;
+    int use_lds = nq <= ADAM_LDS_ROWS;
     if (!use_lds) al = 0;
     if ((rc = kn_lds_optin<adam_kernel>((int)al, "smooth_weights"))) return rc;
     hipLaunchKernelGGL(adam_kernel, dim3(1), dim3(1024), al, st, (long)nq, dim, scale, max_iter, (const float*)gram, state,
                        xch, use_lds, out_w, out_iters);
     return knnsvc_check_launch("adam");
+}
+
+static int smooth_segs(const int64_t* host_seg, int32_t n_seg, const char* entry, SmoothSegs* sg, size_t* bytes) {
+    KnSegTable t;
+    if (const int rc = kn_seg_table(host_seg, n_seg, entry, &t)) return rc;
+    sg->n = n_seg;
+    size_t at = 0;
+    for (int s = 0; s <= KNNSVC_MAX_SEGMENTS; ++s) {
+        sg->off[s] = t.off[s];
+        if (s < KNNSVC_MAX_SEGMENTS) sg->ws64[s] = (unsigned)(at / 64);
+        if (s < n_seg) at += seg_ws_bytes(t.off[s + 1] - t.off[s]);
+    }
+    if (at / 64 > 0xFFFFFFFFull) return knnsvc_fail(KNNSVC_EINVAL, "%s: segments too long", entry);
+    *bytes = at;
+    return KNNSVC_OK;
+}
+
+extern "C" size_t knnsvc_smooth_seg_workspace_bytes(const int64_t* host_seg, int32_t n_seg) {
+    SmoothSegs sg; size_t bytes = 0;
+    return smooth_segs(host_seg, n_seg, "smooth_seg_workspace_bytes", &sg, &bytes) ? 0 : bytes;
+}
+
+extern "C" int knnsvc_smooth_weights_seg(const int64_t* idx, const int64_t* host_seg, int32_t n_seg, const float* pool, int64_t np,
+                                         int32_t dim, int32_t ld, float scale, const float* row_scale, int32_t max_iter, float* out_w,
+                                         int32_t* out_iters, void* workspace, size_t workspace_bytes, void* stream) {
+    SmoothSegs sg; size_t need = 0;
+    if (const int rc = smooth_segs(host_seg, n_seg, "smooth_weights_seg", &sg, &need)) return rc;
+    KN_REQUIRE(idx && pool && out_w && workspace, "smooth_weights_seg: null pointer");
+    KN_REQUIRE(np > 0 && dim > 0 && ld >= dim && max_iter != 0, "smooth_weights_seg: bad sizes");
+    KN_REQUIRE(((uintptr_t)out_w & 15) == 0, "smooth_weights_seg: out_w must be 16-byte aligned");
+    const size_t gl = (size_t)8 * dim * 4;
+    KN_REQUIRE(gl <= 150 * 1024, "smooth_weights_seg: feature dim too large for LDS");
+    if (workspace_bytes < need)
+        return knnsvc_fail(KNNSVC_EWORKSPACE, "smooth_weights_seg: workspace %zu < %zu bytes", workspace_bytes, need);
+    hipStream_t st = (hipStream_t)stream;
+    float* base = (float*)(((uintptr_t)workspace + 63) & ~(uintptr_t)63);
+    // the loop variant each segment would get alone: 0 one row (no loop), 1..3 adam_reg_kernel<1|2|3>, 4 adam_kernel
+    SegList cls[5];
+    long longest[5] = {0, 0, 0, 0, 0}, lds_rows = 0;
+    for (int c = 0; c < 5; ++c) cls[c].n = 0;
+    for (int s = 0; s < n_seg; ++s) {
+        const long nq = sg.off[s + 1] - sg.off[s];
+        const int c = nq < 2 ? 0 : (nq <= 512 ? 1 : (nq <= 1024 ? 2 : (nq <= 1536 ? 3 : 4)));
+        cls[c].id[cls[c].n++] = (unsigned char)s;
+        if (nq > longest[c]) longest[c] = nq;
+        if (c == 4 && nq <= ADAM_LDS_ROWS && nq > lds_rows) lds_rows = nq;
+    }
+    int rc;
+    if (cls[0].n) {
+        hipLaunchKernelGGL(fill_quarter_seg_kernel, dim3((unsigned)cls[0].n), dim3(64), 0, st, sg, cls[0], out_w, out_iters);
+        if ((rc = knnsvc_check_launch("smooth_weights_seg(fill)"))) return rc;
+    }
+    const long pairs = sg.off[n_seg] - n_seg;
+    if (pairs == 0) return KNNSVC_OK;
+    if ((rc = kn_lds_optin<gram_seg_kernel>((int)gl, "smooth_weights_seg"))) return rc;
+    hipLaunchKernelGGL(gram_seg_kernel, dim3((unsigned)pairs), dim3(256), gl, st, (const long*)idx, sg, pool, (long)np, dim, ld, row_scale, base);
+    if ((rc = knnsvc_check_launch("gram_seg"))) return rc;
+#define KN_ADAM_SEG(F)                                                                                                               \
+    if (cls[F].n) {                                                                                                                  \
+        if ((rc = kn_lds_optin<adam_reg_seg_kernel<F>>(65536, "smooth_weights_seg"))) return rc;                                     \
+        hipLaunchKernelGGL(adam_reg_seg_kernel<F>, dim3((unsigned)cls[F].n), dim3(512), (size_t)longest[F] * 2 * KW * 4, st, sg, cls[F], dim, scale, \
+                           max_iter, base, out_w, out_iters);                                                                        \
+        if ((rc = knnsvc_check_launch("adam_reg_seg"))) return rc;                                                                   \
+    }
+    KN_ADAM_SEG(1) KN_ADAM_SEG(2) KN_ADAM_SEG(3)
+#undef KN_ADAM_SEG
+    if (cls[4].n) {
+        const size_t al = (size_t)lds_rows * 2 * KW * 4;         // of the segments that exchange through LDS; the others take none
+        if ((rc = kn_lds_optin<adam_seg_kernel>((int)al, "smooth_weights_seg"))) return rc;
+        hipLaunchKernelGGL(adam_seg_kernel, dim3((unsigned)cls[4].n), dim3(1024), al, st, sg, cls[4], dim, scale, max_iter, base, out_w, out_iters);
+        if ((rc = knnsvc_check_launch("adam_seg"))) return rc;
+    }
+    return KNNSVC_OK;
 }

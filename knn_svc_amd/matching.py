@@ -386,6 +386,106 @@ def match_features(query_seq, query_f0, matching_list, matching_f0, harmonics_li
     return out_feats, harm_w, shifted
 
 
+# How the match stage of SEVERAL items is put on the chip: "lanes" (one match_features per item on the lane streams, the default) or
+# "segmented" (match_features_many: the items of a batch stacked, one workgroup per item in every recurrence launch).
+MATCH_MODES = ("lanes", "segmented")
+# Items per segmented batch.  16 is a GUESS (a quarter of the 64 segments one launch takes; enough items for the kNN groups to stay
+# ahead of the batches) until tools/match_seg_ab.py has been run on the hardware: its sweep row for 32 x 30 s sources replaces it.
+MATCH_BATCH_DEFAULT = 16
+
+
+def match_mode(match=None) -> str:
+    """The route: the argument, else KNNSVC_MATCH, else "lanes"."""
+    m = match if match is not None else (os.environ.get("KNNSVC_MATCH") or "lanes")
+    if m not in MATCH_MODES:
+        raise ValueError(f"match must be one of {MATCH_MODES}, got {m!r}")
+    return m
+
+
+def match_batch_size(match_batch=None) -> int:
+    """Items per segmented batch: the argument, else KNNSVC_MATCH_BATCH, else MATCH_BATCH_DEFAULT."""
+    n = int(match_batch if match_batch is not None else (os.environ.get("KNNSVC_MATCH_BATCH") or MATCH_BATCH_DEFAULT))
+    if n < 1:
+        raise ValueError("match_batch must be >= 1")
+    return n
+
+
+def match_features_many(query_seqs, query_f0s, matching_list, matching_f0, harmonics_list, ckpt_type, post_opt, nn32s=None,
+                        nan_flags=None, pool_prep=None, synth_list=None, return_debug=False):
+    """``match_features`` for several query utterances against one pool, run ONCE over their stacked frames -> a list of per-item
+    tuples with the meaning of match_features' return value (views of the stacked outputs).  The row-wise stages (row norms, f0
+    re-rank, weighted sums) take the stacked rows as they are; the per-sequence stages (median, shift, concat re-selection,
+    smoothness weights) take the segment table: one workgroup per item running the code of the single-sequence call, so item i's
+    tensors are bit-identical to ``match_features`` of item i with the same ``nn32``.  ``nn32s``: per-item neighbour lists (or
+    None: one search over the stacked frames)."""
+    lens = [int(q.shape[0]) for q in query_seqs]
+    seg = [0]
+    for n in lens:
+        seg.append(seg[-1] + n)
+    q = torch.cat([t.contiguous() for t in query_seqs], 0).contiguous()
+    query_f0 = torch.cat([t.reshape(-1) for t in query_f0s], 0).contiguous()
+    P = matching_list
+    qn, qs = ops.row_norms(q)
+    pn, ps = pool_prep["stats"] if pool_prep is not None else ops.row_norms(P)
+    nan_flag = None
+    if nn32s is None or any(t is None for t in nn32s):
+        nn32, _, nan_flag = ops.knn_topk(q, P, C.KNN_K, q_stats=(qn, qs), p_stats=(pn, ps), check_nan=False,
+                                         return_flag=True, prepared=pool_prep["split"] if pool_prep is not None else None)
+    else:
+        nn32 = torch.cat(list(nn32s), 0).contiguous()
+    cw, run_adam = parse_post_opt(post_opt)
+    with_harm = "wavlm_only" not in ckpt_type and "no_harm_no_amp" not in ckpt_type
+    # the two branches on the lane stream and its partner, as in match_features
+    main = torch.cuda.current_stream()
+    side = _side_stream(q.device)
+    side.wait_stream(main)
+    it1 = it2 = None
+    w = w2 = harm_w = None
+    with torch.cuda.stream(side):
+        qmed, pmed = ops.log_f0_median_seg(query_f0, seg), ops.log_f0_median(matching_f0)      # the pool's median once
+        shifted = ops.shift_f0_seg(query_f0, seg, qmed, pmed)
+        ranked = ops.f0_rerank(nn32, shifted, matching_f0)
+        idx2 = ranked[:, :C.KNN_USE].contiguous()
+        if cw != -1:
+            idx2 = ops.concat_reselect_seg(idx2, seg, q, qn, P, pn, shifted, matching_f0, concat_weight=cw)
+        if with_harm:
+            if run_adam:
+                w2, it2 = ops.smooth_weights_seg(idx2, seg, harmonics_list, 1000.0, return_iters=True)
+            harm_w = ops.weighted_gather(idx2, w2, harmonics_list)
+    idx = nn32[:, :C.KNN_USE].contiguous()
+    if cw != -1:
+        idx = ops.concat_reselect_seg(idx, seg, q, qn, P, pn, concat_weight=cw)
+    Ps = synth_list if synth_list is not None else P
+    if run_adam:
+        w, it1 = ops.smooth_weights_seg(idx, seg, Ps, 0.1, return_iters=True)
+    out_feats = ops.weighted_gather(idx, w, Ps)
+    main.wait_stream(side)
+    for t in (shifted, idx2, harm_w, w2, it2):
+        if t is not None:
+            t.record_stream(main)
+    if nan_flag is not None:
+        if nan_flags is not None:
+            nan_flags.append(nan_flag)
+        else:
+            try:
+                ops.raise_if_nan(nan_flag)
+            except ops.KnnOverflow:         # as match_features: once more on the dot-matrix route
+                with ops.fused_off():
+                    return match_features_many(query_seqs, query_f0s, matching_list, matching_f0, harmonics_list, ckpt_type, post_opt,
+                                               pool_prep=pool_prep, synth_list=synth_list, return_debug=return_debug)
+    parts = lambda t: t.split(lens) if t is not None else [None] * len(lens)
+    out = []
+    dbg = [parts(t) for t in (nn32, idx, w, idx2, w2)]
+    for i, (of, hw, sf) in enumerate(zip(parts(out_feats), parts(harm_w), parts(shifted))):
+        if return_debug:
+            out.append((of, hw, sf, dict(nn32=dbg[0][i], idx_wavlm=dbg[1][i], w_wavlm=dbg[2][i], idx_harm=dbg[3][i], w_harm=dbg[4][i],
+                                         iters_wavlm=it1[i:i + 1] if it1 is not None else 0,
+                                         iters_harm=it2[i:i + 1] if it2 is not None else 0)))
+        else:
+            out.append((of, hw, sf))
+    return out
+
+
 def _mix_of(weights, wavlm):
     """A layer weighting as the encoder takes it: None for the one-hot on its exit layer (the live path), else the tuple."""
     if weights is None:
@@ -528,16 +628,31 @@ def match_at_inference_time(src_wav_file, ref_wav_file, wavlm: WavLMEncoder, mat
                                   harmonics_list, ckpt_type, post_opt, nan_flags=flags, pool_prep=prep, nn32=nn.get(item), **extra)
         # match bodies in flight at once (each is a chain of single-workgroup recurrences: more lanes = more of them side by side)
         lanes = min(int(os.environ.get("KNNSVC_MATCH_LANES", "3")), len(items)) if matching_list.is_cuda else 1   # (CPU tensors: injected kernels in the gloo tests)
+        # KNNSVC_MATCH=segmented (unsharded pool, several items): the items in order, in batches of KNNSVC_MATCH_BATCH, each batch one
+        # match_features_many on a lane
+        segmented = match_mode() == "segmented" and shard is None and len(items) > 1 and matching_list.is_cuda
+        def body_many(batch):
+            for item in batch:
+                wait_for_neighbours(nn.get(item), nn_ready.get(item), matching_list.device)
+            return match_features_many([query_pool[it] for it in batch], [query_f0_pool[it] for it in batch], matching_list, matching_f0,
+                                       harmonics_list, ckpt_type, post_opt, nn32s=[nn.get(it) for it in batch], nan_flags=flags,
+                                       pool_prep=prep, synth_list=synth_list)
+        nb = match_batch_size()
+        batches = [items[a:a + nb] for a in range(0, len(items), nb)]
         if vocode_fn is not None and len(items) > 0:
             assert waves_out is not None
             tail = lambda item, r: r + (vocode_fn(r[0], r[2], r[1]),)
-            if matching_list.is_cuda:
+            if segmented:
+                results = pipeline.LanePipeline(matching_list.device, max(1, lanes)).run_batched(batches, body_many, tail)
+            elif matching_list.is_cuda:
                 results = pipeline.LanePipeline(matching_list.device, max(1, lanes)).run(items, body, tail)
             else:
                 results = [tail(i, body(i)) for i in items]
             for item, r in zip(items, results):
                 waves_out[item] = r[3]
             results = [r[:3] for r in results]
+        elif segmented:
+            results = pipeline.LanePipeline(matching_list.device, max(1, lanes)).run_batched(batches, body_many)
         else:
             results = pipeline.LanePipeline(matching_list.device, lanes).run(items, body) if lanes > 1 else [body(i) for i in items]
         for f in flags:

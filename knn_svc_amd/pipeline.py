@@ -280,3 +280,42 @@ class LanePipeline:
         for t in _tensors(out):
             t.record_stream(cur)
         return out
+
+    def run_batched(self, batches, head_many, tail=None):
+        """``run`` for heads that take several items at once (matching.match_features_many): ``head_many(batch)`` runs on a lane
+        (batch b on lane b mod L) and returns one result per item of the batch; item i's ``tail`` (i counted over all batches) then
+        runs on tail stream i mod tails behind the lane's event.  -> the results in item order.  Same rules as ``run``: enqueue
+        only, and every tensor handed from a lane to a tail stream is recorded on it."""
+        cur = torch.cuda.current_stream(self.device)
+        for s in self.lanes + self.tail_streams:
+            s.wait_stream(cur)
+        out = []
+        i = 0
+        for b, batch in enumerate(batches):
+            lane = self.lanes[b % len(self.lanes)]
+            with torch.cuda.stream(lane):
+                hs = list(head_many(batch))
+                done = lane.record_event()
+            if len(hs) != len(batch):
+                raise ValueError(f"head_many returned {len(hs)} results for a batch of {len(batch)} items")
+            for item, h in zip(batch, hs):
+                if tail is None:
+                    out.append(h)
+                else:
+                    k = i % len(self.tail_streams)
+                    ts = self.tail_streams[k]
+                    with torch.cuda.stream(ts):
+                        ts.wait_event(done)
+                        for t in _tensors(h):
+                            t.record_stream(ts)
+                        _TAIL.k = k
+                        try:
+                            out.append(tail(item, h))
+                        finally:
+                            _TAIL.k = 0
+                i += 1
+        for s in self.lanes + self.tail_streams:
+            cur.wait_stream(s)
+        for t in _tensors(out):
+            t.record_stream(cur)
+        return out

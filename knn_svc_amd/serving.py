@@ -85,13 +85,18 @@ class TargetVoice:
 
 class BatchConverter:
     def __init__(self, vc, target: TargetVoice, ckpt_type: str = "mix", post_opt: str = "post_opt_0.2", lanes: int | None = None,
-                 max_encode_batch: int = 32):
+                 max_encode_batch: int = 32, match: str | None = None, match_batch: int | None = None):
         if "wavlm_only_original" in ckpt_type:
             raise NotImplementedError("wavlm_only_original needs hifigan/models.py, absent upstream")
         self.vc, self.target, self.ckpt_type, self.post_opt = vc, target, ckpt_type, post_opt
         self.f0only = "wavlm_only" in ckpt_type or "no_harm_no_amp" in ckpt_type
         self.lanes = lanes if lanes is not None else int(os.environ.get("KNNSVC_MATCH_LANES", "3"))
         self.max_encode_batch = max_encode_batch
+        # the match stage of a batch: "lanes" (default; one match body per source on the lane streams) or "segmented" (the sources
+        # in order, in batches of match_batch, each batch ONE stacked match body: matching.match_features_many).  Defaults from
+        # KNNSVC_MATCH / KNNSVC_MATCH_BATCH.
+        self.match = M.match_mode(match)
+        self.match_batch = M.match_batch_size(match_batch)
 
     def _load(self, src, check=False):
         """A request is a path, or (wav [L] float32 16 kHz mono as array / tensor, f0 [L // 320 + 1] or None).
@@ -165,9 +170,18 @@ class BatchConverter:
                 M.wait_for_neighbours(nn.get(i), ready.get(i), dev)
                 return M.match_features(qpool[i], f0s[i], tg.feats, tg.f0, tg.harm, self.ckpt_type, post_opt,
                                         nan_flags=flags, pool_prep=tg.prep, nn32=nn.get(i))
+            def body_many(batch):
+                for i in batch:
+                    M.wait_for_neighbours(nn.get(i), ready.get(i), dev)
+                return M.match_features_many([qpool[i] for i in batch], [f0s[i] for i in batch], tg.feats, tg.f0, tg.harm, self.ckpt_type,
+                                             post_opt, nn32s=[nn.get(i) for i in batch], nan_flags=flags, pool_prep=tg.prep)
             tail = lambda i, r: voc(r[0], r[2], r[1])
             n_lanes = max(1, min(self.lanes, len(items)))
-            ys = pipeline.LanePipeline(dev, n_lanes).run(items, body, tail)
+            if self.match == "segmented" and len(items) > 1:
+                batches = [items[a:a + self.match_batch] for a in range(0, len(items), self.match_batch)]
+                ys = pipeline.LanePipeline(dev, n_lanes).run_batched(batches, body_many, tail)
+            else:
+                ys = pipeline.LanePipeline(dev, n_lanes).run(items, body, tail)
             peak = torch.stack([y.abs().max() for y in ys])
             for f in flags:
                 ops.raise_if_nan(f)                          # one host read per search, after everything is enqueued
