@@ -469,10 +469,10 @@ int knnsvc_smooth_weights(const int64_t* idx, int64_t nq, const float* pool, int
  * sequences' arrays stacked in order; host_seg is a HOST array int64 [n_seg + 1] of row offsets: host_seg[0] == 0,
  * strictly ascending (no empty segment), host_seg[n_seg] = total rows, 1 <= n_seg <= KNNSVC_MAX_SEGMENTS.  It is
  * validated on the host, sizes the grids and reaches the kernels by value as a kernel argument: no device-side
- * table, no allocation, no synchronisation; the calls stay hipGraph-capturable.  One workgroup per segment runs
- * the code of the single-sequence entry point: every output row of segment s, and its result / out_iters
- * entry, is bit-identical to that entry point called on the segment's rows alone.  All argument checks run
- * before the first HIP call.
+ * table, no allocation, no synchronisation; the calls stay hipGraph-capturable.  One workgroup per segment; the
+ * single-sequence entry points above are the one-segment case (the same kernels and host path with a table
+ * {0, n}), so every output row of segment s, and its result / out_iters entry, is bit-identical to that entry
+ * point called on the segment's rows alone.  All argument checks run before the first HIP call.
  * ------------------------------------------------------------------------------------------ */
 #define KNNSVC_MAX_SEGMENTS 64
 /* knnsvc_log_f0_median per segment (ddsp_prematch_dataset.py:1224-1225).  result [n_seg][2]: (lower median of

@@ -29,8 +29,9 @@ static inline int knnsvc_check_launch(const char* what) {
 
 static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
-// Segment table of the *_seg entry points (n independent sequences stacked row-wise): validated on the host, then handed to the
-// kernels BY VALUE as a kernel argument (528 bytes) — no device-side table, no allocation, no copy to wait for.
+// Segment table of the match-stage entry points (n independent sequences stacked row-wise; the single-sequence calls are n = 1):
+// validated on the host, then handed to the kernels BY VALUE as a kernel argument (528 bytes) — no device-side table, no
+// allocation, no copy to wait for.
 struct KnSegTable { int n; long off[KNNSVC_MAX_SEGMENTS + 1]; };
 
 static inline int kn_seg_table(const int64_t* host_seg, int32_t n_seg, const char* entry, KnSegTable* out) {
@@ -45,6 +46,13 @@ static inline int kn_seg_table(const int64_t* host_seg, int32_t n_seg, const cha
     out->n = n_seg;
     for (int s = 0; s <= KNNSVC_MAX_SEGMENTS; ++s) out->off[s] = host_seg[s < n_seg ? s : n_seg];
     return KNNSVC_OK;
+}
+
+// The table of ONE sequence of n rows: the single-sequence entry points are the one-segment case of the segmented ones.
+static inline int kn_seg_one(int64_t n, const char* entry, KnSegTable* out) {
+    if (n <= 0) return knnsvc_fail(KNNSVC_EINVAL, "%s: bad sizes (%lld rows)", entry, (long long)n);
+    const int64_t one[2] = {0, n};
+    return kn_seg_table(one, 1, entry, out);
 }
 
 // Opt-in of KERNEL to `bytes` of dynamic LDS (a launch with more than 64 KiB fails without it).  The attribute is set once per

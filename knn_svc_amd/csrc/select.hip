@@ -22,7 +22,7 @@ __device__ __forceinline__ float s2f(unsigned s) {
 }
 
 // lower median (torch.median) of log(f0) over f0 != 0, by 4-pass byte radix select in one block (1024 threads).  The body of
-// log_f0_median_kernel (one sequence) and log_f0_median_seg_kernel (block s = segment s): pointers already at the sequence.
+// log_f0_median_kernel (block s = segment s): pointers already at the sequence.
 __device__ __forceinline__ void log_f0_median_body(const float* __restrict__ f0, long n,
                                                    float* __restrict__ result, float* __restrict__ ws) {
     __shared__ unsigned hist[256];
@@ -65,12 +65,7 @@ __device__ __forceinline__ void log_f0_median_body(const float* __restrict__ f0,
     if (tid == 0) { result[0] = s2f(s_prefix); result[1] = (float)nv; }
 }
 
-__global__ __launch_bounds__(1024) void log_f0_median_kernel(const float* __restrict__ f0, long n,
-                                                            float* __restrict__ result, float* __restrict__ ws) {
-    log_f0_median_body(f0, n, result, ws);
-}
-
-__global__ __launch_bounds__(1024) void log_f0_median_seg_kernel(const float* __restrict__ f0, const KnSegTable seg,
+__global__ __launch_bounds__(1024) void log_f0_median_kernel(const float* __restrict__ f0, const KnSegTable seg,
                                                                 float* __restrict__ result, float* __restrict__ ws) {
     const long o = seg.off[blockIdx.x];
     log_f0_median_body(f0 + o, seg.off[blockIdx.x + 1] - o, result + 2 * blockIdx.x, ws + o);
@@ -85,13 +80,8 @@ __device__ __forceinline__ void shift_f0_body(const float* __restrict__ f0, long
     out[i] = f != 0.f ? exp_rn((log_rn(f) + pmed[0]) - qmed[0]) : f;
 }
 
-__global__ void shift_f0_kernel(const float* __restrict__ f0, long n, const float* __restrict__ qmed,
-                                const float* __restrict__ pmed, float* __restrict__ out) {
-    shift_f0_body(f0, n, qmed, pmed, out, (long)blockIdx.x * blockDim.x + threadIdx.x);
-}
-
 // blockIdx.y = segment, blockIdx.x covers the longest segment
-__global__ void shift_f0_seg_kernel(const float* __restrict__ f0, const KnSegTable seg, const float* __restrict__ qmed,
+__global__ void shift_f0_kernel(const float* __restrict__ f0, const KnSegTable seg, const float* __restrict__ qmed,
                                     const float* __restrict__ pmed, float* __restrict__ out) {
     const long o = seg.off[blockIdx.y];
     shift_f0_body(f0 + o, seg.off[blockIdx.y + 1] - o, qmed + 2 * blockIdx.y, pmed, out + o, (long)blockIdx.x * blockDim.x + threadIdx.x);
@@ -247,16 +237,8 @@ __device__ __forceinline__ void concat_reselect_body(
     }
 }
 
-__global__ __launch_bounds__(256) void concat_reselect_kernel(
-    const long* __restrict__ idx_in, const float* __restrict__ q, const float* __restrict__ qn, long nq,
-    const float* __restrict__ pool, const float* __restrict__ pn, long np, int dim,
-    const float* __restrict__ sf0, const float* __restrict__ pf0, int use_f0, float concat_weight,
-    long* __restrict__ idx_out) {
-    concat_reselect_body(idx_in, q, qn, nq, pool, pn, np, dim, sf0, pf0, use_f0, concat_weight, idx_out);
-}
-
 // block s walks segment s: a sequence of its own (its frame 0 keeps its neighbours, nothing is read across a boundary)
-__global__ __launch_bounds__(256) void concat_reselect_seg_kernel(
+__global__ __launch_bounds__(256) void concat_reselect_kernel(
     const long* __restrict__ idx_in, const float* __restrict__ q, const float* __restrict__ qn, const KnSegTable seg,
     const float* __restrict__ pool, const float* __restrict__ pn, long np, int dim,
     const float* __restrict__ sf0, const float* __restrict__ pf0, int use_f0, float concat_weight,
@@ -615,17 +597,9 @@ __device__ __forceinline__ void concat_reselect_pipe_body(
 #undef KN_TICK
 }
 
-template <bool use_f0>
-__global__ __launch_bounds__(LT) void concat_reselect_pipe_kernel(
-    const long* __restrict__ idx_in, const float* __restrict__ q, const float* __restrict__ qn, long nq,
-    const float* __restrict__ pool, const float* __restrict__ pn, long np, int dim,
-    const float* __restrict__ sf0, const float* __restrict__ pf0, float concat_weight, long* __restrict__ idx_out) {
-    concat_reselect_pipe_body<use_f0>(idx_in, q, qn, nq, pool, pn, np, dim, sf0, pf0, concat_weight, idx_out);
-}
-
 // block s walks segment s; the query's buffer resource covers the segment's own rows
 template <bool use_f0>
-__global__ __launch_bounds__(LT) void concat_reselect_pipe_seg_kernel(
+__global__ __launch_bounds__(LT) void concat_reselect_pipe_kernel(
     const long* __restrict__ idx_in, const float* __restrict__ q, const float* __restrict__ qn, const KnSegTable seg,
     const float* __restrict__ pool, const float* __restrict__ pn, long np, int dim,
     const float* __restrict__ sf0, const float* __restrict__ pf0, float concat_weight, long* __restrict__ idx_out) {
@@ -636,18 +610,71 @@ __global__ __launch_bounds__(LT) void concat_reselect_pipe_seg_kernel(
 
 }  // namespace
 
+// ---- one launcher per stage: the argument checks, the route and the launch for a validated segment table.  `entry`: the public
+//      entry point, for the messages.  The single-sequence entry points are the one-segment case (kn_seg_one). -----------------
+static int log_f0_median_launch(const KnSegTable& seg, const char* entry, const float* f0, float* result, float* workspace,
+                                void* stream) {
+    KN_REQUIRE(f0 && result && workspace, "%s: null pointer", entry);
+    hipLaunchKernelGGL(log_f0_median_kernel, dim3((unsigned)seg.n), dim3(1024), 0, (hipStream_t)stream, f0, seg, result, workspace);
+    return knnsvc_check_launch(entry);
+}
+
+static int shift_f0_launch(const KnSegTable& seg, const char* entry, const float* f0, const float* query_median,
+                           const float* pool_median, float* shifted, void* stream) {
+    KN_REQUIRE(f0 && query_median && pool_median && shifted, "%s: null pointer", entry);
+    long longest = 0;
+    for (int s = 0; s < seg.n; ++s) longest = seg.off[s + 1] - seg.off[s] > longest ? seg.off[s + 1] - seg.off[s] : longest;
+    hipLaunchKernelGGL(shift_f0_kernel, dim3((unsigned)cdiv64(longest, 256), (unsigned)seg.n), dim3(256), 0, (hipStream_t)stream,
+                       f0, seg, query_median, pool_median, shifted);
+    return knnsvc_check_launch(entry);
+}
+
+static int concat_reselect_launch(const KnSegTable& seg, const char* entry, const int64_t* idx_in, const float* q, const float* q_norm,
+                                  const float* pool, const float* p_norm, int64_t np, int32_t dim, const float* shifted_f0,
+                                  const float* pool_f0, int32_t use_f0, float concat_weight, int64_t* idx_out, void* stream) {
+    KN_REQUIRE(idx_in && q && q_norm && pool && p_norm && idx_out, "%s: null pointer", entry);
+    KN_REQUIRE(np > 0 && dim > 0 && dim % 4 == 0, "%s: bad sizes", entry);
+    KN_REQUIRE(!use_f0 || (shifted_f0 && pool_f0), "%s: f0 variant needs both f0 arrays", entry);
+    KN_REQUIRE(((uintptr_t)q & 15) == 0 && ((uintptr_t)pool & 15) == 0, "%s: 16-byte alignment", entry);
+    const size_t lds = (size_t)(2 * NC + 2) * dim * 4;
+    KN_REQUIRE(dim <= 1024 || lds <= 150 * 1024, "%s: feature dim too large for LDS", entry);
+    const long nq = seg.off[seg.n];        // the route is chosen on the stacked arrays
+    const dim3 grid((unsigned)seg.n);
+    if (dim <= 1024 && (unsigned long long)np * dim * 4 < 0xFFFFFFFFull && (unsigned long long)nq * dim * 4 < 0xFFFFFFFFull) {
+        // KNNSVC_CONCAT_OWN_CU=1: ask for (nearly) the whole LDS of the CU so that no other kernel's workgroup is placed next to this
+        // one.  Debugging aid from round 3's determinism hunt (see the Makefile's note on -fno-slp-vectorize: with compiler-made
+        // packed-fp32 math this kernel's sums were perturbed by MFMA-issuing neighbours on its CU; isolation removed the symptom
+        // before the cause was found).
+        size_t pl = (size_t)26 * dim * 4;
+        { const char* e = getenv("KNNSVC_CONCAT_OWN_CU"); if (e && e[0] == '1' && pl < (size_t)158 * 1024) pl = (size_t)158 * 1024; }
+        if (const int rc = use_f0 ? kn_lds_optin<concat_reselect_pipe_kernel<true>>((int)pl, entry)
+                                  : kn_lds_optin<concat_reselect_pipe_kernel<false>>((int)pl, entry))
+            return rc;
+        if (use_f0)
+            hipLaunchKernelGGL(concat_reselect_pipe_kernel<true>, grid, dim3(LT), pl, (hipStream_t)stream, (const long*)idx_in, q, q_norm,
+                               seg, pool, p_norm, (long)np, dim, shifted_f0, pool_f0, concat_weight, (long*)idx_out);
+        else
+            hipLaunchKernelGGL(concat_reselect_pipe_kernel<false>, grid, dim3(LT), pl, (hipStream_t)stream, (const long*)idx_in, q, q_norm,
+                               seg, pool, p_norm, (long)np, dim, shifted_f0, pool_f0, concat_weight, (long*)idx_out);
+        return knnsvc_check_launch(entry);
+    }
+    if (const int rc = kn_lds_optin<concat_reselect_kernel>((int)lds, entry)) return rc;
+    hipLaunchKernelGGL(concat_reselect_kernel, grid, dim3(256), lds, (hipStream_t)stream, (const long*)idx_in, q, q_norm, seg, pool,
+                       p_norm, (long)np, dim, shifted_f0, pool_f0, use_f0, concat_weight, (long*)idx_out);
+    return knnsvc_check_launch(entry);
+}
+
 extern "C" int knnsvc_log_f0_median(const float* f0, int64_t n, float* result, float* workspace, void* stream) {
-    KN_REQUIRE(f0 && result && workspace && n > 0, "log_f0_median: bad arguments");
-    hipLaunchKernelGGL(log_f0_median_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, f0, (long)n, result, workspace);
-    return knnsvc_check_launch("log_f0_median");
+    KnSegTable seg;
+    if (const int rc = kn_seg_one(n, "log_f0_median", &seg)) return rc;
+    return log_f0_median_launch(seg, "log_f0_median", f0, result, workspace, stream);
 }
 
 extern "C" int knnsvc_shift_f0(const float* f0, int64_t n, const float* query_median, const float* pool_median,
                                float* shifted, void* stream) {
-    KN_REQUIRE(f0 && query_median && pool_median && shifted && n > 0, "shift_f0: bad arguments");
-    hipLaunchKernelGGL(shift_f0_kernel, dim3((unsigned)cdiv64(n, 256)), dim3(256), 0, (hipStream_t)stream, f0, (long)n,
-                       query_median, pool_median, shifted);
-    return knnsvc_check_launch("shift_f0");
+    KnSegTable seg;
+    if (const int rc = kn_seg_one(n, "shift_f0", &seg)) return rc;
+    return shift_f0_launch(seg, "shift_f0", f0, query_median, pool_median, shifted, stream);
 }
 
 extern "C" int knnsvc_f0_rerank(const int64_t* nn_idx, int64_t nq, int32_t k, const float* shifted_f0,
@@ -663,58 +690,26 @@ extern "C" int knnsvc_concat_reselect(const int64_t* idx_in, const float* q, con
                                       const float* pool, const float* p_norm, int64_t np, int32_t dim,
                                       const float* shifted_f0, const float* pool_f0, int32_t use_f0,
                                       float concat_weight, int64_t* idx_out, void* stream) {
-    KN_REQUIRE(idx_in && q && q_norm && pool && p_norm && idx_out, "concat_reselect: null pointer");
-    KN_REQUIRE(nq > 0 && np > 0 && dim > 0 && dim % 4 == 0, "concat_reselect: bad sizes");
-    KN_REQUIRE(!use_f0 || (shifted_f0 && pool_f0), "concat_reselect: f0 variant needs both f0 arrays");
-    KN_REQUIRE(((uintptr_t)q & 15) == 0 && ((uintptr_t)pool & 15) == 0, "concat_reselect: 16-byte alignment");
-    if (dim <= 1024 && (unsigned long long)np * dim * 4 < 0xFFFFFFFFull && (unsigned long long)nq * dim * 4 < 0xFFFFFFFFull) {
-        // KNNSVC_CONCAT_OWN_CU=1: ask for (nearly) the whole LDS of the CU so that no other kernel's workgroup is placed next to this
-        // one.  Debugging aid from round 3's determinism hunt (see the Makefile's note on -fno-slp-vectorize: with compiler-made
-        // packed-fp32 math this kernel's sums were perturbed by MFMA-issuing neighbours on its CU; isolation removed the symptom
-        // before the cause was found).
-        size_t pl = (size_t)26 * dim * 4;
-        { const char* e = getenv("KNNSVC_CONCAT_OWN_CU"); if (e && e[0] == '1' && pl < (size_t)158 * 1024) pl = (size_t)158 * 1024; }
-        if (const int rc = use_f0 ? kn_lds_optin<concat_reselect_pipe_kernel<true>>((int)pl, "concat_reselect")
-                                  : kn_lds_optin<concat_reselect_pipe_kernel<false>>((int)pl, "concat_reselect"))
-            return rc;
-        if (use_f0)
-            hipLaunchKernelGGL(concat_reselect_pipe_kernel<true>, dim3(1), dim3(LT), pl, (hipStream_t)stream, (const long*)idx_in, q, q_norm,
-                               (long)nq, pool, p_norm, (long)np, dim, shifted_f0, pool_f0, concat_weight, (long*)idx_out);
-        else
-            hipLaunchKernelGGL(concat_reselect_pipe_kernel<false>, dim3(1), dim3(LT), pl, (hipStream_t)stream, (const long*)idx_in, q, q_norm,
-                               (long)nq, pool, p_norm, (long)np, dim, shifted_f0, pool_f0, concat_weight, (long*)idx_out);
-        return knnsvc_check_launch("concat_reselect_pipe");
-    }
-    const size_t lds = (size_t)(2 * NC + 2) * dim * 4;
-    KN_REQUIRE(lds <= 150 * 1024, "concat_reselect: feature dim too large for LDS");
-    if (const int rc = kn_lds_optin<concat_reselect_kernel>((int)lds, "concat_reselect")) return rc;
-    hipLaunchKernelGGL(concat_reselect_kernel, dim3(1), dim3(256), lds, (hipStream_t)stream, (const long*)idx_in, q,
-                       q_norm, (long)nq, pool, p_norm, (long)np, dim, shifted_f0, pool_f0, use_f0, concat_weight,
-                       (long*)idx_out);
-    return knnsvc_check_launch("concat_reselect");
+    KnSegTable seg;
+    if (const int rc = kn_seg_one(nq, "concat_reselect", &seg)) return rc;
+    return concat_reselect_launch(seg, "concat_reselect", idx_in, q, q_norm, pool, p_norm, np, dim, shifted_f0, pool_f0, use_f0,
+                                  concat_weight, idx_out, stream);
 }
 
-// ---- the same stages for n_seg independent sequences stacked row-wise (host_seg: offsets, validated on the host and handed to
-//      the kernels by value): block s runs the single-sequence body on segment s ----------------------------------------------
+// ---- n_seg independent sequences stacked row-wise (host_seg: row offsets, validated on the host and handed to the kernels by
+//      value): block s runs the sequence body on segment s ------------------------------------------------------------------
 extern "C" int knnsvc_log_f0_median_seg(const float* f0, const int64_t* host_seg, int32_t n_seg, float* result, float* workspace,
                                         void* stream) {
     KnSegTable seg;
     if (const int rc = kn_seg_table(host_seg, n_seg, "log_f0_median_seg", &seg)) return rc;
-    KN_REQUIRE(f0 && result && workspace, "log_f0_median_seg: null pointer");
-    hipLaunchKernelGGL(log_f0_median_seg_kernel, dim3((unsigned)n_seg), dim3(1024), 0, (hipStream_t)stream, f0, seg, result, workspace);
-    return knnsvc_check_launch("log_f0_median_seg");
+    return log_f0_median_launch(seg, "log_f0_median_seg", f0, result, workspace, stream);
 }
 
 extern "C" int knnsvc_shift_f0_seg(const float* f0, const int64_t* host_seg, int32_t n_seg, const float* query_median,
                                    const float* pool_median, float* shifted, void* stream) {
     KnSegTable seg;
     if (const int rc = kn_seg_table(host_seg, n_seg, "shift_f0_seg", &seg)) return rc;
-    KN_REQUIRE(f0 && query_median && pool_median && shifted, "shift_f0_seg: null pointer");
-    long longest = 0;
-    for (int s = 0; s < n_seg; ++s) longest = seg.off[s + 1] - seg.off[s] > longest ? seg.off[s + 1] - seg.off[s] : longest;
-    hipLaunchKernelGGL(shift_f0_seg_kernel, dim3((unsigned)cdiv64(longest, 256), (unsigned)n_seg), dim3(256), 0, (hipStream_t)stream,
-                       f0, seg, query_median, pool_median, shifted);
-    return knnsvc_check_launch("shift_f0_seg");
+    return shift_f0_launch(seg, "shift_f0_seg", f0, query_median, pool_median, shifted, stream);
 }
 
 extern "C" int knnsvc_concat_reselect_seg(const int64_t* idx_in, const float* q, const float* q_norm, const int64_t* host_seg,
@@ -723,29 +718,6 @@ extern "C" int knnsvc_concat_reselect_seg(const int64_t* idx_in, const float* q,
                                           int64_t* idx_out, void* stream) {
     KnSegTable seg;
     if (const int rc = kn_seg_table(host_seg, n_seg, "concat_reselect_seg", &seg)) return rc;
-    KN_REQUIRE(idx_in && q && q_norm && pool && p_norm && idx_out, "concat_reselect_seg: null pointer");
-    KN_REQUIRE(np > 0 && dim > 0 && dim % 4 == 0, "concat_reselect_seg: bad sizes");
-    KN_REQUIRE(!use_f0 || (shifted_f0 && pool_f0), "concat_reselect_seg: f0 variant needs both f0 arrays");
-    KN_REQUIRE(((uintptr_t)q & 15) == 0 && ((uintptr_t)pool & 15) == 0, "concat_reselect_seg: 16-byte alignment");
-    const size_t lds = (size_t)(2 * NC + 2) * dim * 4;
-    KN_REQUIRE(dim <= 1024 || lds <= 150 * 1024, "concat_reselect_seg: feature dim too large for LDS");
-    const long nq = seg.off[n_seg];        // the route is chosen on the stacked arrays
-    if (dim <= 1024 && (unsigned long long)np * dim * 4 < 0xFFFFFFFFull && (unsigned long long)nq * dim * 4 < 0xFFFFFFFFull) {
-        size_t pl = (size_t)26 * dim * 4;  // (see knnsvc_concat_reselect)
-        { const char* e = getenv("KNNSVC_CONCAT_OWN_CU"); if (e && e[0] == '1' && pl < (size_t)158 * 1024) pl = (size_t)158 * 1024; }
-        if (const int rc = use_f0 ? kn_lds_optin<concat_reselect_pipe_seg_kernel<true>>((int)pl, "concat_reselect_seg")
-                                  : kn_lds_optin<concat_reselect_pipe_seg_kernel<false>>((int)pl, "concat_reselect_seg"))
-            return rc;
-        if (use_f0)
-            hipLaunchKernelGGL(concat_reselect_pipe_seg_kernel<true>, dim3((unsigned)n_seg), dim3(LT), pl, (hipStream_t)stream, (const long*)idx_in,
-                               q, q_norm, seg, pool, p_norm, (long)np, dim, shifted_f0, pool_f0, concat_weight, (long*)idx_out);
-        else
-            hipLaunchKernelGGL(concat_reselect_pipe_seg_kernel<false>, dim3((unsigned)n_seg), dim3(LT), pl, (hipStream_t)stream, (const long*)idx_in,
-                               q, q_norm, seg, pool, p_norm, (long)np, dim, shifted_f0, pool_f0, concat_weight, (long*)idx_out);
-        return knnsvc_check_launch("concat_reselect_pipe_seg");
-    }
-    if (const int rc = kn_lds_optin<concat_reselect_seg_kernel>((int)lds, "concat_reselect_seg")) return rc;
-    hipLaunchKernelGGL(concat_reselect_seg_kernel, dim3((unsigned)n_seg), dim3(256), lds, (hipStream_t)stream, (const long*)idx_in, q,
-                       q_norm, seg, pool, p_norm, (long)np, dim, shifted_f0, pool_f0, use_f0, concat_weight, (long*)idx_out);
-    return knnsvc_check_launch("concat_reselect_seg");
+    return concat_reselect_launch(seg, "concat_reselect_seg", idx_in, q, q_norm, pool, p_norm, np, dim, shifted_f0, pool_f0, use_f0,
+                                  concat_weight, idx_out, stream);
 }

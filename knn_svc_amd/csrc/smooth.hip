@@ -28,8 +28,7 @@ __device__ __forceinline__ int tri(int i, int j) { return i < j ? i * 7 - i * (i
 // row_scale (optional) [nq][4]: candidate k of frame t and its +-1 neighbours are multiplied by row_scale[t][k]
 // (compute_weight_with_amp, ddsp_prematch_dataset.py:684-713); the centring argument is unchanged because the
 // coefficient vector still sums to zero.
-// The body of gram_kernel (one sequence, block t = pair t) and gram_seg_kernel (all pairs of all segments): idx, row_scale and
-// gram already at the sequence, nq its length.
+// The body of gram_kernel (all pairs of all segments): idx, row_scale and gram already at the sequence, nq its length, t the pair.
 __device__ __forceinline__ void gram_body(const long* __restrict__ idx, long nq, const float* __restrict__ pool,
                                           long np, int dim, int ld, const float* __restrict__ row_scale,
                                           float* __restrict__ gram, const long t) {
@@ -77,14 +76,9 @@ __device__ __forceinline__ void gram_body(const long* __restrict__ idx, long nq,
     }
 }
 
-__global__ __launch_bounds__(256) void gram_kernel(const long* __restrict__ idx, long nq, const float* __restrict__ pool,
-                                                  long np, int dim, int ld, const float* __restrict__ row_scale,
-                                                  float* __restrict__ gram) {
-    gram_body(idx, nq, pool, np, dim, ld, row_scale, gram, blockIdx.x);
-}
-
-// Segments of knnsvc_smooth_weights_seg: row offsets, and where each segment's workspace (Gram | state | exchange, the layout of
-// the single-sequence call) starts, in units of 64 bytes from the aligned workspace base.  By value, like KnSegTable.
+// Segments of knnsvc_smooth_weights[_seg]: row offsets, and where each segment's workspace (Gram [28][nq] | state: theta, m, v, vmax,
+// best, scratch, 6 x [nq] float4 | exchange [2][nq][4] when LDS is too small) starts, in units of 64 bytes from the aligned
+// workspace base.  By value, like KnSegTable.
 struct SmoothSegs { int n; long off[KNNSVC_MAX_SEGMENTS + 1]; unsigned ws64[KNNSVC_MAX_SEGMENTS]; };
 // the segments one launch works on: block b -> segment id[b]
 struct SegList { int n; unsigned char id[KNNSVC_MAX_SEGMENTS]; };
@@ -92,7 +86,7 @@ struct SegList { int n; unsigned char id[KNNSVC_MAX_SEGMENTS]; };
 __device__ __forceinline__ float* seg_ws(float* base, const SmoothSegs& sg, int s) { return base + (size_t)sg.ws64[s] * 16; }
 
 // one launch over the adjacent pairs of all segments: segment s has len - 1 of them, pair numbers start at off[s] - s
-__global__ __launch_bounds__(256) void gram_seg_kernel(const long* __restrict__ idx, const SmoothSegs sg, const float* __restrict__ pool,
+__global__ __launch_bounds__(256) void gram_kernel(const long* __restrict__ idx, const SmoothSegs sg, const float* __restrict__ pool,
                                                       long np, int dim, int ld, const float* __restrict__ row_scale,
                                                       float* __restrict__ ws) {
     const long b = blockIdx.x;
@@ -242,16 +236,9 @@ __device__ __forceinline__ void adam_body(long nq, int dim, float scale, int max
 inline size_t ws_floats(long nq) { return (size_t)GE * nq + (size_t)6 * 4 * nq + (size_t)2 * 4 * nq; }
 constexpr long ADAM_LDS_ROWS = 144 * 1024 / (2 * KW * 4);     // longest sequence whose weight / gradient exchange fits LDS (adam_kernel)
 
-__global__ __launch_bounds__(1024) void adam_kernel(long nq, int dim, float scale, int max_iter,
-                                                   const float* __restrict__ gram, float* __restrict__ state,
-                                                   float* __restrict__ xch_global, int use_lds,
-                                                   float* __restrict__ out_w, int* __restrict__ out_iters) {
-    adam_body(nq, dim, scale, max_iter, gram, state, xch_global, use_lds, out_w, out_iters);
-}
-
 // block b runs the loop of segment list.id[b] in that segment's own workspace; LDS or the global exchange buffer as the segment
 // would get alone
-__global__ __launch_bounds__(1024) void adam_seg_kernel(const SmoothSegs sg, const SegList list, int dim, float scale, int max_iter,
+__global__ __launch_bounds__(1024) void adam_kernel(const SmoothSegs sg, const SegList list, int dim, float scale, int max_iter,
                                                        float* __restrict__ ws, float* __restrict__ out_w, int* __restrict__ out_iters) {
     const int s = list.id[blockIdx.x];
     const long o = sg.off[s], nq = sg.off[s + 1] - o;
@@ -390,27 +377,15 @@ __device__ __forceinline__ void adam_reg_body(long nq, int dim, float scale, int
 }
 
 template <int FPT>
-__global__ __launch_bounds__(512) void adam_reg_kernel(long nq, int dim, float scale, int max_iter,
-                                                      const float* __restrict__ gram, float* __restrict__ out_w,
-                                                      int* __restrict__ out_iters) {
-    adam_reg_body<FPT>(nq, dim, scale, max_iter, gram, out_w, out_iters);
-}
-
-template <int FPT>
-__global__ __launch_bounds__(512) void adam_reg_seg_kernel(const SmoothSegs sg, const SegList list, int dim, float scale, int max_iter,
+__global__ __launch_bounds__(512) void adam_reg_kernel(const SmoothSegs sg, const SegList list, int dim, float scale, int max_iter,
                                                           float* __restrict__ ws, float* __restrict__ out_w, int* __restrict__ out_iters) {
     const int s = list.id[blockIdx.x];
     const long o = sg.off[s];
     adam_reg_body<FPT>(sg.off[s + 1] - o, dim, scale, max_iter, seg_ws(ws, sg, s), out_w + o * KW, out_iters ? out_iters + s : out_iters);
 }
 
-__global__ void fill_quarter_kernel(float* w, long n) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) w[i] = 0.25f;
-}
-
-// segments of one row (no adjacent pair): softmax(0) and zero iterations, as knnsvc_smooth_weights answers them
-__global__ void fill_quarter_seg_kernel(const SmoothSegs sg, const SegList list, float* __restrict__ out_w, int* __restrict__ out_iters) {
+// segments of one row (no adjacent pair): softmax(0) and zero iterations
+__global__ void fill_quarter_kernel(const SmoothSegs sg, const SegList list, float* __restrict__ out_w, int* __restrict__ out_iters) {
     const int s = list.id[blockIdx.x];
     if (threadIdx.x < KW) out_w[sg.off[s] * KW + threadIdx.x] = 0.25f;
     if (threadIdx.x == 0 && out_iters) out_iters[s] = 0;
@@ -423,91 +398,40 @@ inline size_t seg_ws_bytes(long nq) { return (ws_floats(nq) * 4 + 64 + 63) & ~(s
 
 extern "C" size_t knnsvc_smooth_workspace_bytes(int64_t nq) { return nq > 0 ? ws_floats(nq) * 4 + 64 : 0; }
 
-extern "C" int knnsvc_smooth_weights(const int64_t* idx, int64_t nq, const float* pool, int64_t np, int32_t dim,
-                                     int32_t ld, float scale, const float* row_scale, int32_t max_iter, float* out_w,
-                                     int32_t* out_iters, void* workspace, size_t workspace_bytes, void* stream) {
-    KN_REQUIRE(idx && pool && out_w && workspace, "smooth_weights: null pointer");
-    KN_REQUIRE(nq > 0 && np > 0 && dim > 0 && ld >= dim && max_iter != 0, "smooth_weights: bad sizes");
-    KN_REQUIRE(((uintptr_t)out_w & 15) == 0, "smooth_weights: out_w must be 16-byte aligned");
-    if (workspace_bytes < knnsvc_smooth_workspace_bytes(nq))
-        return knnsvc_fail(KNNSVC_EWORKSPACE, "smooth_weights: workspace %zu < %zu bytes", workspace_bytes,
-                           knnsvc_smooth_workspace_bytes(nq));
-    hipStream_t st = (hipStream_t)stream;
-    if (nq < 2) {      // no adjacent pair: the reference's loss is NaN and never improves -> softmax(0)
-        hipLaunchKernelGGL(fill_quarter_kernel, dim3(1), dim3(64), 0, st, out_w, (long)nq * 4);
-        if (out_iters) (void)kn_zero_async(out_iters, sizeof(int), st);
-        return knnsvc_check_launch("smooth_weights(fill)");
-    }
-    float* base = (float*)(((uintptr_t)workspace + 63) & ~(uintptr_t)63);
-    float* gram = base;                                 // [36][nq]
-    float* state = gram + (size_t)GE * nq;        // theta, m, v, vmax, best, scratch : 6 x [nq] float4
-    float* xch = state + (size_t)6 * 4 * nq;            // [2][nq][4] when LDS is too small
-    const size_t gl = (size_t)8 * dim * 4;
-    KN_REQUIRE(gl <= 150 * 1024, "smooth_weights: feature dim too large for LDS");
-    if (const int rc = kn_lds_optin<gram_kernel>((int)gl, "smooth_weights")) return rc;
-    hipLaunchKernelGGL(gram_kernel, dim3((unsigned)(nq - 1)), dim3(256), gl, st, (const long*)idx, (long)nq, pool, (long)np,
-                       dim, ld, row_scale, gram);
-    int rc = knnsvc_check_launch("gram");
-    if (rc) return rc;
-    if (nq <= 1536) {            // register-resident loop
-        const size_t rl = (size_t)nq * 2 * KW * 4;
-        if ((rc = kn_lds_optin<adam_reg_kernel<1>>(65536, "smooth_weights")) || (rc = kn_lds_optin<adam_reg_kernel<2>>(65536, "smooth_weights")) ||
-            (rc = kn_lds_optin<adam_reg_kernel<3>>(65536, "smooth_weights")))
-            return rc;
-#define KN_ADAM(F)                                                                                                     \
-    hipLaunchKernelGGL(adam_reg_kernel<F>, dim3(1), dim3(512), rl, st, (long)nq, dim, scale, max_iter, (const float*)gram, out_w, out_iters);
-        if (nq <= 512) { KN_ADAM(1) } else if (nq <= 1024) { KN_ADAM(2) } else { KN_ADAM(3) }
-#undef KN_ADAM
-        return knnsvc_check_launch("adam_reg");
-    }
-    size_t al = (size_t)nq * 2 * KW * 4;
-    int use_lds = nq <= ADAM_LDS_ROWS;
-    if (!use_lds) al = 0;
-    if ((rc = kn_lds_optin<adam_kernel>((int)al, "smooth_weights"))) return rc;
-    hipLaunchKernelGGL(adam_kernel, dim3(1), dim3(1024), al, st, (long)nq, dim, scale, max_iter, (const float*)gram, state,
-                       xch, use_lds, out_w, out_iters);
-    return knnsvc_check_launch("adam");
-}
-
-static int smooth_segs(const int64_t* host_seg, int32_t n_seg, const char* entry, SmoothSegs* sg, size_t* bytes) {
-    KnSegTable t;
-    if (const int rc = kn_seg_table(host_seg, n_seg, entry, &t)) return rc;
-    sg->n = n_seg;
+// row offsets and workspace placement of a validated table; *bytes: the workspace of the segmented call
+static int smooth_segs(const KnSegTable& t, const char* entry, SmoothSegs* sg, size_t* bytes) {
+    sg->n = t.n;
     size_t at = 0;
     for (int s = 0; s <= KNNSVC_MAX_SEGMENTS; ++s) {
         sg->off[s] = t.off[s];
         if (s < KNNSVC_MAX_SEGMENTS) sg->ws64[s] = (unsigned)(at / 64);
-        if (s < n_seg) at += seg_ws_bytes(t.off[s + 1] - t.off[s]);
+        if (s < t.n) at += seg_ws_bytes(t.off[s + 1] - t.off[s]);
     }
     if (at / 64 > 0xFFFFFFFFull) return knnsvc_fail(KNNSVC_EINVAL, "%s: segments too long", entry);
     *bytes = at;
     return KNNSVC_OK;
 }
 
-extern "C" size_t knnsvc_smooth_seg_workspace_bytes(const int64_t* host_seg, int32_t n_seg) {
-    SmoothSegs sg; size_t bytes = 0;
-    return smooth_segs(host_seg, n_seg, "smooth_seg_workspace_bytes", &sg, &bytes) ? 0 : bytes;
-}
-
-extern "C" int knnsvc_smooth_weights_seg(const int64_t* idx, const int64_t* host_seg, int32_t n_seg, const float* pool, int64_t np,
-                                         int32_t dim, int32_t ld, float scale, const float* row_scale, int32_t max_iter, float* out_w,
-                                         int32_t* out_iters, void* workspace, size_t workspace_bytes, void* stream) {
-    SmoothSegs sg; size_t need = 0;
-    if (const int rc = smooth_segs(host_seg, n_seg, "smooth_weights_seg", &sg, &need)) return rc;
-    KN_REQUIRE(idx && pool && out_w && workspace, "smooth_weights_seg: null pointer");
-    KN_REQUIRE(np > 0 && dim > 0 && ld >= dim && max_iter != 0, "smooth_weights_seg: bad sizes");
-    KN_REQUIRE(((uintptr_t)out_w & 15) == 0, "smooth_weights_seg: out_w must be 16-byte aligned");
+// The argument checks, the class-by-length choice and the launches, once.  `need`: the workspace size the entry point documents
+// (knnsvc_smooth_workspace_bytes for the single call, knnsvc_smooth_seg_workspace_bytes for the segmented one); `entry`: its name,
+// for the messages.
+static int smooth_weights_launch(const SmoothSegs& sg, size_t need, const char* entry, const int64_t* idx, const float* pool,
+                                 int64_t np, int32_t dim, int32_t ld, float scale, const float* row_scale, int32_t max_iter,
+                                 float* out_w, int32_t* out_iters, void* workspace, size_t workspace_bytes, void* stream) {
+    KN_REQUIRE(idx && pool && out_w && workspace, "%s: null pointer", entry);
+    KN_REQUIRE(np > 0 && dim > 0 && ld >= dim && max_iter != 0, "%s: bad sizes", entry);
+    KN_REQUIRE(((uintptr_t)out_w & 15) == 0, "%s: out_w must be 16-byte aligned", entry);
     const size_t gl = (size_t)8 * dim * 4;
-    KN_REQUIRE(gl <= 150 * 1024, "smooth_weights_seg: feature dim too large for LDS");
-    if (workspace_bytes < need)
-        return knnsvc_fail(KNNSVC_EWORKSPACE, "smooth_weights_seg: workspace %zu < %zu bytes", workspace_bytes, need);
+    KN_REQUIRE(gl <= 150 * 1024, "%s: feature dim too large for LDS", entry);
+    if (workspace_bytes < need) return knnsvc_fail(KNNSVC_EWORKSPACE, "%s: workspace %zu < %zu bytes", entry, workspace_bytes, need);
     hipStream_t st = (hipStream_t)stream;
     float* base = (float*)(((uintptr_t)workspace + 63) & ~(uintptr_t)63);
-    // the loop variant each segment would get alone: 0 one row (no loop), 1..3 adam_reg_kernel<1|2|3>, 4 adam_kernel
+    // the loop variant each segment would get alone: 0 one row (no adjacent pair: the reference's loss is NaN and never improves ->
+    // softmax(0), no loop), 1..3 adam_reg_kernel<1|2|3>, 4 adam_kernel
     SegList cls[5];
     long longest[5] = {0, 0, 0, 0, 0}, lds_rows = 0;
     for (int c = 0; c < 5; ++c) cls[c].n = 0;
-    for (int s = 0; s < n_seg; ++s) {
+    for (int s = 0; s < sg.n; ++s) {
         const long nq = sg.off[s + 1] - sg.off[s];
         const int c = nq < 2 ? 0 : (nq <= 512 ? 1 : (nq <= 1024 ? 2 : (nq <= 1536 ? 3 : 4)));
         cls[c].id[cls[c].n++] = (unsigned char)s;
@@ -516,28 +440,56 @@ extern "C" int knnsvc_smooth_weights_seg(const int64_t* idx, const int64_t* host
     }
     int rc;
     if (cls[0].n) {
-        hipLaunchKernelGGL(fill_quarter_seg_kernel, dim3((unsigned)cls[0].n), dim3(64), 0, st, sg, cls[0], out_w, out_iters);
-        if ((rc = knnsvc_check_launch("smooth_weights_seg(fill)"))) return rc;
+        hipLaunchKernelGGL(fill_quarter_kernel, dim3((unsigned)cls[0].n), dim3(64), 0, st, sg, cls[0], out_w, out_iters);
+        if ((rc = knnsvc_check_launch(entry))) return rc;
     }
-    const long pairs = sg.off[n_seg] - n_seg;
+    const long pairs = sg.off[sg.n] - sg.n;
     if (pairs == 0) return KNNSVC_OK;
-    if ((rc = kn_lds_optin<gram_seg_kernel>((int)gl, "smooth_weights_seg"))) return rc;
-    hipLaunchKernelGGL(gram_seg_kernel, dim3((unsigned)pairs), dim3(256), gl, st, (const long*)idx, sg, pool, (long)np, dim, ld, row_scale, base);
-    if ((rc = knnsvc_check_launch("gram_seg"))) return rc;
+    if ((rc = kn_lds_optin<gram_kernel>((int)gl, entry))) return rc;
+    hipLaunchKernelGGL(gram_kernel, dim3((unsigned)pairs), dim3(256), gl, st, (const long*)idx, sg, pool, (long)np, dim, ld, row_scale, base);
+    if ((rc = knnsvc_check_launch(entry))) return rc;
 #define KN_ADAM_SEG(F)                                                                                                               \
     if (cls[F].n) {                                                                                                                  \
-        if ((rc = kn_lds_optin<adam_reg_seg_kernel<F>>(65536, "smooth_weights_seg"))) return rc;                                     \
-        hipLaunchKernelGGL(adam_reg_seg_kernel<F>, dim3((unsigned)cls[F].n), dim3(512), (size_t)longest[F] * 2 * KW * 4, st, sg, cls[F], dim, scale, \
+        if ((rc = kn_lds_optin<adam_reg_kernel<F>>(65536, entry))) return rc;                                                    \
+        hipLaunchKernelGGL(adam_reg_kernel<F>, dim3((unsigned)cls[F].n), dim3(512), (size_t)longest[F] * 2 * KW * 4, st, sg, cls[F], dim, scale, \
                            max_iter, base, out_w, out_iters);                                                                        \
-        if ((rc = knnsvc_check_launch("adam_reg_seg"))) return rc;                                                                   \
+        if ((rc = knnsvc_check_launch(entry))) return rc;                                                                            \
     }
     KN_ADAM_SEG(1) KN_ADAM_SEG(2) KN_ADAM_SEG(3)
 #undef KN_ADAM_SEG
     if (cls[4].n) {
         const size_t al = (size_t)lds_rows * 2 * KW * 4;         // of the segments that exchange through LDS; the others take none
-        if ((rc = kn_lds_optin<adam_seg_kernel>((int)al, "smooth_weights_seg"))) return rc;
-        hipLaunchKernelGGL(adam_seg_kernel, dim3((unsigned)cls[4].n), dim3(1024), al, st, sg, cls[4], dim, scale, max_iter, base, out_w, out_iters);
-        if ((rc = knnsvc_check_launch("adam_seg"))) return rc;
+        if ((rc = kn_lds_optin<adam_kernel>((int)al, entry))) return rc;
+        hipLaunchKernelGGL(adam_kernel, dim3((unsigned)cls[4].n), dim3(1024), al, st, sg, cls[4], dim, scale, max_iter, base, out_w, out_iters);
+        if ((rc = knnsvc_check_launch(entry))) return rc;
     }
     return KNNSVC_OK;
+}
+
+extern "C" int knnsvc_smooth_weights(const int64_t* idx, int64_t nq, const float* pool, int64_t np, int32_t dim,
+                                     int32_t ld, float scale, const float* row_scale, int32_t max_iter, float* out_w,
+                                     int32_t* out_iters, void* workspace, size_t workspace_bytes, void* stream) {
+    KnSegTable t; SmoothSegs sg; size_t seg_bytes = 0;
+    int rc;
+    if ((rc = kn_seg_one(nq, "smooth_weights", &t)) || (rc = smooth_segs(t, "smooth_weights", &sg, &seg_bytes))) return rc;
+    // Its own size, not seg_bytes (which rounds up to 64): the one segment starts at the 64-byte-aligned base, at most 63 bytes
+    // into the workspace, and ends ws_floats(nq) * 4 bytes later.
+    return smooth_weights_launch(sg, knnsvc_smooth_workspace_bytes(nq), "smooth_weights", idx, pool, np, dim, ld, scale, row_scale,
+                                 max_iter, out_w, out_iters, workspace, workspace_bytes, stream);
+}
+
+extern "C" size_t knnsvc_smooth_seg_workspace_bytes(const int64_t* host_seg, int32_t n_seg) {
+    KnSegTable t; SmoothSegs sg; size_t bytes = 0;
+    if (kn_seg_table(host_seg, n_seg, "smooth_seg_workspace_bytes", &t) || smooth_segs(t, "smooth_seg_workspace_bytes", &sg, &bytes)) return 0;
+    return bytes;
+}
+
+extern "C" int knnsvc_smooth_weights_seg(const int64_t* idx, const int64_t* host_seg, int32_t n_seg, const float* pool, int64_t np,
+                                         int32_t dim, int32_t ld, float scale, const float* row_scale, int32_t max_iter, float* out_w,
+                                         int32_t* out_iters, void* workspace, size_t workspace_bytes, void* stream) {
+    KnSegTable t; SmoothSegs sg; size_t need = 0;
+    int rc;
+    if ((rc = kn_seg_table(host_seg, n_seg, "smooth_weights_seg", &t)) || (rc = smooth_segs(t, "smooth_weights_seg", &sg, &need))) return rc;
+    return smooth_weights_launch(sg, need, "smooth_weights_seg", idx, pool, np, dim, ld, scale, row_scale, max_iter, out_w, out_iters,
+                                 workspace, workspace_bytes, stream);
 }

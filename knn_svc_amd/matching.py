@@ -322,68 +322,12 @@ def wait_for_neighbours(nn_item, ready_event, device):
 
 def match_features(query_seq, query_f0, matching_list, matching_f0, harmonics_list, ckpt_type, post_opt,
                    return_debug=False, nn32=None, nan_flags=None, pool_prep=None, synth_list=None):
-    """The per-query body (ddsp_prematch_dataset.py:1189-1450) on device tensors.  ``synth_list``: the pool under the SYNTHESIS
-    layer weighting when it differs from the matching one (:349-350, 1157): the search and the concat re-selection run on
-    ``matching_list``, the smoothness weights and the weighted sums on ``synth_list`` (:1260, 1347-1350).  ``nn32`` may carry
-    neighbours already found by the pool-sharded search (knn_svc_amd.dist.sharded_knn).  ``nan_flags``: a
-    list that receives the kNN NaN flag instead of the host checking it here (the caller then calls
-    ``ops.raise_if_nan`` on each entry once everything is enqueued — keeps a stream pipeline free of syncs)."""
-    q = query_seq.contiguous()
-    P = matching_list
-    qn, qs = ops.row_norms(q)
-    pn, ps = pool_prep["stats"] if pool_prep is not None else ops.row_norms(P)
-    nan_flag = None
-    if nn32 is None:
-        # NaN check deferred to the end of the launch sequence (one host sync instead of a split stream)
-        nn32, _, nan_flag = ops.knn_topk(q, P, C.KNN_K, q_stats=(qn, qs), p_stats=(pn, ps), check_nan=False,
-                                         return_flag=True, prepared=pool_prep["split"] if pool_prep is not None else None)
-    cw, run_adam = parse_post_opt(post_opt)
-    with_harm = "wavlm_only" not in ckpt_type and "no_harm_no_amp" not in ckpt_type
-    # The WavLM-feature branch (concat re-selection -> Adam -> weighted sum) and the pitched branch
-    # (f0 shift -> re-rank -> concat re-selection -> Adam on harmonics) only share nn32, and each is a
-    # chain of single-workgroup latency-bound kernels: run them on two HIP streams.
-    main = torch.cuda.current_stream()
-    side = _side_stream(q.device)
-    side.wait_stream(main)
-    it1 = it2 = None
-    w = w2 = harm_w = None
-    with torch.cuda.stream(side):
-        qmed, pmed = ops.log_f0_median(query_f0), ops.log_f0_median(matching_f0)
-        shifted = ops.shift_f0(query_f0, qmed, pmed)
-        ranked = ops.f0_rerank(nn32, shifted, matching_f0)
-        idx2 = ranked[:, :C.KNN_USE].contiguous()
-        if cw != -1:
-            idx2 = ops.concat_reselect(idx2, q, qn, P, pn, shifted, matching_f0, concat_weight=cw)
-        if with_harm:
-            if run_adam:
-                w2, it2 = ops.smooth_weights(idx2, harmonics_list, 1000.0, return_iters=True)
-            harm_w = ops.weighted_gather(idx2, w2, harmonics_list)
-    idx = nn32[:, :C.KNN_USE].contiguous()
-    if cw != -1:
-        idx = ops.concat_reselect(idx, q, qn, P, pn, concat_weight=cw)
-    Ps = synth_list if synth_list is not None else P
-    if run_adam:
-        w, it1 = ops.smooth_weights(idx, Ps, 0.1, return_iters=True)
-    out_feats = ops.weighted_gather(idx, w, Ps)
-    main.wait_stream(side)
-    for t in (shifted, idx2, harm_w, w2):
-        if t is not None:
-            t.record_stream(main)
-    if nan_flag is not None:
-        if nan_flags is not None:
-            nan_flags.append(nan_flag)
-        else:
-            try:
-                ops.raise_if_nan(nan_flag)
-            except ops.KnnOverflow:         # the fused route's candidate buffer overflowed: once more on the dot-matrix route
-                with ops.fused_off():
-                    return match_features(query_seq, query_f0, matching_list, matching_f0, harmonics_list, ckpt_type, post_opt,
-                                          return_debug=return_debug, pool_prep=pool_prep, synth_list=synth_list)
-    if return_debug:
-        return out_feats, harm_w, shifted, dict(nn32=nn32, idx_wavlm=idx, w_wavlm=w, idx_harm=idx2, w_harm=w2,
-                                                iters_wavlm=it1 if it1 is not None else 0,
-                                                iters_harm=it2 if it2 is not None else 0)
-    return out_feats, harm_w, shifted
+    """The per-query body (ddsp_prematch_dataset.py:1189-1450) on device tensors: ``match_features_many`` (below, where the
+    arguments are described) of one utterance.  ``nn32`` may carry neighbours already found by the pool-sharded search
+    (knn_svc_amd.dist.sharded_knn); in the debug dict ``iters_*`` are one-element tensors, or 0 without the Adam stage."""
+    return match_features_many([query_seq], [query_f0], matching_list, matching_f0, harmonics_list, ckpt_type, post_opt,
+                               nn32s=None if nn32 is None else [nn32], nan_flags=nan_flags, pool_prep=pool_prep,
+                               synth_list=synth_list, return_debug=return_debug)[0]
 
 
 # How the match stage of SEVERAL items is put on the chip: "lanes" (one match_features per item on the lane streams, the default) or
@@ -410,32 +354,44 @@ def match_batch_size(match_batch=None) -> int:
     return n
 
 
+def _stacked(ts):
+    """The tensors' rows one after the other (a single tensor as it is)."""
+    return ts[0].contiguous() if len(ts) == 1 else torch.cat([t.contiguous() for t in ts], 0).contiguous()
+
+
 def match_features_many(query_seqs, query_f0s, matching_list, matching_f0, harmonics_list, ckpt_type, post_opt, nn32s=None,
                         nan_flags=None, pool_prep=None, synth_list=None, return_debug=False):
-    """``match_features`` for several query utterances against one pool, run ONCE over their stacked frames -> a list of per-item
-    tuples with the meaning of match_features' return value (views of the stacked outputs).  The row-wise stages (row norms, f0
-    re-rank, weighted sums) take the stacked rows as they are; the per-sequence stages (median, shift, concat re-selection,
-    smoothness weights) take the segment table: one workgroup per item running the code of the single-sequence call, so item i's
-    tensors are bit-identical to ``match_features`` of item i with the same ``nn32``.  ``nn32s``: per-item neighbour lists (or
-    None: one search over the stacked frames)."""
+    """The per-query body (ddsp_prematch_dataset.py:1189-1450) for several query utterances against one pool, run ONCE over their
+    stacked frames -> a list of per-item tuples (out_feats, harm or None, shifted_f0[, debug dict]) (views of the stacked outputs).
+    The row-wise stages (row norms, f0 re-rank, weighted sums) take the stacked rows as they are; the per-sequence stages (median,
+    shift, concat re-selection, smoothness weights) take the segment table: one workgroup per item, so item i's tensors are
+    bit-identical to the call with item i alone and the same ``nn32``.  ``synth_list``: the pool under the SYNTHESIS layer weighting
+    when it differs from the matching one (:349-350, 1157): the search and the concat re-selection run on ``matching_list``, the
+    smoothness weights and the weighted sums on ``synth_list`` (:1260, 1347-1350).  ``nn32s``: per-item neighbour lists (or None: one
+    search over the stacked frames).  ``nan_flags``: a list that receives the kNN NaN flag instead of the host checking it here
+    (the caller then calls ``ops.raise_if_nan`` on each entry once everything is enqueued — keeps a stream pipeline free of syncs)."""
     lens = [int(q.shape[0]) for q in query_seqs]
     seg = [0]
     for n in lens:
         seg.append(seg[-1] + n)
-    q = torch.cat([t.contiguous() for t in query_seqs], 0).contiguous()
-    query_f0 = torch.cat([t.reshape(-1) for t in query_f0s], 0).contiguous()
+    seg = ops.Segments(seg)                   # the host tables once for the six segmented calls
+    q = _stacked(query_seqs)
+    query_f0 = _stacked([t.reshape(-1) for t in query_f0s])
     P = matching_list
     qn, qs = ops.row_norms(q)
     pn, ps = pool_prep["stats"] if pool_prep is not None else ops.row_norms(P)
     nan_flag = None
     if nn32s is None or any(t is None for t in nn32s):
+        # NaN check deferred to the end of the launch sequence (one host sync instead of a split stream)
         nn32, _, nan_flag = ops.knn_topk(q, P, C.KNN_K, q_stats=(qn, qs), p_stats=(pn, ps), check_nan=False,
                                          return_flag=True, prepared=pool_prep["split"] if pool_prep is not None else None)
     else:
-        nn32 = torch.cat(list(nn32s), 0).contiguous()
+        nn32 = _stacked(list(nn32s))
     cw, run_adam = parse_post_opt(post_opt)
     with_harm = "wavlm_only" not in ckpt_type and "no_harm_no_amp" not in ckpt_type
-    # the two branches on the lane stream and its partner, as in match_features
+    # The WavLM-feature branch (concat re-selection -> Adam -> weighted sum) and the pitched branch
+    # (f0 shift -> re-rank -> concat re-selection -> Adam on harmonics) only share nn32, and each is a
+    # chain of single-workgroup latency-bound kernels: run them on two HIP streams.
     main = torch.cuda.current_stream()
     side = _side_stream(q.device)
     side.wait_stream(main)
@@ -469,7 +425,7 @@ def match_features_many(query_seqs, query_f0s, matching_list, matching_f0, harmo
         else:
             try:
                 ops.raise_if_nan(nan_flag)
-            except ops.KnnOverflow:         # as match_features: once more on the dot-matrix route
+            except ops.KnnOverflow:         # the fused route's candidate buffer overflowed: once more on the dot-matrix route
                 with ops.fused_off():
                     return match_features_many(query_seqs, query_f0s, matching_list, matching_f0, harmonics_list, ckpt_type, post_opt,
                                                pool_prep=pool_prep, synth_list=synth_list, return_debug=return_debug)
@@ -484,6 +440,24 @@ def match_features_many(query_seqs, query_f0s, matching_list, matching_f0, harmo
         else:
             out.append((of, hw, sf))
     return out
+
+
+def run_match_bodies(items, body, body_many, tail=None, *, device, lanes, match="lanes", match_batch=None):
+    """The match bodies of ``items``, and ``tail(item, result)`` behind each, on the lane / tail streams of a pipeline.LanePipeline
+    -> the results in item order.  ``match`` "lanes": ``body(item)`` per item; "segmented" (several items): the items in order, in
+    batches of ``match_batch``, each batch one ``body_many(batch)`` on a lane.  CPU tensors (the injected kernels of the gloo tests)
+    and a single lane without a tail run on the caller's stream, one after the other."""
+    items = list(items)
+    dev = torch.device(device)
+    segmented = match == "segmented" and len(items) > 1 and dev.type == "cuda"
+    if not items or dev.type != "cuda" or (tail is None and lanes <= 1 and not segmented):
+        heads = (body(i) for i in items)
+        return [h if tail is None else tail(i, h) for i, h in zip(items, heads)]
+    pipe = pipeline.LanePipeline(dev, max(1, lanes))
+    if segmented:
+        nb = match_batch_size(match_batch)
+        return pipe.run_batched([items[a:a + nb] for a in range(0, len(items), nb)], body_many, tail)
+    return pipe.run(items, body, tail)
 
 
 def _mix_of(weights, wavlm):
@@ -626,35 +600,25 @@ def match_at_inference_time(src_wav_file, ref_wav_file, wavlm: WavLMEncoder, mat
             extra = dict(synth_list=synth_list) if synth_list is not None else {}
             return match_features(query_pool[item], query_f0_pool[item], matching_list, matching_f0,
                                   harmonics_list, ckpt_type, post_opt, nan_flags=flags, pool_prep=prep, nn32=nn.get(item), **extra)
-        # match bodies in flight at once (each is a chain of single-workgroup recurrences: more lanes = more of them side by side)
-        lanes = min(int(os.environ.get("KNNSVC_MATCH_LANES", "3")), len(items)) if matching_list.is_cuda else 1   # (CPU tensors: injected kernels in the gloo tests)
-        # KNNSVC_MATCH=segmented (unsharded pool, several items): the items in order, in batches of KNNSVC_MATCH_BATCH, each batch one
-        # match_features_many on a lane
-        segmented = match_mode() == "segmented" and shard is None and len(items) > 1 and matching_list.is_cuda
         def body_many(batch):
             for item in batch:
                 wait_for_neighbours(nn.get(item), nn_ready.get(item), matching_list.device)
             return match_features_many([query_pool[it] for it in batch], [query_f0_pool[it] for it in batch], matching_list, matching_f0,
                                        harmonics_list, ckpt_type, post_opt, nn32s=[nn.get(it) for it in batch], nan_flags=flags,
                                        pool_prep=prep, synth_list=synth_list)
-        nb = match_batch_size()
-        batches = [items[a:a + nb] for a in range(0, len(items), nb)]
+        # match bodies in flight at once (each is a chain of single-workgroup recurrences: more lanes = more of them side by side);
+        # KNNSVC_MATCH=segmented (unsharded pool, several items): batches of KNNSVC_MATCH_BATCH items, each one body_many on a lane
+        lanes = min(int(os.environ.get("KNNSVC_MATCH_LANES", "3")), len(items))
+        tail = None
         if vocode_fn is not None and len(items) > 0:
             assert waves_out is not None
             tail = lambda item, r: r + (vocode_fn(r[0], r[2], r[1]),)
-            if segmented:
-                results = pipeline.LanePipeline(matching_list.device, max(1, lanes)).run_batched(batches, body_many, tail)
-            elif matching_list.is_cuda:
-                results = pipeline.LanePipeline(matching_list.device, max(1, lanes)).run(items, body, tail)
-            else:
-                results = [tail(i, body(i)) for i in items]
+        results = run_match_bodies(items, body, body_many, tail, device=matching_list.device, lanes=lanes,
+                                   match=match_mode() if shard is None else "lanes")
+        if tail is not None:
             for item, r in zip(items, results):
                 waves_out[item] = r[3]
             results = [r[:3] for r in results]
-        elif segmented:
-            results = pipeline.LanePipeline(matching_list.device, max(1, lanes)).run_batched(batches, body_many)
-        else:
-            results = pipeline.LanePipeline(matching_list.device, lanes).run(items, body) if lanes > 1 else [body(i) for i in items]
         for f in flags:
             ops.raise_if_nan(f)
         return items, results

@@ -800,24 +800,29 @@ def concat_reselect(idx4, q, q_norm, pool, p_norm, shifted_f0=None, pool_f0=None
 ADAM_FORCED_ITERS = None     # measurement aid (bench.py "value_long_adam"): run exactly this many iterations per loop
 
 
-def smooth_weights(idx4, pool, scale, max_iter=100000, return_iters=False, row_scale=None):
-    """``row_scale`` [nq,4]: the amp_ratio of compute_weight_with_amp (ddsp_prematch_dataset.py:684-804)."""
+def _smooth_args(name, idx4, pool, max_iter, row_scale):
+    """The checks smooth_weights and smooth_weights_seg share -> (contiguous idx4, max_iter as the library takes it)."""
     if ADAM_FORCED_ITERS:
         max_iter = -int(ADAM_FORCED_ITERS)
     _need(idx4, torch.int64, "idx4"); _need(pool, name="pool")
     if row_scale is not None:
         _need(row_scale, name="row_scale")
         if tuple(row_scale.shape) != tuple(idx4.shape) or not row_scale.is_contiguous():
-            raise KnnSvcError("smooth_weights: row_scale must be a contiguous [nq,4] tensor")
+            raise KnnSvcError(f"{name}: row_scale must be a contiguous [rows,4] tensor")
+    return idx4.contiguous(), int(max_iter)
+
+
+def smooth_weights(idx4, pool, scale, max_iter=100000, return_iters=False, row_scale=None):
+    """``row_scale`` [nq,4]: the amp_ratio of compute_weight_with_amp (ddsp_prematch_dataset.py:684-804)."""
+    idx4, max_iter = _smooth_args("smooth_weights", idx4, pool, max_iter, row_scale)
     lib = _lib.load()
-    idx4 = idx4.contiguous()
     nq = idx4.shape[0]
     npool, dim = pool.shape
     ws_bytes = lib.knnsvc_smooth_workspace_bytes(nq)
     ws = torch.empty(ws_bytes, device=pool.device, dtype=torch.uint8)
     w = torch.empty(nq, 4, device=pool.device, dtype=torch.float32)
     iters = torch.zeros(1, device=pool.device, dtype=torch.int32)
-    check(lib.knnsvc_smooth_weights(_p(idx4), nq, _p(pool), npool, dim, pool.stride(0), float(scale), _p(row_scale), int(max_iter),
+    check(lib.knnsvc_smooth_weights(_p(idx4), nq, _p(pool), npool, dim, pool.stride(0), float(scale), _p(row_scale), max_iter,
                                     _p(w), _p(iters), _p(ws), ws_bytes, _stream()), "smooth_weights")
     return (w, iters) if return_iters else w
 
@@ -839,39 +844,50 @@ def _seg_chunks(seg):
     return out
 
 
-def _rows_match(seg, t, name):
-    if t.shape[0] != int(seg[-1]):
-        raise KnnSvcError(f"{name}: {t.shape[0]} rows for a segment table that ends at {int(seg[-1])}")
+class Segments:
+    """Row offsets prepared once (the host tables of _seg_chunks) for any number of *_seg calls; each takes the Python list or this."""
+
+    def __init__(self, seg):
+        self.chunks, self.n, self.total = _seg_chunks(seg), len(seg) - 1, int(seg[-1])
+
+
+def _segments(seg, name, *stacked):
+    """``seg`` as Segments, checked against the row count of the ``stacked`` tensors."""
+    seg = seg if isinstance(seg, Segments) else Segments(seg)
+    for t in stacked:
+        if t.shape[0] != seg.total:
+            raise KnnSvcError(f"{name}: {t.shape[0]} rows for a segment table that ends at {seg.total}")
+    return seg
 
 
 def log_f0_median_seg(f0, seg):
     """-> tensor [n_seg, 2]: ``log_f0_median`` of every segment."""
-    _need(f0, name="f0"); _rows_match(seg, f0, "log_f0_median_seg")
+    _need(f0, name="f0"); seg = _segments(seg, "log_f0_median_seg", f0)
     f0 = f0.contiguous()
-    res = torch.empty(len(seg) - 1, 2, device=f0.device, dtype=torch.float32)
+    res = torch.empty(seg.n, 2, device=f0.device, dtype=torch.float32)
     ws = torch.empty(f0.numel(), device=f0.device, dtype=torch.float32)
-    for a, r0, tab in _seg_chunks(seg):
+    for a, r0, tab in seg.chunks:
         check(_lib.load().knnsvc_log_f0_median_seg(_p(f0[r0:]), tab, len(tab) - 1, _p(res[a:]), _p(ws[r0:]), _stream()), "log_f0_median_seg")
     return res
 
 
 def shift_f0_seg(f0, seg, qmed, pmed):
     """``qmed`` [n_seg, 2] from log_f0_median_seg, ``pmed`` [2] -> shifted f0 of the stacked rows."""
-    _need(f0, name="f0"); _rows_match(seg, f0, "shift_f0_seg")
+    _need(f0, name="f0"); seg = _segments(seg, "shift_f0_seg", f0)
     f0 = f0.contiguous()
     out = torch.empty_like(f0)
-    for a, r0, tab in _seg_chunks(seg):
+    for a, r0, tab in seg.chunks:
         check(_lib.load().knnsvc_shift_f0_seg(_p(f0[r0:]), tab, len(tab) - 1, _p(qmed[a:]), _p(pmed), _p(out[r0:]), _stream()), "shift_f0_seg")
     return out
 
 
 def concat_reselect_seg(idx4, seg, q, q_norm, pool, p_norm, shifted_f0=None, pool_f0=None, concat_weight=0.2):
     """``concat_reselect`` of every segment of the stacked rows: one workgroup per segment in one launch."""
-    _need(idx4, torch.int64, "idx4"); _rows_match(seg, idx4, "concat_reselect_seg"); _rows_match(seg, q, "concat_reselect_seg")
+    _need(idx4, torch.int64, "idx4"); seg = _segments(seg, "concat_reselect_seg", idx4, q)
     idx4 = idx4.contiguous()
     out = torch.empty_like(idx4)
     use_f0 = shifted_f0 is not None
-    for a, r0, tab in _seg_chunks(seg):
+    for a, r0, tab in seg.chunks:
         check(_lib.load().knnsvc_concat_reselect_seg(_p(idx4[r0:]), _p(q[r0:]), _p(q_norm[r0:]), tab, len(tab) - 1, _p(pool), _p(p_norm),
                                                      pool.shape[0], q.shape[1], _p(shifted_f0[r0:]) if use_f0 else _p(None), _p(pool_f0),
                                                      1 if use_f0 else 0, float(concat_weight), _p(out[r0:]), _stream()), "concat_reselect_seg")
@@ -880,23 +896,17 @@ def concat_reselect_seg(idx4, seg, q, q_norm, pool, p_norm, shifted_f0=None, poo
 
 def smooth_weights_seg(idx4, seg, pool, scale, max_iter=100000, return_iters=False, row_scale=None):
     """``smooth_weights`` of every segment of the stacked rows -> w [total, 4] (and iters [n_seg])."""
-    if ADAM_FORCED_ITERS:
-        max_iter = -int(ADAM_FORCED_ITERS)
-    _need(idx4, torch.int64, "idx4"); _need(pool, name="pool"); _rows_match(seg, idx4, "smooth_weights_seg")
-    if row_scale is not None:
-        _need(row_scale, name="row_scale")
-        if tuple(row_scale.shape) != tuple(idx4.shape) or not row_scale.is_contiguous():
-            raise KnnSvcError("smooth_weights_seg: row_scale must be a contiguous [total,4] tensor")
+    idx4, max_iter = _smooth_args("smooth_weights_seg", idx4, pool, max_iter, row_scale)
+    seg = _segments(seg, "smooth_weights_seg", idx4)
     lib = _lib.load()
-    idx4 = idx4.contiguous()
     npool, dim = pool.shape
     w = torch.empty(idx4.shape[0], 4, device=pool.device, dtype=torch.float32)
-    iters = torch.zeros(len(seg) - 1, device=pool.device, dtype=torch.int32)
-    for a, r0, tab in _seg_chunks(seg):
+    iters = torch.zeros(seg.n, device=pool.device, dtype=torch.int32)
+    for a, r0, tab in seg.chunks:
         ws_bytes = lib.knnsvc_smooth_seg_workspace_bytes(tab, len(tab) - 1)
         ws = torch.empty(ws_bytes, device=pool.device, dtype=torch.uint8)
         check(lib.knnsvc_smooth_weights_seg(_p(idx4[r0:]), tab, len(tab) - 1, _p(pool), npool, dim, pool.stride(0), float(scale),
-                                            _p(row_scale[r0:]) if row_scale is not None else _p(None), int(max_iter), _p(w[r0:]),
+                                            _p(row_scale[r0:]) if row_scale is not None else _p(None), max_iter, _p(w[r0:]),
                                             _p(iters[a:]), _p(ws), ws_bytes, _stream()), "smooth_weights_seg")
     return (w, iters) if return_iters else w
 

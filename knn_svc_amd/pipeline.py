@@ -249,43 +249,18 @@ class LanePipeline:
         self.tail_stream = self.tail_streams[0]
 
     def run(self, items, head, tail=None):
-        """results[i] = tail(item_i, head(item_i)) (or head(item_i) without a tail), in item order.
+        """results[i] = tail(item_i, head(item_i)) (or head(item_i) without a tail), in item order: ``run_batched`` over batches
+        of one item (item i on lane i mod L, its tail on tail stream i mod tails).
 
         ``head`` and ``tail`` must only enqueue GPU work (no host synchronisation — a ``.item()`` inside them
         would serialise the pipeline); they see their lane / the tail stream as the current stream."""
-        cur = torch.cuda.current_stream(self.device)
-        for s in self.lanes + self.tail_streams:
-            s.wait_stream(cur)
-        out = []
-        for i, item in enumerate(items):
-            lane = self.lanes[i % len(self.lanes)]
-            with torch.cuda.stream(lane):
-                h = head(item)
-                done = lane.record_event()
-            if tail is None:
-                out.append(h)
-                continue
-            ts = self.tail_streams[i % len(self.tail_streams)]
-            with torch.cuda.stream(ts):
-                ts.wait_event(done)
-                for t in _tensors(h):
-                    t.record_stream(ts)
-                _TAIL.k = i % len(self.tail_streams)
-                try:
-                    out.append(tail(item, h))
-                finally:
-                    _TAIL.k = 0
-        for s in self.lanes + self.tail_streams:
-            cur.wait_stream(s)
-        for t in _tensors(out):
-            t.record_stream(cur)
-        return out
+        return self.run_batched(([item] for item in items), lambda batch: [head(batch[0])], tail)
 
     def run_batched(self, batches, head_many, tail=None):
-        """``run`` for heads that take several items at once (matching.match_features_many): ``head_many(batch)`` runs on a lane
+        """Heads that take several items at once (matching.match_features_many): ``head_many(batch)`` runs on a lane
         (batch b on lane b mod L) and returns one result per item of the batch; item i's ``tail`` (i counted over all batches) then
         runs on tail stream i mod tails behind the lane's event.  -> the results in item order.  Same rules as ``run``: enqueue
-        only, and every tensor handed from a lane to a tail stream is recorded on it."""
+        only; every tensor handed from a lane to a tail stream is recorded on it."""
         cur = torch.cuda.current_stream(self.device)
         for s in self.lanes + self.tail_streams:
             s.wait_stream(cur)

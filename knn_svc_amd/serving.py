@@ -32,7 +32,7 @@ from pathlib import Path
 import numpy as np
 import torch
 
-from . import audio_io, config as C, ops, pipeline
+from . import audio_io, config as C, ops
 from . import matching as M
 
 
@@ -176,12 +176,8 @@ class BatchConverter:
                 return M.match_features_many([qpool[i] for i in batch], [f0s[i] for i in batch], tg.feats, tg.f0, tg.harm, self.ckpt_type,
                                              post_opt, nn32s=[nn.get(i) for i in batch], nan_flags=flags, pool_prep=tg.prep)
             tail = lambda i, r: voc(r[0], r[2], r[1])
-            n_lanes = max(1, min(self.lanes, len(items)))
-            if self.match == "segmented" and len(items) > 1:
-                batches = [items[a:a + self.match_batch] for a in range(0, len(items), self.match_batch)]
-                ys = pipeline.LanePipeline(dev, n_lanes).run_batched(batches, body_many, tail)
-            else:
-                ys = pipeline.LanePipeline(dev, n_lanes).run(items, body, tail)
+            ys = M.run_match_bodies(items, body, body_many, tail, device=dev, lanes=max(1, min(self.lanes, len(items))),
+                                    match=self.match, match_batch=self.match_batch)
             peak = torch.stack([y.abs().max() for y in ys])
             for f in flags:
                 ops.raise_if_nan(f)                          # one host read per search, after everything is enqueued

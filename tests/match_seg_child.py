@@ -163,6 +163,40 @@ def case_smooth():
                 note(tag + "/rows-sum-to-1", dev1 < 1e-5, f"max |sum - 1| = {dev1:.2e}")
 
 
+# ------------------------------------------------------------------ 3b. the single call in its own (smaller) workspace
+def case_single_workspace():
+    """knnsvc_smooth_weights is the one-segment case of the segmented call but keeps its own workspace size (no rounding of the
+    segment up to 64 bytes): a workspace of exactly knnsvc_smooth_workspace_bytes(nq) bytes that starts 4 bytes behind a 64-byte
+    boundary — the aligned base is then 60 bytes in, the most the size allows for — inside a buffer of sentinel bytes.  One length
+    per loop variant; 4609 = ADAM_LDS_ROWS + 1, where the exchange buffer is the last region of the workspace."""
+    import ctypes
+    from knn_svc_amd import _lib
+    lib = _lib.load()
+    gen = torch.Generator().manual_seed(29)
+    pool = S.clustered_features(300, 64, seed=3, n_centres=10)
+    pool = ((pool + torch.roll(pool, 1, 0) + torch.roll(pool, 2, 0)) / 3).to(DEV)
+    lead, trail, mark = 4, 4096, 0xA5
+    for nq in (1, 2, 513, 1537, 4609):
+        idx = torch.randint(0, 300, (nq, 4), generator=gen)
+        idx[::50] = torch.tensor([0, 299, 1, 298])
+        idx = idx.to(DEV)
+        rsc = (torch.rand(nq, 4, generator=gen) * 2 + 0.3).to(DEV)
+        for rs in (None, rsc):
+            w_ref, it_ref = ops.smooth_weights(idx, pool, 0.1, max_iter=50, return_iters=True, row_scale=rs)
+            need = lib.knnsvc_smooth_workspace_bytes(nq)
+            buf = torch.full((lead + need + trail,), mark, device=DEV, dtype=torch.uint8)
+            assert buf.data_ptr() % 64 == 0
+            w = torch.empty(nq, 4, device=DEV, dtype=torch.float32)
+            it = torch.zeros(1, device=DEV, dtype=torch.int32)
+            rc = lib.knnsvc_smooth_weights(ops._p(idx), nq, ops._p(pool), 300, 64, pool.stride(0), 0.1, ops._p(rs), 50, ops._p(w), ops._p(it),
+                                           ctypes.c_void_p(buf.data_ptr() + lead), need, ops._stream())
+            torch.cuda.synchronize()
+            clean = bool((buf[:lead] == mark).all()) and bool((buf[lead + need:] == mark).all())
+            ok = rc == 0 and same(w, w_ref) and int(it) == int(it_ref) and clean
+            note(f"single_ws/nq{nq}/{'row_scale' if rs is not None else 'plain'}", ok,
+                 f"rc {rc}, workspace {need} bytes, weights equal {same(w, w_ref)}, iterations {int(it)} / {int(it_ref)}, sentinels intact {clean}")
+
+
 # ------------------------------------------------------------------ 4. wrapper chunking
 def case_chunking():
     lens = [1 + i % 3 for i in range(70)]
@@ -273,7 +307,8 @@ def case_product(tmp):
 
 def main(out_path):
     torch.cuda.set_device(0)
-    cases = [("walk", case_walk), ("median", case_median), ("smooth", case_smooth), ("chunking", case_chunking),
+    cases = [("walk", case_walk), ("median", case_median), ("smooth", case_smooth), ("single_ws", case_single_workspace),
+             ("chunking", case_chunking),
              ("match_many", case_match_many), ("product", None)]
     rc = 0
     with torch.inference_mode(), tempfile.TemporaryDirectory() as tmp:

@@ -13,6 +13,8 @@ Cases (the smallest sizes that reach every kernel variant and boundary):
   median     segments [1, 7, 1024, 1025, 3000]: all-unvoiced (NaN median), a single voiced frame, an even voiced count.
   smooth     [1, 2, 37, 512, 513, 1024, 1025, 1536, 1537] (every register variant, the LDS loop) and [4700, 3] (global exchange
              buffer); scale 0.1 on a dim-64 pool, 1000 on a dim-49 pool with ld 64; with and without row_scale; max_iter 300.
+  single_ws  knnsvc_smooth_weights (the one-segment case) in a workspace of exactly its own size at a base 4 bytes off alignment, between
+             sentinel bytes: [1, 2, 513, 1537, 4609] rows, with and without row_scale, max_iter 50.
   chunking   70 segments through the wrappers (two library calls).
   match_many six items of 1 / 2 / 31 / 150 / 151 / 600 frames, "mix" and "wavlm_only", with and without post_opt, synth_list once.
   product    BatchConverter(match="segmented", match_batch=4) against match="lanes", both generator kinds, three runs; many_to_one
@@ -72,6 +74,10 @@ def test_median_and_shift_segments_equal_single_sequences(report):
 
 def test_smooth_weights_segments_equal_single_sequences(report):
     _check(report, "smooth/", 2 * 2 * 2 * 3 + 1)
+
+
+def test_single_smooth_weights_fits_its_own_workspace_size(report):
+    _check(report, "single_ws/", 5 * 2 + 1)
 
 
 def test_wrappers_split_more_than_64_segments(report):

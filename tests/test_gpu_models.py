@@ -464,6 +464,36 @@ def test_generators_on_three_tails_equal_one_generator():
         assert torch.equal(a, b)
 
 
+def test_lane_pipeline_placement():
+    """Where LanePipeline puts things: ``run`` is ``run_batched`` over batches of one item, so item i's head sees lane i mod L as
+    the current stream, its tail tail stream i mod tails (and current_tail() says so); a batch b of ``run_batched`` sees lane
+    b mod L, item i's tail (i counted over all batches) tail stream i mod tails.  Results come back in item order."""
+    from knn_svc_amd import pipeline
+    pipe = pipeline.LanePipeline(DEV, lanes=3)
+    nt = len(pipe.tail_streams)
+    lane_of = {s.cuda_stream: k for k, s in enumerate(pipe.lanes)}
+    tail_of = {s.cuda_stream: k for k, s in enumerate(pipe.tail_streams)}
+    assert len(lane_of) == 3 and len(tail_of) == nt and not set(lane_of) & set(tail_of)
+    cur = lambda: torch.cuda.current_stream().cuda_stream
+    heads, tails = [], []
+
+    def tail(i, h):
+        tails.append((i, tail_of.get(cur()), pipeline.current_tail()))
+        return (i, h)
+    out = pipe.run(range(7), lambda i: (heads.append((i, lane_of.get(cur()))), 10 * i)[1], tail)
+    assert heads == [(i, i % 3) for i in range(7)]
+    assert tails == [(i, i % nt, i % nt) for i in range(7)]
+    assert out == [(i, 10 * i) for i in range(7)] and pipeline.current_tail() == 0
+    assert pipe.run(range(7), lambda i: 10 * i) == [10 * i for i in range(7)]
+    heads.clear(); tails.clear()
+    batches = [[0, 1, 2], [3, 4], [5, 6]]
+    out = pipe.run_batched(batches, lambda b: (heads.append((tuple(b), lane_of.get(cur()))), [10 * i for i in b])[1], tail)
+    assert heads == [(tuple(b), k % 3) for k, b in enumerate(batches)]
+    assert tails == [(i, i % nt, i % nt) for i in range(7)]
+    assert out == [(i, 10 * i) for i in range(7)] and pipeline.current_tail() == 0
+    torch.cuda.synchronize()
+
+
 def test_prematch_files_match_reference(golden, tmp_path):
     """per_spk_extract on the GPU writes the reference's files (g12: pool.npy, pool_harmonics.npy, per-utterance
     pickles with slice / nearest_nbrs / nearest_nbrs_f0_priority / amp_ratio / harmonics_best_weight_para)."""

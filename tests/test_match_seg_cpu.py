@@ -92,6 +92,33 @@ def test_seg_entry_points_refuse_bad_sizes_and_null_pointers():
     assert b"aligned" in lib.knnsvc_last_error()
 
 
+def test_single_entry_points_answer_under_their_own_names():
+    """The single-sequence entry points are the one-segment case of the segmented ones, but speak as themselves: their own
+    name in the message, their own workspace size.  Per row the workspace is the Gram matrix's 28 off-diagonal entries + 6 float4
+    of optimiser state + 2 float4 of exchange buffer = 60 floats (smooth.hip, ws_floats), then 64 bytes to align the base: 240 n +
+    64 — the value the function returned before the single call became a one-segment call (the 68 floats / 272 bytes per row some
+    notes quote are the 36-entry Gram layout of an older version)."""
+    lib = _lib()
+    d = 256
+    calls = {
+        "log_f0_median": lambda: lib.knnsvc_log_f0_median(d, 0, d, d, None),
+        "shift_f0": lambda: lib.knnsvc_shift_f0(d, 0, d, d, d, None),
+        "concat_reselect": lambda: lib.knnsvc_concat_reselect(d, d, d, 0, d, d, 300, 64, d, d, 1, 0.2, d, None),
+        "smooth_weights": lambda: lib.knnsvc_smooth_weights(d, 0, d, 300, 64, 64, 0.1, None, 300, d, d, d, 1 << 30, None),
+    }
+    for name, call in calls.items():
+        rc = call()
+        msg = lib.knnsvc_last_error()
+        assert rc != 0 and name.encode() in msg and b"_seg" not in msg, (name, rc, msg)
+    for n in (1, 7, 600, 5000):
+        need = lib.knnsvc_smooth_workspace_bytes(n)
+        assert need == (28 + 6 * 4 + 2 * 4) * 4 * n + 64 == 240 * n + 64, (n, need)
+        rc = lib.knnsvc_smooth_weights(d, n, d, 300, 64, 64, 0.1, None, 300, d, d, d, need - 1, None)
+        msg = lib.knnsvc_last_error()
+        assert rc == 2 and b"smooth_weights:" in msg and b"workspace" in msg, (n, rc, msg)          # KNNSVC_EWORKSPACE
+    assert lib.knnsvc_smooth_workspace_bytes(0) == 0
+
+
 def test_segment_chunks_of_the_wrapper():
     """ops._seg_chunks: a table of more than 64 segments becomes consecutive calls with tables that start at 0."""
     from knn_svc_amd import ops
