@@ -154,6 +154,71 @@ __global__ __launch_bounds__(256) void attention_kernel(const float* __restrict_
 
 
 // ---------------------------------------------------------------------------------------------
+// Pieces of the split-operand flash kernels below (attention3_kernel, attention2q_kernel, attention2w_kernel) that do not depend
+// on the number format, each written once.
+// ---------------------------------------------------------------------------------------------
+typedef unsigned au32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned au32x2 __attribute__((ext_vector_type(2)));
+typedef __attribute__((address_space(3))) char lc;
+typedef __attribute__((address_space(3))) au32x4 l_u4;
+typedef __attribute__((address_space(3))) au32x2 l_u2;
+typedef __attribute__((address_space(3))) float l_f;
+
+// keys this batch row may attend to: WavLM's key_padding_mask (wavlm/WavLM.py:311-321, modules.py:540-563) for a chunk that
+// sits zero-padded inside a longer bucket; rows >= Tk still get (unused, finite) outputs
+__device__ __forceinline__ int att_kv_len(const int* kv_len, int b, int T) {
+    int Tk = T;
+    if (kv_len) { Tk = kv_len[b]; Tk = Tk < 1 ? 1 : (Tk > T ? T : Tk); }
+    return Tk;
+}
+
+// bias table + 64 zero floats: the last key tile indexes past 2T-2 before it is masked
+constexpr size_t att_table_bytes(int T) { return (size_t)(2 * T - 1 + 64) * 4; }
+template <int NT>
+__device__ __forceinline__ void att_fill_table(l_f* tb, const float* table, int head, int T) {
+    for (int i = threadIdx.x; i < 2 * T - 1 + 64; i += NT) tb[i] = i < 2 * T - 1 ? table[(long)head * (2 * T - 1) + i] : 0.f;
+}
+
+// The 64-key K / V tile at key K0 from `qkv` into the registers rk / rv, by NT threads: 16 threads per key row (4 channels each),
+// NT / 16 rows per pass, 1024 / NT passes; keys past T read as zeros.  This and KN_ATT2_INIT are function-like macros on purpose
+// (as the pieces of gemm2_core.h): as inline functions the same statements reach the optimiser in another order, and the kernels
+// that sit at their register budget began to spill — 12 to 44 bytes of scratch in the two 256-VGPR kernels, 183 -> 195 VGPRs
+// in attention3_kernel (device assembly, tools/isa_diff.py).  Uses the kernel's names: rk, rv, base, ld, E, head, T.
+#define KN_ATT_LOAD_KV(NT, K0)                                                                                 \
+    _Pragma("unroll") for (int j = 0; j < KT * 16 / (NT); ++j) {                                              \
+        const int key = (K0) + (threadIdx.x >> 4) + ((NT) / 16) * j;                                           \
+        f32x4 kk = {0.f, 0.f, 0.f, 0.f}, vv = {0.f, 0.f, 0.f, 0.f};                                             \
+        if (key < T) {                                                                                         \
+            const float* p = base + (long)key * ld + head * HD + (threadIdx.x & 15) * 4;                       \
+            kk = *(const f32x4*)(p + E);                                                                       \
+            vv = *(const f32x4*)(p + 2 * E);                                                                   \
+        }                                                                                                      \
+        rk[j] = kk; rv[j] = vv;                                                                                \
+    }
+
+// One query's 64 output channels (row = b T + qi of `out`), o * inv: plain fp32, or (out_split) the f16x2 split layout the output
+// projection stages with plain copies (4 consecutive channels of the row per store)
+__device__ __forceinline__ void att_store(float* out, long row, int E, int head, const f32x16 (&o)[2], float inv, int out_split) {
+    const int lh = (threadIdx.x & 63) >> 5;
+    float* op = out + row * E + head * HD;
+#pragma unroll
+    for (int d = 0; d < 2; ++d)
+#pragma unroll
+        for (int r4 = 0; r4 < 4; ++r4) {
+            f32x4 v = {o[d][r4 * 4 + 0] * inv, o[d][r4 * 4 + 1] * inv, o[d][r4 * 4 + 2] * inv, o[d][r4 * 4 + 3] * inv};
+            if (out_split) {
+                g2_u32x2 hi, lo;
+                f16x2_split4(v, KN_F16X2_A_SCALE, hi, lo);
+                const int c = head * HD + d * 32 + r4 * 8 + lh * 4;
+                char* ob = (char*)(out + row * E) + (c >> 5) * 128 + (c & 31) * 2;
+                *(g2_u32x2*)ob = hi;
+                *(g2_u32x2*)(ob + 64) = lo;
+            } else
+                *(f32x4*)(op + d * 32 + r4 * 8 + lh * 4) = v;
+        }
+}
+
+// ---------------------------------------------------------------------------------------------
 // bf16x3 variant: the same transposed flash schedule, but every fp32 product of S^T = K.Q^T and
 // O^T += V^T.P^T is evaluated as six v_mfma_f32_32x32x16_bf16 on truncation-split operands
 // (x = hi + mid + lo, see gemm3_core.h): fp32-level accuracy at 6/16 of the fp32-MFMA cycles.
@@ -165,8 +230,6 @@ __global__ __launch_bounds__(256) void attention_kernel(const float* __restrict_
 //   P       : exp() results are split in registers and used directly as the B operand of V^T.P^T
 // ---------------------------------------------------------------------------------------------
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef unsigned au32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned au32x2 __attribute__((ext_vector_type(2)));
 constexpr int KP3 = 400;      // K row pitch (bytes)
 constexpr int VP3 = 392;      // V^T row pitch (bytes)
 
@@ -183,14 +246,10 @@ __global__ __launch_bounds__(256, 2) void attention3_kernel(const float* __restr
                                                            const float* __restrict__ table, const int* __restrict__ kv_len, int T, int heads,
                                                            float* __restrict__ out) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    typedef __attribute__((address_space(3))) char lc;
-    typedef __attribute__((address_space(3))) au32x4 l_u4;
-    typedef __attribute__((address_space(3))) au32x2 l_u2;
     typedef __attribute__((address_space(3))) unsigned short l_u16;
-    typedef __attribute__((address_space(3))) float l_f;
     lc* Ks = (lc*)lds;                       // 64 * 400
     lc* Vs = Ks + KT * KP3;                  // 64 * 392
-    l_f* tb = (l_f*)(Vs + HD * VP3);         // [2T-1]
+    l_f* tb = (l_f*)(Vs + HD * VP3);         // [2T-1+64]
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int li = lane & 31, lh = lane >> 5;
@@ -200,13 +259,8 @@ __global__ __launch_bounds__(256, 2) void attention3_kernel(const float* __restr
     const float* base = qkv + (long)b * T * ld;
     const int qi = blockIdx.x * 128 + wave * 32 + li;
     const bool qvalid = qi < T;
-    // keys this batch row may attend to: WavLM's key_padding_mask (wavlm/WavLM.py:311-321, modules.py:540-563) for a chunk that
-    // sits zero-padded inside a longer bucket; rows >= Tk still get (unused, finite) outputs
-    int Tk = T;
-    if (kv_len) { Tk = kv_len[b]; Tk = Tk < 1 ? 1 : (Tk > T ? T : Tk); }
-
-    // bias table + 64 zero floats: the last key tile indexes past 2T-2 before it is masked
-    for (int i = tid; i < 2 * T - 1 + 64; i += 256) tb[i] = i < 2 * T - 1 ? table[(long)head * (2 * T - 1) + i] : 0.f;
+    const int Tk = att_kv_len(kv_len, b, T);
+    att_fill_table<256>(tb, table, head, T);
 
     // scores live in the log2 domain (softmax via v_exp_f32): Q carries 1/8 * log2(e)
     const float L2E = 1.44269504088896341f;
@@ -242,20 +296,7 @@ __global__ __launch_bounds__(256, 2) void attention3_kernel(const float* __restr
 
     const int srow = tid >> 4, scol = (tid & 15) * 4;       // staging: rows (keys) srow + 16 j, d = scol..scol+3
     f32x4 rk[4], rv[4];
-    auto gload = [&](int k0) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int key = k0 + srow + 16 * j;
-            f32x4 kk = {0.f, 0.f, 0.f, 0.f}, vv = {0.f, 0.f, 0.f, 0.f};
-            if (key < T) {
-                const float* p = base + (long)key * ld + head * HD + scol;
-                kk = *(const f32x4*)(p + E);
-                vv = *(const f32x4*)(p + 2 * E);
-            }
-            rk[j] = kk; rv[j] = vv;
-        }
-    };
-    gload(0);
+    KN_ATT_LOAD_KV(256, 0)
     const int ntiles = (Tk + KT - 1) / KT;
     for (int t = 0; t < ntiles; ++t) {
         __syncthreads();
@@ -279,7 +320,7 @@ __global__ __launch_bounds__(256, 2) void attention3_kernel(const float* __restr
             }
         }
         __syncthreads();
-        if (t + 1 < ntiles) gload((t + 1) * KT);
+        if (t + 1 < ntiles) { KN_ATT_LOAD_KV(256, (t + 1) * KT) }
 
 #pragma unroll
         for (int sub = 0; sub < 2; ++sub) {
@@ -369,355 +410,267 @@ __global__ __launch_bounds__(256, 2) void attention3_kernel(const float* __restr
             }
         }
     }
-    if (qvalid) {
-        const float inv = 1.0f / l_run;
-        float* op = out + ((long)b * T + qi) * E + head * HD;
-#pragma unroll
-        for (int d = 0; d < 2; ++d)
-#pragma unroll
-            for (int r4 = 0; r4 < 4; ++r4) {
-                f32x4 v = {o[d][r4 * 4 + 0] * inv, o[d][r4 * 4 + 1] * inv, o[d][r4 * 4 + 2] * inv, o[d][r4 * 4 + 3] * inv};
-                *(f32x4*)(op + d * 32 + r4 * 8 + lh * 4) = v;
-            }
-    }
+    if (qvalid) att_store(out, (long)b * T + qi, E, head, o, 1.0f / l_run, 0);
 }
 
 // ---------------------------------------------------------------------------------------------
-// f16x2 variant (default): the schedule of attention3_kernel with every fp32 product evaluated as
+// f16x2 variant (default): the flash step of attention3_kernel with every fp32 product evaluated as
 // three v_mfma_f32_32x32x16_f16 on (hi, lo) fp16 splits of power-of-two-scaled operands
 // (gemm2_core.h): half the matrix-core work of bf16x3 at the same accuracy class.
-//   K tile : LDS [64 keys][2 planes][64 d] fp16, row pitch 272 B;  V tile : LDS [64 d][2 planes][64 keys], pitch 264 B
+//   K tile : LDS [64 keys][2 planes][64 d] fp16, row pitch 272 B;  V tile : LDS [64 keys][2 planes][64 d], pitch 320 B
 //   scales : Q' = 16 (log2 e / 8) Q, K' = 16 K  (scores x 256, undone inside the exp2 argument);
 //            P' = 2^14 P (folded into the exp2 argument, cancels in O / l);  V' = 16 V (undone at the end)
+// The step is written once (Att2Wave and att2_stage below) for QB blocks of 32 queries per wave, and attention2q_kernel<QB> is
+// the four-wave schedule around it (QB = 1 and 2).  attention2w_kernel (eight waves) still carries its own copy of the same
+// statements: built on the shared pieces it compiled to the same MFMA / LDS / exp counts at 256 VGPRs without scratch and gave
+// the same bits, but ran 12-17 us slower per launch at 21 x 1500 x 16 (650 -> 664 us, pre-split 633 -> 650; alternating A/B,
+// profiles/attention_shared_step_ab.txt), so it keeps the text whose schedule the compiler gets right.
+// Per query every kernel performs the same floating-point operations in the same order: results are bit-identical.
+// The timing aids -DKN_ATT_NOBIAS / NOEXP / NOS / NOPV (tools/attn_whatif.sh; wrong results) sit in the shared step, i.e. in
+// both instances of attention2q_kernel (KNNSVC_ATT_NW=4 selects it at the benchmark's shape); attention2w_kernel has none.
 // ---------------------------------------------------------------------------------------------
 typedef short short4v __attribute__((ext_vector_type(4)));
 constexpr int KP2 = 272;
 constexpr int VP2 = 320;          // V image: row = key, [hi 64 d | lo 64 d] + pad; 80 dwords = 16 (mod 64): the four rows of a
                                   // ds_read_b64_tr_b16 block cover the 64 banks exactly once
+// LDS of the f16x2 kernels: `nbuf` tiles of [64 K rows | 64 V rows] (V row-major like K, read transposed: see PV), then the bias table
+constexpr int ATT2_V = KT * KP2, ATT2_TILE = KT * KP2 + KT * VP2;
+constexpr size_t att2_lds_bytes(int nbuf, int T) { return (size_t)nbuf * ATT2_TILE + att_table_bytes(T); }
 
-__global__ __launch_bounds__(256, 3) void attention2_kernel(const float* __restrict__ qkv, const float* __restrict__ gate,
-                                                           const float* __restrict__ table, const int* __restrict__ kv_len, int T, int heads,
-                                                           float* __restrict__ out, int out_split, int kv_split) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    typedef __attribute__((address_space(3))) char lc;
-    typedef __attribute__((address_space(3))) au32x4 l_u4;
-    typedef __attribute__((address_space(3))) au32x2 l_u2;
-    typedef __attribute__((address_space(3))) float l_f;
-    lc* Ks = (lc*)lds;                       // 64 keys * 272 B
-    lc* Vs = Ks + KT * KP2;                  // 64 keys * 320 B, row-major like K (read transposed, see the PV product)
-    l_f* tb = (l_f*)(Vs + KT * VP2);         // [2T-1+64]
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int li = lane & 31, lh = lane >> 5;
-    const int head = blockIdx.y, b = blockIdx.z;
-    const int E = heads * HD;
-    const long ld = 3L * E;
-    const float* base = qkv + (long)b * T * ld;
-    const int qi = blockIdx.x * 128 + wave * 32 + li;
-    const bool qvalid = qi < T;
-    // keys this batch row may attend to: WavLM's key_padding_mask (wavlm/WavLM.py:311-321, modules.py:540-563) for a chunk that
-    // sits zero-padded inside a longer bucket; rows >= Tk still get (unused, finite) outputs
-    int Tk = T;
-    if (kv_len) { Tk = kv_len[b]; Tk = Tk < 1 ? 1 : (Tk > T ? T : Tk); }
-
-    // bias table + 64 zero floats: the last key tile indexes past 2T-2 before it is masked
-    for (int i = tid; i < 2 * T - 1 + 64; i += 256) tb[i] = i < 2 * T - 1 ? table[(long)head * (2 * T - 1) + i] : 0.f;
-
-    // scores live in the log2 domain (softmax via v_exp_f32) and carry the operand scales: Q' = 16 log2(e)/8 Q,
-    // K' = 16 K  ->  accumulator = 256 * log2-score; the bias enters as 256 log2(e) g b, exp2 undoes the 256.
-    const float L2E = 1.44269504088896341f;
-    const float qscale = 0.125f * L2E * 16.0f;
-    // Q (scaled) split into two fp16 planes: qf[s][p] = 8 halves of d = 16 s + 8 h + 0..7
-    au32x4 qf[4][2];
+// The tile in rk / rv (KN_ATT_LOAD_KV) -> the LDS tile at `tile`
+template <int NT, int NJ>
+__device__ __forceinline__ void att2_stage(lc* tile, const f32x4 (&rk)[NJ], const f32x4 (&rv)[NJ], int kv_split) {
+    static_assert(NJ * (NT / 16) == KT, "rk / rv hold one tile");
+    const int tid = threadIdx.x, srow = tid >> 4, scol = (tid & 15) * 4;
+    if (kv_split) {
+        // K and V columns of `qkv` already hold the f16x2 split layout (written by the QKV GEMM's epilogue, scale 16):
+        // the 16 bytes a thread loaded are piece pc = tid & 15 of its key's 256-byte head slice — 8 halves of plane
+        // (pc >> 2) & 1, channels 32 (pc >> 3) + 8 (pc & 3) .. + 7.  Staging is a copy: every query block of a head
+        // (12 at T = 1500) used to redo the same split of the same keys (~110 VALU per thread and tile).
+        const int pc = tid & 15, plane = (pc >> 2) & 1, d0 = (pc >> 3) * 32 + (pc & 3) * 8;
 #pragma unroll
-    for (int s = 0; s < 4; ++s) {
-        f32x4 v0 = {0.f, 0.f, 0.f, 0.f}, v1 = v0;
-        if (qvalid) {
-            const float* p = base + (long)qi * ld + head * HD + s * 16 + lh * 8;
-            v0 = *(const f32x4*)p; v1 = *(const f32x4*)(p + 4);
+        for (int j = 0; j < NJ; ++j) {
+            const int key = srow + (NT / 16) * j;
+            *(l_u4*)(tile + key * KP2 + plane * 128 + d0 * 2) = __builtin_bit_cast(au32x4, rk[j]);
+            *(l_u4*)(tile + ATT2_V + key * VP2 + plane * 128 + d0 * 2) = __builtin_bit_cast(au32x4, rv[j]);
         }
-        g2_u32x2 h0, l0, h1, l1;
-        f16x2_split4(v0, qscale, h0, l0); f16x2_split4(v1, qscale, h1, l1);
-        qf[s][0] = (au32x4){h0[0], h0[1], h1[0], h1[1]};
-        qf[s][1] = (au32x4){l0[0], l0[1], l1[0], l1[1]};
-    }
-    const float g_i = qvalid ? gate[((long)b * T + qi) * heads + head] * (L2E * 256.0f) : 0.f;
-    const l_f* tbq = tb + (T - 1 - (qvalid ? qi : T - 1)) + 4 * lh;     // tbq[key] = table[key - qi + T - 1]
-    // transposed-read address of this lane inside a 16-key x 32-d block of V: key 4 (lane >> 5) + ((lane & 15) >> 2),
-    // columns 16 ((lane >> 4) & 1) + 4 (lane & 3)
-    const lc* v_tr = Vs + (4 * (lane >> 5) + ((lane & 15) >> 2)) * VP2 + (16 * ((lane >> 4) & 1) + 4 * (lane & 3)) * 2;
-
-
-    f32x16 o[2];
+    } else {
 #pragma unroll
-    for (int d = 0; d < 2; ++d)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) o[d][r] = 0.f;
-    float m_run = -__builtin_inff(), l_run = 0.f;
-
-    const int srow = tid >> 4, scol = (tid & 15) * 4;       // staging: rows (keys) srow + 16 j, d = scol..scol+3
-    f32x4 rk[4], rv[4];
-    auto gload = [&](int k0) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int key = k0 + srow + 16 * j;
-            f32x4 kk = {0.f, 0.f, 0.f, 0.f}, vv = {0.f, 0.f, 0.f, 0.f};
-            if (key < T) {
-                const float* p = base + (long)key * ld + head * HD + scol;
-                kk = *(const f32x4*)(p + E);
-                vv = *(const f32x4*)(p + 2 * E);
-            }
-            rk[j] = kk; rv[j] = vv;
-        }
-    };
-    gload(0);
-    const int ntiles = (Tk + KT - 1) / KT;
-    for (int t = 0; t < ntiles; ++t) {
-#ifdef KN_ATT_NOSTAGE      // timing aid: the first tile's K / V serve every tile, no barriers after it
-        if (t == 0) {
-#endif
-        __syncthreads();
-        if (kv_split) {
-            // K and V columns of `qkv` already hold the f16x2 split layout (written by the QKV GEMM's epilogue, scale 16):
-            // the 16 bytes a thread loaded are piece pc = tid & 15 of its key's 256-byte head slice — 8 halves of plane
-            // (pc >> 2) & 1, channels 32 (pc >> 3) + 8 (pc & 3) .. + 7.  Staging is a copy: every query block of a head
-            // (12 at T = 1500) used to redo the same split of the same keys (~110 VALU per thread and tile).
-            const int pc = tid & 15, plane = (pc >> 2) & 1, d0 = (pc >> 3) * 32 + (pc & 3) * 8;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int key = srow + 16 * j;
-                *(l_u4*)(Ks + key * KP2 + plane * 128 + d0 * 2) = __builtin_bit_cast(au32x4, rk[j]);
-                *(l_u4*)(Vs + key * VP2 + plane * 128 + d0 * 2) = __builtin_bit_cast(au32x4, rv[j]);
-            }
-        } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int key = srow + 16 * j;
+        for (int j = 0; j < NJ; ++j) {
+            const int key = srow + (NT / 16) * j;
             g2_u32x2 hi, lo;
             f16x2_split4(rk[j], 16.0f, hi, lo);
-            lc* kd = Ks + key * KP2 + scol * 2;
+            lc* kd = tile + key * KP2 + scol * 2;
             *(l_u2*)(kd) = hi;
             *(l_u2*)(kd + 128) = lo;
             f16x2_split4(rv[j], 16.0f, hi, lo);
-            lc* vd = Vs + key * VP2 + scol * 2;
+            lc* vd = tile + ATT2_V + key * VP2 + scol * 2;
             *(l_u2*)(vd) = hi;
             *(l_u2*)(vd + 128) = lo;
         }
-        }
-        __syncthreads();
-#ifdef KN_ATT_NOSTAGE
-        }
-#else
-        if (t + 1 < ntiles) gload((t + 1) * KT);
-#endif
+    }
+}
 
+// One wave's state for QB blocks of 32 queries (lane = one query of each block, the two lane halves share its keys) and the
+// three parts of a 32-key step.  Every K fragment and every transposed V fragment read from LDS feeds QB independent products.
+template <int QB>
+struct Att2Wave {
+    int qi[QB]; bool qvalid[QB];
+    au32x4 qf[QB][4][2];              // Q' in two fp16 planes: qf[u][s][p] = 8 halves of d = 16 s + 8 h + 0..7
+    float g_i[QB];
+    const l_f* tbq[QB];               // tbq[u][key] = table[key - qi + T - 1]
+    f32x16 o[QB][2];
+    float m_run[QB], l_run[QB];
+    f32x16 s[QB];
+
+    // ---- S^T = K . Q^T for keys 32 sub .. + 31 of the LDS tile: 4 d-steps x 3 products, every K fragment pair is read once ----
+    __device__ __forceinline__ void S(const lc* tile, int sub) {
+        const int lane = threadIdx.x & 63, li = lane & 31, lh = lane >> 5;
 #pragma unroll
-        for (int sub = 0; sub < 2; ++sub) {
-            const int kbase = t * KT + sub * 32;
-            if (kbase >= Tk) break;
-            // ---- S^T = K . Q^T : 4 d-steps x 6 products -----------------------------------------------
-            f32x16 s;
+        for (int u = 0; u < QB; ++u)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) s[r] = 0.f;
-            const lc* kp = Ks + (sub * 32 + li) * KP2 + lh * 16;
+            for (int r = 0; r < 16; ++r) s[u][r] = 0.f;
+        const lc* kp = tile + (sub * 32 + li) * KP2 + lh * 16;
 #pragma unroll
-            for (int st = 0; st < 4; ++st) {
-                const f16x8 k0 = __builtin_bit_cast(f16x8, *(const l_u4*)(kp + st * 32));
-                const f16x8 k1 = __builtin_bit_cast(f16x8, *(const l_u4*)(kp + 128 + st * 32));
-                const f16x8 q0 = __builtin_bit_cast(f16x8, qf[st][0]), q1 = __builtin_bit_cast(f16x8, qf[st][1]);
+        for (int st = 0; st < 4; ++st) {
+            const f16x8 k0 = __builtin_bit_cast(f16x8, *(const l_u4*)(kp + st * 32));
+            const f16x8 k1 = __builtin_bit_cast(f16x8, *(const l_u4*)(kp + 128 + st * 32));
+#pragma unroll
+            for (int u = 0; u < QB; ++u) {
+                const f16x8 q0 = __builtin_bit_cast(f16x8, qf[u][st][0]), q1 = __builtin_bit_cast(f16x8, qf[u][st][1]);
 #ifdef KN_ATT_NOS          // timing aid: one product instead of twelve
-                if (st == 0) s = __builtin_amdgcn_mfma_f32_32x32x16_f16(k1, q0, s, 0, 0, 0);
-                else { s[st] += __builtin_bit_cast(float, __builtin_bit_cast(au32x4, k0)[0] ^ __builtin_bit_cast(au32x4, k1)[1] ^ __builtin_bit_cast(au32x4, q1)[0]); }
+                if (st == 0) s[u] = __builtin_amdgcn_mfma_f32_32x32x16_f16(k1, q0, s[u], 0, 0, 0);
+                else s[u][st] += __builtin_bit_cast(float, __builtin_bit_cast(au32x4, k0)[0] ^ __builtin_bit_cast(au32x4, k1)[1] ^ __builtin_bit_cast(au32x4, q1)[0]);
 #else
-                s = __builtin_amdgcn_mfma_f32_32x32x16_f16(k1, q0, s, 0, 0, 0);
-                s = __builtin_amdgcn_mfma_f32_32x32x16_f16(k0, q1, s, 0, 0, 0);
-                s = __builtin_amdgcn_mfma_f32_32x32x16_f16(k0, q0, s, 0, 0, 0);
+                s[u] = __builtin_amdgcn_mfma_f32_32x32x16_f16(k1, q0, s[u], 0, 0, 0);
+                s[u] = __builtin_amdgcn_mfma_f32_32x32x16_f16(k0, q1, s[u], 0, 0, 0);
+                s[u] = __builtin_amdgcn_mfma_f32_32x32x16_f16(k0, q0, s[u], 0, 0, 0);
 #endif
             }
-            // rows past T hold zero Q (and zero gate): their scores are finite, nothing is written for them
-            const l_f* tp = tbq + kbase;
-#ifndef KN_ATT_NOBIAS
+        }
+    }
+
+    // ---- bias, mask, online softmax of the step whose first key is kbase (lane-local + one exchange with lane ^ 32) ----
+    // rows past T hold zero Q (and zero gate): their scores are finite, nothing is written for them
+    __device__ __forceinline__ void softmax(int kbase, int Tk) {
+        const int lh = (threadIdx.x & 63) >> 5;
 #pragma unroll
-            for (int r = 0; r < 16; ++r) s[r] = fmaf(g_i, tp[(r & 3) + 8 * (r >> 2)], s[r]);
+        for (int u = 0; u < QB; ++u) {
+#ifndef KN_ATT_NOBIAS
+            const l_f* tp = tbq[u] + kbase;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) s[u][r] = fmaf(g_i[u], tp[(r & 3) + 8 * (r >> 2)], s[u][r]);
 #endif
             if (kbase + 32 > Tk) {                                    // wave-uniform: only the last key tile masks
 #pragma unroll
                 for (int r = 0; r < 16; ++r)
-                    if (kbase + (r & 3) + 8 * (r >> 2) + 4 * lh >= Tk) s[r] = -__builtin_inff();
+                    if (kbase + (r & 3) + 8 * (r >> 2) + 4 * lh >= Tk) s[u][r] = -__builtin_inff();
             }
 #ifdef KN_ATT_NOEXP       // timing aid: no max / exp / sums
-            float mx = s[0];
+            float mx = s[u][0];
 #else
-            float mx = fmaxf(fmaxf(s[0], s[1]), fmaxf(s[2], s[3]));
+            float mx = fmaxf(fmaxf(s[u][0], s[u][1]), fmaxf(s[u][2], s[u][3]));
 #pragma unroll
-            for (int r = 4; r < 16; r += 4) mx = fmaxf(mx, fmaxf(fmaxf(s[r], s[r + 1]), fmaxf(s[r + 2], s[r + 3])));
+            for (int r = 4; r < 16; r += 4) mx = fmaxf(mx, fmaxf(fmaxf(s[u][r], s[u][r + 1]), fmaxf(s[u][r + 2], s[u][r + 3])));
 #endif
             mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-            const float m_new = fmaxf(m_run, mx);                    // key 0 is always valid: finite from the first tile on
-            const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * (1.0f / 256.0f));
+            const float m_new = fmaxf(m_run[u], mx);                 // key 0 is always valid: finite from the first tile on
+            const float alpha = __builtin_amdgcn_exp2f((m_run[u] - m_new) * (1.0f / 256.0f));
             const float mneg = fmaf(m_new, -1.0f / 256.0f, 14.0f);       // P carries 2^14 (cancels in O / l)
             float ps = 0.f;
-#pragma unroll
 #ifdef KN_ATT_NOEXP
-            for (int r = 0; r < 16; ++r) { s[r] = s[r] * 1e-9f; } ps = s[3] + mneg;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) s[u][r] = s[u][r] * 1e-9f;
+            ps = s[u][3] + mneg;
 #else
-            for (int r = 0; r < 16; ++r) { s[r] = __builtin_amdgcn_exp2f(fmaf(s[r], 1.0f / 256.0f, mneg)); ps += s[r]; }
+#pragma unroll
+            for (int r = 0; r < 16; ++r) { s[u][r] = __builtin_amdgcn_exp2f(fmaf(s[u][r], 1.0f / 256.0f, mneg)); ps += s[u][r]; }
 #endif
             ps += __shfl_xor(ps, 32, 64);
-            l_run = l_run * alpha + ps;
-            m_run = m_new;
+            l_run[u] = l_run[u] * alpha + ps;
+            m_run[u] = m_new;
             if (__builtin_amdgcn_ballot_w64(alpha != 1.f)) {
 #pragma unroll
                 for (int d = 0; d < 2; ++d)
 #pragma unroll
-                    for (int r = 0; r < 16; ++r) o[d][r] *= alpha;
+                    for (int r = 0; r < 16; ++r) o[u][d][r] *= alpha;
             }
-            // ---- O^T += V^T . P^T : 2 key-steps x 2 d-tiles x 6 products ---------------------------------------
+        }
+    }
+
+    // ---- O^T += V^T . P^T for the same keys: 2 key-steps x 2 d-tiles x 3 products, every transposed V fragment is read once ----
+    __device__ __forceinline__ void PV(const lc* tile, int sub) {
+        const int lane = threadIdx.x & 63;
+        // transposed-read address of this lane inside a 16-key x 32-d block of V: key 4 (lane >> 5) + ((lane & 15) >> 2),
+        // columns 16 ((lane >> 4) & 1) + 4 (lane & 3)
+        const lc* v_tr = tile + ATT2_V + (4 * (lane >> 5) + ((lane & 15) >> 2)) * VP2 + (16 * ((lane >> 4) & 1) + 4 * (lane & 3)) * 2;
 #pragma unroll
-            for (int st = 0; st < 2; ++st) {
+        for (int st = 0; st < 2; ++st) {
+            f16x8 b0[QB], b1[QB];
+#pragma unroll
+            for (int u = 0; u < QB; ++u) {
                 g2_u32x2 h0, l0, h1, l1;
-                f16x2_split4((f32x4){s[8 * st + 0], s[8 * st + 1], s[8 * st + 2], s[8 * st + 3]}, 1.0f, h0, l0);
-                f16x2_split4((f32x4){s[8 * st + 4], s[8 * st + 5], s[8 * st + 6], s[8 * st + 7]}, 1.0f, h1, l1);
-                const f16x8 b0 = __builtin_bit_cast(f16x8, (au32x4){h0[0], h0[1], h1[0], h1[1]});
-                const f16x8 b1 = __builtin_bit_cast(f16x8, (au32x4){l0[0], l0[1], l1[0], l1[1]});
-                // element e of this lane's fragment is key sub*32 + 16 st + 8 (e>>2) + 4 h + (e&3): two runs of four keys.
-                // V sits row-major in LDS (row = key) and is read TRANSPOSED by the hardware (ds_read_b64_tr_b16): each
-                // 16-lane group fetches a block of 4 keys x 16 d and lane i of the group receives d = base + i of the four
-                // keys; lane 4 q + p supplies the address of key q, columns 4 p .. 4 p + 3 (tools/probe/tr_read_probe.hip).
-                // The transposed 2-byte stores this replaces put 64 lanes on ~4 banks: 48 % of the kernel's LDS cycles
-                // were bank conflicts.  EXEC is full here (no lane-divergent control flow around the reads).
-                const lc* vrow = v_tr + (sub * 32 + 16 * st) * VP2;
+                f16x2_split4((f32x4){s[u][8 * st + 0], s[u][8 * st + 1], s[u][8 * st + 2], s[u][8 * st + 3]}, 1.0f, h0, l0);
+                f16x2_split4((f32x4){s[u][8 * st + 4], s[u][8 * st + 5], s[u][8 * st + 6], s[u][8 * st + 7]}, 1.0f, h1, l1);
+                b0[u] = __builtin_bit_cast(f16x8, (au32x4){h0[0], h0[1], h1[0], h1[1]});
+                b1[u] = __builtin_bit_cast(f16x8, (au32x4){l0[0], l0[1], l1[0], l1[1]});
+            }
+            // element e of this lane's fragment is key sub*32 + 16 st + 8 (e>>2) + 4 h + (e&3): two runs of four keys.
+            // V sits row-major in LDS (row = key) and is read TRANSPOSED by the hardware (ds_read_b64_tr_b16): each
+            // 16-lane group fetches a block of 4 keys x 16 d and lane i of the group receives d = base + i of the four
+            // keys; lane 4 q + p supplies the address of key q, columns 4 p .. 4 p + 3 (tools/probe/tr_read_probe.hip).
+            // The transposed 2-byte stores this replaces put 64 lanes on ~4 banks: 48 % of the kernel's LDS cycles
+            // were bank conflicts.  EXEC is full here (no lane-divergent control flow around the reads).
+            const lc* vrow = v_tr + (sub * 32 + 16 * st) * VP2;
 #pragma unroll
-                for (int dt = 0; dt < 2; ++dt) {
-                    typedef __attribute__((address_space(3))) short4v l_s4;
-                    const lc* vp = vrow + dt * 64;
-                    const au32x2 x0 = __builtin_bit_cast(au32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((l_s4*)(vp)));
-                    const au32x2 x1 = __builtin_bit_cast(au32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((l_s4*)(vp + 8 * VP2)));
-                    const au32x2 y0 = __builtin_bit_cast(au32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((l_s4*)(vp + 128)));
-                    const au32x2 y1 = __builtin_bit_cast(au32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((l_s4*)(vp + 8 * VP2 + 128)));
-                    const f16x8 v0 = __builtin_bit_cast(f16x8, (au32x4){x0[0], x0[1], x1[0], x1[1]});
-                    const f16x8 v1 = __builtin_bit_cast(f16x8, (au32x4){y0[0], y0[1], y1[0], y1[1]});
-                    f32x16 c = o[dt];
+            for (int dt = 0; dt < 2; ++dt) {
+                typedef __attribute__((address_space(3))) short4v l_s4;
+                const lc* vp = vrow + dt * 64;
+                const au32x2 x0 = __builtin_bit_cast(au32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((l_s4*)(vp)));
+                const au32x2 x1 = __builtin_bit_cast(au32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((l_s4*)(vp + 8 * VP2)));
+                const au32x2 y0 = __builtin_bit_cast(au32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((l_s4*)(vp + 128)));
+                const au32x2 y1 = __builtin_bit_cast(au32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((l_s4*)(vp + 8 * VP2 + 128)));
+                const f16x8 v0 = __builtin_bit_cast(f16x8, (au32x4){x0[0], x0[1], x1[0], x1[1]});
+                const f16x8 v1 = __builtin_bit_cast(f16x8, (au32x4){y0[0], y0[1], y1[0], y1[1]});
+#pragma unroll
+                for (int u = 0; u < QB; ++u) {
+                    f32x16 c = o[u][dt];
 #ifdef KN_ATT_NOPV         // timing aid: one product per step instead of six
-                    if (dt == 0) c = __builtin_amdgcn_mfma_f32_32x32x16_f16(v1, b0, c, 0, 0, 0);
-                    else c[st] += __builtin_bit_cast(float, __builtin_bit_cast(au32x4, v0)[0] ^ __builtin_bit_cast(au32x4, v1)[1] ^ __builtin_bit_cast(au32x4, b1)[0]);
+                    if (dt == 0) c = __builtin_amdgcn_mfma_f32_32x32x16_f16(v1, b0[u], c, 0, 0, 0);
+                    else c[st] += __builtin_bit_cast(float, __builtin_bit_cast(au32x4, v0)[0] ^ __builtin_bit_cast(au32x4, v1)[1] ^ __builtin_bit_cast(au32x4, b1[u])[0]);
 #else
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_f16(v1, b0, c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_f16(v0, b1, c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_f16(v0, b0, c, 0, 0, 0);
+                    c = __builtin_amdgcn_mfma_f32_32x32x16_f16(v1, b0[u], c, 0, 0, 0);
+                    c = __builtin_amdgcn_mfma_f32_32x32x16_f16(v0, b1[u], c, 0, 0, 0);
+                    c = __builtin_amdgcn_mfma_f32_32x32x16_f16(v0, b0[u], c, 0, 0, 0);
 #endif
-                    o[dt] = c;
+                    o[u][dt] = c;
                 }
             }
         }
     }
-    if (qvalid) {
-        const float inv = 0.0625f / l_run;          // V carried a factor 16
-        float* op = out + ((long)b * T + qi) * E + head * HD;
+
+    __device__ __forceinline__ void store(float* out, int b, int T, int E, int head, int out_split) const {
 #pragma unroll
-        for (int d = 0; d < 2; ++d)
-#pragma unroll
-            for (int r4 = 0; r4 < 4; ++r4) {
-                f32x4 v = {o[d][r4 * 4 + 0] * inv, o[d][r4 * 4 + 1] * inv, o[d][r4 * 4 + 2] * inv, o[d][r4 * 4 + 3] * inv};
-                if (out_split) {          // f16x2 split layout for the output projection (4 consecutive channels of the row)
-                    g2_u32x2 hi, lo;
-                    f16x2_split4(v, KN_F16X2_A_SCALE, hi, lo);
-                    const int c = head * HD + d * 32 + r4 * 8 + lh * 4;
-                    char* ob = (char*)(out + ((long)b * T + qi) * E) + (c >> 5) * 128 + (c & 31) * 2;
-                    *(g2_u32x2*)ob = hi;
-                    *(g2_u32x2*)(ob + 64) = lo;
-                } else
-                    *(f32x4*)(op + d * 32 + r4 * 8 + lh * 4) = v;
-            }
+        for (int u = 0; u < QB; ++u)
+            if (qvalid[u]) att_store(out, (long)b * T + qi[u], E, head, o[u], 0.0625f / l_run[u], out_split);     // V carried a factor 16
     }
-}
+};
+
+// W = Att2Wave<QB> of the wave whose first query is Q0: Q load and split, gate, table pointer, empty accumulators.  A macro for the
+// reason given at KN_ATT_LOAD_KV; uses the kernel's names base, ld, gate, tb, b, T, heads, head.
+// Scores live in the log2 domain (softmax via v_exp_f32) and carry the operand scales: Q' = 16 log2(e)/8 Q, K' = 16 K  ->
+// accumulator = 256 * log2-score; the bias enters as 256 log2(e) g b, exp2 undoes the 256.
+#define KN_ATT2_INIT(W, Q0)                                                                                    \
+    _Pragma("unroll") for (int u = 0; u < QB; ++u) {                                                          \
+        const int lane = threadIdx.x & 63, li = lane & 31, lh = lane >> 5;                                     \
+        const float L2E = 1.44269504088896341f, qscale = 0.125f * L2E * 16.0f;                                 \
+        W.qi[u] = (Q0) + u * 32 + li;                                                                          \
+        W.qvalid[u] = W.qi[u] < T;                                                                             \
+        _Pragma("unroll") for (int s4 = 0; s4 < 4; ++s4) {                                                    \
+            f32x4 v0 = {0.f, 0.f, 0.f, 0.f}, v1 = v0;                                                           \
+            if (W.qvalid[u]) {                                                                                 \
+                const float* p = base + (long)W.qi[u] * ld + head * HD + s4 * 16 + lh * 8;                     \
+                v0 = *(const f32x4*)p; v1 = *(const f32x4*)(p + 4);                                            \
+            }                                                                                                  \
+            g2_u32x2 h0, l0, h1, l1;                                                                           \
+            f16x2_split4(v0, qscale, h0, l0); f16x2_split4(v1, qscale, h1, l1);                                \
+            W.qf[u][s4][0] = (au32x4){h0[0], h0[1], h1[0], h1[1]};                                             \
+            W.qf[u][s4][1] = (au32x4){l0[0], l0[1], l1[0], l1[1]};                                             \
+        }                                                                                                      \
+        W.g_i[u] = W.qvalid[u] ? gate[((long)b * T + W.qi[u]) * heads + head] * (L2E * 256.0f) : 0.f;          \
+        W.tbq[u] = tb + (T - 1 - (W.qvalid[u] ? W.qi[u] : T - 1)) + 4 * lh;                                    \
+        W.m_run[u] = -__builtin_inff(); W.l_run[u] = 0.f;                                                      \
+        _Pragma("unroll") for (int d = 0; d < 2; ++d)                                                         \
+            _Pragma("unroll") for (int r = 0; r < 16; ++r) W.o[u][d][r] = 0.f;                                \
+    }
 
 // ---------------------------------------------------------------------------------------------
-// attention2_kernel with QB blocks of 32 queries per wave (QB = 2: 64 queries per wave, 256 per workgroup).  Every K
-// fragment and every transposed V fragment read from LDS feeds QB independent products, and a staged K / V tile (and its
-// two barriers) serves twice the queries: half the LDS reads and half the staging per unit of work, two independent
-// S / softmax / PV chains per wave to interleave, and 2016 workgroups on 512 resident slots (3.94 rounds; the 128-query
-// kernel: 4032 on 768 = 5.25 -> the sixth round a quarter full).  Costs a wave per SIMD (2 instead of 3: ~230 VGPRs).
-// Per query the operations and their order are those of attention2_kernel: results are bit-identical.
+// Four waves per workgroup, 32 QB queries per wave, one K / V buffer and two barriers per tile.
+//   QB = 1 (128 queries per workgroup, three waves per SIMD): small grids, where larger workgroups leave CUs idle.
+//   QB = 2 (256 queries per workgroup): a staged K / V tile (and its two barriers) serves twice the queries — half the LDS reads
+//     and half the staging per unit of work, two independent S / softmax / PV chains per wave to interleave, and 2016 workgroups
+//     on 512 resident slots (3.94 rounds; QB = 1: 4032 on 768 = 5.25 -> the sixth round a quarter full).  Costs a wave per SIMD
+//     (2 instead of 3: ~230 VGPRs).
+// Timing aids of this schedule (KNNSVC_ATT_NW=4 selects it at the benchmark's shape): -DKN_ATT_NOSTAGE, -DKN_ATT_PROF.
 // ---------------------------------------------------------------------------------------------
 template <int QB>
-__global__ __launch_bounds__(256, 2) void attention2q_kernel(const float* __restrict__ qkv, const float* __restrict__ gate,
-                                                            const float* __restrict__ table, const int* __restrict__ kv_len, int T, int heads,
-                                                            float* __restrict__ out, int out_split, int kv_split) {
+__global__ __launch_bounds__(256, QB == 1 ? 3 : 2) void attention2q_kernel(const float* __restrict__ qkv, const float* __restrict__ gate,
+                                                                          const float* __restrict__ table, const int* __restrict__ kv_len, int T,
+                                                                          int heads, float* __restrict__ out, int out_split, int kv_split) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    typedef __attribute__((address_space(3))) char lc;
-    typedef __attribute__((address_space(3))) au32x4 l_u4;
-    typedef __attribute__((address_space(3))) au32x2 l_u2;
-    typedef __attribute__((address_space(3))) float l_f;
     lc* Ks = (lc*)lds;
-    lc* Vs = Ks + KT * KP2;
-    l_f* tb = (l_f*)(Vs + KT * VP2);
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int li = lane & 31, lh = lane >> 5;
-    const int head = blockIdx.y, b = blockIdx.z;
+    l_f* tb = (l_f*)(Ks + ATT2_TILE);
+    const int wave = threadIdx.x >> 6, head = blockIdx.y, b = blockIdx.z;
     const int E = heads * HD;
     const long ld = 3L * E;
     const float* base = qkv + (long)b * T * ld;
-    int Tk = T;
-    if (kv_len) { Tk = kv_len[b]; Tk = Tk < 1 ? 1 : (Tk > T ? T : Tk); }
+    const int Tk = att_kv_len(kv_len, b, T);
+    att_fill_table<256>(tb, table, head, T);
+    Att2Wave<QB> w;
+    KN_ATT2_INIT(w, blockIdx.x * (128 * QB) + wave * (32 * QB))
 
-    for (int i = tid; i < 2 * T - 1 + 64; i += 256) tb[i] = i < 2 * T - 1 ? table[(long)head * (2 * T - 1) + i] : 0.f;
-
-    const float L2E = 1.44269504088896341f;
-    const float qscale = 0.125f * L2E * 16.0f;
-    int qi[QB]; bool qvalid[QB];
-    au32x4 qf[QB][4][2];
-    float g_i[QB];
-    const l_f* tbq[QB];
-#pragma unroll
-    for (int u = 0; u < QB; ++u) {
-        qi[u] = blockIdx.x * (128 * QB) + wave * (32 * QB) + u * 32 + li;
-        qvalid[u] = qi[u] < T;
-#pragma unroll
-        for (int s4 = 0; s4 < 4; ++s4) {
-            f32x4 v0 = {0.f, 0.f, 0.f, 0.f}, v1 = v0;
-            if (qvalid[u]) {
-                const float* p = base + (long)qi[u] * ld + head * HD + s4 * 16 + lh * 8;
-                v0 = *(const f32x4*)p; v1 = *(const f32x4*)(p + 4);
-            }
-            g2_u32x2 h0, l0, h1, l1;
-            f16x2_split4(v0, qscale, h0, l0); f16x2_split4(v1, qscale, h1, l1);
-            qf[u][s4][0] = (au32x4){h0[0], h0[1], h1[0], h1[1]};
-            qf[u][s4][1] = (au32x4){l0[0], l0[1], l1[0], l1[1]};
-        }
-        g_i[u] = qvalid[u] ? gate[((long)b * T + qi[u]) * heads + head] * (L2E * 256.0f) : 0.f;
-        tbq[u] = tb + (T - 1 - (qvalid[u] ? qi[u] : T - 1)) + 4 * lh;
-    }
-    const lc* v_tr = Vs + (4 * (lane >> 5) + ((lane & 15) >> 2)) * VP2 + (16 * ((lane >> 4) & 1) + 4 * (lane & 3)) * 2;
-
-    f32x16 o[QB][2];
-    float m_run[QB], l_run[QB];
-#pragma unroll
-    for (int u = 0; u < QB; ++u) {
-        m_run[u] = -__builtin_inff(); l_run[u] = 0.f;
-#pragma unroll
-        for (int d = 0; d < 2; ++d)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) o[u][d][r] = 0.f;
-    }
-
-    const int srow = tid >> 4, scol = (tid & 15) * 4;
     f32x4 rk[4], rv[4];
-    auto gload = [&](int k0) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int key = k0 + srow + 16 * j;
-            f32x4 kk = {0.f, 0.f, 0.f, 0.f}, vv = {0.f, 0.f, 0.f, 0.f};
-            if (key < T) {
-                const float* p = base + (long)key * ld + head * HD + scol;
-                kk = *(const f32x4*)(p + E);
-                vv = *(const f32x4*)(p + 2 * E);
-            }
-            rk[j] = kk; rv[j] = vv;
-        }
-    };
-    gload(0);
+    KN_ATT_LOAD_KV(256, 0)
     const int ntiles = (Tk + KT - 1) / KT;
 #ifdef KN_ATT_PROF          // timing aid (tools/attn_whatif.sh): where one wave's cycles go, printed by a few workgroups
     unsigned long long pf[4] = {0, 0, 0, 0}, tq = __builtin_readcyclecounter();
@@ -727,158 +680,41 @@ __global__ __launch_bounds__(256, 2) void attention2q_kernel(const float* __rest
 #define KN_ATICK(K)
 #endif
     for (int t = 0; t < ntiles; ++t) {
+#ifdef KN_ATT_NOSTAGE      // timing aid: the first tile's K / V serve every tile, no barriers after it
+        if (t == 0) {
+#endif
+        __syncthreads();                       // previous tile's LDS reads are done (also covers tb on t == 0)
+        att2_stage<256>(Ks, rk, rv, kv_split);
         __syncthreads();
-        if (kv_split) {
-            const int pc = tid & 15, plane = (pc >> 2) & 1, d0 = (pc >> 3) * 32 + (pc & 3) * 8;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int key = srow + 16 * j;
-                *(l_u4*)(Ks + key * KP2 + plane * 128 + d0 * 2) = __builtin_bit_cast(au32x4, rk[j]);
-                *(l_u4*)(Vs + key * VP2 + plane * 128 + d0 * 2) = __builtin_bit_cast(au32x4, rv[j]);
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int key = srow + 16 * j;
-                g2_u32x2 hi, lo;
-                f16x2_split4(rk[j], 16.0f, hi, lo);
-                lc* kd = Ks + key * KP2 + scol * 2;
-                *(l_u2*)(kd) = hi;
-                *(l_u2*)(kd + 128) = lo;
-                f16x2_split4(rv[j], 16.0f, hi, lo);
-                lc* vd = Vs + key * VP2 + scol * 2;
-                *(l_u2*)(vd) = hi;
-                *(l_u2*)(vd + 128) = lo;
-            }
+#ifdef KN_ATT_NOSTAGE
         }
-        __syncthreads();
-        if (t + 1 < ntiles) gload((t + 1) * KT);
+#else
+        if (t + 1 < ntiles) { KN_ATT_LOAD_KV(256, (t + 1) * KT) }
+#endif
         KN_ATICK(0)
-
 #pragma unroll
         for (int sub = 0; sub < 2; ++sub) {
             const int kbase = t * KT + sub * 32;
             if (kbase >= Tk) break;
-
-            // ---- S^T = K . Q^T for the QB query blocks: every K fragment pair is read once --------------
-            f32x16 s[QB];
-#pragma unroll
-            for (int u = 0; u < QB; ++u)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) s[u][r] = 0.f;
-            const lc* kp = Ks + (sub * 32 + li) * KP2 + lh * 16;
-#pragma unroll
-            for (int st = 0; st < 4; ++st) {
-                const f16x8 k0 = __builtin_bit_cast(f16x8, *(const l_u4*)(kp + st * 32));
-                const f16x8 k1 = __builtin_bit_cast(f16x8, *(const l_u4*)(kp + 128 + st * 32));
-#pragma unroll
-                for (int u = 0; u < QB; ++u) {
-                    const f16x8 q0 = __builtin_bit_cast(f16x8, qf[u][st][0]), q1 = __builtin_bit_cast(f16x8, qf[u][st][1]);
-                    s[u] = __builtin_amdgcn_mfma_f32_32x32x16_f16(k1, q0, s[u], 0, 0, 0);
-                    s[u] = __builtin_amdgcn_mfma_f32_32x32x16_f16(k0, q1, s[u], 0, 0, 0);
-                    s[u] = __builtin_amdgcn_mfma_f32_32x32x16_f16(k0, q0, s[u], 0, 0, 0);
-                }
-            }
+            w.S(Ks, sub);
             KN_ATICK(1)
-            // ---- online softmax per query block (lane-local + one exchange with lane ^ 32) ----------------
-#pragma unroll
-            for (int u = 0; u < QB; ++u) {
-                const l_f* tp = tbq[u] + kbase;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) s[u][r] = fmaf(g_i[u], tp[(r & 3) + 8 * (r >> 2)], s[u][r]);
-                if (kbase + 32 > Tk) {
-#pragma unroll
-                    for (int r = 0; r < 16; ++r)
-                        if (kbase + (r & 3) + 8 * (r >> 2) + 4 * lh >= Tk) s[u][r] = -__builtin_inff();
-                }
-                float mx = fmaxf(fmaxf(s[u][0], s[u][1]), fmaxf(s[u][2], s[u][3]));
-#pragma unroll
-                for (int r = 4; r < 16; r += 4) mx = fmaxf(mx, fmaxf(fmaxf(s[u][r], s[u][r + 1]), fmaxf(s[u][r + 2], s[u][r + 3])));
-                mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-                const float m_new = fmaxf(m_run[u], mx);
-                const float alpha = __builtin_amdgcn_exp2f((m_run[u] - m_new) * (1.0f / 256.0f));
-                const float mneg = fmaf(m_new, -1.0f / 256.0f, 14.0f);
-                float ps = 0.f;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) { s[u][r] = __builtin_amdgcn_exp2f(fmaf(s[u][r], 1.0f / 256.0f, mneg)); ps += s[u][r]; }
-                ps += __shfl_xor(ps, 32, 64);
-                l_run[u] = l_run[u] * alpha + ps;
-                m_run[u] = m_new;
-                if (__builtin_amdgcn_ballot_w64(alpha != 1.f)) {
-#pragma unroll
-                    for (int d = 0; d < 2; ++d)
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) o[u][d][r] *= alpha;
-                }
-            }
+            w.softmax(kbase, Tk);
             KN_ATICK(2)
-            // ---- O^T += V^T . P^T: every transposed V fragment is read once -------------------------------
-#pragma unroll
-            for (int st = 0; st < 2; ++st) {
-                f16x8 b0[QB], b1[QB];
-#pragma unroll
-                for (int u = 0; u < QB; ++u) {
-                    g2_u32x2 h0, l0, h1, l1;
-                    f16x2_split4((f32x4){s[u][8 * st + 0], s[u][8 * st + 1], s[u][8 * st + 2], s[u][8 * st + 3]}, 1.0f, h0, l0);
-                    f16x2_split4((f32x4){s[u][8 * st + 4], s[u][8 * st + 5], s[u][8 * st + 6], s[u][8 * st + 7]}, 1.0f, h1, l1);
-                    b0[u] = __builtin_bit_cast(f16x8, (au32x4){h0[0], h0[1], h1[0], h1[1]});
-                    b1[u] = __builtin_bit_cast(f16x8, (au32x4){l0[0], l0[1], l1[0], l1[1]});
-                }
-                const lc* vrow = v_tr + (sub * 32 + 16 * st) * VP2;
-#pragma unroll
-                for (int dt = 0; dt < 2; ++dt) {
-                    typedef __attribute__((address_space(3))) short4v l_s4;
-                    const lc* vp = vrow + dt * 64;
-                    const au32x2 x0 = __builtin_bit_cast(au32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((l_s4*)(vp)));
-                    const au32x2 x1 = __builtin_bit_cast(au32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((l_s4*)(vp + 8 * VP2)));
-                    const au32x2 y0 = __builtin_bit_cast(au32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((l_s4*)(vp + 128)));
-                    const au32x2 y1 = __builtin_bit_cast(au32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((l_s4*)(vp + 8 * VP2 + 128)));
-                    const f16x8 v0 = __builtin_bit_cast(f16x8, (au32x4){x0[0], x0[1], x1[0], x1[1]});
-                    const f16x8 v1 = __builtin_bit_cast(f16x8, (au32x4){y0[0], y0[1], y1[0], y1[1]});
-#pragma unroll
-                    for (int u = 0; u < QB; ++u) {
-                        f32x16 c = o[u][dt];
-                        c = __builtin_amdgcn_mfma_f32_32x32x16_f16(v1, b0[u], c, 0, 0, 0);
-                        c = __builtin_amdgcn_mfma_f32_32x32x16_f16(v0, b1[u], c, 0, 0, 0);
-                        c = __builtin_amdgcn_mfma_f32_32x32x16_f16(v0, b0[u], c, 0, 0, 0);
-                        o[u][dt] = c;
-                    }
-                }
-            }
+            w.PV(Ks, sub);
             KN_ATICK(3)
         }
     }
 #ifdef KN_ATT_PROF
-    if (tid == 0 && blockIdx.x == 2 && blockIdx.y == 3 && (blockIdx.z % 5) == 0)
+    if (threadIdx.x == 0 && blockIdx.x == 2 && blockIdx.y == 3 && (blockIdx.z % 5) == 0)
         printf("att prof (cycles per 64-key tile, wave 0 of batch %d): stage+barriers %.0f  S (K reads + issue) %.0f  softmax (incl. wait for S) %.0f  PV (split, V reads, issue) %.0f  | whole block %.0f\n",
                (int)blockIdx.z, (double)pf[0] / ntiles, (double)pf[1] / ntiles, (double)pf[2] / ntiles, (double)pf[3] / ntiles, (double)(__builtin_readcyclecounter() - t_begin));
 #endif
 #undef KN_ATICK
-#pragma unroll
-    for (int u = 0; u < QB; ++u) {
-        if (!qvalid[u]) continue;
-        const float inv = 0.0625f / l_run[u];
-        float* op = out + ((long)b * T + qi[u]) * E + head * HD;
-#pragma unroll
-        for (int d = 0; d < 2; ++d)
-#pragma unroll
-            for (int r4 = 0; r4 < 4; ++r4) {
-                f32x4 v = {o[u][d][r4 * 4 + 0] * inv, o[u][d][r4 * 4 + 1] * inv, o[u][d][r4 * 4 + 2] * inv, o[u][d][r4 * 4 + 3] * inv};
-                if (out_split) {
-                    g2_u32x2 hi, lo;
-                    f16x2_split4(v, KN_F16X2_A_SCALE, hi, lo);
-                    const int c = head * HD + d * 32 + r4 * 8 + lh * 4;
-                    char* ob = (char*)(out + ((long)b * T + qi[u]) * E) + (c >> 5) * 128 + (c & 31) * 2;
-                    *(g2_u32x2*)ob = hi;
-                    *(g2_u32x2*)(ob + 64) = lo;
-                } else
-                    *(f32x4*)(op + d * 32 + r4 * 8 + lh * 4) = v;
-            }
-    }
+    w.store(out, b, T, E, head, out_split);
 }
 
 // ---------------------------------------------------------------------------------------------
-// attention2q_kernel with EIGHT waves per workgroup (512 queries, one workgroup per CU) and the two waves of a SIMD out of
+// The f16x2 step (a copy of Att2Wave's statements, see above) with EIGHT waves per workgroup (512 queries, one workgroup per CU) and the two waves of a SIMD out of
 // phase.  Round 3's phase counters: a wave spends ~11 000 cycles per 64-key tile — 3 072 of MFMA, ~3 700 of VALU (softmax,
 // split of P), 2 000-3 500 around the staging and its two barriers — and the two waves of a SIMD, released by the same
 // barriers, want the matrix pipe at the same time and the VALU at the same time: the sum, not the maximum.
@@ -888,17 +724,13 @@ __global__ __launch_bounds__(256, 2) void attention2q_kernel(const float* __rest
 //     BEFORE the S that opens the next tile, waves 4-7 (their SIMD neighbours) BEHIND it: when the barrier opens one group
 //     starts on the matrix pipe and the other on the VALU.  That S may read the first half of the NEXT tile before this
 //     tile's barrier, which is why tiles are staged two ahead (that tile was published by the previous barrier).
-// Per query the same operations in the same order as attention2q_kernel / attention2_kernel: results are bit-identical.
+// Per query the same operations in the same order as attention2q_kernel: results are bit-identical.
 // ---------------------------------------------------------------------------------------------
 template <int QB>
 __global__ __launch_bounds__(512, 1) void attention2w_kernel(const float* __restrict__ qkv, const float* __restrict__ gate,
                                                             const float* __restrict__ table, const int* __restrict__ kv_len, int T, int heads,
                                                             float* __restrict__ out, int out_split, int kv_split) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    typedef __attribute__((address_space(3))) char lc;
-    typedef __attribute__((address_space(3))) au32x4 l_u4;
-    typedef __attribute__((address_space(3))) au32x2 l_u2;
-    typedef __attribute__((address_space(3))) float l_f;
     constexpr int NT = 512, NJ = KT * 16 / NT;        // 16 threads per key row: 32 rows per pass, two passes
     constexpr int KVB = KT * KP2 + KT * VP2;          // bytes of one K + V tile
     lc* Ks = (lc*)lds;
@@ -1134,8 +966,21 @@ __global__ __launch_bounds__(512, 1) void attention2w_kernel(const float* __rest
     }
 }
 
-
+#undef KN_ATT_LOAD_KV
+#undef KN_ATT2_INIT
 }  // namespace
+
+// One route's launch: the 160 KB LDS limit (t_max: the hint of its message), the kernel's LDS opt-in, a grid of
+// ceil(T / q_per_wg) x heads x batches workgroups, the launch and its check.
+template <auto KERNEL, class... Args>
+static int att_launch(int q_per_wg, int threads, size_t lds_bytes, int t_max, const char* tag, int T, int heads, int batches, void* stream,
+                      Args... args) {
+    KN_REQUIRE(lds_bytes <= 160 * 1024, "wavlm_attention: T too long for the LDS bias table (T <= ~%d)", t_max);
+    if (const int rc = kn_lds_optin<KERNEL>((int)lds_bytes, "wavlm_attention")) return rc;
+    dim3 grid((unsigned)((T + q_per_wg - 1) / q_per_wg), (unsigned)heads, (unsigned)batches);
+    hipLaunchKernelGGL(KERNEL, grid, dim3(threads), lds_bytes, (hipStream_t)stream, args...);
+    return knnsvc_check_launch(tag);
+}
 
 extern "C" int knnsvc_wavlm_attention(const float* qkv, const float* gate, const float* table, int32_t batches,
                                       int32_t T, int32_t heads, float* out, int32_t out_f16x2, int32_t kv_f16x2, const int32_t* kv_len,
@@ -1152,9 +997,6 @@ extern "C" int knnsvc_wavlm_attention(const float* qkv, const float* gate, const
     const int mode = (out_f16x2 & 4) && env_mode == 2 ? 3 : env_mode;
     out_f16x2 &= 1;
     if (mode == 2) {
-        const size_t l2 = (size_t)KT * KP2 + (size_t)KT * VP2 + (size_t)(2 * T - 1 + 64) * 4;
-        KN_REQUIRE(l2 <= 160 * 1024, "wavlm_attention: T too long for the LDS bias table (T <= ~16000)");
-        if (const int rc = kn_lds_optin<attention2_kernel>((int)l2, "wavlm_attention")) return rc;
         // 64 queries per wave once the 128-query grid is at least two rounds of the 768 resident workgroups (bench batch, 21 x 1500:
         // 0.86 -> 0.78 ms); below that the larger workgroups leave CUs idle (3 x 777: 0.054 vs 0.063 ms).  Same results either
         // way, bit for bit.  KNNSVC_ATT_QB=1 / 2 forces one of them.
@@ -1166,35 +1008,19 @@ extern "C" int knnsvc_wavlm_attention(const float* qkv, const float* gate, const
             // grid is at least two rounds of one workgroup per CU; KNNSVC_ATT_NW=4 / 8 forces one.  Same results, bit for bit.
             const char* ew = getenv("KNNSVC_ATT_NW");
             const long blocks512 = (long)((T + 511) / 512) * heads * batches;
-            const size_t l2w = (size_t)3 * (KT * KP2 + KT * VP2) + (size_t)(2 * T - 1 + 64) * 4;
-            if ((ew ? ew[0] == '8' : blocks512 >= 512) && l2w <= 160 * 1024) {
-                if (const int rc = kn_lds_optin<attention2w_kernel<2>>((int)l2w, "wavlm_attention")) return rc;
-                dim3 gridw((unsigned)((T + 511) / 512), (unsigned)heads, (unsigned)batches);
-                hipLaunchKernelGGL(attention2w_kernel<2>, gridw, dim3(512), l2w, (hipStream_t)stream, qkv, gate, table, kv_len, T, heads, out, out_f16x2, kv_f16x2);
-                return knnsvc_check_launch("wavlm_attention2w");
-            }
-            if (const int rc = kn_lds_optin<attention2q_kernel<2>>((int)l2, "wavlm_attention")) return rc;
-            dim3 gridq((unsigned)((T + 255) / 256), (unsigned)heads, (unsigned)batches);
-            hipLaunchKernelGGL(attention2q_kernel<2>, gridq, dim3(256), l2, (hipStream_t)stream, qkv, gate, table, kv_len, T, heads, out, out_f16x2, kv_f16x2);
-            return knnsvc_check_launch("wavlm_attention2q");
+            if ((ew ? ew[0] == '8' : blocks512 >= 512) && att2_lds_bytes(3, T) <= 160 * 1024)
+                return att_launch<attention2w_kernel<2>>(512, 512, att2_lds_bytes(3, T), 16000, "wavlm_attention2w", T, heads, batches, stream,
+                                                         qkv, gate, table, kv_len, T, heads, out, out_f16x2, kv_f16x2);
+            return att_launch<attention2q_kernel<2>>(256, 256, att2_lds_bytes(1, T), 16000, "wavlm_attention2q", T, heads, batches, stream,
+                                                     qkv, gate, table, kv_len, T, heads, out, out_f16x2, kv_f16x2);
         }
-        dim3 grid2((unsigned)((T + 127) / 128), (unsigned)heads, (unsigned)batches);
-        hipLaunchKernelGGL(attention2_kernel, grid2, dim3(256), l2, (hipStream_t)stream, qkv, gate, table, kv_len, T, heads, out, out_f16x2, kv_f16x2);
-        return knnsvc_check_launch("wavlm_attention2");
+        return att_launch<attention2q_kernel<1>>(128, 256, att2_lds_bytes(1, T), 16000, "wavlm_attention2", T, heads, batches, stream,
+                                                 qkv, gate, table, kv_len, T, heads, out, out_f16x2, kv_f16x2);
     }
     KN_REQUIRE(!out_f16x2 && !kv_f16x2, "wavlm_attention: split output / pre-split K,V are only implemented by the f16x2 kernel");
-    if (mode == 3) {
-        const size_t l3 = (size_t)KT * KP3 + (size_t)HD * VP3 + (size_t)(2 * T - 1 + 64) * 4;
-        KN_REQUIRE(l3 <= 160 * 1024, "wavlm_attention: T too long for the LDS bias table (T <= ~13000)");
-        if (const int rc = kn_lds_optin<attention3_kernel>((int)l3, "wavlm_attention")) return rc;
-        dim3 grid3((unsigned)((T + 127) / 128), (unsigned)heads, (unsigned)batches);
-        hipLaunchKernelGGL(attention3_kernel, grid3, dim3(256), l3, (hipStream_t)stream, qkv, gate, table, kv_len, T, heads, out);
-        return knnsvc_check_launch("wavlm_attention3");
-    }
-    const size_t lds = (size_t)(KT * LDKK + KT * LDV + 2 * T - 1) * 4;
-    KN_REQUIRE(lds <= 160 * 1024, "wavlm_attention: T too long for the LDS bias table (T <= ~16000)");
-    if (const int rc = kn_lds_optin<attention_kernel>((int)lds, "wavlm_attention")) return rc;
-    dim3 grid((unsigned)((T + 127) / 128), (unsigned)heads, (unsigned)batches);
-    hipLaunchKernelGGL(attention_kernel, grid, dim3(256), lds, (hipStream_t)stream, qkv, gate, table, kv_len, T, heads, out);
-    return knnsvc_check_launch("wavlm_attention");
+    if (mode == 3)
+        return att_launch<attention3_kernel>(128, 256, (size_t)KT * KP3 + (size_t)HD * VP3 + att_table_bytes(T), 13000, "wavlm_attention3", T, heads,
+                                             batches, stream, qkv, gate, table, kv_len, T, heads, out);
+    return att_launch<attention_kernel>(128, 256, (size_t)(KT * LDKK + KT * LDV + 2 * T - 1) * 4, 16000, "wavlm_attention", T, heads, batches,
+                                        stream, qkv, gate, table, kv_len, T, heads, out);
 }

@@ -68,8 +68,9 @@ def test_wavlm_large_six_layers_one_full_chunk_golden(golden):
 
 
 def test_attention_full_length_vs_oracle():
-    """attention2_kernel at E=1024 / H=16 / T=1500 (12 query blocks x many key tiles per head, distances beyond the
-    last log bucket, ragged last tile since 1500 % 128 != 0) vs F.scaled_dot_product_attention with the gated bias."""
+    """The f16x2 attention at E=1024 / H=16 / T=1500 as dispatched for one chunk (attention2q_kernel<1>: 12 query blocks x
+    many key tiles per head, distances beyond the last log bucket, ragged last tile since 1500 % 128 != 0) vs
+    F.scaled_dot_product_attention with the gated bias."""
     from knn_svc_amd import ops
     from oracle import wavlm_ref
     cfg = dict(C.WAVLM_LARGE, encoder_layers=1)

@@ -391,14 +391,21 @@ def test_attention_and_gate():
     table = sd[p + "relative_attention_bias.weight"][lut].T.contiguous()        # [H, 2T-1]
     qkv = torch.cat([q, k, v], -1).transpose(0, 1).reshape(B * T, 3 * E).contiguous().to(DEV)
     out = ops.wavlm_attention(qkv, gate, table.to(DEV), B, T, H)
+    print(f"attention T=333: f16x2 max|d| {_err(out, ref)[0]:.2e}")
     assert _err(out, ref)[0] < 2e-5
+    # the wide-range route (attention3_kernel, bf16x3) on the same inputs: three 128-query blocks with a ragged last one, six key
+    # tiles with a one-step last tile.  Its split carries 24 mantissa bits against 22 for f16x2: the same bound.
+    out3 = ops.wavlm_attention(qkv, gate, table.to(DEV), B, T, H, wide=True)
+    print(f"attention T=333: bf16x3 (wide) max|d| {_err(out3, ref)[0]:.2e}")
+    assert _err(out3, ref)[0] < 2e-5
 
 
 @pytest.mark.parametrize("B,T,split", [(2, 333, False), (3, 700, True), (1, 1500, True)])
 def test_attention_64_queries_per_wave_equals_32(B, T, split, monkeypatch):
-    """attention2q_kernel<2> (64 queries per wave: the large-batch dispatch) against attention2_kernel (32 per wave): the
-    same operations per query in the same order — bit-identical, with ragged last blocks, key-padding lengths, pre-split K / V
-    and split output."""
+    """attention2q_kernel<2> (64 queries per wave: the large-batch dispatch) against attention2q_kernel<1> (32 per wave: small
+    grids), two instances of the four-wave schedule around the one f16x2 flash step: the same operations per query in the same
+    order — bit-identical, with ragged last blocks, key-padding lengths, pre-split K / V and split output.  A wrong per-block
+    index or a tile shared wrongly between the two query blocks of a wave shows here."""
     ops = _ops()
     H, E = 16, 1024
     g = torch.Generator().manual_seed(B * 1000 + T)
@@ -419,9 +426,10 @@ def test_attention_64_queries_per_wave_equals_32(B, T, split, monkeypatch):
 @pytest.mark.parametrize("B,T,split", [(2, 333, False), (3, 700, True), (1, 1500, True), (2, 1061, True)])
 def test_attention_eight_waves_per_workgroup_equals_four(B, T, split, monkeypatch):
     """attention2w_kernel (512 queries per workgroup, K / V tiles in three LDS buffers staged two ahead, one barrier per tile at a
-    different point of the step for the two waves of a SIMD — the large-batch dispatch) against attention2q_kernel: per query the
-    same operations in the same order, so bit-identical — with an odd number of 32-key steps (T = 333, 1061: the last tile has one
-    step), fewer than three tiles after key padding, ragged last query blocks, pre-split K / V and split output."""
+    different point of the step for the two waves of a SIMD — the large-batch dispatch) against attention2q_kernel<2>: its own
+    copy of the f16x2 flash step against the shared one, per query the same operations in the same order, so bit-identical — with an odd
+    number of 32-key steps (T = 333, 1061: the last tile has one step), fewer than three tiles after key padding, ragged last
+    query blocks, pre-split K / V and split output."""
     ops = _ops()
     H, E = 16, 1024
     g = torch.Generator().manual_seed(B * 1000 + T + 1)
