@@ -31,7 +31,7 @@ extern "C" {
 #define KNNSVC_EHIP      3   /* a HIP runtime call failed                  */
 #define KNNSVC_ENAN      4   /* NaN distance (the reference sys.exit()s)   */
 
-#define KNNSVC_ABI_VERSION 18
+#define KNNSVC_ABI_VERSION 19
 
 int knnsvc_abi_version(void);
 const char* knnsvc_last_error(void);
@@ -575,6 +575,42 @@ int knnsvc_additive_synth(const float* f0, const float* amp, int64_t N, int32_t 
                           int32_t sample_rate, int32_t mode, const float* prenet_w, const float* prenet_b,
                           int32_t n_ch, float* cond, int32_t ld_cond, float* exc, double* frame_phase,
                           const int32_t* n_dyn, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Output loudness (csrc/loudness.hip).  The reference documents tgt_loudness_db as "float db used to normalize the output
+ * volume" and does gain(prediction, tgt - torchaudio.functional.loudness(prediction)) (ddsp_matcher.py:533, 947; live in its
+ * `match`, commented out in special_match :997-1003).
+ * ------------------------------------------------------------------------------------------ */
+/* Integrated loudness (LKFS) of a mono fp32 signal wav[0..n) on the device, after ITU-R BS.1770-4 with the constants and biquad
+ * forms of torchaudio.functional.loudness:
+ *   K-weighting  two biquads in cascade, direct form  y[i] = b0 x[i] + b1 x[i-1] + b2 x[i-2] - a1 y[i-1] - a2 y[i-2],  zero initial
+ *                state, coefficients computed in fp64 and divided by a0, intermediate signals NOT clamped:
+ *                high-shelf +4 dB at 1500 Hz, Q = 1/sqrt 2 (w0 = 2 pi 1500 / sr, A = 10^(4/40), alpha = sin w0 / (2Q),
+ *                  b = [A((A+1)+(A-1)cos w0+2 sqrt(A) alpha), -2A((A-1)+(A+1)cos w0), A((A+1)+(A-1)cos w0-2 sqrt(A) alpha)],
+ *                  a = [(A+1)-(A-1)cos w0+2 sqrt(A) alpha, 2((A-1)-(A+1)cos w0), (A+1)-(A-1)cos w0-2 sqrt(A) alpha]),  then
+ *                high-pass at 38 Hz, Q = 0.5 (b = [(1+cos w0)/2, -(1+cos w0), (1+cos w0)/2], a = [1+alpha, -2 cos w0, 1-alpha]);
+ *   blocks       G = 0.4 sr samples every S = G/4 (sample_rate must be a multiple of 10, 8000 .. 768000): nb = (n - G) / S + 1
+ *                blocks when n >= G, else none (a trailing partial step is ignored);  e_j = mean(y^2) over block j,
+ *                l_j = -0.691 + 10 log10 e_j;
+ *   gating       keep l_j > -70;  Gamma = -0.691 + 10 log10(mean of the kept e_j) - 10;  keep l_j > Gamma as well;
+ *                result = -0.691 + 10 log10(mean of the twice-kept e_j), -inf without blocks or when a gate leaves nothing.
+ * All arithmetic between the samples and the result is fp64 in a fixed order (bit-stable from run to run).
+ * lkfs: ONE device float.  counts (device int32 [3], may be NULL): blocks, blocks kept by the absolute gate, blocks kept by both.
+ * n == 0 and n < G are valid; n may not exceed 2^36 samples (the block counts are int32; the functions below refuse more).
+ * Two of the four launches are a single workgroup whose serial work per thread grows linearly with n (negligible for clips and
+ * for hours of audio, see csrc/loudness.hip).  workspace: 8-byte aligned device memory of at least knnsvc_loudness_workspace_bytes(n, sample_rate)
+ * bytes (a HOST function; 0 with knnsvc_last_error() set for n < 0 or a bad rate); a smaller one is refused before anything is
+ * launched.  Asynchronous on `stream`, no allocation, no host synchronisation, capturable. */
+size_t knnsvc_loudness_workspace_bytes(int64_t n, int32_t sample_rate);
+/* HOST: the lengths at which the measure changes path: samples per lane (`chunk`; the filter state crosses these boundaries)
+ * and samples per workgroup (`group`).  Tests take their edge lengths from here; either pointer may be NULL. */
+void knnsvc_loudness_layout(int32_t* chunk, int32_t* group);
+int knnsvc_loudness(const float* wav, int64_t n, int32_t sample_rate, float* lkfs, int32_t* counts, void* workspace,
+                    size_t workspace_bytes, void* stream);
+/* out[i] = wav[i] * g,  g = (float)10^((target_db - *lkfs) / 20) evaluated in fp64 on the device from the DEVICE float lkfs
+ * (what knnsvc_loudness wrote); g = 1 when *lkfs is -inf, +inf or NaN (silence stays silence, a NaN waveform stays as it is for
+ * the caller's finiteness check).  out may alias wav. */
+int knnsvc_loudness_gain(float* wav, int64_t n, const float* lkfs, float target_db, float* out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -11,7 +11,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("KNNSVC_LIB") or os.path.join(_HERE, "libknnsvc_hip.so")      # KNNSVC_LIB: an A/B build (csrc/Makefile)
-ABI_VERSION = 18
+ABI_VERSION = 19
 
 vp, i32, i64, f32, sz = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_size_t
 
@@ -172,6 +172,10 @@ SIGNATURES = {
     "knnsvc_complex_mag": (i32, [vp, i64, i32, i32, vp, vp]),
     "knnsvc_harmonic_amps": (i32, [vp, vp, i64, i32, i32, vp, vp]),
     "knnsvc_additive_synth": (i32, [vp, vp, i64, i32, i32, i32, i32, vp, vp, i32, vp, i32, vp, vp, vp, vp]),
+    "knnsvc_loudness_workspace_bytes": (sz, [i64, i32]),
+    "knnsvc_loudness_layout": (None, [C.POINTER(i32), C.POINTER(i32)]),
+    "knnsvc_loudness": (i32, [vp, i64, i32, vp, vp, vp, sz, vp]),
+    "knnsvc_loudness_gain": (i32, [vp, i64, vp, f32, vp, vp]),
 }
 
 _lib = None

@@ -5,9 +5,13 @@
 SRC/TGT are both audio files (single conversion, output next to SRC as
 ``<src>_to_<tgt>_knn_<ckpt_type>_<post_opt>.wav``) or both dataset roots (folders of
 speaker folders; outputs under ``<tgt parent>/<src>_to_<tgt>_<ckpt_type>_post_opt_<post_opt>/``,
-prefixed ``duration_limit_<n>_`` when --dur_limit is given).  --topk and
---tgt_loudness_db are accepted and ignored, as upstream; --dur_limit is compared in
-seconds, as upstream (ddsp_prematch_dataset.py:408-411).
+prefixed ``duration_limit_<n>_`` when --dur_limit is given).  --topk is accepted and
+ignored, as upstream.  --tgt_loudness_db (default -16) is accepted and, as upstream,
+ignored unless --normalize_loudness true is given (an extension, default false): every
+output is then brought to that integrated loudness (BS.1770) on the GPU before it is
+written; file names do not change, and a clip normalised past full scale is written
+lower than asked (save_audio divides by a peak above 1, as upstream).  --dur_limit is
+compared in seconds, as upstream (ddsp_prematch_dataset.py:408-411).
 """
 from __future__ import annotations
 
@@ -42,6 +46,8 @@ def build_parser() -> argparse.ArgumentParser:
     for flag, kw in FLAGS:
         ap.add_argument(flag, **kw)
     ap.add_argument("--prioritize_f0", type=_bool, default=True)
+    ap.add_argument("--normalize_loudness", type=_bool, default=False,
+                    help="(extension) normalise every output to --tgt_loudness_db LKFS")
     ap.add_argument("--weights", default="auto", choices=["auto", "checkpoint", "seeded"],
                     help="(extension) 'seeded' runs with random weights when the released checkpoints are unavailable")
     return ap
@@ -61,7 +67,7 @@ def main(argv=None) -> int:
     knn = knn_vc(pretrained=True, progress=True, prematched=True, device=a.device, ckpt_type=a.ckpt_type,
                  local_ckpt_dir=a.ckpt_dir, weights=a.weights)
     common = dict(topk=a.topk, device=a.device, prioritize_f0=a.prioritize_f0, ckpt_type=a.ckpt_type,
-                  tgt_loudness_db=a.tgt_loudness_db, post_opt=a.post_opt)
+                  tgt_loudness_db=a.tgt_loudness_db, post_opt=a.post_opt, normalize_loudness=a.normalize_loudness)
     if os.path.isfile(a.src) and os.path.isfile(a.tgt):
         knn.special_match(src_wav_file=a.src, ref_wav_file=a.tgt, **common)
         return 0

@@ -2,8 +2,14 @@
 
 Mirror of ddsp_matcher.py:303-1155 restricted to its live methods: ``vocode``
 (:375-406), ``special_match`` (:937-1023) and ``bulk_match`` (:1027-1155), with the
-same argument names, output file naming and ignored arguments (``topk``,
-``tgt_loudness_db``).  Differences that are deliberate: ``special_match`` returns
+same argument names, output file naming and ignored argument (``topk``).
+``tgt_loudness_db`` is accepted and, as in the reference's live methods, ignored UNLESS
+``normalize_loudness=True`` is passed (an extension, off by default): the generator's waveform is
+then brought to that integrated loudness on the GPU (ops.normalize_loudness; what the reference
+documents for the argument, ddsp_matcher.py:533, 947, and does in its commented-out block
+:997-1003).  ``audio_io.save_audio`` keeps the reference's peak rule — a waveform whose peak
+exceeds 1 is divided by it — so a clip normalised past full scale is written lower than asked;
+there is no limiter.  Other differences that are deliberate: ``special_match`` returns
 the waveform instead of calling ``sys.exit()`` after saving (the CLI exits 0, the
 observable behaviour), and ``bulk_match`` does not ``rm -rf`` a hard-coded cache
 directory (ddsp_matcher.py:1066-1068).
@@ -37,16 +43,17 @@ class KNeighborsVC:
         self.hop_length = 320
 
     @torch.inference_mode()
-    def vocode(self, c, f0=None, harmonics_out_feats_weighted=None):
-        """c (bs, seq_len, c_dim), f0 (bs, seq_len, 1), harmonics (bs, seq_len, 49) -> (bs, seq_len*320)."""
+    def vocode(self, c, f0=None, harmonics_out_feats_weighted=None, loudness_db=None):
+        """c (bs, seq_len, c_dim), f0 (bs, seq_len, 1), harmonics (bs, seq_len, 49) -> (bs, seq_len*320).
+        ``loudness_db`` (extension): every waveform is normalised to that integrated loudness before the finiteness check."""
         if f0 is None:
             raise NotImplementedError("the f0-free 'wavlm_only_original' generator (hifigan/models.py) is missing "
                                       "from the reference snapshot and unsupported")
         outs = []
         for b in range(c.shape[0]):
             harm = harmonics_out_feats_weighted[b] if harmonics_out_feats_weighted is not None else None
-            outs.append(self.hifigan.forward(c[b].to(self.device).float(), f0[b].reshape(-1).to(self.device).float(),
-                                             None if harm is None else harm.to(self.device).float()))
+            outs.append(self._vocode_async(c[b].to(self.device), f0[b].to(self.device), None if harm is None else harm.to(self.device),
+                                           loudness_db=loudness_db))
         wav = torch.stack(outs, 0)
         self._check_finite(wav)
         return wav
@@ -57,13 +64,24 @@ class KNeighborsVC:
         if not bool(torch.isfinite(wav).all()):
             raise ops.KnnSvcError("vocode: non-finite waveform (non-finite features, f0, harmonics or weights)")
 
-    def _vocode_async(self, c, f0, harm=None):
-        """One utterance, enqueue only (no host sync): the tail stage of the dataset-mode pipeline."""
-        return self.hifigan.forward(c.float(), f0.reshape(-1).float(), None if harm is None else harm.float())
+    def _vocode_async(self, c, f0, harm=None, loudness_db=None):
+        """One utterance, enqueue only (no host sync): the tail stage of the dataset-mode pipeline.  ``loudness_db``: the
+        waveform is measured and scaled to that level on the same stream (in place: ``Vocoder.forward`` hands out a copy)."""
+        y = self.hifigan.forward(c.float(), f0.reshape(-1).float(), None if harm is None else harm.float())
+        if loudness_db is not None:
+            ops.normalize_loudness(y, loudness_db, self.sr, out=y)
+        return y
+
+    def _tail(self, f0only, loudness_db=None):
+        """``vocode_fn(out_feats, shifted_f0, harm)`` of the stream pipeline: generator, then loudness when asked for."""
+        if f0only:
+            return lambda c, f0, _h: self._vocode_async(c, f0, loudness_db=loudness_db)
+        return lambda c, f0, h: self._vocode_async(c, f0, h, loudness_db=loudness_db)
 
     @torch.inference_mode()
     def special_match(self, src_wav_file, ref_wav_file, topk: int = 4, device=None, prioritize_f0=True,
-                      ckpt_type="wavlm_only", tgt_loudness_db=-16, post_opt="no_post_opt", save=True):
+                      ckpt_type="wavlm_only", tgt_loudness_db=-16, post_opt="no_post_opt", save=True, normalize_loudness=False):
+        level = tgt_loudness_db if normalize_loudness else None
         f0only = "wavlm_only" in ckpt_type or "no_harm_no_amp" in ckpt_type
         if "wavlm_only_original" in ckpt_type:
             raise NotImplementedError("wavlm_only_original needs hifigan/models.py, absent upstream")
@@ -72,13 +90,13 @@ class KNeighborsVC:
             of, hw, _a, sf0 = match_at_inference_time(Path(src_wav_file), Path(ref_wav_file), self.wavlm,
                                                       self.weighting, self.weighting, topk=topk, device=self.device,
                                                       prioritize_f0=prioritize_f0, ckpt_type=ckpt_type, post_opt=post_opt)
-            pred = self.vocode(of[key][None], sf0[key][None, :, None], hw[key][None]).squeeze()
+            pred = self.vocode(of[key][None], sf0[key][None, :, None], hw[key][None], loudness_db=level).squeeze()
         else:
             # the reference does not forward post_opt on this branch (ddsp_matcher.py:970)
             of, _a, sf0 = match_at_inference_time(Path(src_wav_file), Path(ref_wav_file), self.wavlm,
                                                   self.weighting, self.weighting, topk=topk, device=self.device,
                                                   prioritize_f0=prioritize_f0, ckpt_type=ckpt_type)
-            pred = self.vocode(of[key][None], sf0[key][None, :, None]).squeeze()
+            pred = self.vocode(of[key][None], sf0[key][None, :, None], loudness_db=level).squeeze()
         src_id = os.path.basename(src_wav_file).split(".")[0]
         ref_id = os.path.basename(ref_wav_file).split(".")[0]
         out_file = str(Path(src_wav_file).parent) + "/" + src_id + "_to_" + ref_id + f"_knn_{ckpt_type}_{post_opt}.wav"
@@ -89,24 +107,26 @@ class KNeighborsVC:
 
     @torch.inference_mode()
     def many_to_one(self, src_files, ref_wav_file, converted_audio_dir=None, ckpt_type="mix", post_opt="post_opt_0.2",
-                    duration_limit=None, target=None, match=None):
+                    duration_limit=None, target=None, match=None, loudness_db=None):
         """BASELINE cfg 5 (no counterpart upstream: the reference would call ``special_match`` once per source and rebuild the
         target pool each time, ddsp_matcher.py:937-1023): MANY sources against ONE target pool that is built once and stays
         resident, all sources through the stream pipeline as one batch (knn_svc_amd/serving.py).  Under a process group the
         sources are dealt over the ranks (no collective).  ``target``: a serving.TargetVoice to reuse.  -> written paths (all
         ranks' on every rank), named like ``special_match``'s outputs.  ``match``: "lanes" | "segmented" (serving.BatchConverter; default
-        from KNNSVC_MATCH)."""
+        from KNNSVC_MATCH).  ``loudness_db``: every waveform is normalised to that integrated loudness (None: left as generated)."""
         from . import serving
         if target is None:
             target = serving.TargetVoice(self, ref_wav_file, duration_limit)
         mine = kdist.my_share([str(p) for p in src_files])
-        written = serving.BatchConverter(self, target, ckpt_type, post_opt, match=match).convert_files(mine, converted_audio_dir)
+        written = serving.BatchConverter(self, target, ckpt_type, post_opt, match=match,
+                                         loudness_db=loudness_db).convert_files(mine, converted_audio_dir)
         return kdist.gather_paths(written)
 
     @torch.inference_mode()
     def bulk_match(self, src_dataset_path, tgt_dataset_path, converted_audio_dir, topk: int = 4, device=None,
                    prioritize_f0=True, ckpt_type="mix", tgt_loudness_db=-16, required_subset_file=None,
-                   post_opt="no_post_opt", duration_limit=None):
+                   post_opt="no_post_opt", duration_limit=None, normalize_loudness=False):
+        level = tgt_loudness_db if normalize_loudness else None
         assert os.path.isdir(src_dataset_path) and os.path.isdir(tgt_dataset_path)
         Path(converted_audio_dir).mkdir(parents=True, exist_ok=True)
         spk = lambda root: sorted([p for p in Path(root).iterdir() if p.is_dir() and "f0_cache" not in os.path.basename(p)])
@@ -147,14 +167,15 @@ class KNeighborsVC:
                               pool_sharded=shard, share_items=shard)
                 # the generator of every utterance is the tail stage of the match pipeline (same kernels and inputs as
                 # `vocode` after the fact, ddsp_matcher.py:1114-1128, but enqueued under the next utterances' matching);
-                # one finiteness check per speaker pair instead of one host sync per utterance
+                # one finiteness check per speaker pair instead of one host sync per utterance; with normalize_loudness the
+                # tail is generator + loudness, still enqueue-only
                 preds = {}
                 if not f0only:
                     match_at_inference_time(Path(s), Path(t), self.wavlm, self.weighting, self.weighting, post_opt=post_opt,
-                                            vocode_fn=self._vocode_async, waves_out=preds, **common)
+                                            vocode_fn=self._tail(False, level), waves_out=preds, **common)
                 else:
                     match_at_inference_time(Path(s), Path(t), self.wavlm, self.weighting, self.weighting,
-                                            vocode_fn=lambda c, f0, _h: self._vocode_async(c, f0), waves_out=preds, **common)
+                                            vocode_fn=self._tail(True, level), waves_out=preds, **common)
                 if preds:      # max |x| of a waveform is NaN / inf iff the waveform holds one
                     self._check_finite(torch.stack([p.abs().max() for p in preds.values()]))
                 for k, pred in preds.items():

@@ -1022,3 +1022,50 @@ def additive_synth(f0, amp, prenet_w, prenet_b, cond, ld_cond, *, hop=320, sr=16
     check(_lib.load().knnsvc_additive_synth(_p(f0), _p(amp), N, H, hop, sr, mode, _p(prenet_w), _p(prenet_b), n_ch,
                                             _p(cond), ld_cond, _p(exc), _p(ph), _p(n_dyn), _stream()), "additive_synth")
     return exc
+
+
+# ------------------------------------------------------------------ output loudness
+def loudness_layout():
+    """(samples one lane filters, samples one workgroup covers) as the library reports them (csrc/loudness.hip: LD_C, LD_W): the
+    lengths at which the measure changes path; the filter state crosses the first kind of boundary."""
+    chunk, group = C.c_int32(0), C.c_int32(0)
+    _lib.load().knnsvc_loudness_layout(C.byref(chunk), C.byref(group))
+    return chunk.value, group.value
+
+
+def loudness(wav, sample_rate=16000, return_counts=False):
+    """Integrated loudness (LKFS) of a mono signal after ITU-R BS.1770-4 — K-weighting, 400 ms blocks, absolute gate at -70 and
+    relative gate at -10 (the definition in include/knnsvc_hip.h; fp64 on the device, csrc/loudness.hip) -> 0-d fp32 device
+    tensor, -inf for a signal shorter than one block or one that the gates empty.  return_counts: (lkfs, int32 [3] = blocks,
+    blocks kept by the absolute gate, blocks kept by both).  Enqueue only: no host read."""
+    _need(wav, name="loudness.wav")
+    if wav.dim() != 1:
+        raise KnnSvcError(f"loudness: expected a mono waveform [L], got shape {tuple(wav.shape)}")
+    wav = wav.contiguous()
+    lib = _lib.load()
+    n = wav.numel()
+    nbytes = lib.knnsvc_loudness_workspace_bytes(n, int(sample_rate))
+    if nbytes == 0:
+        check(1, "loudness_workspace_bytes")
+    ws = torch.empty((nbytes + 7) // 8, device=wav.device, dtype=torch.float64)
+    lkfs = torch.empty((), device=wav.device, dtype=torch.float32)
+    counts = torch.empty(3, device=wav.device, dtype=torch.int32) if return_counts else None
+    check(lib.knnsvc_loudness(_p(wav), n, int(sample_rate), _p(lkfs), _p(counts), _p(ws), ws.numel() * 8, _stream()), "loudness")
+    return (lkfs, counts) if return_counts else lkfs
+
+
+def normalize_loudness(wav, target_db, sample_rate=16000, out=None):
+    """wav scaled to ``target_db`` LKFS: out = wav * 10^((target_db - loudness(wav)) / 20) -> (out, lkfs of wav as a 0-d device
+    tensor).  A signal without a measurable loudness (-inf: silence, or shorter than 400 ms) comes back unchanged.  ``out`` may
+    be ``wav`` itself (in place).  Enqueue only: no host read.  Nothing limits the result: a quiet, peaky signal can pass full
+    scale, and audio_io.save_audio then divides by the peak (the reference's rule), so the FILE is lower than asked."""
+    _need(wav, name="normalize_loudness.wav")
+    if not wav.is_contiguous():
+        raise KnnSvcError("normalize_loudness: expected a contiguous waveform")
+    lkfs = loudness(wav, sample_rate)
+    if out is None:
+        out = torch.empty_like(wav)
+    elif not (_need(out, name="normalize_loudness.out").is_contiguous() and out.shape == wav.shape):
+        raise KnnSvcError("normalize_loudness: out must be a contiguous fp32 tensor of wav's shape")
+    check(_lib.load().knnsvc_loudness_gain(_p(wav), wav.numel(), _p(lkfs), float(target_db), _p(out), _stream()), "loudness_gain")
+    return out, lkfs

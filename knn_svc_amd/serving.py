@@ -85,7 +85,8 @@ class TargetVoice:
 
 class BatchConverter:
     def __init__(self, vc, target: TargetVoice, ckpt_type: str = "mix", post_opt: str = "post_opt_0.2", lanes: int | None = None,
-                 max_encode_batch: int = 32, match: str | None = None, match_batch: int | None = None):
+                 max_encode_batch: int = 32, match: str | None = None, match_batch: int | None = None,
+                 loudness_db: float | None = None):
         if "wavlm_only_original" in ckpt_type:
             raise NotImplementedError("wavlm_only_original needs hifigan/models.py, absent upstream")
         self.vc, self.target, self.ckpt_type, self.post_opt = vc, target, ckpt_type, post_opt
@@ -97,6 +98,9 @@ class BatchConverter:
         # KNNSVC_MATCH / KNNSVC_MATCH_BATCH.
         self.match = M.match_mode(match)
         self.match_batch = M.match_batch_size(match_batch)
+        # integrated loudness every waveform is brought to (ops.normalize_loudness as part of the tail, on the tail's stream,
+        # enqueue-only); None: the generator's own level.  A RequestQueue in front of this converter inherits it.
+        self.loudness_db = None if loudness_db is None else float(loudness_db)
 
     def _load(self, src, check=False):
         """A request is a path, or (wav [L] float32 16 kHz mono as array / tensor, f0 [L // 320 + 1] or None).
@@ -157,7 +161,7 @@ class BatchConverter:
         qpool = dict(enumerate(feats))
         # the reference does not forward post_opt to the f0-only generators (ddsp_matcher.py:970, 1102-1110)
         post_opt = "no_post_opt" if self.f0only else self.post_opt
-        voc = (lambda c, f0, h: vc._vocode_async(c, f0)) if self.f0only else vc._vocode_async
+        voc = vc._tail(self.f0only, self.loudness_db)
 
         def run():
             flags = []
