@@ -92,6 +92,12 @@ __device__ __forceinline__ void resolve_scales(ConvArgs& a) {
 
 // |v| as ordered bits: NaN sorts above inf, so a NaN anywhere in the output reaches the slot (fmaxf would drop it)
 __device__ __forceinline__ unsigned abs_bits(float v) { return __float_as_uint(v) & 0x7FFFFFFFu; }
+// ... of an accumulator row that may lie past M: the epilogues that leave the row test of their stores to the buffer range check
+// still compute such rows (act(bias) of an all-zero A row, or the partial sums of the taps that reach back into the sequence), and
+// what is not stored must not enter the slot: the slot is max |out| of the stored block, whatever the tile height.  The row test
+// becomes the mask of the `and` that abs_bits has anyway.
+__device__ __forceinline__ unsigned row_keep(bool row_valid) { return row_valid ? 0x7FFFFFFFu : 0u; }
+__device__ __forceinline__ unsigned abs_bits(float v, unsigned keep) { return __float_as_uint(v) & keep; }
 // block-level fold: wave maxima meet in LDS, thread 0 sends the block's ONE atomic (zero is never sent: the slot starts there)
 __device__ __forceinline__ void publish_absmax(float* stripe, unsigned m) {
     __shared__ unsigned s_wave_max[16];
@@ -434,8 +440,8 @@ __device__ __forceinline__ void conv_epilogue_lin(const ConvArgs& a, typename G:
                 if (rz) v += rv[r];
                 if (a.accumulate) v += av[r];
                 if (a.div != 1.0f) v = v / a.div;
-                // (rows past M hold act(bias) of an all-zero A row: they are not stored, but may enter the bound — harmless)
-                if (a.out_absmax) { const unsigned ab = abs_bits(v); amax = ab > amax ? ab : amax; }
+                // (rows past M are computed but not stored: row_keep leaves them out of the slot)
+                if (a.out_absmax) { const unsigned ab = abs_bits(v, row_keep(row0 + (r & 3) + 8 * (r >> 2) < a.m)); amax = ab > amax ? ab : amax; }
                 __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), o_rsrc, off, 0, 0);
             }
         }
@@ -555,8 +561,9 @@ __device__ __forceinline__ void conv_epilogue_wide(const ConvArgs& a, typename G
             if (use_acc) v += av;
             if (a.div != 1.0f) v = v / a.div;
             if (a.out_absmax) {
+                const unsigned keep = row_keep(m < a.m);
 #pragma unroll
-                for (int e = 0; e < 4; ++e) { const unsigned ab = abs_bits(v[e]); amax = ab > amax ? ab : amax; }
+                for (int e = 0; e < 4; ++e) { const unsigned ab = abs_bits(v[e], keep); amax = ab > amax ? ab : amax; }
             }
             __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), o_rsrc, off, 0, 0);
         }
@@ -814,9 +821,10 @@ __device__ __forceinline__ void conv_epilogue_wide32(const ConvArgs& a, typename
                 ok = ok && m < a.m && o >= 0 && o < a.t_out;
                 off = (o * a.ldo + col) * 4;
             } else off = (m * a.ldo + n) * 4;
-            if (a.out_absmax && (!CONVT || ok)) {
+            if (a.out_absmax) {
+                const unsigned keep = row_keep(CONVT ? ok : m < a.m);
 #pragma unroll
-                for (int e = 0; e < 4; ++e) { const unsigned ab = abs_bits(v[e]); amax = ab > amax ? ab : amax; }
+                for (int e = 0; e < 4; ++e) { const unsigned ab = abs_bits(v[e], keep); amax = ab > amax ? ab : amax; }
             }
             __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), o_rsrc, ok ? off : OOB, 0, 0);
         }

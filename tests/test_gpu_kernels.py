@@ -1142,6 +1142,11 @@ def test_branches_in_one_grid_equal_one_launch_per_branch(C_, T):
     a, sa, na = run(False)
     b, sb, nb = run(True)
     print(f"C = {C_}, T = {T}: per-branch kernels {na}, merged grid {nb}")
+    # the tile-shape rules count the merged grid's workgroups: three branches together pass the deep-prefetch limit (256 tiles of
+    # 64 rows) where one alone does not; C = 32 / 64 take the fused pair and launch no convolution of their own
+    want = {(256, 3750): (["W128D"] * 3, ["W128Sx"]), (128, 15000): (["W128D"] * 3, ["W128Sx"]), (256, 1500): (["W128D"] * 3, ["W128Dx"]),
+            (64, 7000): ([], []), (32, 9001): ([], [])}[(C_, T)]
+    assert (na, nb) == want, (na, nb, want)
     for j in range(3):
         assert torch.equal(a[j], b[j]), (j, float((a[j] - b[j]).abs().max()))
         assert float(sa[j].max()) == float(sb[j].max()) == float(a[j].abs().max())
