@@ -31,7 +31,7 @@ extern "C" {
 #define KNNSVC_EHIP      3   /* a HIP runtime call failed                  */
 #define KNNSVC_ENAN      4   /* NaN distance (the reference sys.exit()s)   */
 
-#define KNNSVC_ABI_VERSION 19
+#define KNNSVC_ABI_VERSION 20
 
 int knnsvc_abi_version(void);
 const char* knnsvc_last_error(void);
@@ -499,8 +499,26 @@ int knnsvc_smooth_weights_seg(const int64_t* idx, const int64_t* host_seg, int32
                               int32_t dim, int32_t ld, float scale, const float* row_scale, int32_t max_iter, float* out_w,
                               int32_t* out_iters, void* workspace, size_t workspace_bytes, void* stream);
 
-/* out[i,:] = sum_k w[i,k] * pool[idx[i,k], :]   (ddsp_prematch_dataset.py:1358, 1444; w NULL = mean of 4
- * for harmonics :1446 / softmax(ones) :1361-1364) */
+/* The three segmented calls above that carry a [.., 4], for k neighbours per frame (topk), 1 <= k <= 8: idx_in / idx_out /
+ * idx / out_w / row_scale are [total, k].  The entry points above are the k = 4 call of the same launchers and keep their
+ * kernels; any other k runs the generic-K kernels (a four-wave walk over 2k candidates per frame in (4k + 2) * dim * 4
+ * bytes of LDS; a Gram of k(2k - 1) entries per frame pair and one Adam loop with its state in the workspace, exchanging
+ * weights and gradients through LDS while 2 * k * 4 * rows bytes fit 144 KB).  KNNSVC_MATCH_GENERIC_K=1 (read per call)
+ * sends k = 4 there too.  A one-row segment gets 1 / k and 0 iterations.  Refused before the first HIP call: k outside 1..8
+ * (KNNSVC_EINVAL; the workspace size is then 0), an LDS need above 150 KB, misaligned q / pool / out_w, a workspace below
+ * knnsvc_smooth_seg_workspace_bytes_k (KNNSVC_EWORKSPACE).  At k = 4 that size equals knnsvc_smooth_seg_workspace_bytes. */
+int knnsvc_concat_reselect_seg_k(const int64_t* idx_in, int32_t k, const float* q, const float* q_norm, const int64_t* host_seg,
+                                 int32_t n_seg, const float* pool, const float* p_norm, int64_t np, int32_t dim,
+                                 const float* shifted_f0, const float* pool_f0, int32_t use_f0, float concat_weight,
+                                 int64_t* idx_out, void* stream);
+size_t knnsvc_smooth_seg_workspace_bytes_k(const int64_t* host_seg, int32_t n_seg, int32_t k);
+int knnsvc_smooth_weights_seg_k(const int64_t* idx, int32_t k, const int64_t* host_seg, int32_t n_seg, const float* pool, int64_t np,
+                                int32_t dim, int32_t ld, float scale, const float* row_scale, int32_t max_iter, float* out_w,
+                                int32_t* out_iters, void* workspace, size_t workspace_bytes, void* stream);
+
+/* out[i,:] = sum_k w[i,k] * pool[idx[i,k], :]   (ddsp_prematch_dataset.py:1358, 1444).  w NULL = uniform weights:
+ * mean_mode 0 multiplies every row by 1.0f / k (softmax(ones), :1361-1364), mean_mode 1 sums in order and divides by k
+ * (torch.mean, harmonics :1446); any k >= 1, the two are bit-identical when k is a power of two. */
 int knnsvc_weighted_gather(const int64_t* idx, const float* w, int64_t nq, int32_t k, const float* pool,
                            int32_t dim, int32_t ld, int32_t mean_mode, float* out, void* stream);
 

@@ -11,7 +11,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("KNNSVC_LIB") or os.path.join(_HERE, "libknnsvc_hip.so")      # KNNSVC_LIB: an A/B build (csrc/Makefile)
-ABI_VERSION = 19
+ABI_VERSION = 20
 
 vp, i32, i64, f32, sz = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_size_t
 
@@ -158,6 +158,9 @@ SIGNATURES = {
     "knnsvc_concat_reselect_seg": (i32, [vp, vp, vp, vp, i32, vp, vp, i64, i32, vp, vp, i32, f32, vp, vp]),
     "knnsvc_smooth_seg_workspace_bytes": (sz, [vp, i32]),
     "knnsvc_smooth_weights_seg": (i32, [vp, vp, i32, vp, i64, i32, i32, f32, vp, i32, vp, vp, vp, sz, vp]),
+    "knnsvc_concat_reselect_seg_k": (i32, [vp, i32, vp, vp, vp, i32, vp, vp, i64, i32, vp, vp, i32, f32, vp, vp]),
+    "knnsvc_smooth_seg_workspace_bytes_k": (sz, [vp, i32, i32]),
+    "knnsvc_smooth_weights_seg_k": (i32, [vp, i32, vp, i32, vp, i64, i32, i32, f32, vp, i32, vp, vp, vp, sz, vp]),
     "knnsvc_weighted_gather": (i32, [vp, vp, i64, i32, vp, i32, i32, i32, vp, vp]),
     "knnsvc_round_f16": (i32, [vp, i64, vp, vp]),
     "knnsvc_amp_ratio": (i32, [vp, i32, vp, i32, i64, vp, i64, i32, i32, vp, vp]),

@@ -222,17 +222,19 @@ __global__ __launch_bounds__(256) void gate_kernel(const float* __restrict__ xn,
 
 __global__ __launch_bounds__(256) void weighted_gather_kernel(const long* __restrict__ idx, const float* __restrict__ w,
                                                              long nq, int k, const float* __restrict__ pool, int dim,
-                                                             int ld, float* __restrict__ out) {
+                                                             int ld, int mean_mode, float* __restrict__ out) {
 #pragma clang fp contract(off)
     const long row = blockIdx.x;
+    const bool mean = !w && mean_mode == 1;        // torch.mean: the sum in order, divided by k
     for (int c = threadIdx.x; c < dim; c += 256) {
         float acc = 0.f;
         for (int j = 0; j < k; ++j) {
             const float wj = w ? w[row * k + j] : 1.0f / (float)k;
-            const float t = pool[idx[row * k + j] * (long)ld + c] * wj;
+            const float x = pool[idx[row * k + j] * (long)ld + c];
+            const float t = mean ? x : x * wj;
             acc = j == 0 ? t : acc + t;
         }
-        out[row * (long)dim + c] = acc;
+        out[row * (long)dim + c] = mean ? acc / (float)k : acc;
     }
 }
 
@@ -406,12 +408,13 @@ extern "C" int knnsvc_wavlm_gate(const float* xn, int64_t rows, int32_t heads, i
 
 extern "C" int knnsvc_weighted_gather(const int64_t* idx, const float* w, int64_t nq, int32_t k, const float* pool,
                                       int32_t dim, int32_t ld, int32_t mean_mode, float* out, void* stream) {
-    (void)mean_mode;   // mean of k == sum of x * (1/k) bit for bit when k is a power of two (k = 4 on the path)
+    // uniform weights (w NULL): mean_mode 0 = sum of x * (1.0f / k), the softmax(ones) form; 1 = (sum of x) / k, torch.mean.  The two
+    // agree bit for bit when k is a power of two (k = 4, the default path).
     KN_REQUIRE(idx && pool && out && k > 0 && dim > 0 && ld >= dim, "weighted_gather: bad arguments");
-    KN_REQUIRE(w || (k & (k - 1)) == 0, "weighted_gather: uniform weights need a power-of-two k");
+    KN_REQUIRE(mean_mode == 0 || mean_mode == 1, "weighted_gather: mean_mode %d is neither 0 nor 1", (int)mean_mode);
     if (nq <= 0) return KNNSVC_OK;
     hipLaunchKernelGGL(weighted_gather_kernel, dim3((unsigned)nq), dim3(256), 0, (hipStream_t)stream,
-                       (const long*)idx, w, (long)nq, k, pool, dim, ld, out);
+                       (const long*)idx, w, (long)nq, k, pool, dim, ld, mean_mode, out);
     return knnsvc_check_launch("weighted_gather");
 }
 

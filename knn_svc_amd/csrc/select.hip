@@ -248,6 +248,132 @@ __global__ __launch_bounds__(256) void concat_reselect_kernel(
                          sf0 ? sf0 + o : sf0, pf0, use_f0, concat_weight, idx_out + o * KC);
 }
 
+// ---------------------------------------------------------------------------------------------
+// The same walk for K neighbours per frame, 1 <= K <= 8 (topk): concat_reselect_body with KC -> K.  Candidates per frame: the
+// frame's K neighbours, then previous selection + 1 (clamped at the pool's end) — 2K rows per ring slot, (4K + 2) * dim floats of
+// LDS.  Distance formula, thresholding, sticky weight, NaN rule and tie rule are the ones above; the median over the previous
+// selection is torch's lower median, the element of rank (K - 1) / 2 (for K = 4 the second smallest, as above).
+// ---------------------------------------------------------------------------------------------
+template <int K>
+__device__ __forceinline__ void concat_reselect_k_body(
+    const long* __restrict__ idx_in, const float* __restrict__ q, const float* __restrict__ qn, long nq,
+    const float* __restrict__ pool, const float* __restrict__ pn, long np, int dim,
+    const float* __restrict__ sf0, const float* __restrict__ pf0, int use_f0, float concat_weight,
+    long* __restrict__ idx_out) {
+#pragma clang fp contract(off)
+    constexpr int N2 = 2 * K;                       // candidates per frame
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    float* ring = sm;                               // [2][N2][dim]
+    float* qrow = ring + 2 * N2 * dim;              // [2][dim]
+    __shared__ float s_match[N2], s_cc[K][N2], s_base;
+    __shared__ long s_cand[2][N2];
+    __shared__ int s_prev_slot[K];                  // slots (in the previous ring half) of the kept rows
+    __shared__ long s_prev_idx[K];
+    __shared__ float s_w;
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    // frame 0 keeps its neighbours
+    if (tid < K) {
+        const long id = idx_in[tid];
+        idx_out[tid] = id;
+        s_prev_idx[tid] = id; s_prev_slot[tid] = tid; s_cand[0][tid] = id;
+    }
+    if (tid == 0) s_w = concat_weight;
+    __syncthreads();
+    for (int r = 0; r < K; ++r)
+        for (int c = tid * 4; c < dim; c += 1024) *(f32x4*)&ring[(0 * N2 + r) * dim + c] = *(const f32x4*)(pool + s_cand[0][r] * (long)dim + c);
+    for (int c = tid * 4; c < dim; c += 1024) *(f32x4*)&qrow[c] = *(const f32x4*)(q + c);
+    __syncthreads();
+
+    for (long i = 1; i < nq; ++i) {
+        const int cur = (int)(i & 1), prv = cur ^ 1;
+        if (tid < N2) {
+            long id;
+            if (tid < K) id = idx_in[i * K + tid];
+            else { id = s_prev_idx[tid - K] + 1; if (id >= np) id = np - 1; }
+            s_cand[cur][tid] = id;
+        }
+        __syncthreads();
+        // stage the 2K candidate rows and q[i]
+        for (int r = 0; r < N2; ++r) {
+            const float* src = pool + s_cand[cur][r] * (long)dim;
+            for (int c = tid * 4; c < dim; c += 1024) *(f32x4*)&ring[(cur * N2 + r) * dim + c] = *(const f32x4*)(src + c);
+        }
+        for (int c = tid * 4; c < dim; c += 1024) *(f32x4*)&qrow[cur * dim + c] = *(const f32x4*)(q + i * (long)dim + c);
+        __syncthreads();
+        // 2K match + 2K * K concat + 1 baseline squared distances, spread over the 4 waves
+        for (int job = wave; job < N2 + K * N2 + 1; job += 4) {
+            if (job < N2) {
+                const float ss = sqdiff(&qrow[cur * dim], &ring[(cur * N2 + job) * dim], dim, lane);
+                if (lane == 0) s_match[job] = cos_from_cd(ss, qn[i], pn[s_cand[cur][job]]);
+            } else if (job < N2 + K * N2) {
+                const int a = (job - N2) / N2, b = (job - N2) % N2;
+                const float ss = sqdiff(&ring[(prv * N2 + s_prev_slot[a]) * dim], &ring[(cur * N2 + b) * dim], dim, lane);
+                if (lane == 0) s_cc[a][b] = cos_from_cd(ss, pn[s_prev_idx[a]], pn[s_cand[cur][b]]);
+            } else {
+                const float ss = sqdiff(&qrow[prv * dim], &qrow[cur * dim], dim, lane);
+                if (lane == 0) s_base = cos_from_cd(ss, qn[i - 1], qn[i]) * 2.0f;
+            }
+        }
+        __syncthreads();
+        if (wave == 0) {
+            float total = __builtin_inff();
+            const float base = s_base;
+            float w = s_w;
+            if (use_f0 && !(base < 0.08f)) w = 0.f;            // sticky: stays 0 for every later frame
+            if (lane < N2) {
+                float ck[K];
+#pragma unroll
+                for (int a = 0; a < K; ++a) {
+                    float c = s_cc[a][lane];
+                    if (use_f0) { if (base < 0.08f && c < 5.0f * base) c = 0.f; }
+                    else if (c > base) c = 1.5f * c - base;
+                    ck[a] = c;
+                }
+                // lower median of K: the element of rank (K - 1) / 2 (a NaN among them leaves NaN, which ranks as +inf below)
+                float med = __builtin_nanf("");
+#pragma unroll
+                for (int a = 0; a < K; ++a) {
+                    int r = 0;
+#pragma unroll
+                    for (int b = 0; b < K; ++b) r += (ck[b] < ck[a] || (ck[b] == ck[a] && b < a)) ? 1 : 0;
+                    if (r == (K - 1) / 2) med = ck[a];
+                }
+                total = w * med + s_match[lane];
+                if (use_f0) {
+                    const float lp = log2_rn(pf0[s_cand[cur][lane]] + 1e-5f), lq = log2_rn(sf0[i] + 1e-5f);
+                    total = total + fabsf(lp - lq);
+                }
+            }
+            if (!(total == total)) total = __builtin_inff();   // a NaN cost ranks as +inf, ties by candidate number (see above)
+            int rank = 0;
+#pragma unroll
+            for (int j = 0; j < N2; ++j) {
+                const float tj = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, total), j));
+                rank += (tj < total || (tj == total && j < lane)) ? 1 : 0;
+            }
+            if (lane < N2 && rank < K) {
+                const long id = s_cand[cur][lane];
+                s_prev_idx[rank] = id; s_prev_slot[rank] = lane;
+                idx_out[i * K + rank] = id;
+            }
+            if (lane == 0) s_w = w;
+        }
+        __syncthreads();
+    }
+}
+
+template <int K>
+__global__ __launch_bounds__(256) void concat_reselect_k_kernel(
+    const long* __restrict__ idx_in, const float* __restrict__ q, const float* __restrict__ qn, const KnSegTable seg,
+    const float* __restrict__ pool, const float* __restrict__ pn, long np, int dim,
+    const float* __restrict__ sf0, const float* __restrict__ pf0, int use_f0, float concat_weight,
+    long* __restrict__ idx_out) {
+    const long o = seg.off[blockIdx.x];
+    concat_reselect_k_body<K>(idx_in + o * K, q + o * dim, qn + o, seg.off[blockIdx.x + 1] - o, pool, pn, np, dim,
+                              sf0 ? sf0 + o : sf0, pf0, use_f0, concat_weight, idx_out + o * K);
+}
+
 // buffer resource over a whole array (< 4 GiB: the dispatcher sends larger pools to the generic kernel)
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t sel_rsrc(const void* p, unsigned long long bytes) {
     const unsigned long long u = (unsigned long long)p;
@@ -629,12 +755,40 @@ static int shift_f0_launch(const KnSegTable& seg, const char* entry, const float
     return knnsvc_check_launch(entry);
 }
 
-static int concat_reselect_launch(const KnSegTable& seg, const char* entry, const int64_t* idx_in, const float* q, const float* q_norm,
+// KNNSVC_MATCH_GENERIC_K=1 (read per call): k = 4 takes the generic-K kernels too (concat_reselect_k_kernel, smooth.hip's gram_k /
+// adam_k kernels) — holds them against the reference's own k = 4 fixtures, and an A/B aid.
+bool knnsvc_match_generic_k() { const char* e = getenv("KNNSVC_MATCH_GENERIC_K"); return e && e[0] == '1'; }
+
+// the generic-K walk: every check before the first HIP call
+static int concat_reselect_k_launch(const KnSegTable& seg, const char* entry, int k, const int64_t* idx_in, const float* q,
+                                    const float* q_norm, const float* pool, const float* p_norm, int64_t np, int32_t dim,
+                                    const float* shifted_f0, const float* pool_f0, int32_t use_f0, float concat_weight,
+                                    int64_t* idx_out, void* stream) {
+    const size_t lds = (size_t)(4 * k + 2) * dim * 4;
+    KN_REQUIRE(lds <= 150 * 1024, "%s: feature dim %d too large for LDS at k = %d (%zu bytes)", entry, (int)dim, k, lds);
+    KN_REQUIRE(((uintptr_t)q & 15) == 0 && ((uintptr_t)pool & 15) == 0, "%s: 16-byte alignment", entry);
+    int rc = KNNSVC_EINVAL;
+#define KN_WALK_K(KK)                                                                                                                \
+    case KK:                                                                                                                         \
+        if ((rc = kn_lds_optin<concat_reselect_k_kernel<KK>>((int)lds, entry))) return rc;                                           \
+        hipLaunchKernelGGL(concat_reselect_k_kernel<KK>, dim3((unsigned)seg.n), dim3(256), lds, (hipStream_t)stream, (const long*)idx_in, q, \
+                           q_norm, seg, pool, p_norm, (long)np, dim, shifted_f0, pool_f0, use_f0, concat_weight, (long*)idx_out);   \
+        break;
+    switch (k) { KN_WALK_K(1) KN_WALK_K(2) KN_WALK_K(3) KN_WALK_K(4) KN_WALK_K(5) KN_WALK_K(6) KN_WALK_K(7) KN_WALK_K(8) default: return rc; }
+#undef KN_WALK_K
+    return knnsvc_check_launch(entry);
+}
+
+static int concat_reselect_launch(const KnSegTable& seg, const char* entry, int k, const int64_t* idx_in, const float* q, const float* q_norm,
                                   const float* pool, const float* p_norm, int64_t np, int32_t dim, const float* shifted_f0,
                                   const float* pool_f0, int32_t use_f0, float concat_weight, int64_t* idx_out, void* stream) {
+    KN_REQUIRE(k >= 1 && k <= 8, "%s: k = %d outside 1..8", entry, k);
     KN_REQUIRE(idx_in && q && q_norm && pool && p_norm && idx_out, "%s: null pointer", entry);
     KN_REQUIRE(np > 0 && dim > 0 && dim % 4 == 0, "%s: bad sizes", entry);
     KN_REQUIRE(!use_f0 || (shifted_f0 && pool_f0), "%s: f0 variant needs both f0 arrays", entry);
+    if (k != KC || knnsvc_match_generic_k())
+        return concat_reselect_k_launch(seg, entry, k, idx_in, q, q_norm, pool, p_norm, np, dim, shifted_f0, pool_f0, use_f0,
+                                        concat_weight, idx_out, stream);
     KN_REQUIRE(((uintptr_t)q & 15) == 0 && ((uintptr_t)pool & 15) == 0, "%s: 16-byte alignment", entry);
     const size_t lds = (size_t)(2 * NC + 2) * dim * 4;
     KN_REQUIRE(dim <= 1024 || lds <= 150 * 1024, "%s: feature dim too large for LDS", entry);
@@ -692,7 +846,7 @@ extern "C" int knnsvc_concat_reselect(const int64_t* idx_in, const float* q, con
                                       float concat_weight, int64_t* idx_out, void* stream) {
     KnSegTable seg;
     if (const int rc = kn_seg_one(nq, "concat_reselect", &seg)) return rc;
-    return concat_reselect_launch(seg, "concat_reselect", idx_in, q, q_norm, pool, p_norm, np, dim, shifted_f0, pool_f0, use_f0,
+    return concat_reselect_launch(seg, "concat_reselect", KC, idx_in, q, q_norm, pool, p_norm, np, dim, shifted_f0, pool_f0, use_f0,
                                   concat_weight, idx_out, stream);
 }
 
@@ -718,6 +872,17 @@ extern "C" int knnsvc_concat_reselect_seg(const int64_t* idx_in, const float* q,
                                           int64_t* idx_out, void* stream) {
     KnSegTable seg;
     if (const int rc = kn_seg_table(host_seg, n_seg, "concat_reselect_seg", &seg)) return rc;
-    return concat_reselect_launch(seg, "concat_reselect_seg", idx_in, q, q_norm, pool, p_norm, np, dim, shifted_f0, pool_f0, use_f0,
+    return concat_reselect_launch(seg, "concat_reselect_seg", KC, idx_in, q, q_norm, pool, p_norm, np, dim, shifted_f0, pool_f0, use_f0,
+                                  concat_weight, idx_out, stream);
+}
+
+// idx_in / idx_out [total, k], 1 <= k <= 8
+extern "C" int knnsvc_concat_reselect_seg_k(const int64_t* idx_in, int32_t k, const float* q, const float* q_norm, const int64_t* host_seg,
+                                            int32_t n_seg, const float* pool, const float* p_norm, int64_t np, int32_t dim,
+                                            const float* shifted_f0, const float* pool_f0, int32_t use_f0, float concat_weight,
+                                            int64_t* idx_out, void* stream) {
+    KnSegTable seg;
+    if (const int rc = kn_seg_table(host_seg, n_seg, "concat_reselect_seg_k", &seg)) return rc;
+    return concat_reselect_launch(seg, "concat_reselect_seg_k", k, idx_in, q, q_norm, pool, p_norm, np, dim, shifted_f0, pool_f0, use_f0,
                                   concat_weight, idx_out, stream);
 }

@@ -391,21 +391,248 @@ __global__ void fill_quarter_kernel(const SmoothSegs sg, const SegList list, flo
     if (threadIdx.x == 0 && out_iters) out_iters[s] = 0;
 }
 
+
+// ---------------------------------------------------------------------------------------------
+// The same optimisation for K neighbours per frame, 1 <= K <= 8 (topk).  gram_k_body is gram_body with 2K vectors per pair (mean
+// over 2K, the K(2K - 1) strict-upper-triangle entries of the centred 2K x 2K Gram); adam_k_body is adam_body with its state in
+// the workspace as [K][rows] planes (thread t touches element t of each plane: coalesced, and conflict-free where the exchange
+// planes sit in LDS).  Sums over a row's K values are pairwise trees, which at K = 4 is the (a + b) + (c + d) of the code above.
+// Workspace per segment: Gram [K(2K-1)][nq] | theta, m, v, vmax, best, scratch: 6 x [K][nq] | exchange [2][K][nq].
+// ---------------------------------------------------------------------------------------------
+template <int N>
+__device__ __forceinline__ float tree_sum(const float* p) {
+    if constexpr (N == 1) return p[0];
+    else return tree_sum<N / 2>(p) + tree_sum<N - N / 2>(p + N / 2);
+}
+template <int R>
+__device__ __forceinline__ constexpr int tri_r(int i, int j) {      // i != j, R x R
+    return i < j ? i * (R - 1) - i * (i - 1) / 2 + (j - i - 1) : j * (R - 1) - j * (j - 1) / 2 + (i - j - 1);
+}
+
+template <int K>
+__device__ __forceinline__ void gram_k_body(const long* __restrict__ idx, long nq, const float* __restrict__ pool,
+                                            long np, int dim, int ld, const float* __restrict__ row_scale,
+                                            float* __restrict__ gram, const long t) {
+    constexpr int R = 2 * K, GEK = K * (2 * K - 1), NQ = (GEK + 3) / 4;
+    extern __shared__ float sm[];           // [R][dim] centred vectors of the current term
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    double acc[NQ];
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) acc[q] = 0.0;
+    float rs[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) rs[r] = row_scale ? (r < K ? row_scale[(t + 1) * K + r] : row_scale[t * K + (r - K)]) : 1.f;
+    for (int term = 0; term < 2; ++term) {
+        __syncthreads();
+        for (int c = tid; c < dim; c += 256) {
+            float v[R], mean = 0.f;
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                long id;
+                if (r < K) id = idx[(t + 1) * K + r] + (term == 0 ? -1 : 0);
+                else id = idx[t * K + (r - K)] + (term == 0 ? 0 : 1);
+                id = id < 0 ? 0 : (id > np - 1 ? np - 1 : id);
+                v[r] = pool[id * (long)ld + c];
+                if (row_scale) v[r] *= rs[r];
+                mean += v[r];
+            }
+            mean = mean / (float)R;
+#pragma unroll
+            for (int r = 0; r < R; ++r) sm[r * dim + c] = v[r] - mean;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) {
+            const int e = wave + 4 * q;                 // wave-uniform
+            if (e < GEK) {
+                int i = 0, rem = e;                       // unpack e -> (i < j)
+                while (rem >= R - 1 - i) { rem -= R - 1 - i; ++i; }
+                const int j = i + 1 + rem;
+                double s = 0.0;
+                for (int c = lane; c < dim; c += 64) s += (double)sm[i * dim + c] * (double)sm[j * dim + c];
+                acc[q] += wave_sum_d(s);
+            }
+        }
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int q = 0; q < NQ; ++q)
+            if (wave + 4 * q < GEK) gram[((long)(wave + 4 * q)) * nq + t] = (float)acc[q];
+    }
+}
+
+template <int K>
+__global__ __launch_bounds__(256) void gram_k_kernel(const long* __restrict__ idx, const SmoothSegs sg, const float* __restrict__ pool,
+                                                        long np, int dim, int ld, const float* __restrict__ row_scale,
+                                                        float* __restrict__ ws) {
+    const long b = blockIdx.x;
+    int s = 0;
+    for (int j = 1; j < sg.n; ++j) if (sg.off[j] - j <= b) s = j;       // the last segment whose first pair is <= b (uniform)
+    const long o = sg.off[s];
+    gram_k_body<K>(idx + o * K, sg.off[s + 1] - o, pool, np, dim, ld, row_scale ? row_scale + o * K : row_scale, seg_ws(ws, sg, s),
+                   b - (o - s));
+}
+
+template <int K>
+__device__ __forceinline__ void adam_k_body(long nq, int dim, float scale, int max_iter,
+                                            const float* __restrict__ gram, float* __restrict__ state,
+                                            float* __restrict__ xch_global, int use_lds,
+                                            float* __restrict__ out_w, int* __restrict__ out_iters) {
+    constexpr int R = 2 * K;
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    __shared__ double red[2][16];
+    float* xw = use_lds ? sm : xch_global;                 // [K][nq] softmax weights
+    float* xg = xw + nq * K;                               // [K][nq] gradient w.r.t. w from the pair (t-1, t)
+    float* theta = state;                                  // [K][nq] each
+    float* m1 = theta + nq * K; float* v2 = m1 + nq * K; float* vmax = v2 + nq * K; float* best = vmax + nq * K;
+    float* gs = best + nq * K;                             // gradient w.r.t. w[t,:] from the pair (t, t+1)
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const double S = (double)scale / ((double)dim * (double)(nq - 1));
+    const float twoS = (float)(2.0 * S);
+    for (long t = tid; t < nq; t += 1024) {
+#pragma unroll
+        for (int k = 0; k < K; ++k) { const long a = k * nq + t; theta[a] = 0.f; m1[a] = 0.f; v2[a] = 0.f; vmax[a] = 0.f; best[a] = 0.f; }
+    }
+    __syncthreads();
+
+    double min_loss = 20000.0, conv_min = 20000.0;
+    int since = 0, it = 0;
+    const float b2 = 0.999f, omb1 = (float)(1.0 - 0.9), omb2 = (float)(1.0 - 0.999), eps = 1e-8f;
+    double pb1 = 1.0, pb2 = 1.0;
+    const bool forced = max_iter < 0;            // measurement mode: exactly |max_iter| iterations, stopping rules off
+    const int cap = forced ? -max_iter : max_iter;
+    for (it = 0; it < cap; ++it) {
+        // ---- phase 1: softmax weights ---------------------------------------------------------
+        for (long t = tid; t < nq; t += 1024) {
+#pragma clang fp contract(off)
+            float e[K], mx = theta[t];
+#pragma unroll
+            for (int k = 1; k < K; ++k) mx = fmaxf(mx, theta[k * nq + t]);
+#pragma unroll
+            for (int k = 0; k < K; ++k) e[k] = __builtin_amdgcn_exp2f((theta[k * nq + t] - mx) * 1.44269504088896341f);
+            const float rden = __builtin_amdgcn_rcpf(tree_sum<K>(e));      // den >= 1: the maximum contributes exp2(0)
+#pragma unroll
+            for (int k = 0; k < K; ++k) xw[k * nq + t] = e[k] * rden;
+        }
+        __syncthreads();
+        // ---- phase 2: per pair quadratic forms, gradient w.r.t. the weights ---------------------
+        double lsum = 0.0;
+        for (long t = tid; t < nq - 1; t += 1024) {
+            float c[R], y[R];
+#pragma unroll
+            for (int k = 0; k < K; ++k) { c[k] = xw[k * nq + t + 1]; c[K + k] = -xw[k * nq + t]; }
+#pragma unroll
+            for (int i = 0; i < R; ++i) {
+                float s = 0.f;
+#pragma unroll
+                for (int j = 0; j < R; ++j) if (j != i) s += gram[(long)tri_r<R>(i, j) * nq + t] * (c[j] - c[i]);
+                y[i] = s;
+            }
+            float qf = 0.f;
+#pragma unroll
+            for (int i = 0; i < R; ++i) qf += c[i] * y[i];
+            lsum += (double)qf;
+#pragma unroll
+            for (int k = 0; k < K; ++k) { xg[k * nq + t + 1] = twoS * y[k]; gs[k * nq + t] = -twoS * y[K + k]; }
+        }
+        lsum = wave_sum_d_dpp(lsum);
+        if (lane == 0) red[it & 1][wave] = lsum;
+        __syncthreads();
+        double tot = 0.0;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) tot += red[it & 1][i];
+        const float loss = (float)(S * tot);
+        // ---- phase 3: the reference's loop control (uniform across the block) -------------------
+        if (it % 100 == 1) {
+            if (!forced && fabs(min_loss - conv_min) < 1e-5) break;
+            conv_min = min_loss;
+        }
+        const bool improved = loss < (float)min_loss;
+        if (improved) { min_loss = (double)loss; since = 0; } else ++since;
+        if (!forced && since >= 1000) break;
+        // ---- phase 4: gradient through softmax + Adam(amsgrad) ----------------------------------
+        pb1 *= 0.9; pb2 *= 0.999;
+        const float step_size = (float)(-(0.1 / (1.0 - pb1)));
+        const float bc2_sqrt = (float)sqrt(1.0 - pb2);
+        const float rbc2 = 1.0f / bc2_sqrt;
+        for (long t = tid; t < nq; t += 1024) {
+            float w[K], g[K], wg[K];
+#pragma unroll
+            for (int k = 0; k < K; ++k) {
+                w[k] = xw[k * nq + t];
+                float gk = 0.f;
+                if (t >= 1) gk = xg[k * nq + t];
+                if (t < nq - 1) gk += gs[k * nq + t];
+                g[k] = gk; wg[k] = w[k] * gk;
+            }
+            const float dotwg = tree_sum<K>(wg);
+#pragma unroll
+            for (int k = 0; k < K; ++k) {
+                const long a = k * nq + t;
+                const float gt = w[k] * (g[k] - dotwg);
+                float th = theta[a];
+                if (improved) best[a] = th;
+                float mm = m1[a], vv = v2[a], vm = vmax[a];
+                mm = mm + (gt - mm) * omb1;
+                vv = vv * b2 + (omb2 * gt) * gt;
+                vm = fmaxf(vm, vv);
+                th = loop_step(th, mm, vm, rbc2, eps, step_size);
+                theta[a] = th; m1[a] = mm; v2[a] = vv; vmax[a] = vm;
+            }
+        }
+    }
+    // softmax(best): expf and the IEEE divide
+    __syncthreads();
+    for (long t = tid; t < nq; t += 1024) {
+        float e[K], mx = best[t];
+#pragma unroll
+        for (int k = 1; k < K; ++k) mx = fmaxf(mx, best[k * nq + t]);
+#pragma unroll
+        for (int k = 0; k < K; ++k) e[k] = expf(best[k * nq + t] - mx);
+        const float den = tree_sum<K>(e);
+#pragma unroll
+        for (int k = 0; k < K; ++k) out_w[t * K + k] = e[k] / den;
+    }
+    if (tid == 0 && out_iters) out_iters[0] = it;
+}
+
+inline size_t ws_floats_k(long nq, int k) { return (size_t)(k * (2 * k - 1)) * nq + (size_t)6 * k * nq + (size_t)2 * k * nq; }
+// longest sequence whose two exchange planes fit 144 KB of LDS (adam_k_kernel; 2304 rows at K = 8)
+__host__ __device__ constexpr long adam_k_lds_rows(int k) { return 144 * 1024 / (2 * k * 4); }
+
+template <int K>
+__global__ __launch_bounds__(1024) void adam_k_kernel(const SmoothSegs sg, const SegList list, int dim, float scale, int max_iter,
+                                                         float* __restrict__ ws, float* __restrict__ out_w, int* __restrict__ out_iters) {
+    const int s = list.id[blockIdx.x];
+    const long o = sg.off[s], nq = sg.off[s + 1] - o;
+    float* gram = seg_ws(ws, sg, s);
+    float* state = gram + (size_t)(K * (2 * K - 1)) * nq;
+    adam_k_body<K>(nq, dim, scale, max_iter, gram, state, state + (size_t)6 * K * nq, nq <= adam_k_lds_rows(K), out_w + o * K,
+                   out_iters ? out_iters + s : out_iters);
+}
+
+// segments of one row (no adjacent pair): softmax(0) = 1 / k and zero iterations
+__global__ void fill_uniform_kernel(const SmoothSegs sg, const SegList list, int k, float* __restrict__ out_w, int* __restrict__ out_iters) {
+    const int s = list.id[blockIdx.x];
+    if ((int)threadIdx.x < k) out_w[sg.off[s] * k + threadIdx.x] = 1.0f / (float)k;
+    if (threadIdx.x == 0 && out_iters) out_iters[s] = 0;
+}
+
 // bytes of segment workspace: what the segment needs alone, rounded up to 64
-inline size_t seg_ws_bytes(long nq) { return (ws_floats(nq) * 4 + 64 + 63) & ~(size_t)63; }
+inline size_t seg_ws_bytes(long nq, int k = KW) { return (ws_floats_k(nq, k) * 4 + 64 + 63) & ~(size_t)63; }
 
 }  // namespace
 
 extern "C" size_t knnsvc_smooth_workspace_bytes(int64_t nq) { return nq > 0 ? ws_floats(nq) * 4 + 64 : 0; }
 
 // row offsets and workspace placement of a validated table; *bytes: the workspace of the segmented call
-static int smooth_segs(const KnSegTable& t, const char* entry, SmoothSegs* sg, size_t* bytes) {
+static int smooth_segs(const KnSegTable& t, const char* entry, SmoothSegs* sg, size_t* bytes, int k = KW) {
     sg->n = t.n;
     size_t at = 0;
     for (int s = 0; s <= KNNSVC_MAX_SEGMENTS; ++s) {
         sg->off[s] = t.off[s];
         if (s < KNNSVC_MAX_SEGMENTS) sg->ws64[s] = (unsigned)(at / 64);
-        if (s < t.n) at += seg_ws_bytes(t.off[s + 1] - t.off[s]);
+        if (s < t.n) at += seg_ws_bytes(t.off[s + 1] - t.off[s], k);
     }
     if (at / 64 > 0xFFFFFFFFull) return knnsvc_fail(KNNSVC_EINVAL, "%s: segments too long", entry);
     *bytes = at;
@@ -415,9 +642,60 @@ static int smooth_segs(const KnSegTable& t, const char* entry, SmoothSegs* sg, s
 // The argument checks, the class-by-length choice and the launches, once.  `need`: the workspace size the entry point documents
 // (knnsvc_smooth_workspace_bytes for the single call, knnsvc_smooth_seg_workspace_bytes for the segmented one); `entry`: its name,
 // for the messages.
-static int smooth_weights_launch(const SmoothSegs& sg, size_t need, const char* entry, const int64_t* idx, const float* pool,
+// The generic-K route (k != 4, or KNNSVC_MATCH_GENERIC_K=1): one-row segments filled with 1 / k, one Gram launch, one loop launch.
+// Every check runs before the first HIP call.
+static int smooth_weights_k_launch(const SmoothSegs& sg, size_t need, const char* entry, int k, const int64_t* idx, const float* pool,
+                                   int64_t np, int32_t dim, int32_t ld, float scale, const float* row_scale, int32_t max_iter,
+                                   float* out_w, int32_t* out_iters, void* workspace, size_t workspace_bytes, void* stream) {
+    KN_REQUIRE(idx && pool && out_w && workspace, "%s: null pointer", entry);
+    KN_REQUIRE(np > 0 && dim > 0 && ld >= dim && max_iter != 0, "%s: bad sizes", entry);
+    KN_REQUIRE(((uintptr_t)out_w & 3) == 0, "%s: out_w must be 4-byte aligned", entry);      // written float by float
+    const size_t gl = (size_t)2 * k * dim * 4;
+    KN_REQUIRE(gl <= 150 * 1024, "%s: feature dim %d too large for LDS at k = %d", entry, (int)dim, k);
+    if (workspace_bytes < need) return knnsvc_fail(KNNSVC_EWORKSPACE, "%s: workspace %zu < %zu bytes", entry, workspace_bytes, need);
+    hipStream_t st = (hipStream_t)stream;
+    float* base = (float*)(((uintptr_t)workspace + 63) & ~(uintptr_t)63);
+    SegList one, loop;
+    one.n = loop.n = 0;
+    long lds_rows = 0;
+    for (int s = 0; s < sg.n; ++s) {
+        const long nq = sg.off[s + 1] - sg.off[s];
+        if (nq < 2) { one.id[one.n++] = (unsigned char)s; continue; }
+        loop.id[loop.n++] = (unsigned char)s;
+        if (nq <= adam_k_lds_rows(k) && nq > lds_rows) lds_rows = nq;
+    }
+    int rc;
+    if (one.n) {
+        hipLaunchKernelGGL(fill_uniform_kernel, dim3((unsigned)one.n), dim3(64), 0, st, sg, one, k, out_w, out_iters);
+        if ((rc = knnsvc_check_launch(entry))) return rc;
+    }
+    const long pairs = sg.off[sg.n] - sg.n;
+    if (pairs == 0) return KNNSVC_OK;
+    const size_t al = (size_t)lds_rows * 2 * k * 4;              // of the segments that exchange through LDS; the others take none
+#define KN_SMOOTH_K(KK)                                                                                                              \
+    case KK:                                                                                                                         \
+        if ((rc = kn_lds_optin<gram_k_kernel<KK>>((int)gl, entry))) return rc;                                                       \
+        hipLaunchKernelGGL(gram_k_kernel<KK>, dim3((unsigned)pairs), dim3(256), gl, st, (const long*)idx, sg, pool, (long)np, dim, ld, \
+                           row_scale, base);                                                                                         \
+        if ((rc = knnsvc_check_launch(entry))) return rc;                                                                            \
+        if ((rc = kn_lds_optin<adam_k_kernel<KK>>((int)al, entry))) return rc;                                                       \
+        hipLaunchKernelGGL(adam_k_kernel<KK>, dim3((unsigned)loop.n), dim3(1024), al, st, sg, loop, dim, scale, max_iter, base, out_w, \
+                           out_iters);                                                                                               \
+        break;
+    switch (k) {
+        KN_SMOOTH_K(1) KN_SMOOTH_K(2) KN_SMOOTH_K(3) KN_SMOOTH_K(4) KN_SMOOTH_K(5) KN_SMOOTH_K(6) KN_SMOOTH_K(7) KN_SMOOTH_K(8)
+        default: return knnsvc_fail(KNNSVC_EINVAL, "%s: k = %d outside 1..8", entry, k);
+    }
+#undef KN_SMOOTH_K
+    return knnsvc_check_launch(entry);
+}
+
+static int smooth_weights_launch(const SmoothSegs& sg, size_t need, const char* entry, int k, const int64_t* idx, const float* pool,
                                  int64_t np, int32_t dim, int32_t ld, float scale, const float* row_scale, int32_t max_iter,
                                  float* out_w, int32_t* out_iters, void* workspace, size_t workspace_bytes, void* stream) {
+    if (k != KW || knnsvc_match_generic_k())
+        return smooth_weights_k_launch(sg, need, entry, k, idx, pool, np, dim, ld, scale, row_scale, max_iter, out_w, out_iters, workspace,
+                                       workspace_bytes, stream);
     KN_REQUIRE(idx && pool && out_w && workspace, "%s: null pointer", entry);
     KN_REQUIRE(np > 0 && dim > 0 && ld >= dim && max_iter != 0, "%s: bad sizes", entry);
     KN_REQUIRE(((uintptr_t)out_w & 15) == 0, "%s: out_w must be 16-byte aligned", entry);
@@ -474,7 +752,7 @@ extern "C" int knnsvc_smooth_weights(const int64_t* idx, int64_t nq, const float
     if ((rc = kn_seg_one(nq, "smooth_weights", &t)) || (rc = smooth_segs(t, "smooth_weights", &sg, &seg_bytes))) return rc;
     // Its own size, not seg_bytes (which rounds up to 64): the one segment starts at the 64-byte-aligned base, at most 63 bytes
     // into the workspace, and ends ws_floats(nq) * 4 bytes later.
-    return smooth_weights_launch(sg, knnsvc_smooth_workspace_bytes(nq), "smooth_weights", idx, pool, np, dim, ld, scale, row_scale,
+    return smooth_weights_launch(sg, knnsvc_smooth_workspace_bytes(nq), "smooth_weights", KW, idx, pool, np, dim, ld, scale, row_scale,
                                  max_iter, out_w, out_iters, workspace, workspace_bytes, stream);
 }
 
@@ -490,6 +768,27 @@ extern "C" int knnsvc_smooth_weights_seg(const int64_t* idx, const int64_t* host
     KnSegTable t; SmoothSegs sg; size_t need = 0;
     int rc;
     if ((rc = kn_seg_table(host_seg, n_seg, "smooth_weights_seg", &t)) || (rc = smooth_segs(t, "smooth_weights_seg", &sg, &need))) return rc;
-    return smooth_weights_launch(sg, need, "smooth_weights_seg", idx, pool, np, dim, ld, scale, row_scale, max_iter, out_w, out_iters,
+    return smooth_weights_launch(sg, need, "smooth_weights_seg", KW, idx, pool, np, dim, ld, scale, row_scale, max_iter, out_w, out_iters,
+                                 workspace, workspace_bytes, stream);
+}
+
+// ---- the segmented calls for k neighbours per frame (1 <= k <= 8); the ones above are k = 4 ------------------------------------
+extern "C" size_t knnsvc_smooth_seg_workspace_bytes_k(const int64_t* host_seg, int32_t n_seg, int32_t k) {
+    KnSegTable t; SmoothSegs sg; size_t bytes = 0;
+    if (k < 1 || k > 8) { knnsvc_fail(KNNSVC_EINVAL, "smooth_seg_workspace_bytes_k: k = %d outside 1..8", (int)k); return 0; }
+    if (kn_seg_table(host_seg, n_seg, "smooth_seg_workspace_bytes_k", &t) || smooth_segs(t, "smooth_seg_workspace_bytes_k", &sg, &bytes, k))
+        return 0;
+    return bytes;
+}
+
+extern "C" int knnsvc_smooth_weights_seg_k(const int64_t* idx, int32_t k, const int64_t* host_seg, int32_t n_seg, const float* pool,
+                                           int64_t np, int32_t dim, int32_t ld, float scale, const float* row_scale, int32_t max_iter,
+                                           float* out_w, int32_t* out_iters, void* workspace, size_t workspace_bytes, void* stream) {
+    KnSegTable t; SmoothSegs sg; size_t need = 0;
+    int rc;
+    if ((rc = kn_seg_table(host_seg, n_seg, "smooth_weights_seg_k", &t))) return rc;
+    KN_REQUIRE(k >= 1 && k <= 8, "smooth_weights_seg_k: k = %d outside 1..8", (int)k);
+    if ((rc = smooth_segs(t, "smooth_weights_seg_k", &sg, &need, k))) return rc;
+    return smooth_weights_launch(sg, need, "smooth_weights_seg_k", k, idx, pool, np, dim, ld, scale, row_scale, max_iter, out_w, out_iters,
                                  workspace, workspace_bytes, stream);
 }

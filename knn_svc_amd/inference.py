@@ -5,8 +5,10 @@
 SRC/TGT are both audio files (single conversion, output next to SRC as
 ``<src>_to_<tgt>_knn_<ckpt_type>_<post_opt>.wav``) or both dataset roots (folders of
 speaker folders; outputs under ``<tgt parent>/<src>_to_<tgt>_<ckpt_type>_post_opt_<post_opt>/``,
-prefixed ``duration_limit_<n>_`` when --dur_limit is given).  --topk is accepted and
-ignored, as upstream.  --tgt_loudness_db (default -16) is accepted and, as upstream,
+prefixed ``duration_limit_<n>_`` when --dur_limit is given).  --topk is accepted and, as
+upstream, ignored unless --use_topk true is given (an extension, default false): the match
+stage then mixes that many (1..8) of the 32 neighbours per frame instead of the hard-coded 4;
+file names do not change.  --tgt_loudness_db (default -16) is accepted and, as upstream,
 ignored unless --normalize_loudness true is given (an extension, default false): every
 output is then brought to that integrated loudness (BS.1770) on the GPU before it is
 written; file names do not change, and a clip normalised past full scale is written
@@ -48,6 +50,8 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--prioritize_f0", type=_bool, default=True)
     ap.add_argument("--normalize_loudness", type=_bool, default=False,
                     help="(extension) normalise every output to --tgt_loudness_db LKFS")
+    ap.add_argument("--use_topk", type=_bool, default=False,
+                    help="(extension) mix --topk (1..8) neighbours per frame instead of the reference's hard-coded 4")
     ap.add_argument("--weights", default="auto", choices=["auto", "checkpoint", "seeded"],
                     help="(extension) 'seeded' runs with random weights when the released checkpoints are unavailable")
     return ap
@@ -67,7 +71,8 @@ def main(argv=None) -> int:
     knn = knn_vc(pretrained=True, progress=True, prematched=True, device=a.device, ckpt_type=a.ckpt_type,
                  local_ckpt_dir=a.ckpt_dir, weights=a.weights)
     common = dict(topk=a.topk, device=a.device, prioritize_f0=a.prioritize_f0, ckpt_type=a.ckpt_type,
-                  tgt_loudness_db=a.tgt_loudness_db, post_opt=a.post_opt, normalize_loudness=a.normalize_loudness)
+                  tgt_loudness_db=a.tgt_loudness_db, post_opt=a.post_opt, normalize_loudness=a.normalize_loudness,
+                  use_topk=a.use_topk)
     if os.path.isfile(a.src) and os.path.isfile(a.tgt):
         knn.special_match(src_wav_file=a.src, ref_wav_file=a.tgt, **common)
         return 0

@@ -2,7 +2,9 @@
 
 Mirror of ddsp_matcher.py:303-1155 restricted to its live methods: ``vocode``
 (:375-406), ``special_match`` (:937-1023) and ``bulk_match`` (:1027-1155), with the
-same argument names, output file naming and ignored argument (``topk``).
+same argument names and output file naming.  ``topk`` is accepted and, as upstream, ignored UNLESS
+``use_topk=True`` is passed (an extension, off by default): the match stage then mixes that many
+(1..8) neighbours per frame instead of the hard-coded 4; file names do not change.
 ``tgt_loudness_db`` is accepted and, as in the reference's live methods, ignored UNLESS
 ``normalize_loudness=True`` is passed (an extension, off by default): the generator's waveform is
 then brought to that integrated loudness on the GPU (ops.normalize_loudness; what the reference
@@ -80,7 +82,8 @@ class KNeighborsVC:
 
     @torch.inference_mode()
     def special_match(self, src_wav_file, ref_wav_file, topk: int = 4, device=None, prioritize_f0=True,
-                      ckpt_type="wavlm_only", tgt_loudness_db=-16, post_opt="no_post_opt", save=True, normalize_loudness=False):
+                      ckpt_type="wavlm_only", tgt_loudness_db=-16, post_opt="no_post_opt", save=True, normalize_loudness=False,
+                      use_topk=False):
         level = tgt_loudness_db if normalize_loudness else None
         f0only = "wavlm_only" in ckpt_type or "no_harm_no_amp" in ckpt_type
         if "wavlm_only_original" in ckpt_type:
@@ -89,13 +92,14 @@ class KNeighborsVC:
         if not f0only:
             of, hw, _a, sf0 = match_at_inference_time(Path(src_wav_file), Path(ref_wav_file), self.wavlm,
                                                       self.weighting, self.weighting, topk=topk, device=self.device,
-                                                      prioritize_f0=prioritize_f0, ckpt_type=ckpt_type, post_opt=post_opt)
+                                                      prioritize_f0=prioritize_f0, ckpt_type=ckpt_type, post_opt=post_opt,
+                                                      use_topk=use_topk)
             pred = self.vocode(of[key][None], sf0[key][None, :, None], hw[key][None], loudness_db=level).squeeze()
         else:
             # the reference does not forward post_opt on this branch (ddsp_matcher.py:970)
             of, _a, sf0 = match_at_inference_time(Path(src_wav_file), Path(ref_wav_file), self.wavlm,
                                                   self.weighting, self.weighting, topk=topk, device=self.device,
-                                                  prioritize_f0=prioritize_f0, ckpt_type=ckpt_type)
+                                                  prioritize_f0=prioritize_f0, ckpt_type=ckpt_type, use_topk=use_topk)
             pred = self.vocode(of[key][None], sf0[key][None, :, None], loudness_db=level).squeeze()
         src_id = os.path.basename(src_wav_file).split(".")[0]
         ref_id = os.path.basename(ref_wav_file).split(".")[0]
@@ -107,25 +111,26 @@ class KNeighborsVC:
 
     @torch.inference_mode()
     def many_to_one(self, src_files, ref_wav_file, converted_audio_dir=None, ckpt_type="mix", post_opt="post_opt_0.2",
-                    duration_limit=None, target=None, match=None, loudness_db=None):
+                    duration_limit=None, target=None, match=None, loudness_db=None, topk=None):
         """BASELINE cfg 5 (no counterpart upstream: the reference would call ``special_match`` once per source and rebuild the
         target pool each time, ddsp_matcher.py:937-1023): MANY sources against ONE target pool that is built once and stays
         resident, all sources through the stream pipeline as one batch (knn_svc_amd/serving.py).  Under a process group the
         sources are dealt over the ranks (no collective).  ``target``: a serving.TargetVoice to reuse.  -> written paths (all
         ranks' on every rank), named like ``special_match``'s outputs.  ``match``: "lanes" | "segmented" (serving.BatchConverter; default
-        from KNNSVC_MATCH).  ``loudness_db``: every waveform is normalised to that integrated loudness (None: left as generated)."""
+        from KNNSVC_MATCH).  ``loudness_db``: every waveform is normalised to that integrated loudness (None: left as generated).
+        ``topk``: neighbours mixed per frame, 1..8 (None: 4)."""
         from . import serving
         if target is None:
             target = serving.TargetVoice(self, ref_wav_file, duration_limit)
         mine = kdist.my_share([str(p) for p in src_files])
         written = serving.BatchConverter(self, target, ckpt_type, post_opt, match=match,
-                                         loudness_db=loudness_db).convert_files(mine, converted_audio_dir)
+                                         loudness_db=loudness_db, topk=topk).convert_files(mine, converted_audio_dir)
         return kdist.gather_paths(written)
 
     @torch.inference_mode()
     def bulk_match(self, src_dataset_path, tgt_dataset_path, converted_audio_dir, topk: int = 4, device=None,
                    prioritize_f0=True, ckpt_type="mix", tgt_loudness_db=-16, required_subset_file=None,
-                   post_opt="no_post_opt", duration_limit=None, normalize_loudness=False):
+                   post_opt="no_post_opt", duration_limit=None, normalize_loudness=False, use_topk=False):
         level = tgt_loudness_db if normalize_loudness else None
         assert os.path.isdir(src_dataset_path) and os.path.isdir(tgt_dataset_path)
         Path(converted_audio_dir).mkdir(parents=True, exist_ok=True)
@@ -164,7 +169,7 @@ class KNeighborsVC:
                 common = dict(topk=topk, device=self.device, prioritize_f0=prioritize_f0, ckpt_type=ckpt_type,
                               src_dataset_path=src_dataset_path, tgt_dataset_path=tgt_dataset_path,
                               required_subset=required, duration_limit=duration_limit,
-                              pool_sharded=shard, share_items=shard)
+                              pool_sharded=shard, share_items=shard, use_topk=use_topk)
                 # the generator of every utterance is the tail stage of the match pipeline (same kernels and inputs as
                 # `vocode` after the fact, ddsp_matcher.py:1114-1128, but enqueued under the next utterances' matching);
                 # one finiteness check per speaker pair instead of one host sync per utterance; with normalize_loudness the

@@ -5,6 +5,8 @@ Host-side mirror of the reference's ``get_complete_spk_pool`` and
 arguments, same returned dict-of-tensors keyed by ``str(path)``, same quirks
 (k hard-coded to 32 -> first 4, ``--dur_limit`` in seconds overshooting by one file,
 ``post_opt`` parsing, ``prioritize_f0`` must be True, pool rebuilt per call).
+``topk`` is ignored as upstream unless ``use_topk=True`` (an extension, off by default): the
+match stage then keeps that many (1..8) of the 32 neighbours per frame instead of 4.
 All arithmetic is done by libknnsvc_hip.so kernels on device-resident tensors; the
 only host work is file I/O and the chunk bookkeeping.
 """
@@ -320,14 +322,23 @@ def wait_for_neighbours(nn_item, ready_event, device):
     nn_item.record_stream(st)
 
 
+def resolve_topk(topk) -> int:
+    """Neighbours mixed per frame: None = C.KNN_USE (4, what the released checkpoints were trained on), else 1..8."""
+    if topk is None:
+        return C.KNN_USE
+    if isinstance(topk, bool) or int(topk) != topk or not 1 <= int(topk) <= 8:
+        raise ValueError(f"topk must be an integer in 1..8 (or None for {C.KNN_USE}), got {topk!r}")
+    return int(topk)
+
+
 def match_features(query_seq, query_f0, matching_list, matching_f0, harmonics_list, ckpt_type, post_opt,
-                   return_debug=False, nn32=None, nan_flags=None, pool_prep=None, synth_list=None):
+                   return_debug=False, nn32=None, nan_flags=None, pool_prep=None, synth_list=None, topk=None):
     """The per-query body (ddsp_prematch_dataset.py:1189-1450) on device tensors: ``match_features_many`` (below, where the
     arguments are described) of one utterance.  ``nn32`` may carry neighbours already found by the pool-sharded search
     (knn_svc_amd.dist.sharded_knn); in the debug dict ``iters_*`` are one-element tensors, or 0 without the Adam stage."""
     return match_features_many([query_seq], [query_f0], matching_list, matching_f0, harmonics_list, ckpt_type, post_opt,
                                nn32s=None if nn32 is None else [nn32], nan_flags=nan_flags, pool_prep=pool_prep,
-                               synth_list=synth_list, return_debug=return_debug)[0]
+                               synth_list=synth_list, return_debug=return_debug, topk=topk)[0]
 
 
 # How the match stage of SEVERAL items is put on the chip: "lanes" (one match_features per item on the lane streams, the default) or
@@ -360,7 +371,7 @@ def _stacked(ts):
 
 
 def match_features_many(query_seqs, query_f0s, matching_list, matching_f0, harmonics_list, ckpt_type, post_opt, nn32s=None,
-                        nan_flags=None, pool_prep=None, synth_list=None, return_debug=False):
+                        nan_flags=None, pool_prep=None, synth_list=None, return_debug=False, topk=None):
     """The per-query body (ddsp_prematch_dataset.py:1189-1450) for several query utterances against one pool, run ONCE over their
     stacked frames -> a list of per-item tuples (out_feats, harm or None, shifted_f0[, debug dict]) (views of the stacked outputs).
     The row-wise stages (row norms, f0 re-rank, weighted sums) take the stacked rows as they are; the per-sequence stages (median,
@@ -369,7 +380,9 @@ def match_features_many(query_seqs, query_f0s, matching_list, matching_f0, harmo
     when it differs from the matching one (:349-350, 1157): the search and the concat re-selection run on ``matching_list``, the
     smoothness weights and the weighted sums on ``synth_list`` (:1260, 1347-1350).  ``nn32s``: per-item neighbour lists (or None: one
     search over the stacked frames).  ``nan_flags``: a list that receives the kNN NaN flag instead of the host checking it here
-    (the caller then calls ``ops.raise_if_nan`` on each entry once everything is enqueued — keeps a stream pipeline free of syncs)."""
+    (the caller then calls ``ops.raise_if_nan`` on each entry once everything is enqueued — keeps a stream pipeline free of syncs).
+    ``topk``: neighbours kept per frame out of the 32 found (1..8; None = 4, the specialised kernels)."""
+    topk = resolve_topk(topk)                 # before any device work
     lens = [int(q.shape[0]) for q in query_seqs]
     seg = [0]
     for n in lens:
@@ -401,20 +414,20 @@ def match_features_many(query_seqs, query_f0s, matching_list, matching_f0, harmo
         qmed, pmed = ops.log_f0_median_seg(query_f0, seg), ops.log_f0_median(matching_f0)      # the pool's median once
         shifted = ops.shift_f0_seg(query_f0, seg, qmed, pmed)
         ranked = ops.f0_rerank(nn32, shifted, matching_f0)
-        idx2 = ranked[:, :C.KNN_USE].contiguous()
+        idx2 = ranked[:, :topk].contiguous()
         if cw != -1:
             idx2 = ops.concat_reselect_seg(idx2, seg, q, qn, P, pn, shifted, matching_f0, concat_weight=cw)
         if with_harm:
             if run_adam:
                 w2, it2 = ops.smooth_weights_seg(idx2, seg, harmonics_list, 1000.0, return_iters=True)
-            harm_w = ops.weighted_gather(idx2, w2, harmonics_list)
-    idx = nn32[:, :C.KNN_USE].contiguous()
+            harm_w = ops.weighted_gather(idx2, w2, harmonics_list, mean=True)        # without Adam: torch.mean (:1446)
+    idx = nn32[:, :topk].contiguous()
     if cw != -1:
         idx = ops.concat_reselect_seg(idx, seg, q, qn, P, pn, concat_weight=cw)
     Ps = synth_list if synth_list is not None else P
     if run_adam:
         w, it1 = ops.smooth_weights_seg(idx, seg, Ps, 0.1, return_iters=True)
-    out_feats = ops.weighted_gather(idx, w, Ps)
+    out_feats = ops.weighted_gather(idx, w, Ps)                                      # without Adam: softmax(ones) (:1361-1364)
     main.wait_stream(side)
     for t in (shifted, idx2, harm_w, w2, it2):
         if t is not None:
@@ -428,7 +441,7 @@ def match_features_many(query_seqs, query_f0s, matching_list, matching_f0, harmo
             except ops.KnnOverflow:         # the fused route's candidate buffer overflowed: once more on the dot-matrix route
                 with ops.fused_off():
                     return match_features_many(query_seqs, query_f0s, matching_list, matching_f0, harmonics_list, ckpt_type, post_opt,
-                                               pool_prep=pool_prep, synth_list=synth_list, return_debug=return_debug)
+                                               pool_prep=pool_prep, synth_list=synth_list, return_debug=return_debug, topk=topk)
     parts = lambda t: t.split(lens) if t is not None else [None] * len(lens)
     out = []
     dbg = [parts(t) for t in (nn32, idx, w, idx2, w2)]
@@ -478,10 +491,11 @@ def match_at_inference_time(src_wav_file, ref_wav_file, wavlm: WavLMEncoder, mat
                             topk: int = 4, device="cuda", prioritize_f0=False, ckpt_type="wavlm_only",
                             src_dataset_path=None, tgt_dataset_path=None, cache_dir=None, required_subset=None,
                             post_opt="no_post_opt", duration_limit=None, vocode_fn=None, waves_out=None,
-                            pool_sharded=None, share_items=False):
-    """Same contract as the reference function (ddsp_prematch_dataset.py:1074).  ``topk`` is accepted and
-    ignored (k = 32 -> 4 is hard-coded upstream, :1203,1246,1398); ``cache_dir`` is ignored (the reference
-    force-disables it, :1086-1087).
+                            pool_sharded=None, share_items=False, use_topk=False):
+    """Same contract as the reference function (ddsp_prematch_dataset.py:1074).  ``topk`` is accepted and, as upstream
+    (k = 32 -> 4 is hard-coded there, :1203,1246,1398), ignored UNLESS ``use_topk=True`` (an extension, off by default): the
+    match stage then keeps ``topk`` (1..8) neighbours per frame.  ``cache_dir`` is ignored (the reference force-disables
+    it, :1086-1087).
 
     Build extension (BASELINE cfg 5, many sources against one pool): ``vocode_fn(out_feats, shifted_f0, harm)`` is
     enqueued as the pipeline's tail stage right behind each item's match body and its waveform stored in
@@ -499,6 +513,7 @@ def match_at_inference_time(src_wav_file, ref_wav_file, wavlm: WavLMEncoder, mat
         rank the per-shard lists of its own items only, and each rank runs the match bodies (and ``vocode_fn``) of its
         own items: the returned dicts hold this rank's items."""
     import torch.distributed as tdist
+    k_use = resolve_topk(topk) if use_topk else None        # refused before any file is read
     if pool_sharded is None:         # by environment: only when there is more than one rank to shard over
         pool_sharded = os.environ.get("KNNSVC_POOL_SHARD") == "1" and kdist.world()[1] > 1
     pool_sharded = bool(pool_sharded) and tdist.is_available() and tdist.is_initialized()   # explicit True: any group, even 1 rank
@@ -598,6 +613,8 @@ def match_at_inference_time(src_wav_file, ref_wav_file, wavlm: WavLMEncoder, mat
         def body(item):
             wait_for_neighbours(nn.get(item), nn_ready.get(item), matching_list.device)      # a group search on the kNN stream
             extra = dict(synth_list=synth_list) if synth_list is not None else {}
+            if k_use is not None:
+                extra["topk"] = k_use
             return match_features(query_pool[item], query_f0_pool[item], matching_list, matching_f0,
                                   harmonics_list, ckpt_type, post_opt, nan_flags=flags, pool_prep=prep, nn32=nn.get(item), **extra)
         def body_many(batch):
@@ -605,7 +622,7 @@ def match_at_inference_time(src_wav_file, ref_wav_file, wavlm: WavLMEncoder, mat
                 wait_for_neighbours(nn.get(item), nn_ready.get(item), matching_list.device)
             return match_features_many([query_pool[it] for it in batch], [query_f0_pool[it] for it in batch], matching_list, matching_f0,
                                        harmonics_list, ckpt_type, post_opt, nn32s=[nn.get(it) for it in batch], nan_flags=flags,
-                                       pool_prep=prep, synth_list=synth_list)
+                                       pool_prep=prep, synth_list=synth_list, topk=k_use)
         # match bodies in flight at once (each is a chain of single-workgroup recurrences: more lanes = more of them side by side);
         # KNNSVC_MATCH=segmented (unsharded pool, several items): batches of KNNSVC_MATCH_BATCH items, each one body_many on a lane
         lanes = min(int(os.environ.get("KNNSVC_MATCH_LANES", "3")), len(items))

@@ -786,8 +786,18 @@ def f0_rerank(nn_idx, shifted_f0, pool_f0):
     return out
 
 
+def _topk_of(name, idx):
+    """k of an [rows, k] neighbour table as the match-stage kernels take it (1..8; 4 runs the specialised kernels)."""
+    if idx.dim() != 2 or not 1 <= idx.shape[1] <= 8:
+        raise KnnSvcError(f"{name}: idx must be [rows, k] with 1 <= k <= 8, got {tuple(idx.shape)}")
+    return int(idx.shape[1])
+
+
 def concat_reselect(idx4, q, q_norm, pool, p_norm, shifted_f0=None, pool_f0=None, concat_weight=0.2):
+    """``idx4`` [nq, k]: k = 4 is the specialised entry point, any other k in 1..8 the one-segment case of the k-taking one."""
     _need(idx4, torch.int64, "idx4")
+    if _topk_of("concat_reselect", idx4) != 4:
+        return concat_reselect_seg(idx4, [0, idx4.shape[0]], q, q_norm, pool, p_norm, shifted_f0, pool_f0, concat_weight)
     idx4 = idx4.contiguous()
     out = torch.empty_like(idx4)
     use_f0 = shifted_f0 is not None
@@ -808,12 +818,14 @@ def _smooth_args(name, idx4, pool, max_iter, row_scale):
     if row_scale is not None:
         _need(row_scale, name="row_scale")
         if tuple(row_scale.shape) != tuple(idx4.shape) or not row_scale.is_contiguous():
-            raise KnnSvcError(f"{name}: row_scale must be a contiguous [rows,4] tensor")
+            raise KnnSvcError(f"{name}: row_scale must be a contiguous [rows,k] tensor")
     return idx4.contiguous(), int(max_iter)
 
 
 def smooth_weights(idx4, pool, scale, max_iter=100000, return_iters=False, row_scale=None):
     """``row_scale`` [nq,4]: the amp_ratio of compute_weight_with_amp (ddsp_prematch_dataset.py:684-804)."""
+    if _topk_of("smooth_weights", idx4) != 4:
+        return smooth_weights_seg(idx4, [0, idx4.shape[0]], pool, scale, max_iter, return_iters, row_scale)
     idx4, max_iter = _smooth_args("smooth_weights", idx4, pool, max_iter, row_scale)
     lib = _lib.load()
     nq = idx4.shape[0]
@@ -884,40 +896,52 @@ def shift_f0_seg(f0, seg, qmed, pmed):
 def concat_reselect_seg(idx4, seg, q, q_norm, pool, p_norm, shifted_f0=None, pool_f0=None, concat_weight=0.2):
     """``concat_reselect`` of every segment of the stacked rows: one workgroup per segment in one launch."""
     _need(idx4, torch.int64, "idx4"); seg = _segments(seg, "concat_reselect_seg", idx4, q)
+    k = _topk_of("concat_reselect_seg", idx4)
     idx4 = idx4.contiguous()
     out = torch.empty_like(idx4)
     use_f0 = shifted_f0 is not None
+    lib = _lib.load()
     for a, r0, tab in seg.chunks:
-        check(_lib.load().knnsvc_concat_reselect_seg(_p(idx4[r0:]), _p(q[r0:]), _p(q_norm[r0:]), tab, len(tab) - 1, _p(pool), _p(p_norm),
-                                                     pool.shape[0], q.shape[1], _p(shifted_f0[r0:]) if use_f0 else _p(None), _p(pool_f0),
-                                                     1 if use_f0 else 0, float(concat_weight), _p(out[r0:]), _stream()), "concat_reselect_seg")
+        tail = (tab, len(tab) - 1, _p(pool), _p(p_norm), pool.shape[0], q.shape[1], _p(shifted_f0[r0:]) if use_f0 else _p(None),
+                _p(pool_f0), 1 if use_f0 else 0, float(concat_weight), _p(out[r0:]), _stream())
+        if k == 4:
+            check(lib.knnsvc_concat_reselect_seg(_p(idx4[r0:]), _p(q[r0:]), _p(q_norm[r0:]), *tail), "concat_reselect_seg")
+        else:
+            check(lib.knnsvc_concat_reselect_seg_k(_p(idx4[r0:]), k, _p(q[r0:]), _p(q_norm[r0:]), *tail), "concat_reselect_seg_k")
     return out
 
 
 def smooth_weights_seg(idx4, seg, pool, scale, max_iter=100000, return_iters=False, row_scale=None):
-    """``smooth_weights`` of every segment of the stacked rows -> w [total, 4] (and iters [n_seg])."""
+    """``smooth_weights`` of every segment of the stacked rows -> w [total, k] (and iters [n_seg]); k = idx4.shape[1] in 1..8."""
     idx4, max_iter = _smooth_args("smooth_weights_seg", idx4, pool, max_iter, row_scale)
     seg = _segments(seg, "smooth_weights_seg", idx4)
+    k = _topk_of("smooth_weights_seg", idx4)
     lib = _lib.load()
     npool, dim = pool.shape
-    w = torch.empty(idx4.shape[0], 4, device=pool.device, dtype=torch.float32)
+    w = torch.empty(idx4.shape[0], k, device=pool.device, dtype=torch.float32)
     iters = torch.zeros(seg.n, device=pool.device, dtype=torch.int32)
     for a, r0, tab in seg.chunks:
-        ws_bytes = lib.knnsvc_smooth_seg_workspace_bytes(tab, len(tab) - 1)
+        ws_bytes = lib.knnsvc_smooth_seg_workspace_bytes(tab, len(tab) - 1) if k == 4 else \
+            lib.knnsvc_smooth_seg_workspace_bytes_k(tab, len(tab) - 1, k)
         ws = torch.empty(ws_bytes, device=pool.device, dtype=torch.uint8)
-        check(lib.knnsvc_smooth_weights_seg(_p(idx4[r0:]), tab, len(tab) - 1, _p(pool), npool, dim, pool.stride(0), float(scale),
-                                            _p(row_scale[r0:]) if row_scale is not None else _p(None), max_iter, _p(w[r0:]),
-                                            _p(iters[a:]), _p(ws), ws_bytes, _stream()), "smooth_weights_seg")
+        tail = (tab, len(tab) - 1, _p(pool), npool, dim, pool.stride(0), float(scale), _p(row_scale[r0:]) if row_scale is not None else _p(None),
+                max_iter, _p(w[r0:]), _p(iters[a:]), _p(ws), ws_bytes, _stream())
+        if k == 4:
+            check(lib.knnsvc_smooth_weights_seg(_p(idx4[r0:]), *tail), "smooth_weights_seg")
+        else:
+            check(lib.knnsvc_smooth_weights_seg_k(_p(idx4[r0:]), k, *tail), "smooth_weights_seg_k")
     return (w, iters) if return_iters else w
 
 
-def weighted_gather(idx4, w, pool):
+def weighted_gather(idx4, w, pool, mean=False):
+    """sum_k w[i, k] * pool[idx4[i, k]].  ``w`` None = uniform weights: each row times 1.0f / k (softmax(ones)), or with ``mean`` the
+    sum in order divided by k (torch.mean); the same bits when k is a power of two."""
     _need(idx4, torch.int64, "idx4")
     idx4 = idx4.contiguous()
     nq, k = idx4.shape
     dim = pool.shape[1]
     out = torch.empty(nq, dim, device=pool.device, dtype=torch.float32)
-    check(_lib.load().knnsvc_weighted_gather(_p(idx4), _p(w), nq, k, _p(pool), dim, pool.stride(0), 0, _p(out),
+    check(_lib.load().knnsvc_weighted_gather(_p(idx4), _p(w), nq, k, _p(pool), dim, pool.stride(0), 1 if mean else 0, _p(out),
                                              _stream()), "weighted_gather")
     return out
 

@@ -86,7 +86,7 @@ class TargetVoice:
 class BatchConverter:
     def __init__(self, vc, target: TargetVoice, ckpt_type: str = "mix", post_opt: str = "post_opt_0.2", lanes: int | None = None,
                  max_encode_batch: int = 32, match: str | None = None, match_batch: int | None = None,
-                 loudness_db: float | None = None):
+                 loudness_db: float | None = None, topk: int | None = None):
         if "wavlm_only_original" in ckpt_type:
             raise NotImplementedError("wavlm_only_original needs hifigan/models.py, absent upstream")
         self.vc, self.target, self.ckpt_type, self.post_opt = vc, target, ckpt_type, post_opt
@@ -101,6 +101,8 @@ class BatchConverter:
         # integrated loudness every waveform is brought to (ops.normalize_loudness as part of the tail, on the tail's stream,
         # enqueue-only); None: the generator's own level.  A RequestQueue in front of this converter inherits it.
         self.loudness_db = None if loudness_db is None else float(loudness_db)
+        # neighbours mixed per frame out of the 32 found: 1..8; None: 4 (the released checkpoints' training condition)
+        self.topk = None if topk is None else M.resolve_topk(topk)
 
     def _load(self, src, check=False):
         """A request is a path, or (wav [L] float32 16 kHz mono as array / tensor, f0 [L // 320 + 1] or None).
@@ -173,12 +175,12 @@ class BatchConverter:
             def body(i):
                 M.wait_for_neighbours(nn.get(i), ready.get(i), dev)
                 return M.match_features(qpool[i], f0s[i], tg.feats, tg.f0, tg.harm, self.ckpt_type, post_opt,
-                                        nan_flags=flags, pool_prep=tg.prep, nn32=nn.get(i))
+                                        nan_flags=flags, pool_prep=tg.prep, nn32=nn.get(i), topk=self.topk)
             def body_many(batch):
                 for i in batch:
                     M.wait_for_neighbours(nn.get(i), ready.get(i), dev)
                 return M.match_features_many([qpool[i] for i in batch], [f0s[i] for i in batch], tg.feats, tg.f0, tg.harm, self.ckpt_type,
-                                             post_opt, nn32s=[nn.get(i) for i in batch], nan_flags=flags, pool_prep=tg.prep)
+                                             post_opt, nn32s=[nn.get(i) for i in batch], nan_flags=flags, pool_prep=tg.prep, topk=self.topk)
             tail = lambda i, r: voc(r[0], r[2], r[1])
             ys = M.run_match_bodies(items, body, body_many, tail, device=dev, lanes=max(1, min(self.lanes, len(items))),
                                     match=self.match, match_batch=self.match_batch)

@@ -1,0 +1,102 @@
+"""GPU: topk — 1 to 8 neighbours per frame through the match stage (knnsvc_concat_reselect_seg_k, knnsvc_smooth_weights_seg_k,
+knnsvc_weighted_gather's mean_mode, matching.match_features_many(topk=), serving.BatchConverter(topk=), special_match(use_topk=))
+against the CPU oracle, which takes k from idx.shape[1], and against fp64 sums.
+
+All GPU work runs in ONE fresh child interpreter (tests/topk_child.py) that writes a report; the tests only read it.  This module
+sorts in front of test_gpu_dist2, which must find the interpreter without an initialised GPU, so nothing here may touch the GPU
+in the pytest process.
+
+Cases (the smallest shapes that reach every boundary; the bars and their CPU-checked preconditions are in topk_child.py):
+  walk            k in {1, 2, 3, 5, 6, 7, 8}, both variants, (1, 40, 64), (2, 40, 256), (3, 9, 768: the clamp, repeated candidates),
+                  (64, 48, 1024: the LDS limit at k = 8), (130, 4000, 512): selected sets equal on every frame, on the long pool
+                  also the order; one segmented call over [1, 2, 3, 64] at k = 8, bit-identical to the single calls.
+  walk-generic4   KNNSVC_MATCH_GENERIC_K=1 on fixture g4_select, exact rows.
+  smooth          k in {1, 2, 3, 5, 8} on two pools (scale 1000 / 0.1) within 4e-4 of the oracle and the same iteration count;
+                  row_scale at k = 5.
+  smooth-seg      max_iter 300, segments [1, 2, 2304, 2305] at k = 8 and [1, 2, 37, 6144, 6145] at k = 3 (LDS | global
+                  exchange), bit-identical to the single calls.
+  smooth-generic4 the knob on fixture g5_smooth, 4e-4 and the fixture's iteration counts.
+  gather          k in {3, 5, 6, 7}, both modes, within k 2^-24 max|x| of the fp64 mean; k = 4: both modes and the parent's
+                  expression bit-identical.
+  chain           match_features_many(topk = 1, 3, 8) on three items (2 / 31 / 150 frames), mix / post_opt_0.2 and
+                  wavlm_only / no_post_opt; topk=4 is topk=None and many is single (k = 8), bit for bit.
+  product         tiny models: BatchConverter(topk=8) lanes == segmented, != default, finite; special_match ignores topk
+                  without use_topk, honours it with, and use_topk with topk=4 is the default, bit for bit."""
+import json
+import os
+import subprocess
+import sys
+
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CHILD_TIMEOUT_S = 600        # a few seconds of GPU work per case; most of the time is the CPU oracle's frame-by-frame walks
+
+
+@pytest.fixture(scope="module")
+def report(tmp_path_factory):
+    if torch.cuda.is_initialized():
+        pytest.skip("ranks are spawned from a process that has not initialised the GPU: run this module first / on its own")
+    out = str(tmp_path_factory.mktemp("topk") / "report.json")
+    try:
+        r = subprocess.run([sys.executable, "tests/topk_child.py", out], timeout=CHILD_TIMEOUT_S, cwd=ROOT,
+                           capture_output=True, text=True)
+    except subprocess.TimeoutExpired as e:
+        return {"__failed__": f"child timed out after {CHILD_TIMEOUT_S} s\n" + str(e.stderr or "")[-3000:]}
+    print(r.stdout[-20000:])
+    rep = {}
+    if os.path.isfile(out):
+        rep = json.load(open(out))
+    if r.returncode != 0:
+        rep["__failed__"] = f"child exited with {r.returncode}\n" + r.stderr[-3000:]
+    return rep
+
+
+def _check(report, prefix, exactly):
+    assert "__failed__" not in report, report["__failed__"]
+    mine = {k: v for k, v in report.items() if k.startswith(prefix)}
+    assert len(mine) == exactly, (prefix, sorted(mine))
+    bad = {k: v["detail"] for k, v in mine.items() if not v["ok"]}
+    assert not bad, bad
+
+
+def test_walk_for_every_k_equals_the_oracle(report):
+    _check(report, "walk/", 7 * 5 * 2 + 1)
+
+
+def test_walk_segments_equal_single_sequences_at_k8(report):
+    _check(report, "walk-seg/", 2)
+
+
+def test_generic_walk_at_k4_matches_the_reference_fixture(report):
+    _check(report, "walk-generic4/", 2 + 1)
+
+
+def test_smooth_weights_for_every_k_equal_the_oracle(report):
+    _check(report, "smooth/", 2 * 5 + 1 + 1)
+
+
+def test_smooth_weights_segments_equal_single_sequences(report):
+    _check(report, "smooth-seg/", 2 + 1)
+
+
+def test_generic_smooth_weights_at_k4_match_the_reference_fixture(report):
+    _check(report, "smooth-generic4/", 2 + 1)
+
+
+def test_uniform_gather_both_modes(report):
+    _check(report, "gather/", 4 * 2 + 1 + 1)
+
+
+def test_match_features_many_with_topk(report):
+    _check(report, "chain/", 2 * (3 * 3 + 2) + 1)
+
+
+def test_product_entry_points_honour_topk(report):
+    _check(report, "product/", 6 + 1)
+
+
+def test_parent_process_left_the_gpu_alone(report):
+    assert not torch.cuda.is_initialized()
