@@ -500,11 +500,12 @@ int knnsvc_smooth_weights_seg(const int64_t* idx, const int64_t* host_seg, int32
                               int32_t* out_iters, void* workspace, size_t workspace_bytes, void* stream);
 
 /* The three segmented calls above that carry a [.., 4], for k neighbours per frame (topk), 1 <= k <= 8: idx_in / idx_out /
- * idx / out_w / row_scale are [total, k].  The entry points above are the k = 4 call of the same launchers and keep their
- * kernels; any other k runs the generic-K kernels (a four-wave walk over 2k candidates per frame in (4k + 2) * dim * 4
- * bytes of LDS; a Gram of k(2k - 1) entries per frame pair and one Adam loop with its state in the workspace, exchanging
- * weights and gradients through LDS while 2 * k * 4 * rows bytes fit 144 KB).  KNNSVC_MATCH_GENERIC_K=1 (read per call)
- * sends k = 4 there too.  A one-row segment gets 1 / k and 0 iterations.  Refused before the first HIP call: k outside 1..8
+ * idx / out_w / row_scale are [total, k].  The entry points above are the k = 4 call of the same launchers.  Each stage
+ * is one K-templated kernel for every k (a four-wave walk over 2k candidates per frame in (4k + 2) * dim * 4 bytes of LDS;
+ * a Gram of k(2k - 1) entries per frame pair; one Adam loop with its state in the workspace, exchanging weights and
+ * gradients through LDS while 2 * k * 4 * rows bytes fit 144 KB), and k = 4 has fast paths beside them: the pipelined
+ * walk (dim <= 1024), the register-resident Adam loops (<= 1536 rows) and a float4 Adam loop for longer sequences.
+ * KNNSVC_MATCH_GENERIC_K=1 (read per call) makes k = 4 skip them.  A one-row segment gets 1 / k and 0 iterations.  Refused before the first HIP call: k outside 1..8
  * (KNNSVC_EINVAL; the workspace size is then 0), an LDS need above 150 KB, misaligned q / pool / out_w, a workspace below
  * knnsvc_smooth_seg_workspace_bytes_k (KNNSVC_EWORKSPACE).  At k = 4 that size equals knnsvc_smooth_seg_workspace_bytes. */
 int knnsvc_concat_reselect_seg_k(const int64_t* idx_in, int32_t k, const float* q, const float* q_norm, const int64_t* host_seg,

@@ -55,7 +55,7 @@ static inline int kn_seg_one(int64_t n, const char* entry, KnSegTable* out) {
     return kn_seg_table(one, 1, entry, out);
 }
 
-// KNNSVC_MATCH_GENERIC_K=1: the match stage's generic-K kernels also at k = 4 (select.hip)
+// KNNSVC_MATCH_GENERIC_K=1: the match stage at k = 4 skips its fast paths and runs the K kernels as any other k (select.hip)
 bool knnsvc_match_generic_k();
 
 // Opt-in of KERNEL to `bytes` of dynamic LDS (a launch with more than 64 KiB fails without it).  The attribute is set once per

@@ -106,13 +106,16 @@ __global__ __launch_bounds__(256) void f0_rerank_kernel(const long* __restrict__
 }
 
 // ---------------------------------------------------------------------------------------------
-// knn_with_concat_cost.  One block (4 waves) walks the frames of one sequence.  Candidate rows
-// live in a two-slot LDS ring so that the previous frame's selection is still resident when the
-// concat costs are formed.  Distances follow fast_cosine_dist on torch.cdist's direct route
+// knn_with_concat_cost for K neighbours per frame, 1 <= K <= 8 (the reference's 4 is one instantiation).  One block (4 waves)
+// walks the frames of one sequence.  Candidates per frame: the frame's K neighbours, then previous selection + 1 (clamped at the
+// pool's end).  The 2K candidate rows live in a two-slot LDS ring so that the previous frame's selection is still resident when
+// the concat costs are formed: (4K + 2) * dim floats of LDS.  Distances follow fast_cosine_dist on torch.cdist's direct route
 // (both sides <= 25 rows): cd = sqrt(sum (x-y)^2); d = 1 - (((-cd^2 + |x|^2) + |y|^2)/2)/(|x||y|).
+// This is the one statement of the walk's rules (distance form, thresholding, sticky weight, NaN rule, tie rule); the pipelined
+// walk below is the k = 4 fast path that has to agree with it.
 // ---------------------------------------------------------------------------------------------
-constexpr int KC = 4;        // neighbours kept per frame
-constexpr int NC = 2 * KC;   // candidates per frame
+constexpr int KC = 4;        // the pipelined walk's neighbours per frame
+constexpr int NC = 2 * KC;   // and its candidates per frame
 
 __device__ __forceinline__ float cos_from_cd(float ss, float xn, float yn) {
 #pragma clang fp contract(off)
@@ -132,130 +135,8 @@ __device__ __forceinline__ float sqdiff(const float* __restrict__ x, const float
     return wave_sum(s);
 }
 
-__device__ __forceinline__ void concat_reselect_body(
-    const long* __restrict__ idx_in, const float* __restrict__ q, const float* __restrict__ qn, long nq,
-    const float* __restrict__ pool, const float* __restrict__ pn, long np, int dim,
-    const float* __restrict__ sf0, const float* __restrict__ pf0, int use_f0, float concat_weight,
-    long* __restrict__ idx_out) {
-#pragma clang fp contract(off)
-    extern __shared__ __attribute__((aligned(16))) float sm[];
-    float* ring = sm;                               // [2][NC][dim]
-    float* qrow = ring + 2 * NC * dim;              // [2][dim]
-    __shared__ float s_match[NC], s_cc[KC][NC], s_base;
-    __shared__ long s_cand[2][NC];
-    __shared__ int s_prev_slot[KC];                 // slots (in the previous ring half) of the kept rows
-    __shared__ long s_prev_idx[KC];
-    __shared__ float s_w;
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    // frame 0 keeps its neighbours
-    if (tid < KC) {
-        const long id = idx_in[tid];
-        idx_out[tid] = id;
-        s_prev_idx[tid] = id; s_prev_slot[tid] = tid; s_cand[0][tid] = id;
-    }
-    if (tid == 0) s_w = concat_weight;
-    __syncthreads();
-    for (int r = 0; r < KC; ++r)
-        for (int c = tid * 4; c < dim; c += 1024) *(f32x4*)&ring[(0 * NC + r) * dim + c] = *(const f32x4*)(pool + s_cand[0][r] * (long)dim + c);
-    for (int c = tid * 4; c < dim; c += 1024) *(f32x4*)&qrow[c] = *(const f32x4*)(q + c);
-    __syncthreads();
-
-    for (long i = 1; i < nq; ++i) {
-        const int cur = (int)(i & 1), prv = cur ^ 1;
-        if (tid < NC) {
-            long id;
-            if (tid < KC) id = idx_in[i * KC + tid];
-            else { id = s_prev_idx[tid - KC] + 1; if (id >= np) id = np - 1; }
-            s_cand[cur][tid] = id;
-        }
-        __syncthreads();
-        // stage the 8 candidate rows and q[i]
-        for (int r = 0; r < NC; ++r) {
-            const float* src = pool + s_cand[cur][r] * (long)dim;
-            for (int c = tid * 4; c < dim; c += 1024) *(f32x4*)&ring[(cur * NC + r) * dim + c] = *(const f32x4*)(src + c);
-        }
-        for (int c = tid * 4; c < dim; c += 1024) *(f32x4*)&qrow[cur * dim + c] = *(const f32x4*)(q + i * (long)dim + c);
-        __syncthreads();
-        // 8 match + 32 concat + 1 baseline squared distances, spread over the 4 waves
-        for (int job = wave; job < NC + KC * NC + 1; job += 4) {
-            if (job < NC) {
-                const float ss = sqdiff(&qrow[cur * dim], &ring[(cur * NC + job) * dim], dim, lane);
-                if (lane == 0) s_match[job] = cos_from_cd(ss, qn[i], pn[s_cand[cur][job]]);
-            } else if (job < NC + KC * NC) {
-                const int a = (job - NC) / NC, b = (job - NC) % NC;
-                const float ss = sqdiff(&ring[(prv * NC + s_prev_slot[a]) * dim], &ring[(cur * NC + b) * dim], dim, lane);
-                if (lane == 0) s_cc[a][b] = cos_from_cd(ss, pn[s_prev_idx[a]], pn[s_cand[cur][b]]);
-            } else {
-                const float ss = sqdiff(&qrow[prv * dim], &qrow[cur * dim], dim, lane);
-                if (lane == 0) s_base = cos_from_cd(ss, qn[i - 1], qn[i]) * 2.0f;
-            }
-        }
-        __syncthreads();
-        if (wave == 0) {
-            float total = __builtin_inff();
-            const float base = s_base;
-            float w = s_w;
-            if (use_f0 && !(base < 0.08f)) w = 0.f;            // sticky: stays 0 for every later frame
-            if (lane < NC) {
-                float c4[KC];
-#pragma unroll
-                for (int a = 0; a < KC; ++a) {
-                    float c = s_cc[a][lane];
-                    if (use_f0) { if (base < 0.08f && c < 5.0f * base) c = 0.f; }
-                    else if (c > base) c = 1.5f * c - base;
-                    c4[a] = c;
-                }
-                // lower median of four = second smallest
-                float lo01 = fminf(c4[0], c4[1]), hi01 = fmaxf(c4[0], c4[1]);
-                float lo23 = fminf(c4[2], c4[3]), hi23 = fmaxf(c4[2], c4[3]);
-                const float med = fminf(fmaxf(lo01, lo23), fminf(hi01, hi23));
-                total = w * med + s_match[lane];
-                if (use_f0) {
-                    const float lp = log2_rn(pf0[s_cand[cur][lane]] + 1e-5f), lq = log2_rn(sf0[i] + 1e-5f);
-                    total = total + fabsf(lp - lq);
-                }
-            }
-            // A NaN cost (NaN features: the reference has exited in fast_cosine_dist by then, here the flag is read only after
-            // everything is enqueued) must still rank: as +inf, ties by candidate number.  Unranked, all eight candidates took
-            // rank 0, the kept-row broadcast read slot 64, and the next frame gathered pool rows through garbage indices.
-            if (!(total == total)) total = __builtin_inff();
-            int rank = 0;
-#pragma unroll
-            for (int j = 0; j < NC; ++j) {          // v_readlane (an SGPR broadcast), not a ds_bpermute round trip per candidate
-                const float tj = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, total), j));
-                rank += (tj < total || (tj == total && j < lane)) ? 1 : 0;
-            }
-            if (lane < NC && rank < KC) {
-                const long id = s_cand[cur][lane];
-                s_prev_idx[rank] = id; s_prev_slot[rank] = lane;
-                idx_out[i * KC + rank] = id;
-            }
-            if (lane == 0) s_w = w;
-        }
-        __syncthreads();
-    }
-}
-
-// block s walks segment s: a sequence of its own (its frame 0 keeps its neighbours, nothing is read across a boundary)
-__global__ __launch_bounds__(256) void concat_reselect_kernel(
-    const long* __restrict__ idx_in, const float* __restrict__ q, const float* __restrict__ qn, const KnSegTable seg,
-    const float* __restrict__ pool, const float* __restrict__ pn, long np, int dim,
-    const float* __restrict__ sf0, const float* __restrict__ pf0, int use_f0, float concat_weight,
-    long* __restrict__ idx_out) {
-    const long o = seg.off[blockIdx.x];
-    concat_reselect_body(idx_in + o * KC, q + o * dim, qn + o, seg.off[blockIdx.x + 1] - o, pool, pn, np, dim,
-                         sf0 ? sf0 + o : sf0, pf0, use_f0, concat_weight, idx_out + o * KC);
-}
-
-// ---------------------------------------------------------------------------------------------
-// The same walk for K neighbours per frame, 1 <= K <= 8 (topk): concat_reselect_body with KC -> K.  Candidates per frame: the
-// frame's K neighbours, then previous selection + 1 (clamped at the pool's end) — 2K rows per ring slot, (4K + 2) * dim floats of
-// LDS.  Distance formula, thresholding, sticky weight, NaN rule and tie rule are the ones above; the median over the previous
-// selection is torch's lower median, the element of rank (K - 1) / 2 (for K = 4 the second smallest, as above).
-// ---------------------------------------------------------------------------------------------
 template <int K>
-__device__ __forceinline__ void concat_reselect_k_body(
+__device__ __forceinline__ void concat_reselect_body(
     const long* __restrict__ idx_in, const float* __restrict__ q, const float* __restrict__ qn, long nq,
     const float* __restrict__ pool, const float* __restrict__ pn, long np, int dim,
     const float* __restrict__ sf0, const float* __restrict__ pf0, int use_f0, float concat_weight,
@@ -330,14 +211,21 @@ __device__ __forceinline__ void concat_reselect_k_body(
                     else if (c > base) c = 1.5f * c - base;
                     ck[a] = c;
                 }
-                // lower median of K: the element of rank (K - 1) / 2 (a NaN among them leaves NaN, which ranks as +inf below)
-                float med = __builtin_nanf("");
+                // torch's lower median of K: the element of rank (K - 1) / 2
+                float med;
+                if constexpr (K == 4) {     // the second smallest of four, by a min / max network
+                    const float lo01 = fminf(ck[0], ck[1]), hi01 = fmaxf(ck[0], ck[1]);
+                    const float lo23 = fminf(ck[2], ck[3]), hi23 = fmaxf(ck[2], ck[3]);
+                    med = fminf(fmaxf(lo01, lo23), fminf(hi01, hi23));
+                } else {                    // by counting (a NaN among them leaves NaN, which ranks as +inf below)
+                    med = __builtin_nanf("");
 #pragma unroll
-                for (int a = 0; a < K; ++a) {
-                    int r = 0;
+                    for (int a = 0; a < K; ++a) {
+                        int r = 0;
 #pragma unroll
-                    for (int b = 0; b < K; ++b) r += (ck[b] < ck[a] || (ck[b] == ck[a] && b < a)) ? 1 : 0;
-                    if (r == (K - 1) / 2) med = ck[a];
+                        for (int b = 0; b < K; ++b) r += (ck[b] < ck[a] || (ck[b] == ck[a] && b < a)) ? 1 : 0;
+                        if (r == (K - 1) / 2) med = ck[a];
+                    }
                 }
                 total = w * med + s_match[lane];
                 if (use_f0) {
@@ -345,10 +233,13 @@ __device__ __forceinline__ void concat_reselect_k_body(
                     total = total + fabsf(lp - lq);
                 }
             }
-            if (!(total == total)) total = __builtin_inff();   // a NaN cost ranks as +inf, ties by candidate number (see above)
+            // A NaN cost (NaN features: the reference has exited in fast_cosine_dist by then, here the flag is read only after
+            // everything is enqueued) must still rank: as +inf, ties by candidate number.  Unranked, all 2K candidates took
+            // rank 0, the kept-row broadcast read slot 64, and the next frame gathered pool rows through garbage indices.
+            if (!(total == total)) total = __builtin_inff();
             int rank = 0;
 #pragma unroll
-            for (int j = 0; j < N2; ++j) {
+            for (int j = 0; j < N2; ++j) {          // v_readlane (an SGPR broadcast), not a ds_bpermute round trip per candidate
                 const float tj = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, total), j));
                 rank += (tj < total || (tj == total && j < lane)) ? 1 : 0;
             }
@@ -363,14 +254,15 @@ __device__ __forceinline__ void concat_reselect_k_body(
     }
 }
 
+// block s walks segment s: a sequence of its own (its frame 0 keeps its neighbours, nothing is read across a boundary)
 template <int K>
-__global__ __launch_bounds__(256) void concat_reselect_k_kernel(
+__global__ __launch_bounds__(256) void concat_reselect_kernel(
     const long* __restrict__ idx_in, const float* __restrict__ q, const float* __restrict__ qn, const KnSegTable seg,
     const float* __restrict__ pool, const float* __restrict__ pn, long np, int dim,
     const float* __restrict__ sf0, const float* __restrict__ pf0, int use_f0, float concat_weight,
     long* __restrict__ idx_out) {
     const long o = seg.off[blockIdx.x];
-    concat_reselect_k_body<K>(idx_in + o * K, q + o * dim, qn + o, seg.off[blockIdx.x + 1] - o, pool, pn, np, dim,
+    concat_reselect_body<K>(idx_in + o * K, q + o * dim, qn + o, seg.off[blockIdx.x + 1] - o, pool, pn, np, dim,
                               sf0 ? sf0 + o : sf0, pf0, use_f0, concat_weight, idx_out + o * K);
 }
 
@@ -755,30 +647,13 @@ static int shift_f0_launch(const KnSegTable& seg, const char* entry, const float
     return knnsvc_check_launch(entry);
 }
 
-// KNNSVC_MATCH_GENERIC_K=1 (read per call): k = 4 takes the generic-K kernels too (concat_reselect_k_kernel, smooth.hip's gram_k /
-// adam_k kernels) — holds them against the reference's own k = 4 fixtures, and an A/B aid.
+// KNNSVC_MATCH_GENERIC_K=1 (read per call): k = 4 skips its fast paths (the pipelined walk here, smooth.hip's adam_reg / adam_kernel
+// loops) and runs the K kernels' code for every length and width — holds that route against the reference's own k = 4 fixtures, and
+// an A/B aid.
 bool knnsvc_match_generic_k() { const char* e = getenv("KNNSVC_MATCH_GENERIC_K"); return e && e[0] == '1'; }
 
-// the generic-K walk: every check before the first HIP call
-static int concat_reselect_k_launch(const KnSegTable& seg, const char* entry, int k, const int64_t* idx_in, const float* q,
-                                    const float* q_norm, const float* pool, const float* p_norm, int64_t np, int32_t dim,
-                                    const float* shifted_f0, const float* pool_f0, int32_t use_f0, float concat_weight,
-                                    int64_t* idx_out, void* stream) {
-    const size_t lds = (size_t)(4 * k + 2) * dim * 4;
-    KN_REQUIRE(lds <= 150 * 1024, "%s: feature dim %d too large for LDS at k = %d (%zu bytes)", entry, (int)dim, k, lds);
-    KN_REQUIRE(((uintptr_t)q & 15) == 0 && ((uintptr_t)pool & 15) == 0, "%s: 16-byte alignment", entry);
-    int rc = KNNSVC_EINVAL;
-#define KN_WALK_K(KK)                                                                                                                \
-    case KK:                                                                                                                         \
-        if ((rc = kn_lds_optin<concat_reselect_k_kernel<KK>>((int)lds, entry))) return rc;                                           \
-        hipLaunchKernelGGL(concat_reselect_k_kernel<KK>, dim3((unsigned)seg.n), dim3(256), lds, (hipStream_t)stream, (const long*)idx_in, q, \
-                           q_norm, seg, pool, p_norm, (long)np, dim, shifted_f0, pool_f0, use_f0, concat_weight, (long*)idx_out);   \
-        break;
-    switch (k) { KN_WALK_K(1) KN_WALK_K(2) KN_WALK_K(3) KN_WALK_K(4) KN_WALK_K(5) KN_WALK_K(6) KN_WALK_K(7) KN_WALK_K(8) default: return rc; }
-#undef KN_WALK_K
-    return knnsvc_check_launch(entry);
-}
-
+// Every check before the first HIP call.  Route: the pipelined walk where it applies (k = 4, feature dim <= 1024, arrays a buffer
+// resource can cover), concat_reselect_kernel<k> otherwise.
 static int concat_reselect_launch(const KnSegTable& seg, const char* entry, int k, const int64_t* idx_in, const float* q, const float* q_norm,
                                   const float* pool, const float* p_norm, int64_t np, int32_t dim, const float* shifted_f0,
                                   const float* pool_f0, int32_t use_f0, float concat_weight, int64_t* idx_out, void* stream) {
@@ -786,15 +661,13 @@ static int concat_reselect_launch(const KnSegTable& seg, const char* entry, int 
     KN_REQUIRE(idx_in && q && q_norm && pool && p_norm && idx_out, "%s: null pointer", entry);
     KN_REQUIRE(np > 0 && dim > 0 && dim % 4 == 0, "%s: bad sizes", entry);
     KN_REQUIRE(!use_f0 || (shifted_f0 && pool_f0), "%s: f0 variant needs both f0 arrays", entry);
-    if (k != KC || knnsvc_match_generic_k())
-        return concat_reselect_k_launch(seg, entry, k, idx_in, q, q_norm, pool, p_norm, np, dim, shifted_f0, pool_f0, use_f0,
-                                        concat_weight, idx_out, stream);
+    const size_t lds = (size_t)(4 * k + 2) * dim * 4;      // of concat_reselect_kernel<k>; the pipelined walk (dim <= 1024) needs less than the bound
+    KN_REQUIRE(lds <= 150 * 1024, "%s: feature dim %d too large for LDS at k = %d (%zu bytes)", entry, (int)dim, k, lds);
     KN_REQUIRE(((uintptr_t)q & 15) == 0 && ((uintptr_t)pool & 15) == 0, "%s: 16-byte alignment", entry);
-    const size_t lds = (size_t)(2 * NC + 2) * dim * 4;
-    KN_REQUIRE(dim <= 1024 || lds <= 150 * 1024, "%s: feature dim too large for LDS", entry);
     const long nq = seg.off[seg.n];        // the route is chosen on the stacked arrays
     const dim3 grid((unsigned)seg.n);
-    if (dim <= 1024 && (unsigned long long)np * dim * 4 < 0xFFFFFFFFull && (unsigned long long)nq * dim * 4 < 0xFFFFFFFFull) {
+    if (k == KC && !knnsvc_match_generic_k() && dim <= 1024 && (unsigned long long)np * dim * 4 < 0xFFFFFFFFull &&
+        (unsigned long long)nq * dim * 4 < 0xFFFFFFFFull) {
         // KNNSVC_CONCAT_OWN_CU=1: ask for (nearly) the whole LDS of the CU so that no other kernel's workgroup is placed next to this
         // one.  Debugging aid from round 3's determinism hunt (see the Makefile's note on -fno-slp-vectorize: with compiler-made
         // packed-fp32 math this kernel's sums were perturbed by MFMA-issuing neighbours on its CU; isolation removed the symptom
@@ -812,9 +685,15 @@ static int concat_reselect_launch(const KnSegTable& seg, const char* entry, int 
                                seg, pool, p_norm, (long)np, dim, shifted_f0, pool_f0, concat_weight, (long*)idx_out);
         return knnsvc_check_launch(entry);
     }
-    if (const int rc = kn_lds_optin<concat_reselect_kernel>((int)lds, entry)) return rc;
-    hipLaunchKernelGGL(concat_reselect_kernel, grid, dim3(256), lds, (hipStream_t)stream, (const long*)idx_in, q, q_norm, seg, pool,
-                       p_norm, (long)np, dim, shifted_f0, pool_f0, use_f0, concat_weight, (long*)idx_out);
+    int rc = KNNSVC_EINVAL;
+#define KN_WALK_K(KK)                                                                                                                \
+    case KK:                                                                                                                         \
+        if ((rc = kn_lds_optin<concat_reselect_kernel<KK>>((int)lds, entry))) return rc;                                             \
+        hipLaunchKernelGGL(concat_reselect_kernel<KK>, grid, dim3(256), lds, (hipStream_t)stream, (const long*)idx_in, q, q_norm, seg, pool, \
+                           p_norm, (long)np, dim, shifted_f0, pool_f0, use_f0, concat_weight, (long*)idx_out);                       \
+        break;
+    switch (k) { KN_WALK_K(1) KN_WALK_K(2) KN_WALK_K(3) KN_WALK_K(4) KN_WALK_K(5) KN_WALK_K(6) KN_WALK_K(7) KN_WALK_K(8) default: return rc; }
+#undef KN_WALK_K
     return knnsvc_check_launch(entry);
 }
 

@@ -1,91 +1,118 @@
-// Concatenation-smoothness weight optimisation, fully on the device.
+// Concatenation-smoothness weight optimisation, fully on the device, for K neighbours per frame (1 <= K <= 8; the reference's 4
+// is one instantiation).
 // Reference: ddsp_prematch_dataset.py:574-680 (compute_wavlm_weight), :807-924
 // (compute_extended_weight), :426-428 (softmax weights), :449-461 (the two MSE costs).
 //
 // The reference runs autograd + torch.optim.Adam(amsgrad) with a host sync per iteration and
-// re-reads 3 x [N,4,D] gathered features every step.  The loss is a quadratic form in the
+// re-reads 3 x [N,K,D] gathered features every step.  The loss is a quadratic form in the
 // softmax weights, so this implementation
-//   1. reduces the features once to two 8x8 Gram matrices per adjacent frame pair
-//      (gram_kernel; vectors are centred on their mean first — the weights of each frame sum
+//   1. reduces the features once to two 2K x 2K Gram matrices per adjacent frame pair
+//      (gram_kernel<K>; vectors are centred on their mean first — the weights of each frame sum
 //      to one, so centring changes neither loss nor softmax gradient but removes cancellation);
 //   2. runs the whole Adam loop — loss, analytic gradient, amsgrad update, best-iterate
-//      tracking and the reference's three stopping rules — inside ONE persistent workgroup
-//      (adam_kernel), O(N*128) flops per iteration and no host round trips.
+//      tracking and the reference's three stopping rules — inside ONE persistent workgroup,
+//      O(N * (2K)^2) flops per iteration and no host round trips.
+// The loop for every K is adam_k_kernel<K>: state in the workspace as [K][rows] planes.  k = 4 has two fast paths beside it, which
+// KNNSVC_MATCH_GENERIC_K=1 skips: adam_reg_kernel<1|2|3> (up to 1536 rows, everything in registers) and adam_kernel (longer
+// sequences, rows of float4: 33 to 55 % faster than the planes at k = 4 and not bit-identical to them, profiles/adam_long_ab.txt).
+// The loop control and the per-element update are the same text in the three bodies: as shared helpers they changed the register
+// loops' instruction streams, so only the bias corrections are functions (adam_step_size, adam_rbc2).
 #include "common.h"
 
 namespace {
 
-constexpr int KW = 4;           // neighbours per frame
-constexpr int GE = 28;          // strict upper triangle of the symmetric 8x8 Gram matrix; the eight centred vectors sum
-                                // to zero, so every row of G sums to zero and the diagonal is implied:
-                                // (G c)_i = sum_{j != i} G_ij (c_j - c_i)
+constexpr int KW = 4;                       // neighbours per frame of the k = 4 fast paths
+constexpr int GE = KW * (2 * KW - 1);       // and their Gram entries per pair (28)
 
-__device__ __forceinline__ int tri(int i, int j) { return i < j ? i * 7 - i * (i - 1) / 2 + (j - i - 1) : j * 7 - j * (j - 1) / 2 + (i - j - 1); }   // i != j
-
-// block per frame pair t.  Both cost terms are quadratic forms in the SAME coefficient vector
-// c = [w[t+1,:], -w[t,:]] (term a over rows F[idx[t+1,k]-1], F[idx[t,k]]; term b over F[idx[t+1,k]], F[idx[t,k]+1]),
-// so only the sum of the two centred 8x8 Gram matrices is kept: its 28 off-diagonal entries per pair.
-// row_scale (optional) [nq][4]: candidate k of frame t and its +-1 neighbours are multiplied by row_scale[t][k]
-// (compute_weight_with_amp, ddsp_prematch_dataset.py:684-713); the centring argument is unchanged because the
-// coefficient vector still sums to zero.
-// The body of gram_kernel (all pairs of all segments): idx, row_scale and gram already at the sequence, nq its length, t the pair.
-__device__ __forceinline__ void gram_body(const long* __restrict__ idx, long nq, const float* __restrict__ pool,
-                                          long np, int dim, int ld, const float* __restrict__ row_scale,
-                                          float* __restrict__ gram, const long t) {
-    extern __shared__ float sm[];           // [8][dim] centred vectors of the current term
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    double acc[GE / 4];
-#pragma unroll
-    for (int q = 0; q < GE / 4; ++q) acc[q] = 0.0;
-    float rs[8];
-#pragma unroll
-    for (int r = 0; r < 8; ++r) rs[r] = row_scale ? (r < 4 ? row_scale[(t + 1) * KW + r] : row_scale[t * KW + (r - 4)]) : 1.f;
-    for (int term = 0; term < 2; ++term) {
-        __syncthreads();
-        for (int c = tid; c < dim; c += 256) {
-            float v[8], mean = 0.f;
-#pragma unroll
-            for (int r = 0; r < 8; ++r) {
-                long id;
-                if (r < 4) id = idx[(t + 1) * KW + r] + (term == 0 ? -1 : 0);
-                else id = idx[t * KW + (r - 4)] + (term == 0 ? 0 : 1);
-                id = id < 0 ? 0 : (id > np - 1 ? np - 1 : id);
-                v[r] = pool[id * (long)ld + c];
-                if (row_scale) v[r] *= rs[r];
-                mean += v[r];
-            }
-            mean *= 0.125f;
-#pragma unroll
-            for (int r = 0; r < 8; ++r) sm[r * dim + c] = v[r] - mean;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int q = 0; q < GE / 4; ++q) {
-            const int e = wave + 4 * q;
-            int i = 0, rem = e;                       // unpack e -> (i < j)
-            while (rem >= 7 - i) { rem -= 7 - i; ++i; }
-            const int j = i + 1 + rem;
-            double s = 0.0;
-            for (int c = lane; c < dim; c += 64) s += (double)sm[i * dim + c] * (double)sm[j * dim + c];
-            acc[q] += wave_sum_d(s);
-        }
-    }
-    if (lane == 0) {
-#pragma unroll
-        for (int q = 0; q < GE / 4; ++q) gram[((long)(wave + 4 * q)) * nq + t] = (float)acc[q];
-    }
+// Sums over a row's K values are pairwise trees: (a + b) + (c + d) at K = 4.
+template <int N>
+__device__ __forceinline__ float tree_sum(const float* p) {
+    if constexpr (N == 1) return p[0];
+    else return tree_sum<N / 2>(p) + tree_sum<N - N / 2>(p + N / 2);
+}
+// Entry (i, j), i != j, of the strict upper triangle of a symmetric R x R Gram matrix, R = 2K.  The R centred vectors sum to zero,
+// so every row of G sums to zero and the diagonal is implied: (G c)_i = sum_{j != i} G_ij (c_j - c_i)
+template <int R>
+__device__ __forceinline__ constexpr int tri_r(int i, int j) {
+    return i < j ? i * (R - 1) - i * (i - 1) / 2 + (j - i - 1) : j * (R - 1) - j * (j - 1) / 2 + (i - j - 1);
 }
 
-// Segments of knnsvc_smooth_weights[_seg]: row offsets, and where each segment's workspace (Gram [28][nq] | state: theta, m, v, vmax,
-// best, scratch, 6 x [nq] float4 | exchange [2][nq][4] when LDS is too small) starts, in units of 64 bytes from the aligned
-// workspace base.  By value, like KnSegTable.
+// Floats of workspace per segment: Gram [K(2K-1)][nq] | theta, m, v, vmax, best, scratch: 6 x [K][nq] | exchange [2][K][nq] (used
+// when LDS is too small).  adam_kernel (k = 4) keeps the same amounts as rows of float4.
+inline size_t ws_floats_k(long nq, int k) { return (size_t)(k * (2 * k - 1)) * nq + (size_t)6 * k * nq + (size_t)2 * k * nq; }
+// longest sequence whose two exchange planes fit 144 KB of LDS (4608 rows at K = 4, 2304 at K = 8)
+__host__ __device__ constexpr long adam_lds_rows(int k) { return 144 * 1024 / (2 * k * 4); }
+
+// Segments of knnsvc_smooth_weights[_seg]: row offsets, and where each segment's workspace starts, in units of 64 bytes from the
+// aligned workspace base.  By value, like KnSegTable.
 struct SmoothSegs { int n; long off[KNNSVC_MAX_SEGMENTS + 1]; unsigned ws64[KNNSVC_MAX_SEGMENTS]; };
 // the segments one launch works on: block b -> segment id[b]
 struct SegList { int n; unsigned char id[KNNSVC_MAX_SEGMENTS]; };
 
 __device__ __forceinline__ float* seg_ws(float* base, const SmoothSegs& sg, int s) { return base + (size_t)sg.ws64[s] * 16; }
 
+// block per frame pair t.  Both cost terms are quadratic forms in the SAME coefficient vector
+// c = [w[t+1,:], -w[t,:]] (term a over rows F[idx[t+1,k]-1], F[idx[t,k]]; term b over F[idx[t+1,k]], F[idx[t,k]+1]),
+// so only the sum of the two centred 2K x 2K Gram matrices is kept: its K(2K - 1) off-diagonal entries per pair.
+// row_scale (optional) [nq][K]: candidate k of frame t and its +-1 neighbours are multiplied by row_scale[t][k]
+// (compute_weight_with_amp, ddsp_prematch_dataset.py:684-713); the centring argument is unchanged because the
+// coefficient vector still sums to zero.
+// The body of gram_kernel (all pairs of all segments): idx, row_scale and gram already at the sequence, nq its length, t the pair.
+template <int K>
+__device__ __forceinline__ void gram_body(const long* __restrict__ idx, long nq, const float* __restrict__ pool,
+                                          long np, int dim, int ld, const float* __restrict__ row_scale,
+                                          float* __restrict__ gram, const long t) {
+    constexpr int R = 2 * K, GEK = K * (2 * K - 1), NQ = (GEK + 3) / 4;
+    constexpr bool whole = GEK % 4 == 0;    // the four waves share the entries evenly: no tail to guard (K = 4, 8)
+    extern __shared__ float sm[];           // [R][dim] centred vectors of the current term
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    double acc[NQ];
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) acc[q] = 0.0;
+    float rs[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) rs[r] = row_scale ? (r < K ? row_scale[(t + 1) * K + r] : row_scale[t * K + (r - K)]) : 1.f;
+    for (int term = 0; term < 2; ++term) {
+        __syncthreads();
+        for (int c = tid; c < dim; c += 256) {
+            float v[R], mean = 0.f;
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                long id;
+                if (r < K) id = idx[(t + 1) * K + r] + (term == 0 ? -1 : 0);
+                else id = idx[t * K + (r - K)] + (term == 0 ? 0 : 1);
+                id = id < 0 ? 0 : (id > np - 1 ? np - 1 : id);
+                v[r] = pool[id * (long)ld + c];
+                if (row_scale) v[r] *= rs[r];
+                mean += v[r];
+            }
+            mean = mean / (float)R;
+#pragma unroll
+            for (int r = 0; r < R; ++r) sm[r * dim + c] = v[r] - mean;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) {
+            const int e = wave + 4 * q;                 // wave-uniform
+            if (whole || e < GEK) {
+                int i = 0, rem = e;                       // unpack e -> (i < j)
+                while (rem >= R - 1 - i) { rem -= R - 1 - i; ++i; }
+                const int j = i + 1 + rem;
+                double s = 0.0;
+                for (int c = lane; c < dim; c += 64) s += (double)sm[i * dim + c] * (double)sm[j * dim + c];
+                acc[q] += wave_sum_d(s);
+            }
+        }
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int q = 0; q < NQ; ++q)
+            if (whole || wave + 4 * q < GEK) gram[((long)(wave + 4 * q)) * nq + t] = (float)acc[q];
+    }
+}
+
 // one launch over the adjacent pairs of all segments: segment s has len - 1 of them, pair numbers start at off[s] - s
+template <int K>
 __global__ __launch_bounds__(256) void gram_kernel(const long* __restrict__ idx, const SmoothSegs sg, const float* __restrict__ pool,
                                                       long np, int dim, int ld, const float* __restrict__ row_scale,
                                                       float* __restrict__ ws) {
@@ -93,11 +120,9 @@ __global__ __launch_bounds__(256) void gram_kernel(const long* __restrict__ idx,
     int s = 0;
     for (int j = 1; j < sg.n; ++j) if (sg.off[j] - j <= b) s = j;       // the last segment whose first pair is <= b (uniform)
     const long o = sg.off[s];
-    gram_body(idx + o * KW, sg.off[s + 1] - o, pool, np, dim, ld, row_scale ? row_scale + o * KW : row_scale, seg_ws(ws, sg, s),
-              b - (o - s));
+    gram_body<K>(idx + o * K, sg.off[s + 1] - o, pool, np, dim, ld, row_scale ? row_scale + o * K : row_scale, seg_ws(ws, sg, s),
+                 b - (o - s));
 }
-
-struct LoopState { double min_loss, conv_min; int since; };
 
 // The two per-element pieces of an iteration that were IEEE divides, square roots and expf: 250 of the 410 VALU instructions a
 // frame costs per iteration (one CU runs the whole loop).  Inside the loop they run on the hardware's 1-ulp v_exp_f32 / v_rcp_f32 /
@@ -121,7 +146,14 @@ __device__ __forceinline__ float loop_step(float th, float m, float vmax, float 
     return th + step_size * (m * __builtin_amdgcn_rcpf(denom));
 }
 
+// The bias corrections of iteration t (pb = beta^t, in double): the step size -lr / (1 - b1^t) with lr = 0.1, and 1 / sqrt(1 - b2^t).
+// These two are all of the loop the three bodies below share as functions: the loop control and the per-element update are written
+// out in each, because as helpers (by reference, by value or as a struct) they change the register loops' instruction streams.
+__device__ __forceinline__ float adam_step_size(double pb1) { return (float)(-(0.1 / (1.0 - pb1))); }
+__device__ __forceinline__ float adam_rbc2(double pb2) { const float bc2_sqrt = (float)sqrt(1.0 - pb2); return 1.0f / bc2_sqrt; }
 
+// The long loop of k = 4 (more than 1536 rows): state in the workspace as rows of float4, softmax weights and gradients exchanged
+// through LDS while they fit (adam_lds_rows(4) rows) and through the workspace beyond.
 __device__ __forceinline__ void adam_body(long nq, int dim, float scale, int max_iter,
                                           const float* __restrict__ gram, float* __restrict__ state,
                                           float* __restrict__ xch_global, int use_lds,
@@ -167,7 +199,7 @@ __device__ __forceinline__ void adam_body(long nq, int dim, float scale, int max
                 for (int i = 0; i < 8; ++i) {
                     float s = 0.f;
 #pragma unroll
-                    for (int j = 0; j < 8; ++j) if (j != i) s += g[tri(i, j)] * (c[j] - c[i]);
+                    for (int j = 0; j < 8; ++j) if (j != i) s += g[tri_r<8>(i, j)] * (c[j] - c[i]);
                     y[i] += s;
                 }
             }
@@ -198,9 +230,7 @@ __device__ __forceinline__ void adam_body(long nq, int dim, float scale, int max
         if (!forced && since >= 1000) break;
         // ---- phase 4: gradient through softmax + Adam(amsgrad) ----------------------------------
         pb1 *= 0.9; pb2 *= 0.999;
-        const float step_size = (float)(-(0.1 / (1.0 - pb1)));
-        const float bc2_sqrt = (float)sqrt(1.0 - pb2);
-        const float rbc2 = 1.0f / bc2_sqrt;
+        const float step_size = adam_step_size(pb1), rbc2 = adam_rbc2(pb2);
         for (long t = tid; t < nq; t += 1024) {
             const f32x4 w = *(const f32x4*)&xw[t * KW];
             f32x4 g = zero;
@@ -233,9 +263,6 @@ __device__ __forceinline__ void adam_body(long nq, int dim, float scale, int max
     if (tid == 0 && out_iters) out_iters[0] = it;
 }
 
-inline size_t ws_floats(long nq) { return (size_t)GE * nq + (size_t)6 * 4 * nq + (size_t)2 * 4 * nq; }
-constexpr long ADAM_LDS_ROWS = 144 * 1024 / (2 * KW * 4);     // longest sequence whose weight / gradient exchange fits LDS (adam_kernel)
-
 // block b runs the loop of segment list.id[b] in that segment's own workspace; LDS or the global exchange buffer as the segment
 // would get alone
 __global__ __launch_bounds__(1024) void adam_kernel(const SmoothSegs sg, const SegList list, int dim, float scale, int max_iter,
@@ -244,7 +271,7 @@ __global__ __launch_bounds__(1024) void adam_kernel(const SmoothSegs sg, const S
     const long o = sg.off[s], nq = sg.off[s + 1] - o;
     float* gram = seg_ws(ws, sg, s);
     float* state = gram + (size_t)GE * nq;
-    adam_body(nq, dim, scale, max_iter, gram, state, state + (size_t)6 * 4 * nq, nq <= ADAM_LDS_ROWS, out_w + o * KW,
+    adam_body(nq, dim, scale, max_iter, gram, state, state + (size_t)6 * 4 * nq, nq <= adam_lds_rows(KW), out_w + o * KW,
               out_iters ? out_iters + s : out_iters);
 }
 
@@ -301,12 +328,12 @@ __device__ __forceinline__ void adam_reg_body(long nq, int dim, float scale, int
 #pragma unroll
                 for (int i = 0; i < 8; ++i)
 #pragma unroll
-                    for (int j = i + 1; j < 8; ++j) dd[tri(i, j)] = c[j] - c[i];
+                    for (int j = i + 1; j < 8; ++j) dd[tri_r<8>(i, j)] = c[j] - c[i];
 #pragma unroll
                 for (int i = 0; i < 8; ++i) {
                     float s = 0.f;
 #pragma unroll
-                    for (int j = 0; j < 8; ++j) if (j != i) s = fmaf(g[f][tri(i, j)], j > i ? dd[tri(i, j)] : -dd[tri(i, j)], s);
+                    for (int j = 0; j < 8; ++j) if (j != i) s = fmaf(g[f][tri_r<8>(i, j)], j > i ? dd[tri_r<8>(i, j)] : -dd[tri_r<8>(i, j)], s);
                     y[i] = s;
                 }
                 float qf = 0.f;
@@ -337,9 +364,7 @@ __device__ __forceinline__ void adam_reg_body(long nq, int dim, float scale, int
         if (improved) { min_loss = (double)loss; since = 0; } else ++since;
         if (!forced && since >= 1000) break;
         pb1 *= 0.9; pb2 *= 0.999;
-        const float step_size = (float)(-(0.1 / (1.0 - pb1)));
-        const float bc2_sqrt = (float)sqrt(1.0 - pb2);
-        const float rbc2 = 1.0f / bc2_sqrt;
+        const float step_size = adam_step_size(pb1), rbc2 = adam_rbc2(pb2);
 #pragma unroll
         for (int f = 0; f < FPT; ++f) {
             const long t = tid + 512L * f;
@@ -384,95 +409,8 @@ __global__ __launch_bounds__(512) void adam_reg_kernel(const SmoothSegs sg, cons
     adam_reg_body<FPT>(sg.off[s + 1] - o, dim, scale, max_iter, seg_ws(ws, sg, s), out_w + o * KW, out_iters ? out_iters + s : out_iters);
 }
 
-// segments of one row (no adjacent pair): softmax(0) and zero iterations
-__global__ void fill_quarter_kernel(const SmoothSegs sg, const SegList list, float* __restrict__ out_w, int* __restrict__ out_iters) {
-    const int s = list.id[blockIdx.x];
-    if (threadIdx.x < KW) out_w[sg.off[s] * KW + threadIdx.x] = 0.25f;
-    if (threadIdx.x == 0 && out_iters) out_iters[s] = 0;
-}
-
-
-// ---------------------------------------------------------------------------------------------
-// The same optimisation for K neighbours per frame, 1 <= K <= 8 (topk).  gram_k_body is gram_body with 2K vectors per pair (mean
-// over 2K, the K(2K - 1) strict-upper-triangle entries of the centred 2K x 2K Gram); adam_k_body is adam_body with its state in
-// the workspace as [K][rows] planes (thread t touches element t of each plane: coalesced, and conflict-free where the exchange
-// planes sit in LDS).  Sums over a row's K values are pairwise trees, which at K = 4 is the (a + b) + (c + d) of the code above.
-// Workspace per segment: Gram [K(2K-1)][nq] | theta, m, v, vmax, best, scratch: 6 x [K][nq] | exchange [2][K][nq].
-// ---------------------------------------------------------------------------------------------
-template <int N>
-__device__ __forceinline__ float tree_sum(const float* p) {
-    if constexpr (N == 1) return p[0];
-    else return tree_sum<N / 2>(p) + tree_sum<N - N / 2>(p + N / 2);
-}
-template <int R>
-__device__ __forceinline__ constexpr int tri_r(int i, int j) {      // i != j, R x R
-    return i < j ? i * (R - 1) - i * (i - 1) / 2 + (j - i - 1) : j * (R - 1) - j * (j - 1) / 2 + (i - j - 1);
-}
-
-template <int K>
-__device__ __forceinline__ void gram_k_body(const long* __restrict__ idx, long nq, const float* __restrict__ pool,
-                                            long np, int dim, int ld, const float* __restrict__ row_scale,
-                                            float* __restrict__ gram, const long t) {
-    constexpr int R = 2 * K, GEK = K * (2 * K - 1), NQ = (GEK + 3) / 4;
-    extern __shared__ float sm[];           // [R][dim] centred vectors of the current term
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    double acc[NQ];
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) acc[q] = 0.0;
-    float rs[R];
-#pragma unroll
-    for (int r = 0; r < R; ++r) rs[r] = row_scale ? (r < K ? row_scale[(t + 1) * K + r] : row_scale[t * K + (r - K)]) : 1.f;
-    for (int term = 0; term < 2; ++term) {
-        __syncthreads();
-        for (int c = tid; c < dim; c += 256) {
-            float v[R], mean = 0.f;
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-                long id;
-                if (r < K) id = idx[(t + 1) * K + r] + (term == 0 ? -1 : 0);
-                else id = idx[t * K + (r - K)] + (term == 0 ? 0 : 1);
-                id = id < 0 ? 0 : (id > np - 1 ? np - 1 : id);
-                v[r] = pool[id * (long)ld + c];
-                if (row_scale) v[r] *= rs[r];
-                mean += v[r];
-            }
-            mean = mean / (float)R;
-#pragma unroll
-            for (int r = 0; r < R; ++r) sm[r * dim + c] = v[r] - mean;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) {
-            const int e = wave + 4 * q;                 // wave-uniform
-            if (e < GEK) {
-                int i = 0, rem = e;                       // unpack e -> (i < j)
-                while (rem >= R - 1 - i) { rem -= R - 1 - i; ++i; }
-                const int j = i + 1 + rem;
-                double s = 0.0;
-                for (int c = lane; c < dim; c += 64) s += (double)sm[i * dim + c] * (double)sm[j * dim + c];
-                acc[q] += wave_sum_d(s);
-            }
-        }
-    }
-    if (lane == 0) {
-#pragma unroll
-        for (int q = 0; q < NQ; ++q)
-            if (wave + 4 * q < GEK) gram[((long)(wave + 4 * q)) * nq + t] = (float)acc[q];
-    }
-}
-
-template <int K>
-__global__ __launch_bounds__(256) void gram_k_kernel(const long* __restrict__ idx, const SmoothSegs sg, const float* __restrict__ pool,
-                                                        long np, int dim, int ld, const float* __restrict__ row_scale,
-                                                        float* __restrict__ ws) {
-    const long b = blockIdx.x;
-    int s = 0;
-    for (int j = 1; j < sg.n; ++j) if (sg.off[j] - j <= b) s = j;       // the last segment whose first pair is <= b (uniform)
-    const long o = sg.off[s];
-    gram_k_body<K>(idx + o * K, sg.off[s + 1] - o, pool, np, dim, ld, row_scale ? row_scale + o * K : row_scale, seg_ws(ws, sg, s),
-                   b - (o - s));
-}
-
+// The loop for K neighbours per frame: adam_body with its state in the workspace as [K][rows] planes (thread t touches element t of
+// each plane: coalesced, and conflict-free where the exchange planes sit in LDS).  K = 1 runs the loop like any other K.
 template <int K>
 __device__ __forceinline__ void adam_k_body(long nq, int dim, float scale, int max_iter,
                                             const float* __restrict__ gram, float* __restrict__ state,
@@ -552,9 +490,7 @@ __device__ __forceinline__ void adam_k_body(long nq, int dim, float scale, int m
         if (!forced && since >= 1000) break;
         // ---- phase 4: gradient through softmax + Adam(amsgrad) ----------------------------------
         pb1 *= 0.9; pb2 *= 0.999;
-        const float step_size = (float)(-(0.1 / (1.0 - pb1)));
-        const float bc2_sqrt = (float)sqrt(1.0 - pb2);
-        const float rbc2 = 1.0f / bc2_sqrt;
+        const float step_size = adam_step_size(pb1), rbc2 = adam_rbc2(pb2);
         for (long t = tid; t < nq; t += 1024) {
             float w[K], g[K], wg[K];
 #pragma unroll
@@ -596,10 +532,6 @@ __device__ __forceinline__ void adam_k_body(long nq, int dim, float scale, int m
     if (tid == 0 && out_iters) out_iters[0] = it;
 }
 
-inline size_t ws_floats_k(long nq, int k) { return (size_t)(k * (2 * k - 1)) * nq + (size_t)6 * k * nq + (size_t)2 * k * nq; }
-// longest sequence whose two exchange planes fit 144 KB of LDS (adam_k_kernel; 2304 rows at K = 8)
-__host__ __device__ constexpr long adam_k_lds_rows(int k) { return 144 * 1024 / (2 * k * 4); }
-
 template <int K>
 __global__ __launch_bounds__(1024) void adam_k_kernel(const SmoothSegs sg, const SegList list, int dim, float scale, int max_iter,
                                                          float* __restrict__ ws, float* __restrict__ out_w, int* __restrict__ out_iters) {
@@ -607,7 +539,7 @@ __global__ __launch_bounds__(1024) void adam_k_kernel(const SmoothSegs sg, const
     const long o = sg.off[s], nq = sg.off[s + 1] - o;
     float* gram = seg_ws(ws, sg, s);
     float* state = gram + (size_t)(K * (2 * K - 1)) * nq;
-    adam_k_body<K>(nq, dim, scale, max_iter, gram, state, state + (size_t)6 * K * nq, nq <= adam_k_lds_rows(K), out_w + o * K,
+    adam_k_body<K>(nq, dim, scale, max_iter, gram, state, state + (size_t)6 * K * nq, nq <= adam_lds_rows(K), out_w + o * K,
                    out_iters ? out_iters + s : out_iters);
 }
 
@@ -623,7 +555,7 @@ inline size_t seg_ws_bytes(long nq, int k = KW) { return (ws_floats_k(nq, k) * 4
 
 }  // namespace
 
-extern "C" size_t knnsvc_smooth_workspace_bytes(int64_t nq) { return nq > 0 ? ws_floats(nq) * 4 + 64 : 0; }
+extern "C" size_t knnsvc_smooth_workspace_bytes(int64_t nq) { return nq > 0 ? ws_floats_k(nq, KW) * 4 + 64 : 0; }
 
 // row offsets and workspace placement of a validated table; *bytes: the workspace of the segmented call
 static int smooth_segs(const KnSegTable& t, const char* entry, SmoothSegs* sg, size_t* bytes, int k = KW) {
@@ -640,108 +572,76 @@ static int smooth_segs(const KnSegTable& t, const char* entry, SmoothSegs* sg, s
 }
 
 // The argument checks, the class-by-length choice and the launches, once.  `need`: the workspace size the entry point documents
-// (knnsvc_smooth_workspace_bytes for the single call, knnsvc_smooth_seg_workspace_bytes for the segmented one); `entry`: its name,
-// for the messages.
-// The generic-K route (k != 4, or KNNSVC_MATCH_GENERIC_K=1): one-row segments filled with 1 / k, one Gram launch, one loop launch.
-// Every check runs before the first HIP call.
-static int smooth_weights_k_launch(const SmoothSegs& sg, size_t need, const char* entry, int k, const int64_t* idx, const float* pool,
-                                   int64_t np, int32_t dim, int32_t ld, float scale, const float* row_scale, int32_t max_iter,
-                                   float* out_w, int32_t* out_iters, void* workspace, size_t workspace_bytes, void* stream) {
+// (knnsvc_smooth_workspace_bytes for the single call, knnsvc_smooth_seg_workspace_bytes[_k] for the segmented ones); `entry`: its
+// name, for the messages.  Every check runs before the first HIP call.
+// One-row segments are filled with 1 / k, one Gram launch covers the pairs of all segments, then one loop launch per loop variant
+// present, each over the list of segments that would get that variant alone.  The k = 4 fast paths (`fast`: k = 4 without
+// KNNSVC_MATCH_GENERIC_K=1) are the register loops up to 1536 rows and adam_kernel beyond; everything else runs adam_k_kernel<k>.
+static int smooth_weights_launch(const SmoothSegs& sg, size_t need, const char* entry, int k, const int64_t* idx, const float* pool,
+                                 int64_t np, int32_t dim, int32_t ld, float scale, const float* row_scale, int32_t max_iter,
+                                 float* out_w, int32_t* out_iters, void* workspace, size_t workspace_bytes, void* stream) {
+    KN_REQUIRE(k >= 1 && k <= 8, "%s: k = %d outside 1..8", entry, k);
     KN_REQUIRE(idx && pool && out_w && workspace, "%s: null pointer", entry);
     KN_REQUIRE(np > 0 && dim > 0 && ld >= dim && max_iter != 0, "%s: bad sizes", entry);
-    KN_REQUIRE(((uintptr_t)out_w & 3) == 0, "%s: out_w must be 4-byte aligned", entry);      // written float by float
+    const bool fast = k == KW && !knnsvc_match_generic_k();
+    // the fast paths write rows of float4, adam_k_kernel float by float
+    KN_REQUIRE(((uintptr_t)out_w & (fast ? 15 : 3)) == 0, "%s: out_w must be %d-byte aligned", entry, fast ? 16 : 4);
     const size_t gl = (size_t)2 * k * dim * 4;
     KN_REQUIRE(gl <= 150 * 1024, "%s: feature dim %d too large for LDS at k = %d", entry, (int)dim, k);
     if (workspace_bytes < need) return knnsvc_fail(KNNSVC_EWORKSPACE, "%s: workspace %zu < %zu bytes", entry, workspace_bytes, need);
     hipStream_t st = (hipStream_t)stream;
     float* base = (float*)(((uintptr_t)workspace + 63) & ~(uintptr_t)63);
-    SegList one, loop;
-    one.n = loop.n = 0;
-    long lds_rows = 0;
-    for (int s = 0; s < sg.n; ++s) {
-        const long nq = sg.off[s + 1] - sg.off[s];
-        if (nq < 2) { one.id[one.n++] = (unsigned char)s; continue; }
-        loop.id[loop.n++] = (unsigned char)s;
-        if (nq <= adam_k_lds_rows(k) && nq > lds_rows) lds_rows = nq;
-    }
-    int rc;
-    if (one.n) {
-        hipLaunchKernelGGL(fill_uniform_kernel, dim3((unsigned)one.n), dim3(64), 0, st, sg, one, k, out_w, out_iters);
-        if ((rc = knnsvc_check_launch(entry))) return rc;
-    }
-    const long pairs = sg.off[sg.n] - sg.n;
-    if (pairs == 0) return KNNSVC_OK;
-    const size_t al = (size_t)lds_rows * 2 * k * 4;              // of the segments that exchange through LDS; the others take none
-#define KN_SMOOTH_K(KK)                                                                                                              \
-    case KK:                                                                                                                         \
-        if ((rc = kn_lds_optin<gram_k_kernel<KK>>((int)gl, entry))) return rc;                                                       \
-        hipLaunchKernelGGL(gram_k_kernel<KK>, dim3((unsigned)pairs), dim3(256), gl, st, (const long*)idx, sg, pool, (long)np, dim, ld, \
-                           row_scale, base);                                                                                         \
-        if ((rc = knnsvc_check_launch(entry))) return rc;                                                                            \
-        if ((rc = kn_lds_optin<adam_k_kernel<KK>>((int)al, entry))) return rc;                                                       \
-        hipLaunchKernelGGL(adam_k_kernel<KK>, dim3((unsigned)loop.n), dim3(1024), al, st, sg, loop, dim, scale, max_iter, base, out_w, \
-                           out_iters);                                                                                               \
-        break;
-    switch (k) {
-        KN_SMOOTH_K(1) KN_SMOOTH_K(2) KN_SMOOTH_K(3) KN_SMOOTH_K(4) KN_SMOOTH_K(5) KN_SMOOTH_K(6) KN_SMOOTH_K(7) KN_SMOOTH_K(8)
-        default: return knnsvc_fail(KNNSVC_EINVAL, "%s: k = %d outside 1..8", entry, k);
-    }
-#undef KN_SMOOTH_K
-    return knnsvc_check_launch(entry);
-}
-
-static int smooth_weights_launch(const SmoothSegs& sg, size_t need, const char* entry, int k, const int64_t* idx, const float* pool,
-                                 int64_t np, int32_t dim, int32_t ld, float scale, const float* row_scale, int32_t max_iter,
-                                 float* out_w, int32_t* out_iters, void* workspace, size_t workspace_bytes, void* stream) {
-    if (k != KW || knnsvc_match_generic_k())
-        return smooth_weights_k_launch(sg, need, entry, k, idx, pool, np, dim, ld, scale, row_scale, max_iter, out_w, out_iters, workspace,
-                                       workspace_bytes, stream);
-    KN_REQUIRE(idx && pool && out_w && workspace, "%s: null pointer", entry);
-    KN_REQUIRE(np > 0 && dim > 0 && ld >= dim && max_iter != 0, "%s: bad sizes", entry);
-    KN_REQUIRE(((uintptr_t)out_w & 15) == 0, "%s: out_w must be 16-byte aligned", entry);
-    const size_t gl = (size_t)8 * dim * 4;
-    KN_REQUIRE(gl <= 150 * 1024, "%s: feature dim too large for LDS", entry);
-    if (workspace_bytes < need) return knnsvc_fail(KNNSVC_EWORKSPACE, "%s: workspace %zu < %zu bytes", entry, workspace_bytes, need);
-    hipStream_t st = (hipStream_t)stream;
-    float* base = (float*)(((uintptr_t)workspace + 63) & ~(uintptr_t)63);
     // the loop variant each segment would get alone: 0 one row (no adjacent pair: the reference's loss is NaN and never improves ->
-    // softmax(0), no loop), 1..3 adam_reg_kernel<1|2|3>, 4 adam_kernel
+    // softmax(0), no loop), 1..3 adam_reg_kernel<1|2|3> (fast only), 4 the long loop
     SegList cls[5];
     long longest[5] = {0, 0, 0, 0, 0}, lds_rows = 0;
     for (int c = 0; c < 5; ++c) cls[c].n = 0;
     for (int s = 0; s < sg.n; ++s) {
         const long nq = sg.off[s + 1] - sg.off[s];
-        const int c = nq < 2 ? 0 : (nq <= 512 ? 1 : (nq <= 1024 ? 2 : (nq <= 1536 ? 3 : 4)));
+        const int c = nq < 2 ? 0 : (!fast || nq > 1536 ? 4 : (nq <= 512 ? 1 : (nq <= 1024 ? 2 : 3)));
         cls[c].id[cls[c].n++] = (unsigned char)s;
         if (nq > longest[c]) longest[c] = nq;
-        if (c == 4 && nq <= ADAM_LDS_ROWS && nq > lds_rows) lds_rows = nq;
+        if (c == 4 && nq <= adam_lds_rows(k) && nq > lds_rows) lds_rows = nq;
     }
     int rc;
     if (cls[0].n) {
-        hipLaunchKernelGGL(fill_quarter_kernel, dim3((unsigned)cls[0].n), dim3(64), 0, st, sg, cls[0], out_w, out_iters);
+        hipLaunchKernelGGL(fill_uniform_kernel, dim3((unsigned)cls[0].n), dim3(64), 0, st, sg, cls[0], k, out_w, out_iters);
         if ((rc = knnsvc_check_launch(entry))) return rc;
     }
     const long pairs = sg.off[sg.n] - sg.n;
     if (pairs == 0) return KNNSVC_OK;
-    if ((rc = kn_lds_optin<gram_kernel>((int)gl, entry))) return rc;
-    hipLaunchKernelGGL(gram_kernel, dim3((unsigned)pairs), dim3(256), gl, st, (const long*)idx, sg, pool, (long)np, dim, ld, row_scale, base);
+#define KN_GRAM_K(KK)                                                                                                                \
+    case KK:                                                                                                                         \
+        if ((rc = kn_lds_optin<gram_kernel<KK>>((int)gl, entry))) return rc;                                                         \
+        hipLaunchKernelGGL(gram_kernel<KK>, dim3((unsigned)pairs), dim3(256), gl, st, (const long*)idx, sg, pool, (long)np, dim, ld, \
+                           row_scale, base);                                                                                         \
+        break;
+    switch (k) { KN_GRAM_K(1) KN_GRAM_K(2) KN_GRAM_K(3) KN_GRAM_K(4) KN_GRAM_K(5) KN_GRAM_K(6) KN_GRAM_K(7) KN_GRAM_K(8) }
+#undef KN_GRAM_K
     if ((rc = knnsvc_check_launch(entry))) return rc;
 #define KN_ADAM_SEG(F)                                                                                                               \
     if (cls[F].n) {                                                                                                                  \
-        if ((rc = kn_lds_optin<adam_reg_kernel<F>>(65536, entry))) return rc;                                                    \
+        if ((rc = kn_lds_optin<adam_reg_kernel<F>>(65536, entry))) return rc;                                                        \
         hipLaunchKernelGGL(adam_reg_kernel<F>, dim3((unsigned)cls[F].n), dim3(512), (size_t)longest[F] * 2 * KW * 4, st, sg, cls[F], dim, scale, \
                            max_iter, base, out_w, out_iters);                                                                        \
         if ((rc = knnsvc_check_launch(entry))) return rc;                                                                            \
     }
     KN_ADAM_SEG(1) KN_ADAM_SEG(2) KN_ADAM_SEG(3)
 #undef KN_ADAM_SEG
-    if (cls[4].n) {
-        const size_t al = (size_t)lds_rows * 2 * KW * 4;         // of the segments that exchange through LDS; the others take none
-        if ((rc = kn_lds_optin<adam_kernel>((int)al, entry))) return rc;
-        hipLaunchKernelGGL(adam_kernel, dim3((unsigned)cls[4].n), dim3(1024), al, st, sg, cls[4], dim, scale, max_iter, base, out_w, out_iters);
-        if ((rc = knnsvc_check_launch(entry))) return rc;
+    if (!cls[4].n) return KNNSVC_OK;
+    const size_t al = (size_t)lds_rows * 2 * k * 4;              // of the segments that exchange through LDS; the others take none
+#define KN_ADAM_LONG(KERNEL)                                                                                                         \
+    if ((rc = kn_lds_optin<KERNEL>((int)al, entry))) return rc;                                                                      \
+    hipLaunchKernelGGL(KERNEL, dim3((unsigned)cls[4].n), dim3(1024), al, st, sg, cls[4], dim, scale, max_iter, base, out_w, out_iters);
+#define KN_ADAM_K(KK) case KK: KN_ADAM_LONG(adam_k_kernel<KK>) break;
+    if (fast) {
+        KN_ADAM_LONG(adam_kernel)
+    } else {
+        switch (k) { KN_ADAM_K(1) KN_ADAM_K(2) KN_ADAM_K(3) KN_ADAM_K(4) KN_ADAM_K(5) KN_ADAM_K(6) KN_ADAM_K(7) KN_ADAM_K(8) }
     }
-    return KNNSVC_OK;
+#undef KN_ADAM_K
+#undef KN_ADAM_LONG
+    return knnsvc_check_launch(entry);
 }
 
 extern "C" int knnsvc_smooth_weights(const int64_t* idx, int64_t nq, const float* pool, int64_t np, int32_t dim,
@@ -751,7 +651,7 @@ extern "C" int knnsvc_smooth_weights(const int64_t* idx, int64_t nq, const float
     int rc;
     if ((rc = kn_seg_one(nq, "smooth_weights", &t)) || (rc = smooth_segs(t, "smooth_weights", &sg, &seg_bytes))) return rc;
     // Its own size, not seg_bytes (which rounds up to 64): the one segment starts at the 64-byte-aligned base, at most 63 bytes
-    // into the workspace, and ends ws_floats(nq) * 4 bytes later.
+    // into the workspace, and ends ws_floats_k(nq, 4) * 4 bytes later.
     return smooth_weights_launch(sg, knnsvc_smooth_workspace_bytes(nq), "smooth_weights", KW, idx, pool, np, dim, ld, scale, row_scale,
                                  max_iter, out_w, out_iters, workspace, workspace_bytes, stream);
 }

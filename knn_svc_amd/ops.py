@@ -787,7 +787,8 @@ def f0_rerank(nn_idx, shifted_f0, pool_f0):
 
 
 def _topk_of(name, idx):
-    """k of an [rows, k] neighbour table as the match-stage kernels take it (1..8; 4 runs the specialised kernels)."""
+    """k of an [rows, k] neighbour table as the match-stage kernels take it (1..8: one K-templated kernel per stage; 4 also has
+    fast paths, which KNNSVC_MATCH_GENERIC_K=1 skips)."""
     if idx.dim() != 2 or not 1 <= idx.shape[1] <= 8:
         raise KnnSvcError(f"{name}: idx must be [rows, k] with 1 <= k <= 8, got {tuple(idx.shape)}")
     return int(idx.shape[1])

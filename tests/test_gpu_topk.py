@@ -10,9 +10,12 @@ Cases (the smallest shapes that reach every boundary; the bars and their CPU-che
   walk            k in {1, 2, 3, 5, 6, 7, 8}, both variants, (1, 40, 64), (2, 40, 256), (3, 9, 768: the clamp, repeated candidates),
                   (64, 48, 1024: the LDS limit at k = 8), (130, 4000, 512): selected sets equal on every frame, on the long pool
                   also the order; one segmented call over [1, 2, 3, 64] at k = 8, bit-identical to the single calls.
+  walk-k4         k = 4 past dim 1024, where the default k leaves the pipelined walk for the K kernel: (3, 9, 1280) and
+                  (130, 4000, 1280), both variants, judged like the other k.
   walk-generic4   KNNSVC_MATCH_GENERIC_K=1 on fixture g4_select, exact rows.
   smooth          k in {1, 2, 3, 5, 8} on two pools (scale 1000 / 0.1) within 4e-4 of the oracle and the same iteration count;
                   row_scale at k = 5.
+  smooth-k4       k = 4 at 1537 rows (the first length past the register loops) on the dim-64 pool, same bar.
   smooth-seg      max_iter 300, segments [1, 2, 2304, 2305] at k = 8 and [1, 2, 37, 6144, 6145] at k = 3 (LDS | global
                   exchange), bit-identical to the single calls.
   smooth-generic4 the knob on fixture g5_smooth, 4e-4 and the fixture's iteration counts.
@@ -66,6 +69,10 @@ def test_walk_for_every_k_equals_the_oracle(report):
     _check(report, "walk/", 7 * 5 * 2 + 1)
 
 
+def test_generic_walk_at_k4_equals_the_oracle(report):
+    _check(report, "walk-k4/", 2 * 2)
+
+
 def test_walk_segments_equal_single_sequences_at_k8(report):
     _check(report, "walk-seg/", 2)
 
@@ -76,6 +83,10 @@ def test_generic_walk_at_k4_matches_the_reference_fixture(report):
 
 def test_smooth_weights_for_every_k_equal_the_oracle(report):
     _check(report, "smooth/", 2 * 5 + 1 + 1)
+
+
+def test_long_smooth_weights_at_k4_equal_the_oracle(report):
+    _check(report, "smooth-k4/", 1 + 1)
 
 
 def test_smooth_weights_segments_equal_single_sequences(report):

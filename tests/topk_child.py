@@ -80,32 +80,41 @@ def compare_walk(got, ref, idx_in, npool, ordered):
 # ------------------------------------------------------------------ 1. walk
 # (nq, npool, dim) -> seed offset s by k (seed = 1000 k + s), found on the CPU: the first s <= 2 whose oracle margin passes
 WALK_SHAPES = [(1, 40, 64), (2, 40, 256), (3, 9, 768), (64, 48, 1024), (130, 4000, 512)]
-WALK_SEED = {(64, 48, 1024): {7: 1}, (130, 4000, 512): {5: 1}}
+# k = 4 leaves the pipelined walk for the K kernel only past dim 1024 (or past 4 GiB): the one route of the default k that nothing
+# else holds against the oracle
+WALK_SHAPES_K4 = [(3, 9, 1280), (130, 4000, 1280)]
+WALK_SEED = {(64, 48, 1024): {7: 1}, (130, 4000, 512): {5: 1}, (130, 4000, 1280): {4: 1}}
+
+
+def walk_case(k, shape, prefix):
+    nq, npool, dim = shape
+    seed = 1000 * k + WALK_SEED.get(shape, {}).get(k, 0)
+    q, p, idx, sf0, pf0 = T.walk_inputs(nq, npool, dim, k, seed)
+    qd, pd = q.to(DEV), p.to(DEV)
+    qn, _ = ops.row_norms(qd); pn, _ = ops.row_norms(pd)
+    for use_f0 in (0, 1):
+        f0c = (sf0, pf0) if use_f0 else (None, None)
+        ref = select_ref.concat_reselect(idx.clone(), q, p, *f0c, concat_weight=0.2)
+        replay, gap, repeated = T.walk_margin(idx.clone(), q, p, *f0c, w=0.2)
+        tag = f"{prefix}/k{k}/{nq}x{npool}x{dim}/f0{use_f0}"
+        assert torch.equal(replay, ref), tag + ": walk_margin does not replay the oracle"
+        assert gap >= WALK_GAP, f"{tag}: oracle margin {gap:.2e} < {WALK_GAP} (seed {seed})"
+        if npool == 4000:
+            assert repeated <= nq // 10, f"{tag}: {repeated} of {nq} frames with a repeated candidate (seed {seed})"
+        got = ops.concat_reselect(idx.to(DEV), qd, qn, pd, pn, *(t.to(DEV) if t is not None else None for t in f0c),
+                                  concat_weight=0.2)
+        sets, order = compare_walk(got, ref, idx, npool, ordered=npool == 4000)
+        inb = bool(((got >= 0) & (got < npool)).all()) and tuple(got.shape) == (nq, k)
+        note(tag, sets and order and inb, f"sets equal {sets}, order equal {order}, in range {inb}; oracle margin {gap:.2e}, "
+                                          f"{repeated} frames with a repeated candidate")
 
 
 def case_walk():
     for k in (1, 2, 3, 5, 6, 7, 8):
         for shape in WALK_SHAPES:
-            nq, npool, dim = shape
-            seed = 1000 * k + WALK_SEED.get(shape, {}).get(k, 0)
-            q, p, idx, sf0, pf0 = T.walk_inputs(nq, npool, dim, k, seed)
-            qd, pd = q.to(DEV), p.to(DEV)
-            qn, _ = ops.row_norms(qd); pn, _ = ops.row_norms(pd)
-            for use_f0 in (0, 1):
-                f0c = (sf0, pf0) if use_f0 else (None, None)
-                ref = select_ref.concat_reselect(idx.clone(), q, p, *f0c, concat_weight=0.2)
-                replay, gap, repeated = T.walk_margin(idx.clone(), q, p, *f0c, w=0.2)
-                tag = f"walk/k{k}/{nq}x{npool}x{dim}/f0{use_f0}"
-                assert torch.equal(replay, ref), tag + ": walk_margin does not replay the oracle"
-                assert gap >= WALK_GAP, f"{tag}: oracle margin {gap:.2e} < {WALK_GAP} (seed {seed})"
-                if npool == 4000:
-                    assert repeated <= nq // 10, f"{tag}: {repeated} of {nq} frames with a repeated candidate (seed {seed})"
-                got = ops.concat_reselect(idx.to(DEV), qd, qn, pd, pn, *(t.to(DEV) if t is not None else None for t in f0c),
-                                          concat_weight=0.2)
-                sets, order = compare_walk(got, ref, idx, npool, ordered=npool == 4000)
-                inb = bool(((got >= 0) & (got < npool)).all()) and tuple(got.shape) == (nq, k)
-                note(tag, sets and order and inb, f"sets equal {sets}, order equal {order}, in range {inb}; oracle margin {gap:.2e}, "
-                                                  f"{repeated} frames with a repeated candidate")
+            walk_case(k, shape, "walk")
+    for shape in WALK_SHAPES_K4:
+        walk_case(4, shape, "walk-k4")
     # one segmented call over [1, 2, 3, 64] at k = 8: bit-identical to the single calls
     lens = [1, 2, 3, 64]
     seg = offsets(lens)
@@ -171,6 +180,18 @@ def case_smooth():
     used = float((plain - w).abs().max())
     note("smooth/row_scale/k5", e < W_BAR and int(it) == it_ref and used > 1e-3,
          f"max|dw| {e:.2e}, iterations {int(it)} / oracle {it_ref}, differs from the unscaled weights by {used:.2e}")
+
+
+def case_smooth_long4():
+    """k = 4 at 1537 rows, the first length past the register loops: the long k = 4 loop against the oracle, as the other k."""
+    idx, pool, scale = T.smooth_inputs("feat", 4, variant=T.SMOOTH_LONG4_VARIANT, rows=1537)
+    spread, ref, it_ref, _ = T.adam_spread(idx, pool, scale)
+    assert spread < SPREAD_BAR, f"smooth-k4: the oracle moves {spread:.2e} under a column permutation"
+    w, it = ops.smooth_weights(idx.to(DEV), pool.to(DEV), scale, return_iters=True)
+    e = float((w.cpu() - ref).abs().max())
+    rows1 = float((w.sum(1) - 1.0).abs().max())
+    note("smooth-k4/feat/1537", e < W_BAR and int(it) == it_ref and tuple(w.shape) == tuple(idx.shape) and rows1 < 1e-5,
+         f"max|dw| {e:.2e}, iterations {int(it)} / oracle {it_ref}, oracle spread {spread:.2e}, max|row sum - 1| {rows1:.1e}")
 
 
 def case_smooth_seg():
@@ -384,13 +405,14 @@ def case_product(tmp):
 
 def main(out_path):
     torch.cuda.set_device(0)
-    cases = [("walk", case_walk), ("walk-generic4", case_walk_generic4), ("smooth", case_smooth), ("smooth-seg", case_smooth_seg),
+    cases = [("walk", case_walk), ("walk-generic4", case_walk_generic4), ("smooth", case_smooth), ("smooth-k4", case_smooth_long4),
+             ("smooth-seg", case_smooth_seg),
              ("smooth-generic4", case_smooth_generic4), ("gather", case_gather), ("chain", case_chain), ("product", None)]
     rc = 0
     with tempfile.TemporaryDirectory() as tmp:
         for name, fn in cases:
             try:
-                with contextlib.nullcontext() if name in ("smooth", "chain") else torch.inference_mode():  # the oracle's Adam needs autograd
+                with contextlib.nullcontext() if name in ("smooth", "smooth-k4", "chain") else torch.inference_mode():  # the oracle's Adam needs autograd
                     fn() if fn is not None else case_product(tmp)
                 torch.cuda.synchronize()
             except Exception:          # nothing more is started on the GPU after an error: report what ran and stop

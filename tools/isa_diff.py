@@ -1,13 +1,15 @@
 #!/usr/bin/env python3
 """Per-kernel comparison of two device-assembly files (hipcc --cuda-device-only -S), no GPU needed.
 
-    tools/isa_diff.py before.s after.s [--show N] [--kernel SUBSTRING]
+    tools/isa_diff.py before.s after.s [--show N] [--kernel SUBSTRING] [--rename OLD=NEW ...]
 
 For every kernel: is the instruction stream identical (comments and directives stripped; the function number
 in .LBB<function>_<block> labels dropped)?
 For those that are not: next_free_vgpr / accum_offset / scratch / LDS of the kernel descriptor and static counts of
 the instructions that matter (v_mfma, ds_read, ds_write, buffer_load, buffer_store, s_barrier, s_waitcnt, scratch_),
 one row per file.  --show N prints the first N differing lines of each such kernel.  Exit status 1 if any kernel differs.
+--rename OLD=NEW (repeatable) replaces OLD by NEW in the demangled names of `before` first, to pair kernels across a rename
+("gram_k_kernel<=gram_kernel<"); kernels are then matched by demangled name.
 Two compiles of one source differ only in the __hip_cuid_* symbol, so a whole-file cmp says nothing; this does.
 """
 import argparse
@@ -75,9 +77,25 @@ def main():
     ap.add_argument("after")
     ap.add_argument("--show", type=int, default=0, metavar="N", help="print the first N differing lines per kernel")
     ap.add_argument("--kernel", default="", metavar="SUBSTRING", help="only kernels whose demangled name contains this")
+    ap.add_argument("--rename", action="append", default=[], metavar="OLD=NEW", help="rename in the demangled names of `before`")
     args = ap.parse_args()
     (ba, ma), (bb, mb) = parse(args.before), parse(args.after)
-    names = demangle(sorted(set(ba) | set(bb)))
+    if args.rename:         # match by demangled name, `before` renamed
+        def rekey(d, dem, ren):
+            out = {}
+            for k, v in d.items():
+                name = dem[k]
+                for r in ren:
+                    old, new = r.split("=", 1)
+                    name = name.replace(old, new)
+                out[name] = v
+            return out
+        da, db = demangle(sorted(ba)), demangle(sorted(bb))
+        ba, ma, bb, mb = rekey(ba, da, args.rename), rekey(ma, da, args.rename), rekey(bb, db, []), rekey(mb, db, [])
+        ma, mb = {k: ma[k] for k in ba}, {k: mb[k] for k in bb}
+        names = {k: k for k in set(ba) | set(bb)}
+    else:
+        names = demangle(sorted(set(ba) | set(bb)))
     same = differ = 0
     for k in sorted((k for k in names if args.kernel in names[k]), key=names.get):
         if k not in ba or k not in bb:

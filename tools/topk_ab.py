@@ -1,6 +1,6 @@
 """Match stage by neighbours per frame: time of matching.match_features with the neighbour lists given (no search), events
 around each call, at the bench's point — 1500 query frames, a 30 000-frame pool, dim 1024, "mix", post_opt_0.2 — for
-topk = 1, 2, 4, 8 and for 4 on the generic-K kernels (KNNSVC_MATCH_GENERIC_K=1).
+topk = 1, 2, 4, 8 and for 4 without its fast paths (KNNSVC_MATCH_GENERIC_K=1).
 
     python tools/topk_ab.py [--reps 9] [--out profiles/topk_match_stage.txt]
 
