@@ -631,6 +631,50 @@ int knnsvc_loudness(const float* wav, int64_t n, int32_t sample_rate, float* lkf
  * the caller's finiteness check).  out may alias wav. */
 int knnsvc_loudness_gain(float* wav, int64_t n, const float* lkfs, float target_db, float* out, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Voice-activity trimming of pool recordings (csrc/vad.hip).  The reference documents vad_trigger_level on get_features
+ * ("optionally perform VAD trimming on start/end", ddsp_matcher.py:438-491: torchaudio's Vad on the signal, then on the flipped
+ * remainder, every cut extended to a whole number of 320-sample hops) and passes 7 for the target pool
+ * (ddsp_prematch_dataset.py:1131), where get_complete_spk_pool drops it.
+ * ------------------------------------------------------------------------------------------ */
+/* Where speech starts and ends in each of n_seg mono fp32 recordings stacked in wav (recording s = wav[host_seg[s] ..
+ * host_seg[s + 1]); host_seg_offsets is a HOST table as for the *_seg calls above, 1 <= n_seg <= KNNSVC_MAX_SEGMENTS).  The
+ * algorithm is the sox `vad` effect with torchaudio's default parameters AS RESTATED HERE (and in fp64 numpy in
+ * tests/vad_oracle.py); this restatement is the specification - parity with torchaudio's own code is not pinned.
+ *   constants    (in brackets: at 16 kHz)  measure_len = int(sr 0.1 + .5) [1600];  dft_len = 16 doubled until >= measure_len [2048];
+ *                period = int(sr / 20 + .5) [800];  spectrum bins [s0, s1): s0 = max(1, int(50 / sr dft_len + .5)) [6],
+ *                s1 = min(int(6000 / sr dft_len + .5), dft_len / 2) [768];  cepstrum bins [c0, c1): c0 = ceil(sr / 2 / 2000) [4],
+ *                c1 = min(floor(sr / 2 / 150), dft_len / 4) [53];  smooth = exp(-1/8), up = exp(-1/2), down = exp(-5),
+ *                trig = exp(-1/5);  periodic Hann windows win[i] = 2 / sqrt(measure_len) (0.5 - 0.5 cos(2 pi i / measure_len)),
+ *                cwin[i] = 2 / sqrt(s1 - s0) (0.5 - 0.5 cos(2 pi i / (s1 - s0))).
+ *   measures     measurement m covers samples [m period, m period + measure_len): M = (L - measure_len) / period + 1 of them, none
+ *                when L < measure_len.  With S = N = 0 before the first:  a_k = |rfft(win frame, zero-padded to dft_len)_k| for k
+ *                in [s0, s1);  m < 6 (boot): b = m + 1, S = b/(1+b) S + 1/(1+b) a, d = S^2, N = d;  later: S = smooth S +
+ *                (1 - smooth) a, d = S^2, N = mu N + (1 - mu) d with mu_k = up if d_k > N_k else down;  e = sqrt(max(0, d - 1.35 N));
+ *                c = zeros(dft_len / 2), c[s0:s1] = e cwin;  r = sum over q in [c0, c1) of |rfft(c)_q|^2;
+ *                meas_m = max(0, 21 + ln(r / (c1 - c0))) if r > 0 else 0.
+ *   trigger      mean = trig mean + (1 - trig) meas_m from mean = 0; the first m with mean >= trigger_level fires.  Walk back over
+ *                meas_m, meas_(m-1), ... for j = 0 .. 19 (before the recording: 0) from jT = jZ = 20:  meas >= level and
+ *                j <= jT + 5: jZ = jT = j;  else meas == 0 and jT >= jZ: jZ = j.  start = max(0, m - min(20, jZ)) period; -1 when
+ *                nothing fires.
+ *   both ends    lstrip = start rounded up to a multiple of 320.  The same procedure on the time-reversed signal, over the
+ *                measurements that fit in L - lstrip samples, gives rstrip (rounded up likewise).  The kept range is
+ *                [lstrip, L - rstrip).  A recording that does not fire in one of the two directions, or whose kept range is shorter
+ *                than measure_len, is dropped.
+ * out_strip: device int64 [n_seg][2] = (lstrip, rstrip), (-1, -1) for a dropped recording.  out_measures (may be NULL): device
+ * double [2][rows], rows = host_seg[n_seg] / period + 1: measure m of recording s is [host_seg[s] / period + m] of the forward half
+ * and of the reversed half (all M of them, also those behind the trigger); the entries between recordings are not written.
+ * sample_rate 8000 .. 20000 (the transform of dft_len <= 2048 points runs in LDS); trigger_level finite and > 0.  All arithmetic
+ * between the samples and the cut points is fp64 in a fixed order: bit-stable from run to run, and a recording's result does not
+ * depend on the others in the call.  workspace: 8-byte aligned device memory of at least
+ * knnsvc_vad_workspace_bytes(host_seg[n_seg], n_seg, sample_rate) bytes (a HOST function; 0 with knnsvc_last_error() set for bad
+ * arguments; about 2 x 762 doubles per 50 ms of audio at 16 kHz); a smaller one is refused before anything is launched.
+ * Asynchronous on `stream`, no allocation, no host synchronisation, capturable. */
+size_t knnsvc_vad_workspace_bytes(int64_t total_samples, int32_t n_seg, int32_t sample_rate);
+int knnsvc_vad_trim_seg(const float* wav, const int64_t* host_seg_offsets, int32_t n_seg, int32_t sample_rate,
+                        double trigger_level, int64_t* out_strip, double* out_measures, void* workspace, size_t workspace_bytes,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("KNNSVC_LIB") or os.path.join(_HERE, "libknnsvc_hip.so")      # KNNSVC_LIB: an A/B build (csrc/Makefile)
 ABI_VERSION = 20
 
-vp, i32, i64, f32, sz = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_size_t
+vp, i32, i64, f32, f64, sz = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_double, C.c_size_t
 
 
 class ConvDesc(C.Structure):
@@ -179,6 +179,8 @@ SIGNATURES = {
     "knnsvc_loudness_layout": (None, [C.POINTER(i32), C.POINTER(i32)]),
     "knnsvc_loudness": (i32, [vp, i64, i32, vp, vp, vp, sz, vp]),
     "knnsvc_loudness_gain": (i32, [vp, i64, vp, f32, vp, vp]),
+    "knnsvc_vad_workspace_bytes": (sz, [i64, i32, i32]),
+    "knnsvc_vad_trim_seg": (i32, [vp, vp, i32, i32, f64, vp, vp, vp, sz, vp]),
 }
 
 _lib = None

@@ -12,7 +12,12 @@ file names do not change.  --tgt_loudness_db (default -16) is accepted and, as u
 ignored unless --normalize_loudness true is given (an extension, default false): every
 output is then brought to that integrated loudness (BS.1770) on the GPU before it is
 written; file names do not change, and a clip normalised past full scale is written
-lower than asked (save_audio divides by a peak above 1, as upstream).  --dur_limit is
+lower than asked (save_audio divides by a peak above 1, as upstream).  --vad_trigger_level
+(default 7, what upstream passes for the target pool and then drops) is ignored unless
+--use_vad true is given (an extension, default false): silence is then trimmed from both ends
+of every target pool file on the GPU (the sox `vad` effect with torchaudio's defaults as
+restated in include/knnsvc_hip.h; parity with torchaudio's own code is not pinned); the
+source, the output length and the file names do not change.  --dur_limit is
 compared in seconds, as upstream (ddsp_prematch_dataset.py:408-411).
 """
 from __future__ import annotations
@@ -52,6 +57,10 @@ def build_parser() -> argparse.ArgumentParser:
                     help="(extension) normalise every output to --tgt_loudness_db LKFS")
     ap.add_argument("--use_topk", type=_bool, default=False,
                     help="(extension) mix --topk (1..8) neighbours per frame instead of the reference's hard-coded 4")
+    ap.add_argument("--use_vad", type=_bool, default=False,
+                    help="(extension) trim silence from both ends of every target pool file (--vad_trigger_level)")
+    ap.add_argument("--vad_trigger_level", type=float, default=7,
+                    help="(extension, with --use_vad true) trigger level of the trimmer; higher keeps less")
     ap.add_argument("--weights", default="auto", choices=["auto", "checkpoint", "seeded"],
                     help="(extension) 'seeded' runs with random weights when the released checkpoints are unavailable")
     return ap
@@ -72,7 +81,7 @@ def main(argv=None) -> int:
                  local_ckpt_dir=a.ckpt_dir, weights=a.weights)
     common = dict(topk=a.topk, device=a.device, prioritize_f0=a.prioritize_f0, ckpt_type=a.ckpt_type,
                   tgt_loudness_db=a.tgt_loudness_db, post_opt=a.post_opt, normalize_loudness=a.normalize_loudness,
-                  use_topk=a.use_topk)
+                  use_topk=a.use_topk, use_vad=a.use_vad, vad_trigger_level=a.vad_trigger_level)
     if os.path.isfile(a.src) and os.path.isfile(a.tgt):
         knn.special_match(src_wav_file=a.src, ref_wav_file=a.tgt, **common)
         return 0

@@ -11,7 +11,13 @@ then brought to that integrated loudness on the GPU (ops.normalize_loudness; wha
 documents for the argument, ddsp_matcher.py:533, 947, and does in its commented-out block
 :997-1003).  ``audio_io.save_audio`` keeps the reference's peak rule — a waveform whose peak
 exceeds 1 is divided by it — so a clip normalised past full scale is written lower than asked;
-there is no limiter.  Other differences that are deliberate: ``special_match`` returns
+there is no limiter.  ``vad_trigger_level`` is accepted and, as in upstream's pool builder
+(ddsp_prematch_dataset.py:1131 passes 7 to a function that drops it), ignored UNLESS ``use_vad=True``
+is passed (an extension, off by default): silence is then trimmed from both ends of every TARGET
+pool file on the GPU before it is encoded (ops.vad_trim: the sox `vad` effect with torchaudio's
+default parameters as restated in include/knnsvc_hip.h; that restatement is the specification,
+parity with torchaudio's own code is not pinned); the source is never trimmed, output length and
+file names do not change.  Other differences that are deliberate: ``special_match`` returns
 the waveform instead of calling ``sys.exit()`` after saving (the CLI exits 0, the
 observable behaviour), and ``bulk_match`` does not ``rm -rf`` a hard-coded cache
 directory (ddsp_matcher.py:1066-1068).
@@ -83,7 +89,7 @@ class KNeighborsVC:
     @torch.inference_mode()
     def special_match(self, src_wav_file, ref_wav_file, topk: int = 4, device=None, prioritize_f0=True,
                       ckpt_type="wavlm_only", tgt_loudness_db=-16, post_opt="no_post_opt", save=True, normalize_loudness=False,
-                      use_topk=False):
+                      use_topk=False, use_vad=False, vad_trigger_level=7):
         level = tgt_loudness_db if normalize_loudness else None
         f0only = "wavlm_only" in ckpt_type or "no_harm_no_amp" in ckpt_type
         if "wavlm_only_original" in ckpt_type:
@@ -93,13 +99,14 @@ class KNeighborsVC:
             of, hw, _a, sf0 = match_at_inference_time(Path(src_wav_file), Path(ref_wav_file), self.wavlm,
                                                       self.weighting, self.weighting, topk=topk, device=self.device,
                                                       prioritize_f0=prioritize_f0, ckpt_type=ckpt_type, post_opt=post_opt,
-                                                      use_topk=use_topk)
+                                                      use_topk=use_topk, use_vad=use_vad, vad_trigger_level=vad_trigger_level)
             pred = self.vocode(of[key][None], sf0[key][None, :, None], hw[key][None], loudness_db=level).squeeze()
         else:
             # the reference does not forward post_opt on this branch (ddsp_matcher.py:970)
             of, _a, sf0 = match_at_inference_time(Path(src_wav_file), Path(ref_wav_file), self.wavlm,
                                                   self.weighting, self.weighting, topk=topk, device=self.device,
-                                                  prioritize_f0=prioritize_f0, ckpt_type=ckpt_type, use_topk=use_topk)
+                                                  prioritize_f0=prioritize_f0, ckpt_type=ckpt_type, use_topk=use_topk,
+                                                  use_vad=use_vad, vad_trigger_level=vad_trigger_level)
             pred = self.vocode(of[key][None], sf0[key][None, :, None], loudness_db=level).squeeze()
         src_id = os.path.basename(src_wav_file).split(".")[0]
         ref_id = os.path.basename(ref_wav_file).split(".")[0]
@@ -111,17 +118,18 @@ class KNeighborsVC:
 
     @torch.inference_mode()
     def many_to_one(self, src_files, ref_wav_file, converted_audio_dir=None, ckpt_type="mix", post_opt="post_opt_0.2",
-                    duration_limit=None, target=None, match=None, loudness_db=None, topk=None):
+                    duration_limit=None, target=None, match=None, loudness_db=None, topk=None, vad_trigger_level=None):
         """BASELINE cfg 5 (no counterpart upstream: the reference would call ``special_match`` once per source and rebuild the
         target pool each time, ddsp_matcher.py:937-1023): MANY sources against ONE target pool that is built once and stays
         resident, all sources through the stream pipeline as one batch (knn_svc_amd/serving.py).  Under a process group the
         sources are dealt over the ranks (no collective).  ``target``: a serving.TargetVoice to reuse.  -> written paths (all
         ranks' on every rank), named like ``special_match``'s outputs.  ``match``: "lanes" | "segmented" (serving.BatchConverter; default
         from KNNSVC_MATCH).  ``loudness_db``: every waveform is normalised to that integrated loudness (None: left as generated).
-        ``topk``: neighbours mixed per frame, 1..8 (None: 4)."""
+        ``topk``: neighbours mixed per frame, 1..8 (None: 4).  ``vad_trigger_level``: the pool's files are trimmed of the silence
+        at both ends with that trigger level (None: left whole; ignored when ``target`` is given)."""
         from . import serving
         if target is None:
-            target = serving.TargetVoice(self, ref_wav_file, duration_limit)
+            target = serving.TargetVoice(self, ref_wav_file, duration_limit, vad_trigger_level=vad_trigger_level)
         mine = kdist.my_share([str(p) for p in src_files])
         written = serving.BatchConverter(self, target, ckpt_type, post_opt, match=match,
                                          loudness_db=loudness_db, topk=topk).convert_files(mine, converted_audio_dir)
@@ -130,7 +138,8 @@ class KNeighborsVC:
     @torch.inference_mode()
     def bulk_match(self, src_dataset_path, tgt_dataset_path, converted_audio_dir, topk: int = 4, device=None,
                    prioritize_f0=True, ckpt_type="mix", tgt_loudness_db=-16, required_subset_file=None,
-                   post_opt="no_post_opt", duration_limit=None, normalize_loudness=False, use_topk=False):
+                   post_opt="no_post_opt", duration_limit=None, normalize_loudness=False, use_topk=False, use_vad=False,
+                   vad_trigger_level=7):
         level = tgt_loudness_db if normalize_loudness else None
         assert os.path.isdir(src_dataset_path) and os.path.isdir(tgt_dataset_path)
         Path(converted_audio_dir).mkdir(parents=True, exist_ok=True)
@@ -169,7 +178,8 @@ class KNeighborsVC:
                 common = dict(topk=topk, device=self.device, prioritize_f0=prioritize_f0, ckpt_type=ckpt_type,
                               src_dataset_path=src_dataset_path, tgt_dataset_path=tgt_dataset_path,
                               required_subset=required, duration_limit=duration_limit,
-                              pool_sharded=shard, share_items=shard, use_topk=use_topk)
+                              pool_sharded=shard, share_items=shard, use_topk=use_topk, use_vad=use_vad,
+                              vad_trigger_level=vad_trigger_level)
                 # the generator of every utterance is the tail stage of the match pipeline (same kernels and inputs as
                 # `vocode` after the fact, ddsp_matcher.py:1114-1128, but enqueued under the next utterances' matching);
                 # one finiteness check per speaker pair instead of one host sync per utterance; with normalize_loudness the

@@ -7,6 +7,10 @@ arguments, same returned dict-of-tensors keyed by ``str(path)``, same quirks
 ``post_opt`` parsing, ``prioritize_f0`` must be True, pool rebuilt per call).
 ``topk`` is ignored as upstream unless ``use_topk=True`` (an extension, off by default): the
 match stage then keeps that many (1..8) of the 32 neighbours per frame instead of 4.
+``vad_trigger_level`` is ignored as in upstream's ``get_complete_spk_pool`` unless ``use_vad=True`` (an extension, off by
+default): silence is then trimmed from both ends of every TARGET pool file on the GPU (ops.vad_trim: the sox `vad` effect with
+torchaudio's defaults as restated in include/knnsvc_hip.h — that restatement is the specification, parity with torchaudio's
+own code is not pinned), which is what the reference documents for the argument (ddsp_matcher.py:438-491).
 All arithmetic is done by libknnsvc_hip.so kernels on device-resident tensors; the
 only host work is file I/O and the chunk bookkeeping.
 """
@@ -111,11 +115,43 @@ def side_features_many(wavs_gpu, f0s_host, Ts):
     return [(f0, harm, spec) for f0, (spec, harm) in zip(f0s, res)]
 
 
-def disk_identity(wavlm) -> tuple:
+VAD_MIN_LEVEL = 1e-3          # trimming is active above this trigger level (upstream's test, ddsp_matcher.py:462)
+
+
+def vad_active(vad_trigger_level) -> bool:
+    return vad_trigger_level is not None and vad_trigger_level > VAD_MIN_LEVEL
+
+
+def vad_tag(vad_trigger_level) -> tuple:
+    """What the trimming adds to a pool-store key: nothing when it is off (existing keys do not move)."""
+    return (("vad", float(vad_trigger_level)),) if vad_active(vad_trigger_level) else ()
+
+
+def disk_identity(wavlm, vad_trigger_level=0) -> tuple:
     """What an on-disk pool-store entry belongs to besides its audio file: the encoder's WEIGHTS, its exit layer and the layer
     weighting the features were mixed under (set_layer_mix bumps ``uid`` for the in-memory tier; the disk tier outlives the
-    process, so it needs the weighting itself — without it a second weighting read back the first one's features)."""
-    return (wavlm.weights_fingerprint(), wavlm.n_layers, getattr(wavlm, "layer_mix", None))
+    process, so it needs the weighting itself — without it a second weighting read back the first one's features), and the
+    trigger level the file was trimmed with, when it was."""
+    return (wavlm.weights_fingerprint(), wavlm.n_layers, getattr(wavlm, "layer_mix", None)) + vad_tag(vad_trigger_level)
+
+
+def slice_f0(f0, lstrip: int, T: int):
+    """The f0 track of a recording trimmed by ``lstrip`` samples in front (a multiple of the hop) and ``T`` frames long: the
+    track is computed and cached on the UNTRIMMED file (``<stem>_f0.npy`` stays valid) and cut here; T or T + 1 values."""
+    assert lstrip % C.HOP == 0, lstrip
+    a = lstrip // C.HOP
+    return f0[a:a + T + 1]
+
+
+def trim_silence(w, f0, vad_trigger_level, wavlm):
+    """One loaded utterance (host arrays) with the silence at both ends removed (ops.vad_trim on the encoder's device) ->
+    (wav, f0) of the kept range, or None when the trimmer finds no speech in it."""
+    strip = ops.vad_trim(torch.from_numpy(w).to(wavlm.device), vad_trigger_level, C.SAMPLE_RATE)
+    lstrip, rstrip = (int(v) for v in strip[0].cpu())
+    if lstrip < 0:
+        return None
+    w = np.ascontiguousarray(w[lstrip:len(w) - rstrip])
+    return w, slice_f0(f0, lstrip, frames_of(len(w), wavlm))
 
 
 def get_complete_spk_pool(path, wavlm: WavLMEncoder, match_weights=None, synth_weights=None, device="cuda",
@@ -129,18 +165,25 @@ def get_complete_spk_pool(path, wavlm: WavLMEncoder, match_weights=None, synth_w
     ``shard_files`` (one process per GPU): every rank walks the same file list and duration limit, but encodes and
     returns only its contiguous share of the kept files (dist.contiguous_share) — the pool shard of BASELINE cfg 4.
     ``gather`` (with shard_files): the shares are all-gathered afterwards (features and f0 only — what a QUERY pool
-    needs), so every rank returns the complete per-file dicts although it encoded only its share."""
+    needs), so every rank returns the complete per-file dicts although it encoded only its share.
+    ``vad_trigger_level`` > 1e-3 (upstream's threshold; an extension — upstream's function never reads the argument): every
+    file is trimmed of the silence at both ends right after it is loaded (``trim_silence``: the restated sox `vad`, parity with
+    torchaudio unpinned); its frame count, features, spectrum and harmonics come from the trimmed waveform, its f0 from the
+    track of the untrimmed file cut to match.  A file without speech is skipped with a printed line, a pool without any file
+    left is an error.  Every rank trims every file it lists, so the kept files and their lengths agree across ranks."""
     dev = wavlm.device
     files = list_audio(path)
     cache = _pool_cache()
-    tag = (wavlm.uid, wavlm.n_layers)
-    dtag = disk_identity(wavlm) if cache.disk_dir else None     # on-disk tier: content identity
+    vad = vad_active(vad_trigger_level)
+    tag = (wavlm.uid, wavlm.n_layers) + vad_tag(vad_trigger_level)
+    dtag = disk_identity(wavlm, vad_trigger_level) if cache.disk_dir else None     # on-disk tier: content identity
     dkeys = {}
     kept, keys, Ts = [], [], []
     loaded = {}                       # index -> (wav host, f0 host) for files that miss the cache
     hits = {}                         # index -> cache entry: held here, a later put() may evict it from the store
     dur = 0.0
-    for i, pth in enumerate(files):
+    for pth in files:
+        i = len(kept)
         key = pool_cache.file_key(pth, tag)
         if dtag is not None:
             dkeys[key] = pool_cache.file_key(pth, dtag)
@@ -153,12 +196,20 @@ def get_complete_spk_pool(path, wavlm: WavLMEncoder, match_weights=None, synth_w
             key = pool_cache.file_key(pth, tag)                   # load_utterance may have just written <stem>_f0.npy,
             if dtag is not None:                                  # which is part of the file's identity
                 dkeys[key] = pool_cache.file_key(pth, dtag)
+            if vad:
+                cut = trim_silence(w, f0, vad_trigger_level, wavlm)
+                if cut is None:
+                    print(f"VAD trimming {pth} {vad_trigger_level}: no speech found, file skipped")
+                    continue
+                w, f0 = cut
             T = frames_of(len(w), wavlm)
             loaded[i] = (w, f0)                                   # host arrays: only this rank's share goes to the device
         kept.append(str(pth)); keys.append(key); Ts.append(T)
         dur += T * C.HOP / C.SAMPLE_RATE
         if duration_limit is not None and dur >= duration_limit:
             break
+    if not kept:
+        raise ops.KnnSvcError(f"VAD trimming at level {vad_trigger_level} left no file of {path} in the pool")
     lo, hi = kdist.contiguous_share(len(kept)) if shard_files else (0, len(kept))
     loaded = {i: (torch.from_numpy(v[0]).to(dev), v[1]) for i, v in loaded.items() if lo <= i < hi}
     miss = sorted(loaded)
@@ -491,11 +542,13 @@ def match_at_inference_time(src_wav_file, ref_wav_file, wavlm: WavLMEncoder, mat
                             topk: int = 4, device="cuda", prioritize_f0=False, ckpt_type="wavlm_only",
                             src_dataset_path=None, tgt_dataset_path=None, cache_dir=None, required_subset=None,
                             post_opt="no_post_opt", duration_limit=None, vocode_fn=None, waves_out=None,
-                            pool_sharded=None, share_items=False, use_topk=False):
+                            pool_sharded=None, share_items=False, use_topk=False, use_vad=False, vad_trigger_level=7):
     """Same contract as the reference function (ddsp_prematch_dataset.py:1074).  ``topk`` is accepted and, as upstream
     (k = 32 -> 4 is hard-coded there, :1203,1246,1398), ignored UNLESS ``use_topk=True`` (an extension, off by default): the
     match stage then keeps ``topk`` (1..8) neighbours per frame.  ``cache_dir`` is ignored (the reference force-disables
-    it, :1086-1087).
+    it, :1086-1087).  ``vad_trigger_level`` (upstream passes 7 for the target pool, :1131, to a function that drops it) takes
+    effect only with ``use_vad=True`` (an extension, off by default): the TARGET pool's files, never the source, are trimmed of
+    the silence at both ends (``get_complete_spk_pool``); output length and file names do not change.
 
     Build extension (BASELINE cfg 5, many sources against one pool): ``vocode_fn(out_feats, shifted_f0, harm)`` is
     enqueued as the pipeline's tail stage right behind each item's match body and its waveform stored in
@@ -514,6 +567,7 @@ def match_at_inference_time(src_wav_file, ref_wav_file, wavlm: WavLMEncoder, mat
         own items: the returned dicts hold this rank's items."""
     import torch.distributed as tdist
     k_use = resolve_topk(topk) if use_topk else None        # refused before any file is read
+    vad_level = vad_trigger_level if use_vad else 0
     if pool_sharded is None:         # by environment: only when there is more than one rank to shard over
         pool_sharded = os.environ.get("KNNSVC_POOL_SHARD") == "1" and kdist.world()[1] > 1
     pool_sharded = bool(pool_sharded) and tdist.is_available() and tdist.is_initialized()   # explicit True: any group, even 1 rank
@@ -533,7 +587,7 @@ def match_at_inference_time(src_wav_file, ref_wav_file, wavlm: WavLMEncoder, mat
     if tgt_dataset_path is None:
         assert os.path.isfile(ref_wav_file)
     matching_pool, _synth, _audio, _spec, f0_pool, harm_pool = get_complete_spk_pool(
-        ref_wav_file, wavlm, device=device, duration_limit=duration_limit, shard_files=pool_sharded)
+        ref_wav_file, wavlm, device=device, duration_limit=duration_limit, shard_files=pool_sharded, vad_trigger_level=vad_level)
     keys = list(matching_pool)
     E = wavlm.E
     cat = lambda pool, shape: (torch.cat([pool[k] for k in keys], 0).contiguous() if keys
@@ -546,7 +600,7 @@ def match_at_inference_time(src_wav_file, ref_wav_file, wavlm: WavLMEncoder, mat
             # (a sharded pool: this rank's share again, under the synthesis weighting; all-gathered below like the matching features —
             #  the search only ever sees the matching features, the gathers and the smoothness weights read the synthesis ones)
             _m, synth_pool, _a2, _s2, _f2, _h2 = get_complete_spk_pool(ref_wav_file, wavlm, device=device, duration_limit=duration_limit,
-                                                                       shard_files=pool_sharded)
+                                                                       shard_files=pool_sharded, vad_trigger_level=vad_level)
         finally:
             wavlm.set_layer_mix(mix_m)
         assert list(synth_pool) == keys

@@ -1094,3 +1094,51 @@ def normalize_loudness(wav, target_db, sample_rate=16000, out=None):
         raise KnnSvcError("normalize_loudness: out must be a contiguous fp32 tensor of wav's shape")
     check(_lib.load().knnsvc_loudness_gain(_p(wav), wav.numel(), _p(lkfs), float(target_db), _p(out), _stream()), "loudness_gain")
     return out, lkfs
+
+
+# ------------------------------------------------------------------ pool-silence trimming
+def vad_trim(wavs, trigger_level, sample_rate=16000, return_measures=False):
+    """Where speech starts and ends in every recording of ``wavs`` (a list of mono fp32 device tensors [L_i], or one such tensor):
+    the sox `vad` effect with torchaudio's default parameters applied to both ends, every cut a whole number of 320-sample hops,
+    as restated in include/knnsvc_hip.h (fp64 on the device, csrc/vad.hip; that restatement, mirrored by tests/vad_oracle.py, is
+    the specification — parity with torchaudio's own code is not pinned) -> int64 device tensor [n, 2] = (lstrip, rstrip): keep
+    wav[lstrip : L - rstrip]; (-1, -1) for a recording to drop (no speech found from one of its ends, or less than one
+    measurement left).  return_measures: (strip, [(forward, reversed) fp64 device vectors of each recording's measures]).
+    Enqueue only: no host read.  A recording's result does not depend on the others in the call."""
+    one = isinstance(wavs, torch.Tensor)
+    wavs = [wavs] if one else list(wavs)
+    if not wavs:
+        raise KnnSvcError("vad_trim: no recording")
+    for w in wavs:
+        _need(w, name="vad_trim.wav")
+        if w.dim() != 1 or w.numel() == 0:
+            raise KnnSvcError(f"vad_trim: expected non-empty mono waveforms [L], got shape {tuple(w.shape)}")
+    level = float(trigger_level)
+    if not (math.isfinite(level) and level > 0.0):
+        raise KnnSvcError(f"vad_trim: trigger_level must be finite and positive, got {trigger_level!r}")
+    lib = _lib.load()
+    dev = wavs[0].device
+    seg = [0]
+    for w in wavs:
+        seg.append(seg[-1] + w.numel())
+    x = wavs[0].contiguous() if len(wavs) == 1 else torch.cat([w.contiguous() for w in wavs])
+    strip = torch.empty(len(wavs), 2, device=dev, dtype=torch.int64)
+    measures = []
+    for a, r0, tab in _seg_chunks(seg):
+        n, total = len(tab) - 1, int(tab[len(tab) - 1])
+        nbytes = lib.knnsvc_vad_workspace_bytes(total, n, int(sample_rate))
+        if nbytes == 0:
+            check(1, "vad_workspace_bytes")
+        ws = torch.empty((nbytes + 7) // 8, device=dev, dtype=torch.float64)
+        period = int(sample_rate / 20.0 + .5)
+        rows = total // period + 1
+        meas = torch.empty(2, rows, device=dev, dtype=torch.float64) if return_measures else None
+        check(lib.knnsvc_vad_trim_seg(_p(x[r0:]), tab, n, int(sample_rate), level, _p(strip[a:]), _p(meas), _p(ws), ws.numel() * 8,
+                                      _stream()), "vad_trim_seg")
+        if return_measures:
+            mlen = int(sample_rate * 0.1 + .5)
+            for s in range(n):
+                L, at = int(tab[s + 1] - tab[s]), int(tab[s]) // period
+                M = (L - mlen) // period + 1 if L >= mlen else 0
+                measures.append((meas[0, at:at + M], meas[1, at:at + M]))
+    return (strip, measures) if return_measures else strip

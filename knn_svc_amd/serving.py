@@ -37,15 +37,18 @@ from . import matching as M
 
 
 class TargetVoice:
-    """The resident pool of one target speaker (a file, or a folder of files; ``duration_limit`` in seconds as --dur_limit)."""
+    """The resident pool of one target speaker (a file, or a folder of files; ``duration_limit`` in seconds as --dur_limit).
+    ``vad_trigger_level``: the files are trimmed of the silence at both ends with that trigger level before they are encoded
+    (matching.get_complete_spk_pool; None: left whole).  Every BatchConverter on this voice then matches against the trimmed pool."""
 
-    def __init__(self, vc, ref_path, duration_limit=None):
+    def __init__(self, vc, ref_path, duration_limit=None, vad_trigger_level=None):
         self.ref_path = str(ref_path)
         self.ref_id = os.path.basename(self.ref_path).split(".")[0]
         with torch.inference_mode():
             vc.wavlm.set_layer_mix(M._mix_of(vc.weighting, vc.wavlm))
             mp, _s, _a, _spec, f0p, hp = M.get_complete_spk_pool(Path(ref_path), vc.wavlm, device=vc.device,
-                                                                 duration_limit=duration_limit)
+                                                                 duration_limit=duration_limit,
+                                                                 vad_trigger_level=0 if vad_trigger_level is None else vad_trigger_level)
             keys = list(mp)
             self.files = keys
             self.feats = torch.cat([mp[k] for k in keys], 0).contiguous()
