@@ -9,6 +9,9 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+import os
+import threading
+from collections import namedtuple
 
 import torch
 
@@ -59,7 +62,6 @@ def pack_convT_weight(w: torch.Tensor, u: int) -> torch.Tensor:
 def gemm_mode() -> str:
     """KNNSVC_GEMM = f16x2 (default) | bf16x3 | fp32: how conv_gemm evaluates fp32 products for weights that
     went through attach_split (all three keep fp32-GEMM accuracy; see gemm2_core.h / gemm3_core.h)."""
-    import os
     mode = os.environ.get("KNNSVC_GEMM", "f16x2")
     if mode not in ("f16x2", "bf16x3", "fp32"):
         raise KnnSvcError(f"KNNSVC_GEMM={mode!r}: expected f16x2, bf16x3 or fp32")
@@ -263,7 +265,6 @@ def absmax(x2d, slot=None):
 
 def resblock_pair_ok(channels: int, taps: int, dil: int) -> bool:
     """The fused ResBlock pair covers the generator's narrow stages (knnsvc_resblock_pair); KNNSVC_FUSED_PAIR=0 switches it off."""
-    import os
     widths = (32, 64, 128) if os.environ.get("KNNSVC_FUSED_PAIR_128", "0") == "1" else (32, 64)
     return (os.environ.get("KNNSVC_FUSED_PAIR", "1") != "0" and gemm_mode() == "f16x2" and channels in widths and
             taps % 2 == 1 and taps <= 11 and dil * (taps - 1) <= 64)
@@ -389,7 +390,6 @@ def wavlm_gate(xn2d, heads, w2, b2, grep_a, x_split=False):
 
 def attention_mode() -> str:
     """KNNSVC_ATTENTION = f16x2 (default) | bf16x3 | fp32, as knnsvc_wavlm_attention reads it."""
-    import os
     e = os.environ.get("KNNSVC_ATTENTION", "")
     return "bf16x3" if e[:1] == "b" else "fp32" if e[:2] == "fp" else "f16x2"
 
@@ -415,13 +415,11 @@ def wavlm_attention(qkv, gate, table, batches, T, heads, out_split=False, kv_spl
 
 
 # ------------------------------------------------------------------ kNN
-import os as _os
-_SLOT_DBG = _os.environ.get("KNNSVC_SLOT_DBG", "")
+_SLOT_DBG = os.environ.get("KNNSVC_SLOT_DBG", "")
 
 
 def range_slots_on() -> bool:
     """KNNSVC_RANGE_SLOTS=0 (A/B aid): f16x2 GEMMs fall back to the fixed activation scale 16 (|x| < 4094)."""
-    import os
     return os.environ.get("KNNSVC_RANGE_SLOTS", "1") != "0"
 
 
@@ -442,149 +440,30 @@ def row_norms(x2d, slot=None):
 def knn_mode() -> str:
     """KNNSVC_KNN = f16x2 | fp32.  f16x2 (default while KNNSVC_GEMM is f16x2): q.p^T from the emulated-fp32 GEMM +
     knnsvc_knn_select; fp32: the fused exact-fp32-MFMA tile kernel (knnsvc_knn_topk)."""
-    import os
     mode = os.environ.get("KNNSVC_KNN", "f16x2" if gemm_mode() == "f16x2" else "fp32")
     if mode not in ("f16x2", "fp32"):
         raise KnnSvcError(f"KNNSVC_KNN={mode!r}: expected f16x2 or fp32")
     return mode
 
 
-def knn_pool_chunks(npool: int, dim: int):
-    """The f16x2 routes' pool chunk plan: [(first row, end row), ...] — balanced chunks (no tail shorter than k) of at most
-    p_cap rows, so that every buffer resource of a chunk (fp32 rows, split image) stays below 1 GiB."""
-    p_cap = ((1 << 30) - 1) // (dim * 4) // 128 * 128
-    n_chunks = max(1, -(-npool // p_cap))
-    p_rows = -(-npool // n_chunks)
-    return [(p0, min(npool, p0 + p_rows)) for p0 in range(0, npool, p_rows)]
-
-
-def prepare_knn_pool(pool, k=32, p_stats=None):
-    """Pre-split image of a pool for the two-kernel kNN route, reusable across searches against the same pool
-    (dataset mode and prematch search one pool once per utterance): list of (first row, rows view, f16x2 image, range
-    slot).  The fp16 split needs a power-of-two pre-scale that fits the features' range; WavLM features have no a-priori
-    bound (outlier channels), so the scale is derived ON THE DEVICE from max|pool| (knnsvc_absmax -> knnsvc_split_f16x2_dyn;
-    the GEMM reads the same slot as w_absmax) — no host round trip, no fixed range.
-    Returns None when the route does not apply (see knn_topk)."""
-    _need(pool, name="knn.pool")
-    npool, dim = pool.shape
-    if not (knn_mode() == "f16x2" and dim % 32 == 0 and npool >= k and pool.is_contiguous()):
-        return None
-    lib = _lib.load()
-    chunks = []
-    for p0, p1 in knn_pool_chunks(npool, dim):
-        pc = pool[p0:p1]
-        npc = pc.shape[0]
-        if npc < k:
-            raise KnnSvcError("knn_topk: pool chunk smaller than k")
-        slot = getattr(p_stats[0], "_slot", None) if p_stats is not None else None      # bound of the whole pool: fine for a chunk
-        if slot is None:
-            slot = absmax(pc)
-        # rows padded to a multiple of 4 (zero images): the dot-matrix GEMM runs on the 256x256 kernel, whose 16-byte epilogue
-        # wants n % 4 == 0 — the padded columns' dots are never looked at (knn_select gets the true row count)
-        npad = -(-npc // 4) * 4
-        p2 = torch.empty(npad * (dim // 32) * 64, device=pool.device, dtype=torch.int16)
-        if npad != npc:
-            p2[npc * (dim // 32) * 64:].zero_()
-        check(lib.knnsvc_split_f16x2_dyn(_p(pc), npc, dim, _p(slot), _p(p2), _stream()), "split_pool")
-        chunks.append((p0, pc, p2, slot))
-    return chunks
-
-
-def knn_rescore_on() -> bool:
-    """KNNSVC_KNN_RESCORE=0 (A/B aid): the lists keep the order of the screening distances (round 4's behaviour) instead of
-    being re-scored from exact dot products (knnsvc_knn_rescore)."""
-    import os
-    return os.environ.get("KNNSVC_KNN_RESCORE", "1") != "0"
-
-
+KNN_RSRC_BYTES = 1 << 30          # every buffer resource of a search stays below this: the one place the bound is written
 KNN_WIDE = 64                     # keys per row of a wide list (include/knnsvc_hip.h, knnsvc_knn_rescore)
 KNN_GUARD = 4.0e-6                # the wide lists keep everything within this of the k-th screening distance (csrc/knn.hip)
-
-
-def knn_guard(dim: int, mode: str = "f16x2") -> float:
-    """Guard band of a search's wide lists (csrc/knn.hip: KNN_GUARD, knn_guard_fp32): the f16x2 routes keep KNN_GUARD, the
-    fp32-MFMA tile route (KNNSVC_KNN=fp32), whose screening error grows with dim, 5e-7 sqrt(dim) and at least KNN_GUARD."""
-    return KNN_GUARD if mode != "fp32" else max(KNN_GUARD, 5.0e-7 * math.sqrt(dim))
-
-
-def _knn_rescore(wide, q, qn, qs, pc, pn, ps, k, idx_offset, mask, idx_out, dist_out):
-    """wide [m, 64] int64 keys -> exact top-k (idx_out / dist_out [m, k])."""
-    m, dim = q.shape
-    check(_lib.load().knnsvc_knn_rescore(_p(wide), m, k, _p(q), _p(qn), _p(qs), _p(pc), _p(pn), _p(ps), pc.shape[0], dim, idx_offset,
-                                         mask[0], mask[1], 1 if knn_rescore_on() else 0, _p(idx_out), _p(dist_out), _stream()), "knn_rescore")
-
-
-def _knn_topk_gemm(q, pool, k, idx_offset, qn, qs, pn, ps, flag, mask=(0, 0), prepared=None, allow_fused=True, max_blocks=0, zeros=None):
-    """q.p^T on the f16x2 matrix-core loop (Gemm2QuadS), then the reference's distance formula + selection.  Two routes over
-    the SAME dot-product bits (both sum over K in the 16x16x32 grouping, whatever the sizes):
-      * fused (default from a few hundred query rows on): knnsvc_knn_screen + knnsvc_knn_refine, no dot matrix (_knn_fused_chunk);
-      * dot matrix: knnsvc_conv_gemm (fixed_tile = 2, pool rows = pre-split "weights") + knnsvc_knn_select.
-    Both operands are scaled by device-chosen powers of two (range slots, see prepare_knn_pool) — exact, so the dots do not
-    depend on the scale.  Pool and query are chunked so that every buffer resource stays below 1 GiB and the dot matrix below
-    ~1 GiB; pool chunks are folded with knnsvc_knn_merge.  ``flag``: bit 0 = NaN distance, bit 1 = the fused route's candidate
-    buffer overflowed (results of that call are then NOT valid: knn_topk / raise_if_nan turn it into a retry on the dot-matrix
-    route) — read by the caller, never here: no host synchronisation inside a search."""
-    lib = _lib.load()
-    nq, dim = q.shape
-    dev = q.device
-    q_rows_cap = ((1 << 30) - 1) // (dim * 4) // 128 * 128
-    parts_i, parts_d = [], []
-    # the queries are split once into the A2 layout (the weight-split kernel writes exactly that image)
-    q_slot = getattr(qn, "_slot", None)
-    if q_slot is None:
-        q_slot = absmax(q)
-    q2 = torch.empty(nq, dim, device=dev, dtype=torch.float32)
-    check(lib.knnsvc_split_f16x2_dyn(_p(q), nq, dim, _p(q_slot), _p(q2), _stream()), "split_queries")
-    fused = allow_fused and knn_fused_on() and nq >= KNN_FUSED_MIN_Q
-    for p0, pc, p2, p_slot in (prepared if prepared is not None else prepare_knn_pool(pool, k, (pn, ps))):
-        npc = pc.shape[0]
-        idx = torch.empty(nq, k, device=dev, dtype=torch.int64)
-        dist = torch.empty(nq, k, device=dev, dtype=torch.float32)
-        KNN_ROUTE_COUNTS["chunks"] += 1
-        if fused and npc >= KNN_FUSED_MIN_P:
-            KNN_ROUTE_COUNTS["fused"] += 1
-            _knn_fused_chunk(q, q2, q_slot, qn, qs, pc, p2, p_slot, pn[p0:], ps[p0:], k, idx_offset + p0,
-                             (mask[0] - p0, mask[1] - p0), idx, dist, flag, max_blocks, zeros)
-        else:
-            KNN_ROUTE_COUNTS["dot"] += 1
-            npad = -(-npc // 4) * 4
-            q_rows = max(128, min(nq, q_rows_cap, (1 << 28) // max(npad, 1) // 128 * 128))
-            for q0 in range(0, nq, q_rows):
-                qc = q2[q0:q0 + q_rows]
-                m = qc.shape[0]
-                dots = torch.empty(m, npad, device=dev, dtype=torch.float32)
-                conv_gemm(qc, pc, dots, m=m, n=npad, cin=dim, w2=p2, x_split=True, x_absmax=q_slot, w_absmax=p_slot,
-                          fixed_tile=2)         # a shard / a query set of any size gives the whole search's distance bits
-                wide = torch.empty(m, KNN_WIDE, device=dev, dtype=torch.int64)
-                check(lib.knnsvc_knn_select(_p(dots), npad, _p(qn[q0:]), _p(qs[q0:]), m, _p(pn[p0:]), _p(ps[p0:]), npc, k,
-                                            mask[0] - p0, mask[1] - p0, _p(wide), _p(flag), _stream()), "knn_select")
-                _knn_rescore(wide, q[q0:q0 + m], qn[q0:], qs[q0:], pc, pn[p0:], ps[p0:], k, idx_offset + p0,
-                             (mask[0] - p0, mask[1] - p0), idx[q0:], dist[q0:])
-        parts_i.append(idx); parts_d.append(dist)
-    if len(parts_i) == 1:
-        return parts_i[0], parts_d[0]
-    return knn_merge(torch.stack(parts_d), torch.stack(parts_i))
-
-
 KNN_ROUTE_COUNTS = {"chunks": 0, "fused": 0, "dot": 0}     # which route each (search, pool chunk) took: tests assert on it
 # The fused route (epochs of knnsvc_knn_screen + knnsvc_knn_refine, no dot matrix) from 256 query frames x 8192 pool rows on.
 # Round 3 (threshold from a separate sample pass: ~0.15 ms whatever the size) had 2048 / 8192; round 2 4096 / 32768.
-KNN_FUSED_MIN_Q = int(_os.environ.get("KNNSVC_KNN_FUSED_MIN_Q", "256"))
-KNN_FUSED_MIN_P = int(_os.environ.get("KNNSVC_KNN_FUSED_MIN_P", "8192"))
+KNN_FUSED_MIN_Q = int(os.environ.get("KNNSVC_KNN_FUSED_MIN_Q", "256"))
+KNN_FUSED_MIN_P = int(os.environ.get("KNNSVC_KNN_FUSED_MIN_P", "8192"))
 KNN_FUSED_CAP = 4096
 KNN_OVERFLOW = 2                  # flag bit: the fused route's candidate buffer overflowed
 KNN_DEBUG_COUNTS = None
-KNN_EPOCH_GROWTH = int(_os.environ.get("KNNSVC_KNN_EPOCH_GROWTH", "4"))
+KNN_EPOCH_GROWTH = int(os.environ.get("KNNSVC_KNN_EPOCH_GROWTH", "4"))
 KNN_COLD_TILES_MAX = 44           # column tiles of the first epoch: ~45 candidates per (row, tile) have to fit the buffer twice over
+_FUSED_OFF = threading.local()    # per host thread (the request-queue worker's retry must not reroute the main thread's searches)
 
 
 def knn_fused_on() -> bool:
-    import os
     return os.environ.get("KNNSVC_KNN_FUSED", "1") != "0" and not getattr(_FUSED_OFF, "on", False)
-
-
-import threading as _threading
-_FUSED_OFF = _threading.local()      # per host thread (the request-queue worker's retry must not reroute the main thread's searches)
 
 
 class fused_off:
@@ -593,6 +472,24 @@ class fused_off:
         self.prev = getattr(_FUSED_OFF, "on", False); _FUSED_OFF.on = True
     def __exit__(self, *a):
         _FUSED_OFF.on = self.prev
+
+
+class KnnOverflow(KnnSvcError):
+    """The fused kNN route met a query row with more candidates than its buffer holds: the search has to be repeated on the
+    dot-matrix route (``with ops.fused_off(): ...``).  Not an error of the data — many near-identical pool rows do it."""
+
+
+def _knn_p_cap(dim: int) -> int:
+    """Most fp32 rows (a multiple of 128) of one buffer resource."""
+    return (KNN_RSRC_BYTES - 1) // (dim * 4) // 128 * 128
+
+
+def knn_pool_chunks(npool: int, dim: int):
+    """The f16x2 routes' pool chunk plan: [(first row, end row), ...] — balanced chunks (no tail shorter than k) of at most
+    p_cap rows, so that every buffer resource of a chunk (fp32 rows, split image) stays below KNN_RSRC_BYTES."""
+    n_chunks = max(1, -(-npool // _knn_p_cap(dim)))
+    p_rows = -(-npool // n_chunks)
+    return [(p0, min(npool, p0 + p_rows)) for p0 in range(0, npool, p_rows)]
 
 
 def knn_epochs(nq: int, npc: int, blocks: int = 256):
@@ -613,29 +510,128 @@ def knn_epochs(nq: int, npc: int, blocks: int = 256):
     return out
 
 
-def _knn_fused_chunk(q, q2, q_slot, qn, qs, pc, p2, p_slot, pn, ps, k, idx_offset, mask, idx_out, dist_out, flag, max_blocks=0, zeros=None):
+# What knn_plan returns.  KnnBlock: query rows [q0, q0 + m) of one pool chunk; fused route: the block's ``epochs`` (knn_epochs) and
+# the int32 words it needs zeroed, ``fill``: candidate counts [m] | the first epoch's workspace: row bounds [m], per-half-tile
+# bounds [2 gy0][m] (the tiles' exchange, knn.hip), arrival counters [gx] one cache line each.  KnnChunkPlan: pool rows
+# [p0, p1), their route, ``npad`` = rows of their split image = columns of their dot matrix, the query blocks.  KnnPlan:
+# ``fill_words``: the first-epoch workspace that rides in the search's one fill (0: every block zeroes its own).
+KnnBlock = namedtuple("KnnBlock", "q0 m epochs fill")
+KnnChunkPlan = namedtuple("KnnChunkPlan", "p0 p1 fused npad blocks")
+KnnPlan = namedtuple("KnnPlan", "chunks fill_words")
+# One chunk of a prepared pool: first row, fp32 rows (a view), their f16x2 image (npad rows), range slot.
+KnnChunk = namedtuple("KnnChunk", "p0 rows image slot")
+
+
+def knn_plan(nq: int, npool: int, dim: int, k: int, *, allow_fused=True, max_blocks=0, chunk_bounds=None) -> KnnPlan:
+    """How an f16x2 search is cut up — integers only, nothing touches the device.  The pool in chunks (``chunk_bounds``: those
+    of a prepared pool, else knn_pool_chunks); each chunk on the fused route (knnsvc_knn_screen + knnsvc_knn_refine) or the
+    dot-matrix route (knnsvc_conv_gemm + knnsvc_knn_select); its queries in blocks so that the split image, the candidate
+    buffer and the dot matrix each stay within KNN_RSRC_BYTES; a fused block in epochs.  ``fill_words`` is non-zero only where
+    the search is ONE pool chunk, fused, in ONE query block: a second chunk or block must not inherit the first one's row
+    bounds and arrival counters."""
+    R = KNN_RSRC_BYTES
+    fused_q = allow_fused and knn_fused_on() and nq >= KNN_FUSED_MIN_Q
+    chunks = []
+    for p0, p1 in (knn_pool_chunks(npool, dim) if chunk_bounds is None else chunk_bounds):
+        npc = p1 - p0
+        if npc < k:
+            raise KnnSvcError("knn_topk: pool chunk smaller than k")
+        # rows padded to a multiple of 4 (zero images): the dot-matrix GEMM runs on the 256x256 kernel, whose 16-byte epilogue
+        # wants n % 4 == 0 — the padded columns' dots are never looked at (knn_select gets the true row count)
+        npad = -(-npc // 4) * 4
+        fused = fused_q and npc >= KNN_FUSED_MIN_P
+        q_rows = (max(256, min(nq, (R // 4 - 1) // dim // 256 * 256, R // (KNN_FUSED_CAP * 8) // 256 * 256)) if fused else
+                  max(128, min(nq, _knn_p_cap(dim), (R // 4) // max(npad, 1) // 128 * 128)))
+        blocks = []
+        for q0 in range(0, nq, q_rows):
+            m = min(q_rows, nq - q0)
+            ep = tuple(knn_epochs(m, npc, int(max_blocks) if max_blocks else 256)) if fused else ()
+            blocks.append(KnnBlock(q0, m, ep, m * (2 + 2 * (ep[0][1] - ep[0][0])) + 32 * -(-m // 256) if fused else 0))
+        chunks.append(KnnChunkPlan(p0, p1, fused, npad, tuple(blocks)))
+    one = len(chunks) == 1 and chunks[0].fused and len(chunks[0].blocks) == 1
+    return KnnPlan(tuple(chunks), chunks[0].blocks[0].fill if one else 0)
+
+
+def knn_search_fill(nq: int, npool: int, dim: int, max_blocks: int = 0) -> int:
+    """int32 words of the fused route's first-epoch workspace that knn_topk folds into its one fill (0: none): knn_plan's."""
+    return knn_plan(nq, npool, dim, 1, max_blocks=max_blocks).fill_words
+
+
+def prepare_knn_pool(pool, k=32, p_stats=None, plan=None):
+    """Pre-split image of a pool for the two-kernel kNN route, reusable across searches against the same pool
+    (dataset mode and prematch search one pool once per utterance): list of KnnChunk (first row, rows view, f16x2 image, range
+    slot), cut where ``plan`` says (a search hands in its own; default: knn_plan's chunks for this pool).  The fp16 split
+    needs a power-of-two pre-scale that fits the features' range; WavLM features have no a-priori bound (outlier channels),
+    so the scale is derived ON THE DEVICE from max|pool| (knnsvc_absmax -> knnsvc_split_f16x2_dyn; the GEMM reads the same
+    slot as w_absmax) — no host round trip, no fixed range.
+    Returns None when the route does not apply (see knn_topk)."""
+    _need(pool, name="knn.pool")
+    npool, dim = pool.shape
+    if not (knn_mode() == "f16x2" and dim % 32 == 0 and npool >= k and pool.is_contiguous()):
+        return None
+    chunks = []
+    for p0, p1, _, npad, _ in (plan or knn_plan(0, npool, dim, k)).chunks:
+        pc, npc = pool[p0:p1], p1 - p0
+        slot = getattr(p_stats[0], "_slot", None) if p_stats is not None else None      # bound of the whole pool: fine for a chunk
+        if slot is None:
+            slot = absmax(pc)
+        p2 = torch.empty(npad * (dim // 32) * 64, device=pool.device, dtype=torch.int16)
+        if npad != npc:
+            p2[npc * (dim // 32) * 64:].zero_()
+        check(_lib.load().knnsvc_split_f16x2_dyn(_p(pc), npc, dim, _p(slot), _p(p2), _stream()), "split_pool")
+        chunks.append(KnnChunk(p0, pc, p2, slot))
+    return chunks
+
+
+def knn_rescore_on() -> bool:
+    """KNNSVC_KNN_RESCORE=0 (A/B aid): the lists keep the order of the screening distances (round 4's behaviour) instead of
+    being re-scored from exact dot products (knnsvc_knn_rescore)."""
+    return os.environ.get("KNNSVC_KNN_RESCORE", "1") != "0"
+
+
+def knn_guard(dim: int, mode: str = "f16x2") -> float:
+    """Guard band of a search's wide lists (csrc/knn.hip: KNN_GUARD, knn_guard_fp32): the f16x2 routes keep KNN_GUARD, the
+    fp32-MFMA tile route (KNNSVC_KNN=fp32), whose screening error grows with dim, 5e-7 sqrt(dim) and at least KNN_GUARD."""
+    return KNN_GUARD if mode != "fp32" else max(KNN_GUARD, 5.0e-7 * math.sqrt(dim))
+
+
+# What every launch of an f16x2 search reads.  ``q2`` / ``q_slot``: the queries' f16x2 image and range slot (_knn_search); ``pn`` /
+# ``ps`` / ``mask`` / ``idx_offset`` count pool rows from the pool's first row — or, in the form the executors get (_knn_search), from a chunk's.
+_KnnSearch = namedtuple("_KnnSearch", "q qn qs pn ps k idx_offset mask flag max_blocks q2 q_slot", defaults=(None, None))
+
+
+def _knn_rescore(s, c, q0, m, wide, idx_out, dist_out):
+    """wide [m, 64] int64 keys of query rows [q0, q0 + m) -> their exact top-k (rows q0.. of idx_out / dist_out [nq, k])."""
+    check(_lib.load().knnsvc_knn_rescore(_p(wide), m, s.k, _p(s.q[q0:]), _p(s.qn[q0:]), _p(s.qs[q0:]), _p(c.rows), _p(s.pn), _p(s.ps),
+                                         c.rows.shape[0], s.q.shape[1], s.idx_offset, s.mask[0], s.mask[1], 1 if knn_rescore_on() else 0,
+                                         _p(idx_out[q0:]), _p(dist_out[q0:]), _stream()), "knn_rescore")
+
+
+def _knn_dot_chunk(s, c, plan, idx_out, dist_out):
+    """One pool chunk through the dot matrix: per query block knnsvc_conv_gemm (fixed_tile = 2, pool rows = pre-split
+    "weights") + knnsvc_knn_select.  ``s`` is chunk-local."""
+    dev, dim, npc = s.q.device, s.q.shape[1], c.rows.shape[0]
+    for q0, m, _, _ in plan.blocks:
+        dots = torch.empty(m, plan.npad, device=dev, dtype=torch.float32)
+        conv_gemm(s.q2[q0:q0 + m], c.rows, dots, m=m, n=plan.npad, cin=dim, w2=c.image, x_split=True, x_absmax=s.q_slot,
+                  w_absmax=c.slot, fixed_tile=2)    # a shard / a query set of any size gives the whole search's distance bits
+        wide = torch.empty(m, KNN_WIDE, device=dev, dtype=torch.int64)
+        check(_lib.load().knnsvc_knn_select(_p(dots), plan.npad, _p(s.qn[q0:]), _p(s.qs[q0:]), m, _p(s.pn), _p(s.ps), npc, s.k,
+                                            s.mask[0], s.mask[1], _p(wide), _p(s.flag), _stream()), "knn_select")
+        _knn_rescore(s, c, q0, m, wide, idx_out, dist_out)
+
+
+def _knn_fused_chunk(s, c, plan, idx_out, dist_out, zeros=None):
     """One pool chunk without a [nq, np] dot matrix: the chunk's rows in epochs (knn_epochs), each one knnsvc_knn_screen (the
     first without thresholds, the later ones against the row's k-th key so far) + one knnsvc_knn_refine (list so far + the new
     candidates -> list, next thresholds).  A row with more survivors than the candidate buffer holds (pathological data: e.g.
-    thousands of bit-identical pool rows inside the first epoch) sets bit 1 of ``flag``; nothing here reads it."""
+    thousands of bit-identical pool rows inside the first epoch) sets bit 1 of the flag; nothing here reads it.  ``s`` is
+    chunk-local; ``zeros``: the block's ``fill`` words, already zeroed as part of the search's ONE fill (knn_plan: fill_words)."""
     lib = _lib.load()
-    nq, dim = q.shape
-    npc = pc.shape[0]
-    dev = q.device
+    dev, dim, npc = s.q.device, s.q.shape[1], c.rows.shape[0]
     row_u16 = (dim // 32) * 64                                     # int16 elements of one pool row in the split image
-    blocks = int(max_blocks) if max_blocks else 256
-    q_rows = max(256, min(nq, ((1 << 28) - 1) // dim // 256 * 256, (1 << 30) // (KNN_FUSED_CAP * 8) // 256 * 256))
-    for q0 in range(0, nq, q_rows):
-        m = min(q_rows, nq - q0)
-        epochs = knn_epochs(m, npc, blocks)
-        # one fill: candidate counts [m] | the first epoch's workspace: row bounds [m], per-half-tile bounds [2 gy0][m] (the tiles'
-        # exchange, knn.hip), arrival counters [gx] one cache line each
-        gy0 = epochs[0][1] - epochs[0][0]
-        nz = m * (2 + 2 * gy0) + 32 * -(-m // 256)
-        if zeros is not None and zeros.numel() == nz and q0 == 0:
-            zeroed = zeros                              # part of the search's ONE fill (knn_topk)
-        else:
-            zeroed = torch.zeros(nz, device=dev, dtype=torch.int32)
+    for q0, m, epochs, fill in plan.blocks:
+        zeroed = zeros if zeros is not None else torch.zeros(fill, device=dev, dtype=torch.int32)
         cnt, bound = zeroed[:m], zeroed[m:]
         cand = torch.empty(m * KNN_FUSED_CAP * 2, device=dev, dtype=torch.int32)
         wide = torch.empty(m, KNN_WIDE, device=dev, dtype=torch.int64)       # the rows' wide lists, handed from epoch to epoch
@@ -646,27 +642,49 @@ def _knn_fused_chunk(q, q2, q_slot, qn, qs, pc, p2, p_slot, pn, ps, k, idx_offse
             last = e == len(epochs) - 1
             # both kernels OR their bits straight into the search's flag (bit 0: NaN distance, bit 1: candidate-buffer overflow
             # or a short list): no glue kernels between the launches
-            check(lib.knnsvc_knn_screen(_p(q2[q0:]), _p(q_slot), _p(qn[q0:]), _p(qs[q0:]), m, _p(p2[c0 * row_u16:]), _p(p_slot), _p(pn[c0:]),
-                                        _p(ps[c0:]), c1 - c0, dim, _p(thr) if e else _p(None), _p(thr_idx) if e else _p(None), mask[0], mask[1],
-                                        c0, _p(cnt), _p(cand), KNN_FUSED_CAP, _p(None) if e else _p(bound), _p(flag), int(max_blocks), _stream()), "knn_screen")
+            check(lib.knnsvc_knn_screen(_p(s.q2[q0:]), _p(s.q_slot), _p(s.qn[q0:]), _p(s.qs[q0:]), m, _p(c.image[c0 * row_u16:]), _p(c.slot),
+                                        _p(s.pn[c0:]), _p(s.ps[c0:]), c1 - c0, dim, _p(thr) if e else _p(None), _p(thr_idx) if e else _p(None),
+                                        s.mask[0], s.mask[1], c0, _p(cnt), _p(cand), KNN_FUSED_CAP, _p(None) if e else _p(bound), _p(s.flag),
+                                        int(s.max_blocks), _stream()), "knn_screen")
             if KNN_DEBUG_COUNTS is not None:           # tools/knn_prof.py: survivors per row and epoch (a clone: refine resets the counts)
                 KNN_DEBUG_COUNTS.append((e, cnt.clone()))
-            check(lib.knnsvc_knn_refine(_p(cnt), _p(cand), KNN_FUSED_CAP, m, k, _p(None) if e else _p(bound), 1 if e else 0, _p(wide),
-                                        _p(None) if last else _p(thr), _p(None) if last else _p(thr_idx), 1 if last else 0, _p(flag),
+            check(lib.knnsvc_knn_refine(_p(cnt), _p(cand), KNN_FUSED_CAP, m, s.k, _p(None) if e else _p(bound), 1 if e else 0, _p(wide),
+                                        _p(None) if last else _p(thr), _p(None) if last else _p(thr_idx), 1 if last else 0, _p(s.flag),
                                         _stream()), "knn_refine")
         # the candidates' order came from the screening products; the order that goes out comes from exact ones
-        _knn_rescore(wide, q[q0:q0 + m], qn[q0:], qs[q0:], pc, pn, ps, k, idx_offset, mask, idx_out[q0:], dist_out[q0:])
+        _knn_rescore(s, c, q0, m, wide, idx_out, dist_out)
 
 
-def knn_search_fill(nq: int, npool: int, dim: int, max_blocks: int = 0) -> int:
-    """int32 words of the fused route's first-epoch workspace that knn_topk folds into its one fill (0: none) — only where the
-    search is one fused launch sequence over ONE pool chunk and one query chunk: a second chunk must not inherit the first one's
-    row bounds and arrival counters."""
-    if not (knn_fused_on() and nq >= KNN_FUSED_MIN_Q and npool >= KNN_FUSED_MIN_P and len(knn_pool_chunks(npool, dim)) == 1 and
-            nq * dim < (1 << 28) and nq * KNN_FUSED_CAP * 8 <= (1 << 30)):
-        return 0
-    ep = knn_epochs(nq, npool, int(max_blocks) if max_blocks else 256)
-    return nq * (2 + 2 * (ep[0][1] - ep[0][0])) + 32 * -(-nq // 256)
+def _knn_search(s, pool, prepared, plan, zeros=None):
+    """``plan`` (knn_plan) carried out: q.p^T on the f16x2 matrix-core loop (Gemm2QuadS), then the reference's distance formula
+    + selection, on two routes over the SAME dot-product bits (both sum over K in the 16x16x32 grouping, whatever the sizes).
+    Both operands are scaled by device-chosen powers of two (range slots, see prepare_knn_pool) — exact, so the dots do not
+    depend on the scale.  Pool chunks are folded with knnsvc_knn_merge.  ``s.flag``: bit 0 = NaN distance, bit 1 = the fused
+    route's candidate buffer overflowed (the results are then NOT valid: knn_topk / raise_if_nan turn it into a retry on the
+    dot-matrix route) — read by the caller, never here: no host synchronisation inside a search.  ``zeros``: plan.fill_words
+    zeroed words."""
+    q, k, dev = s.q, s.k, s.q.device
+    nq, dim = q.shape
+    # the queries are split once into the A2 layout (the weight-split kernel writes exactly that image)
+    q_slot = getattr(s.qn, "_slot", None)
+    if q_slot is None:
+        q_slot = absmax(q)
+    q2 = torch.empty(nq, dim, device=dev, dtype=torch.float32)
+    check(_lib.load().knnsvc_split_f16x2_dyn(_p(q), nq, dim, _p(q_slot), _p(q2), _stream()), "split_queries")
+    s = s._replace(q2=q2, q_slot=q_slot)
+    parts = []
+    for c, cp in zip(prepared if prepared is not None else prepare_knn_pool(pool, k, (s.pn, s.ps), plan), plan.chunks):
+        idx = torch.empty(nq, k, device=dev, dtype=torch.int64)
+        dist = torch.empty(nq, k, device=dev, dtype=torch.float32)
+        KNN_ROUTE_COUNTS["chunks"] += 1; KNN_ROUTE_COUNTS["fused" if cp.fused else "dot"] += 1
+        # the search as this chunk sees it — the one place the chunk-local views are formed
+        loc = s._replace(pn=s.pn[c.p0:], ps=s.ps[c.p0:], mask=(s.mask[0] - c.p0, s.mask[1] - c.p0), idx_offset=s.idx_offset + c.p0)
+        if cp.fused:
+            _knn_fused_chunk(loc, c, cp, idx, dist, zeros)
+        else:
+            _knn_dot_chunk(loc, c, cp, idx, dist)
+        parts.append((idx, dist))
+    return parts[0] if len(parts) == 1 else knn_merge(torch.stack([d for _, d in parts]), torch.stack([i for i, _ in parts]))
 
 
 def knn_topk(q, pool, k=32, idx_offset=0, q_stats=None, p_stats=None, check_nan=True, return_flag=False, mask=None,
@@ -677,6 +695,7 @@ def knn_topk(q, pool, k=32, idx_offset=0, q_stats=None, p_stats=None, check_nan=
     ``check_nan=True``: the flag is read here (one sync); a NaN raises, a candidate-buffer overflow of the fused route repeats the
     search on the dot-matrix route.  ``check_nan=False, return_flag=True``: nothing is read; the caller hands the flag to
     ``raise_if_nan`` once everything is enqueued (KnnOverflow -> it repeats the work with ``fused_off()``).
+    ``prepared``: prepare_knn_pool's chunks of this pool; the search is then planned on their bounds.
     ``max_blocks``: grid cap of the persistent screening kernel (0 = the whole chip)."""
     mask = (0, 0) if mask is None else (int(mask[0]), int(mask[1]))
     _need(q, name="knn.q"); _need(pool, name="knn.pool")
@@ -686,11 +705,14 @@ def knn_topk(q, pool, k=32, idx_offset=0, q_stats=None, p_stats=None, check_nan=
     nq, dim = q.shape
     npool = pool.shape[0]
     f16 = knn_mode() == "f16x2" and dim % 32 == 0 and npool >= k and nq > 0 and 1 <= k <= 32
-    # ONE fill for everything a search needs zeroed — its flag, the two operands' range slots and (fused route, one chunk) the
-    # candidate counts + first-epoch workspace: four tiny fill launches were ~5 us each in front of a 0.4 ms search
+    # ONE fill for everything a search needs zeroed — its flag, the two operands' range slots and (one fused block over a pool
+    # that is not prepared: plan.fill_words) the candidate counts + first-epoch workspace: four tiny fill launches were ~5 us
+    # each in front of a 0.4 ms search
     flag = zeros = None
     if f16:
-        nz = knn_search_fill(nq, npool, dim, max_blocks) if prepared is None else 0
+        bounds = None if prepared is None else [(c.p0, c.p0 + c.rows.shape[0]) for c in prepared]
+        plan = knn_plan(nq, npool, dim, k, max_blocks=max_blocks, chunk_bounds=bounds)
+        nz = plan.fill_words if prepared is None else 0
         zbuf = torch.zeros(64 + 2 * SLOT_W + nz, device=q.device, dtype=torch.int32)
         flag = zbuf[:1]
         sl_q, sl_p = zbuf[64:64 + SLOT_W].view(torch.float32), zbuf[64 + SLOT_W:64 + 2 * SLOT_W].view(torch.float32)
@@ -698,13 +720,14 @@ def knn_topk(q, pool, k=32, idx_offset=0, q_stats=None, p_stats=None, check_nan=
     qn, qs = q_stats if q_stats is not None else row_norms(q, sl_q if f16 else None)
     pn, ps = p_stats if p_stats is not None else row_norms(pool, sl_p if f16 else None)
     if f16:
-        idx, dist = _knn_topk_gemm(q, pool, k, idx_offset, qn, qs, pn, ps, flag, mask, prepared, max_blocks=max_blocks, zeros=zeros)
+        s = _KnnSearch(q, qn, qs, pn, ps, k, idx_offset, mask, flag, max_blocks)
+        idx, dist = _knn_search(s, pool, prepared, plan, zeros)
         if check_nan:
             try:
                 raise_if_nan(flag)
             except KnnOverflow:
                 flag.zero_()
-                idx, dist = _knn_topk_gemm(q, pool, k, idx_offset, qn, qs, pn, ps, flag, mask, prepared, allow_fused=False)
+                idx, dist = _knn_search(s, pool, prepared, knn_plan(nq, npool, dim, k, allow_fused=False, chunk_bounds=bounds))
                 raise_if_nan(flag)
         return (idx, dist, flag) if return_flag else (idx, dist)
     ws_bytes = lib.knnsvc_knn_workspace_bytes(nq, npool, k)
@@ -728,11 +751,6 @@ def retry_on_overflow(fn):
         KNN_ROUTE_COUNTS["overflow_retries"] = KNN_ROUTE_COUNTS.get("overflow_retries", 0) + 1
         with fused_off():
             return fn()
-
-
-class KnnOverflow(KnnSvcError):
-    """The fused kNN route met a query row with more candidates than its buffer holds: the search has to be repeated on the
-    dot-matrix route (``with ops.fused_off(): ...``).  Not an error of the data — many near-identical pool rows do it."""
 
 
 def raise_if_nan(flag):

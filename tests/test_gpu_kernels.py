@@ -1286,3 +1286,75 @@ def test_knn_crowded_guard_band_is_still_exact(dim, spread, monkeypatch):
     mask = (int(at.min()), int(at.min()) + 500)                # a self-mask over part of the crowd
     Dm = knn_ref.exact_distance_matrix(qd, pd, qn, qs, pn, ps, mask=mask)
     _knn_exact_check(ops, knn_ref, qd, pd, Dm, 32, "fused", monkeypatch, f"F5 dim {dim} spread {spread} masked", mask=mask)
+
+
+def test_knn_chunked_search_equals_the_unchunked_one_and_the_exact_oracle(monkeypatch):
+    """Every cut of the f16x2 search's host plan (ops.knn_plan) at a size a test can afford: with the resource bound at 16 MiB,
+    768 x 256 queries against 20000 pool rows are two pool chunks of two query blocks each, on either route — the second fused
+    query block (its offsets into the split image, the norms and the outputs), per-chunk masks and index offsets, and the merge.
+    All of it must give the bits of the one-chunk, one-block search at the default bound."""
+    from oracle import knn_ref
+    ops = _ops()
+    monkeypatch.setenv("KNNSVC_KNN", "f16x2")
+    monkeypatch.setenv("KNNSVC_KNN_FUSED", "1")
+    monkeypatch.setenv("KNNSVC_KNN_RESCORE", "1")
+    nq, npool, dim, k, mb = 768, 20000, 256, 32, 16
+    qd = S.clustered_features(nq, dim, 201, n_centres=60).to(DEV)
+    pd = S.clustered_features(npool, dim, 202, n_centres=60).to(DEV)
+    whole = ops.knn_plan(nq, npool, dim, k, max_blocks=mb)
+    assert len(whole.chunks) == 1 and len(whole.chunks[0].blocks) == 1 and whole.chunks[0].fused and whole.fill_words > 0
+    ref_i, ref_d = ops.knn_topk(qd, pd, k, max_blocks=mb)                          # default bound: one chunk, one block
+
+    def search(**kw):
+        c0 = dict(ops.KNN_ROUTE_COUNTS)
+        idx, dist, flag = ops.knn_topk(qd, pd, k, check_nan=False, return_flag=True, max_blocks=mb, **kw)
+        return idx, dist, int(flag.item()), {r: ops.KNN_ROUTE_COUNTS[r] - c0[r] for r in ("chunks", "fused", "dot")}
+
+    monkeypatch.setattr(ops, "KNN_RSRC_BYTES", 1 << 24)
+    plan = ops.knn_plan(nq, npool, dim, k, max_blocks=mb)
+    chunks = [(c.p0, c.p1) for c in plan.chunks]
+    assert chunks == [(0, 10000), (10000, 20000)] == ops.knn_pool_chunks(npool, dim) and plan.fill_words == 0
+    assert all(c.fused and [(b.q0, b.m) for b in c.blocks] == [(0, 512), (512, 256)] for c in plan.chunks)
+    with ops.fused_off():
+        assert all(not c.fused and len(c.blocks) == 2 for c in ops.knn_plan(nq, npool, dim, k, max_blocks=mb).chunks)
+    idx, dist, fl, ran = search()
+    assert fl == 0 and ran == {"chunks": 2, "fused": 2, "dot": 0}, (fl, ran)
+    with ops.fused_off():
+        di, dd, dfl, dran = search()
+    assert dfl == 0 and dran == {"chunks": 2, "fused": 0, "dot": 2}, (dfl, dran)
+    parts = [ops.knn_topk(qd, pd[a:b].contiguous(), k, idx_offset=a, max_blocks=mb) for a, b in chunks]
+    mi, md = ops.knn_merge(torch.stack([d for _, d in parts]), torch.stack([i for i, _ in parts]))
+    for tag, (i, d) in {"fused": (idx, dist), "dot": (di, dd)}.items():
+        assert torch.equal(i, ref_i) and torch.equal(d, ref_d), tag            # the search at the default bound
+        assert torch.equal(i, mi) and torch.equal(d, md), tag                  # the chunks searched separately, then merged
+    qn, qs = ops.row_norms(qd)
+    pn, ps = ops.row_norms(pd)
+    st = knn_ref.compare_to_exact(idx, dist, knn_ref.exact_distance_matrix(qd, pd, qn, qs, pn, ps), k)
+    print("two chunks x two query blocks vs exact oracle:", st)
+    assert st["bad_lists"] == 0 and st["unexplained"] == 0 and st["left_out"] == 0, st
+    assert int((idx >= chunks[1][0]).sum()) > 0 and int((idx < chunks[1][0]).sum()) > 0       # neighbours come from both chunks
+    prepared = ops.prepare_knn_pool(pd, k)
+    assert [(c.p0, c.rows.shape[0]) for c in prepared] == [(0, 10000), (10000, 10000)]
+    assert [p0 for p0, _rows, _image, _slot in prepared] == [0, 10000]
+    pi, pdist, pfl, pran = search(prepared=prepared)
+    assert pfl == 0 and pran == {"chunks": 2, "fused": 2, "dot": 0} and torch.equal(pi, idx) and torch.equal(pdist, dist)
+    # a self-mask across the chunk boundary: the masked rows query themselves (ddsp_prematch_dataset.py:1606-1607)
+    lo, hi = 9990, 10010
+    qm = qd.clone()
+    qm[:hi - lo] = pd[lo:hi]
+    qmn, qms = ops.row_norms(qm)
+    Dm = knn_ref.exact_distance_matrix(qm, pd, qmn, qms, pn, ps, mask=(lo, hi))
+    for route in ("fused", "dot"):
+        c0 = dict(ops.KNN_ROUTE_COUNTS)
+        if route == "fused":
+            m_i, m_d = ops.knn_topk(qm, pd, k, mask=(lo, hi), max_blocks=mb)
+        else:
+            with ops.fused_off():
+                m_i, m_d = ops.knn_topk(qm, pd, k, mask=(lo, hi), max_blocks=mb)
+        assert ops.KNN_ROUTE_COUNTS[route] - c0[route] == 2, route
+        masked = (m_i >= lo) & (m_i < hi)
+        assert bool((m_d[masked] == 1.0).all()), route
+        own = torch.arange(lo, hi, device=m_i.device)
+        assert bool((m_i[:hi - lo, 0] != own).all()), route                    # without the mask each would find itself at ~0
+        st = knn_ref.compare_to_exact(m_i, m_d, Dm, k)
+        assert st["bad_lists"] == 0 and st["unexplained"] == 0 and st["left_out"] == 0, (route, st)

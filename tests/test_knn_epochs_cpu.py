@@ -24,15 +24,16 @@ def test_north_star_point_is_one_cold_round_and_one_warm_epoch():
 
 
 def _window_points(dim):
-    p_cap = ((1 << 30) - 1) // (dim * 4) // 128 * 128
-    top = ((1 << 30) - 1) // (dim * 4)                          # the largest pool whose fp32 rows stay below 1 GiB
-    return p_cap, top, [p_cap - 1, p_cap, p_cap + 1, top, (1 << 30) // (4 * dim)]
+    R = ops.KNN_RSRC_BYTES
+    p_cap = (R - 1) // (dim * 4) // 128 * 128
+    top = (R - 1) // (dim * 4)                                  # the largest pool whose fp32 rows stay below the bound (1 GiB)
+    return p_cap, top, [p_cap - 1, p_cap, p_cap + 1, top, R // (4 * dim)]
 
 
 @pytest.mark.parametrize("dim", [256, 512, 768, 1024, 2048])
 def test_pool_chunk_plan_and_the_one_fill_agree_at_the_chunk_boundary(dim, monkeypatch):
     """ADVICE r5: the search's one pre-zeroed first-epoch workspace may only go to a search of ONE pool chunk (ops.knn_search_fill);
-    between p_cap (prepare_knn_pool's chunk size) and 2^30 / (4 dim) the pool splits into two chunks, which must each get
+    between p_cap (prepare_knn_pool's chunk size) and KNN_RSRC_BYTES / (4 dim) the pool splits into two chunks, which must each get
     their own.  The plan: balanced chunks of at least k rows that cover [0, npool) once."""
     monkeypatch.delenv("KNNSVC_KNN_FUSED", raising=False)
     p_cap, top, points = _window_points(dim)

@@ -16,7 +16,7 @@ for nq in (300, 900, 1500, 2600):
             i1, d1, f = ops.knn_topk(q, P, 32, q_stats=qs, p_stats=ps, check_nan=False, return_flag=True, max_blocks=mb)
             bad = (i0 != i1).any(1) | (d0 != d1).any(1)
             nb = int(bad.sum())
-            msg = f"nq={nq} max_blocks={mb} rep={rep}: epochs={ops.knn_epochs(nq, 40000, mb or 256)} flag={int(f.item())} bad rows={nb}"
+            msg = f"nq={nq} max_blocks={mb} rep={rep}: plan={ops.knn_plan(nq, 40000, 1024, 32, max_blocks=mb).chunks} flag={int(f.item())} bad rows={nb}"
             if nb:
                 r = int(bad.nonzero()[0])
                 msg += f" first={r} want={i0[r, :6].tolist()} got={i1[r, :6].tolist()} dwant={d0[r, :3].tolist()} dgot={d1[r, :3].tolist()}"

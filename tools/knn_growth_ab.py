@@ -1,5 +1,5 @@
 import sys, os
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from knn_svc_amd import ops, synthetic as S
 nq, npool = 24000, 180000
@@ -13,4 +13,4 @@ for g in (4, 8, 16, 4, 8):
     for _ in range(5): ops.knn_topk(q, p, 32, q_stats=qs, p_stats=ps, check_nan=False)
     e1.record(); torch.cuda.synchronize()
     ms = e0.elapsed_time(e1) / 5
-    print(f"growth {g}: epochs {ops.knn_epochs(nq, npool)}: {ms:.3f} ms {2.0 * nq * npool * 1024 / ms / 1e9:.1f} TFLOP/s", flush=True)
+    print(f"growth {g}: plan {ops.knn_plan(nq, npool, 1024, 32).chunks}: {ms:.3f} ms {2.0 * nq * npool * 1024 / ms / 1e9:.1f} TFLOP/s", flush=True)

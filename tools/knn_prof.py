@@ -52,7 +52,7 @@ e0.record()
 for _ in range(5):
     ops.knn_topk(q, p, 32, q_stats=qs, p_stats=ps, check_nan=False)
 e1.record(); torch.cuda.synchronize()
-print(f"Nq={nq} Np={npool} epochs={ops.knn_epochs(nq, npool)} flag={int(fl.item())} search {e0.elapsed_time(e1) / 5:.3f} ms (prof build)")
+print(f"Nq={nq} Np={npool} plan={ops.knn_plan(nq, npool, q.shape[1], 32).chunks} flag={int(fl.item())} search {e0.elapsed_time(e1) / 5:.3f} ms (prof build)")
 for e, t in enumerate(calls):
     t = t.astype(np.float64)
     live = t[:, 4] > t[:, 0]
