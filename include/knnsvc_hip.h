@@ -483,6 +483,32 @@ int knnsvc_log_f0_median_seg(const float* f0, const int64_t* host_seg, int32_t n
 int knnsvc_shift_f0_seg(const float* f0, const int64_t* host_seg, int32_t n_seg, const float* query_median,
                         const float* pool_median, float* shifted, void* stream);
 
+/* Pitch control (an extension; upstream knows only the median shift): knnsvc_shift_f0_seg with a MODE and a TRANSPOSE t
+ * (semitones, finite, |t| <= KNNSVC_F0_TRANSPOSE_MAX) per segment.  This restatement is the specification.
+ *   L = log_rn(f): the fp32 log evaluated in fp64 and rounded once, as in knnsvc_shift_f0; qm, pm: the fp32 lower medians
+ *   (query_median[s][0], pool_median[0]); LN2 = fp64 ln 2, S = LN2 / 12, d = (double)pm - (double)qm; rint rounds half to
+ *   even; no floating-point contraction anywhere.  Shifted log f0 of a voiced frame:
+ *     KNNSVC_F0_SHIFT_MEDIAN   (0)  v = (L + pm) - qm in fp32, knnsvc_shift_f0's expression; when t != 0: v + (float)(t * S)
+ *     KNNSVC_F0_SHIFT_OCTAVE   (1)  L + (float)(LN2 * rint(d / LN2) + t * S)   pitch classes kept, register moved to the pool's
+ *     KNNSVC_F0_SHIFT_SEMITONE (2)  L + (float)(S * rint(d / S) + t * S)       stays on the source's equal-tempered grid
+ *     KNNSVC_F0_SHIFT_NONE     (3)  L + (float)(t * S)                         the medians are NOT READ
+ *   shifted = exp_rn of that value; an unvoiced frame (f == 0) is copied bit for bit.  MEDIAN with t == 0 gives the bits of
+ *   knnsvc_shift_f0_seg.  A NaN median (no voiced frame on either side) propagates in the three modes that read the medians.
+ *   shift_semitones (device float [n_seg], may be NULL) receives the interval applied, in semitones: d / S + t (MEDIAN),
+ *   (quantised + t * S) / S (OCTAVE, SEMITONE), t (NONE).
+ * host_modes (int32 [n_seg]) and host_transposes (float [n_seg]) are HOST tables read by the call and handed to the kernel
+ * by value like host_seg; NULL = all MEDIAN / all 0.  The interval is chosen on the device by every thread of the segment:
+ * no host read of the medians, one launch, hipGraph-capturable.  Refused before the launch, with a message: a bad table, a
+ * null f0 / query_median / pool_median / shifted, a mode outside 0..3, a transpose that is NaN, infinite or beyond the bound. */
+#define KNNSVC_F0_SHIFT_MEDIAN 0
+#define KNNSVC_F0_SHIFT_OCTAVE 1
+#define KNNSVC_F0_SHIFT_SEMITONE 2
+#define KNNSVC_F0_SHIFT_NONE 3
+#define KNNSVC_F0_TRANSPOSE_MAX 36.0f
+int knnsvc_shift_f0_seg_mode(const float* f0, const int64_t* host_seg, int32_t n_seg, const int32_t* host_modes,
+                             const float* host_transposes, const float* query_median, const float* pool_median,
+                             float* shifted, float* shift_semitones, void* stream);
+
 /* knnsvc_concat_reselect per segment (lib_ongaku_test.py:270-369): every segment is a sequence of its own — its
  * frame 0 keeps its neighbours, the walk never looks across a boundary.  idx_in/out [total, 4]. */
 int knnsvc_concat_reselect_seg(const int64_t* idx_in, const float* q, const float* q_norm, const int64_t* host_seg, int32_t n_seg,

@@ -155,6 +155,7 @@ SIGNATURES = {
     "knnsvc_smooth_weights": (i32, [vp, i64, vp, i64, i32, i32, f32, vp, i32, vp, vp, vp, sz, vp]),
     "knnsvc_log_f0_median_seg": (i32, [vp, vp, i32, vp, vp, vp]),
     "knnsvc_shift_f0_seg": (i32, [vp, vp, i32, vp, vp, vp, vp]),
+    "knnsvc_shift_f0_seg_mode": (i32, [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp]),
     "knnsvc_concat_reselect_seg": (i32, [vp, vp, vp, vp, i32, vp, vp, i64, i32, vp, vp, i32, f32, vp, vp]),
     "knnsvc_smooth_seg_workspace_bytes": (sz, [vp, i32]),
     "knnsvc_smooth_weights_seg": (i32, [vp, vp, i32, vp, i64, i32, i32, f32, vp, i32, vp, vp, vp, sz, vp]),

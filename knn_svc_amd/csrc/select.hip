@@ -87,6 +87,56 @@ __global__ void shift_f0_kernel(const float* __restrict__ f0, const KnSegTable s
     shift_f0_body(f0 + o, seg.off[blockIdx.y + 1] - o, qmed + 2 * blockIdx.y, pmed, out + o, (long)blockIdx.x * blockDim.x + threadIdx.x);
 }
 
+// Per-segment shift mode and transpose (semitones) of shift_f0_mode_kernel: host tables handed over by value like the segment table.
+struct KnShiftModes { int mode[KNNSVC_MAX_SEGMENTS]; float transpose[KNNSVC_MAX_SEGMENTS]; };
+
+// shift_f0_kernel with the interval chosen per segment on the device (include/knnsvc_hip.h, "Pitch control"): every thread derives
+// its segment's interval from the medians, so nothing is read back by the host; thread 0 of the segment's first block reports it.
+// KNNSVC_F0_SHIFT_NONE never reads the medians.
+__global__ void shift_f0_mode_kernel(const float* __restrict__ f0, const KnSegTable seg, const KnShiftModes pm,
+                                     const float* __restrict__ qmed, const float* __restrict__ pmed, float* __restrict__ out,
+                                     float* __restrict__ semis) {
+#pragma clang fp contract(off)
+    const double LN2 = 0.693147180559945309417232121458, S = LN2 / 12.0;
+    const int s = blockIdx.y;
+    const long o = seg.off[s], n = seg.off[s + 1] - o;
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int mode = pm.mode[s];
+    const float t = pm.transpose[s];
+    const double ts = (double)t * S;
+    float q = 0.f, p = 0.f;
+    float add = (float)ts;                   // what is added to log f0 (median: after its own two-step shift, when t != 0)
+    float applied = t;                       // the interval applied, in semitones
+    if (mode != KNNSVC_F0_SHIFT_NONE) {
+        q = qmed[2 * s]; p = pmed[0];
+        const double d = (double)p - (double)q;
+        if (mode == KNNSVC_F0_SHIFT_MEDIAN) {
+            applied = (float)(d / S + (double)t);
+        } else {
+            const double step = mode == KNNSVC_F0_SHIFT_OCTAVE ? LN2 : S;
+            const double interval = step * rint(d / step) + ts;
+            add = (float)interval;
+            applied = (float)(interval / S);
+        }
+    }
+    if (i == 0 && semis) semis[s] = applied;
+    const float f = f0[o + i];
+    float r = f;
+    if (f != 0.f) {
+        const float L = log_rn(f);
+        float v;
+        if (mode == KNNSVC_F0_SHIFT_MEDIAN) {
+            v = (L + p) - q;                 // today's expression, today's bits
+            if (t != 0.f) v = v + add;
+        } else {
+            v = L + add;
+        }
+        r = exp_rn(v);
+    }
+    out[o + i] = r;
+}
+
 // half a wave (32 lanes) per query row; rank by counting gives torch.sort(stable=True) order
 __global__ __launch_bounds__(256) void f0_rerank_kernel(const long* __restrict__ nn, long nq, int k,
                                                        const float* __restrict__ sf0, const float* __restrict__ pf0,
@@ -743,6 +793,33 @@ extern "C" int knnsvc_shift_f0_seg(const float* f0, const int64_t* host_seg, int
     KnSegTable seg;
     if (const int rc = kn_seg_table(host_seg, n_seg, "shift_f0_seg", &seg)) return rc;
     return shift_f0_launch(seg, "shift_f0_seg", f0, query_median, pool_median, shifted, stream);
+}
+
+// Every check before the launch: the table, the pointers, then each segment's mode and transpose (NULL tables: median / 0).
+extern "C" int knnsvc_shift_f0_seg_mode(const float* f0, const int64_t* host_seg, int32_t n_seg, const int32_t* host_modes,
+                                        const float* host_transposes, const float* query_median, const float* pool_median,
+                                        float* shifted, float* shift_semitones, void* stream) {
+    const char* entry = "shift_f0_seg_mode";
+    KnSegTable seg;
+    if (const int rc = kn_seg_table(host_seg, n_seg, entry, &seg)) return rc;
+    KN_REQUIRE(f0 && query_median && pool_median && shifted, "%s: null pointer", entry);
+    KnShiftModes pm;
+    for (int s = 0; s < KNNSVC_MAX_SEGMENTS; ++s) { pm.mode[s] = KNNSVC_F0_SHIFT_MEDIAN; pm.transpose[s] = 0.f; }
+    for (int s = 0; s < seg.n; ++s) {
+        const int m = host_modes ? host_modes[s] : KNNSVC_F0_SHIFT_MEDIAN;
+        const float t = host_transposes ? host_transposes[s] : 0.f;
+        KN_REQUIRE(m >= KNNSVC_F0_SHIFT_MEDIAN && m <= KNNSVC_F0_SHIFT_NONE, "%s: segment %d: unknown mode %d (0 median, 1 octave, 2 semitone, 3 none)",
+                   entry, s, m);
+        KN_REQUIRE(t == t && t >= -KNNSVC_F0_TRANSPOSE_MAX && t <= KNNSVC_F0_TRANSPOSE_MAX,
+                   "%s: segment %d: transpose %g is not a finite number of semitones within +-%g", entry, s, (double)t,
+                   (double)KNNSVC_F0_TRANSPOSE_MAX);
+        pm.mode[s] = m; pm.transpose[s] = t;
+    }
+    long longest = 0;
+    for (int s = 0; s < seg.n; ++s) longest = seg.off[s + 1] - seg.off[s] > longest ? seg.off[s + 1] - seg.off[s] : longest;
+    hipLaunchKernelGGL(shift_f0_mode_kernel, dim3((unsigned)cdiv64(longest, 256), (unsigned)seg.n), dim3(256), 0, (hipStream_t)stream,
+                       f0, seg, pm, query_median, pool_median, shifted, shift_semitones);
+    return knnsvc_check_launch(entry);
 }
 
 extern "C" int knnsvc_concat_reselect_seg(const int64_t* idx_in, const float* q, const float* q_norm, const int64_t* host_seg,

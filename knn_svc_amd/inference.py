@@ -17,7 +17,13 @@ lower than asked (save_audio divides by a peak above 1, as upstream).  --vad_tri
 --use_vad true is given (an extension, default false): silence is then trimmed from both ends
 of every target pool file on the GPU (the sox `vad` effect with torchaudio's defaults as
 restated in include/knnsvc_hip.h; parity with torchaudio's own code is not pinned); the
-source, the output length and the file names do not change.  --dur_limit is
+source, the output length and the file names do not change.  --f0_shift
+{median,octave,semitone,none} (an extension, default median = upstream) chooses how the
+source's f0 is moved towards the target's: by the difference of the log-f0 medians (an
+arbitrary real interval), by that difference rounded to whole octaves (the pitch classes
+are kept) or to whole semitones (the result stays on the source's equal-tempered grid), or
+not at all; --transpose FLOAT (default 0, at most 36 either way) adds that many semitones
+in every mode.  File names do not change.  --dur_limit is
 compared in seconds, as upstream (ddsp_prematch_dataset.py:408-411).
 """
 from __future__ import annotations
@@ -61,6 +67,11 @@ def build_parser() -> argparse.ArgumentParser:
                     help="(extension) trim silence from both ends of every target pool file (--vad_trigger_level)")
     ap.add_argument("--vad_trigger_level", type=float, default=7,
                     help="(extension, with --use_vad true) trigger level of the trimmer; higher keeps less")
+    ap.add_argument("--f0_shift", type=str, default="median", choices=["median", "octave", "semitone", "none"],
+                    help="(extension) how the source's f0 is moved towards the target's: by the difference of the medians, "
+                         "by that difference rounded to octaves or semitones, or not at all")
+    ap.add_argument("--transpose", type=float, default=0.0,
+                    help="(extension) semitones added to the f0 shift in every mode, at most 36 either way")
     ap.add_argument("--weights", default="auto", choices=["auto", "checkpoint", "seeded"],
                     help="(extension) 'seeded' runs with random weights when the released checkpoints are unavailable")
     return ap
@@ -75,13 +86,20 @@ def output_dir_for(src: str, tgt: str, ckpt_type: str, post_opt: str, dur_limit)
 
 
 def main(argv=None) -> int:
-    a = build_parser().parse_args(argv)
+    ap = build_parser()
+    a = ap.parse_args(argv)
+    from .matching import resolve_f0_shift
+    try:
+        resolve_f0_shift(a.f0_shift, a.transpose)          # before the models are loaded
+    except ValueError as e:
+        ap.error(str(e))
     from .hubconf import knn_vc
     knn = knn_vc(pretrained=True, progress=True, prematched=True, device=a.device, ckpt_type=a.ckpt_type,
                  local_ckpt_dir=a.ckpt_dir, weights=a.weights)
     common = dict(topk=a.topk, device=a.device, prioritize_f0=a.prioritize_f0, ckpt_type=a.ckpt_type,
                   tgt_loudness_db=a.tgt_loudness_db, post_opt=a.post_opt, normalize_loudness=a.normalize_loudness,
-                  use_topk=a.use_topk, use_vad=a.use_vad, vad_trigger_level=a.vad_trigger_level)
+                  use_topk=a.use_topk, use_vad=a.use_vad, vad_trigger_level=a.vad_trigger_level,
+                  f0_shift=a.f0_shift, transpose=a.transpose)
     if os.path.isfile(a.src) and os.path.isfile(a.tgt):
         knn.special_match(src_wav_file=a.src, ref_wav_file=a.tgt, **common)
         return 0

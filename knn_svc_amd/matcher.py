@@ -17,7 +17,11 @@ is passed (an extension, off by default): silence is then trimmed from both ends
 pool file on the GPU before it is encoded (ops.vad_trim: the sox `vad` effect with torchaudio's
 default parameters as restated in include/knnsvc_hip.h; that restatement is the specification,
 parity with torchaudio's own code is not pinned); the source is never trimmed, output length and
-file names do not change.  Other differences that are deliberate: ``special_match`` returns
+file names do not change.  ``f0_shift`` ("median", the default and upstream's; "octave", "semitone",
+"none") and ``transpose`` (semitones, |t| <= 36, default 0) are an extension too: they choose how the
+source's f0 is moved towards the target's (matching.F0_SHIFT_MODES; the interval is chosen per
+utterance on the GPU) and take effect as passed; with the defaults nothing changes, and file names do
+not change with any value.  Other differences that are deliberate: ``special_match`` returns
 the waveform instead of calling ``sys.exit()`` after saving (the CLI exits 0, the
 observable behaviour), and ``bulk_match`` does not ``rm -rf`` a hard-coded cache
 directory (ddsp_matcher.py:1066-1068).
@@ -31,7 +35,7 @@ from pathlib import Path
 import torch
 
 from . import audio_io, config as C, dist as kdist, ops
-from .matching import match_at_inference_time
+from .matching import match_at_inference_time, resolve_f0_shift
 from .vocoder import Vocoder
 from .wavlm import WavLMEncoder
 
@@ -89,8 +93,9 @@ class KNeighborsVC:
     @torch.inference_mode()
     def special_match(self, src_wav_file, ref_wav_file, topk: int = 4, device=None, prioritize_f0=True,
                       ckpt_type="wavlm_only", tgt_loudness_db=-16, post_opt="no_post_opt", save=True, normalize_loudness=False,
-                      use_topk=False, use_vad=False, vad_trigger_level=7):
+                      use_topk=False, use_vad=False, vad_trigger_level=7, f0_shift="median", transpose=0.0):
         level = tgt_loudness_db if normalize_loudness else None
+        resolve_f0_shift(f0_shift, transpose)            # refused before a file is read
         f0only = "wavlm_only" in ckpt_type or "no_harm_no_amp" in ckpt_type
         if "wavlm_only_original" in ckpt_type:
             raise NotImplementedError("wavlm_only_original needs hifigan/models.py, absent upstream")
@@ -99,14 +104,16 @@ class KNeighborsVC:
             of, hw, _a, sf0 = match_at_inference_time(Path(src_wav_file), Path(ref_wav_file), self.wavlm,
                                                       self.weighting, self.weighting, topk=topk, device=self.device,
                                                       prioritize_f0=prioritize_f0, ckpt_type=ckpt_type, post_opt=post_opt,
-                                                      use_topk=use_topk, use_vad=use_vad, vad_trigger_level=vad_trigger_level)
+                                                      use_topk=use_topk, use_vad=use_vad, vad_trigger_level=vad_trigger_level,
+                                                      f0_shift=f0_shift, transpose=transpose)
             pred = self.vocode(of[key][None], sf0[key][None, :, None], hw[key][None], loudness_db=level).squeeze()
         else:
             # the reference does not forward post_opt on this branch (ddsp_matcher.py:970)
             of, _a, sf0 = match_at_inference_time(Path(src_wav_file), Path(ref_wav_file), self.wavlm,
                                                   self.weighting, self.weighting, topk=topk, device=self.device,
                                                   prioritize_f0=prioritize_f0, ckpt_type=ckpt_type, use_topk=use_topk,
-                                                  use_vad=use_vad, vad_trigger_level=vad_trigger_level)
+                                                  use_vad=use_vad, vad_trigger_level=vad_trigger_level,
+                                                  f0_shift=f0_shift, transpose=transpose)
             pred = self.vocode(of[key][None], sf0[key][None, :, None], loudness_db=level).squeeze()
         src_id = os.path.basename(src_wav_file).split(".")[0]
         ref_id = os.path.basename(ref_wav_file).split(".")[0]
@@ -118,7 +125,8 @@ class KNeighborsVC:
 
     @torch.inference_mode()
     def many_to_one(self, src_files, ref_wav_file, converted_audio_dir=None, ckpt_type="mix", post_opt="post_opt_0.2",
-                    duration_limit=None, target=None, match=None, loudness_db=None, topk=None, vad_trigger_level=None):
+                    duration_limit=None, target=None, match=None, loudness_db=None, topk=None, vad_trigger_level=None,
+                    f0_shift=None, transpose=None):
         """BASELINE cfg 5 (no counterpart upstream: the reference would call ``special_match`` once per source and rebuild the
         target pool each time, ddsp_matcher.py:937-1023): MANY sources against ONE target pool that is built once and stays
         resident, all sources through the stream pipeline as one batch (knn_svc_amd/serving.py).  Under a process group the
@@ -126,21 +134,25 @@ class KNeighborsVC:
         ranks' on every rank), named like ``special_match``'s outputs.  ``match``: "lanes" | "segmented" (serving.BatchConverter; default
         from KNNSVC_MATCH).  ``loudness_db``: every waveform is normalised to that integrated loudness (None: left as generated).
         ``topk``: neighbours mixed per frame, 1..8 (None: 4).  ``vad_trigger_level``: the pool's files are trimmed of the silence
-        at both ends with that trigger level (None: left whole; ignored when ``target`` is given)."""
+        at both ends with that trigger level (None: left whole; ignored when ``target`` is given).  ``f0_shift`` / ``transpose``:
+        the f0 shift mode and the transpose in semitones of every source (None: "median" / 0)."""
         from . import serving
+        resolve_f0_shift(f0_shift, transpose)            # refused before a file is read
         if target is None:
             target = serving.TargetVoice(self, ref_wav_file, duration_limit, vad_trigger_level=vad_trigger_level)
         mine = kdist.my_share([str(p) for p in src_files])
         written = serving.BatchConverter(self, target, ckpt_type, post_opt, match=match,
-                                         loudness_db=loudness_db, topk=topk).convert_files(mine, converted_audio_dir)
+                                         loudness_db=loudness_db, topk=topk, f0_shift=f0_shift,
+                                         transpose=transpose).convert_files(mine, converted_audio_dir)
         return kdist.gather_paths(written)
 
     @torch.inference_mode()
     def bulk_match(self, src_dataset_path, tgt_dataset_path, converted_audio_dir, topk: int = 4, device=None,
                    prioritize_f0=True, ckpt_type="mix", tgt_loudness_db=-16, required_subset_file=None,
                    post_opt="no_post_opt", duration_limit=None, normalize_loudness=False, use_topk=False, use_vad=False,
-                   vad_trigger_level=7):
+                   vad_trigger_level=7, f0_shift="median", transpose=0.0):
         level = tgt_loudness_db if normalize_loudness else None
+        resolve_f0_shift(f0_shift, transpose)            # refused before a file is read
         assert os.path.isdir(src_dataset_path) and os.path.isdir(tgt_dataset_path)
         Path(converted_audio_dir).mkdir(parents=True, exist_ok=True)
         spk = lambda root: sorted([p for p in Path(root).iterdir() if p.is_dir() and "f0_cache" not in os.path.basename(p)])
@@ -179,7 +191,7 @@ class KNeighborsVC:
                               src_dataset_path=src_dataset_path, tgt_dataset_path=tgt_dataset_path,
                               required_subset=required, duration_limit=duration_limit,
                               pool_sharded=shard, share_items=shard, use_topk=use_topk, use_vad=use_vad,
-                              vad_trigger_level=vad_trigger_level)
+                              vad_trigger_level=vad_trigger_level, f0_shift=f0_shift, transpose=transpose)
                 # the generator of every utterance is the tail stage of the match pipeline (same kernels and inputs as
                 # `vocode` after the fact, ddsp_matcher.py:1114-1128, but enqueued under the next utterances' matching);
                 # one finiteness check per speaker pair instead of one host sync per utterance; with normalize_loudness the

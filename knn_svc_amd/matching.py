@@ -7,6 +7,9 @@ arguments, same returned dict-of-tensors keyed by ``str(path)``, same quirks
 ``post_opt`` parsing, ``prioritize_f0`` must be True, pool rebuilt per call).
 ``topk`` is ignored as upstream unless ``use_topk=True`` (an extension, off by default): the
 match stage then keeps that many (1..8) of the 32 neighbours per frame instead of 4.
+``f0_shift`` / ``transpose`` (an extension; defaults "median" / 0 = upstream) choose how the source's f0 is moved towards the
+target's: by the difference of the log-f0 medians, by that difference rounded to whole octaves or semitones, or not at all, plus
+a transpose in semitones (F0_SHIFT_MODES; the kernel chooses the interval per item on the device).
 ``vad_trigger_level`` is ignored as in upstream's ``get_complete_spk_pool`` unless ``use_vad=True`` (an extension, off by
 default): silence is then trimmed from both ends of every TARGET pool file on the GPU (ops.vad_trim: the sox `vad` effect with
 torchaudio's defaults as restated in include/knnsvc_hip.h — that restatement is the specification, parity with torchaudio's
@@ -382,14 +385,69 @@ def resolve_topk(topk) -> int:
     return int(topk)
 
 
+# How the source's f0 is moved towards the target's (an extension; upstream knows only "median").  The values are the library's
+# KNNSVC_F0_SHIFT_* codes; include/knnsvc_hip.h ("Pitch control") is the specification.
+#   median    by median(log f0 pool) - median(log f0 source): an arbitrary real interval (upstream, the default)
+#   octave    that difference rounded to whole octaves: the pitch classes are kept, the register moves to the target's
+#   semitone  that difference rounded to whole semitones: the result stays on the source's equal-tempered grid
+#   none      no shift: the medians are not read
+# ``transpose`` (semitones, finite, |t| <= F0_TRANSPOSE_MAX) is added on top in every mode.
+F0_SHIFT_MODES = {"median": ops.F0_SHIFT_MEDIAN, "octave": ops.F0_SHIFT_OCTAVE, "semitone": ops.F0_SHIFT_SEMITONE,
+                  "none": ops.F0_SHIFT_NONE}
+F0_TRANSPOSE_MAX = 36.0
+
+
+def _one_f0_shift(mode, transpose):
+    if mode is None:
+        mode = "median"
+    if not isinstance(mode, str) or mode not in F0_SHIFT_MODES:
+        raise ValueError(f"f0_shift must be one of {tuple(F0_SHIFT_MODES)} (or None for 'median'), got {mode!r}")
+    if transpose is None:
+        transpose = 0.0
+    if isinstance(transpose, (bool, np.bool_)) or not isinstance(transpose, (int, float, np.integer, np.floating)):
+        raise ValueError(f"transpose must be a number of semitones, got {transpose!r}")
+    t = float(np.float32(transpose))                  # the value the library sees
+    if not np.isfinite(t) or abs(t) > F0_TRANSPOSE_MAX:
+        raise ValueError(f"transpose must be finite and within +-{F0_TRANSPOSE_MAX:g} semitones, got {transpose!r}")
+    return F0_SHIFT_MODES[mode], t
+
+
+def resolve_f0_shift(mode, transpose, n_items=None):
+    """``f0_shift`` / ``transpose`` as the library takes them, refused before any device work when they are not valid.
+    ``n_items`` None: one mode name (None = "median") and one number (None = 0) -> (code, float).  ``n_items`` = the number of
+    items of a batch: each may also be a list / tuple with one entry per item -> (list of codes, list of floats)."""
+    if n_items is None:
+        if isinstance(mode, (list, tuple)) or isinstance(transpose, (list, tuple)):
+            raise ValueError("f0_shift / transpose: a single value expected here, not a list")
+        return _one_f0_shift(mode, transpose)
+    per = []
+    for name, v in (("f0_shift", mode), ("transpose", transpose)):
+        if isinstance(v, (list, tuple)):
+            if len(v) != n_items:
+                raise ValueError(f"{name}: {len(v)} values for {n_items} items")
+            per.append(list(v))
+        else:
+            per.append([v] * n_items)
+    pairs = [_one_f0_shift(m, t) for m, t in zip(*per)]
+    return [m for m, _ in pairs], [t for _, t in pairs]
+
+
+def f0_shift_is_default(modes, transposes) -> bool:
+    """True when every item takes upstream's median shift untransposed: the match stage then launches what it always did."""
+    return all(m == ops.F0_SHIFT_MEDIAN for m in modes) and all(t == 0.0 for t in transposes)
+
+
 def match_features(query_seq, query_f0, matching_list, matching_f0, harmonics_list, ckpt_type, post_opt,
-                   return_debug=False, nn32=None, nan_flags=None, pool_prep=None, synth_list=None, topk=None):
+                   return_debug=False, nn32=None, nan_flags=None, pool_prep=None, synth_list=None, topk=None,
+                   f0_shift=None, transpose=None):
     """The per-query body (ddsp_prematch_dataset.py:1189-1450) on device tensors: ``match_features_many`` (below, where the
     arguments are described) of one utterance.  ``nn32`` may carry neighbours already found by the pool-sharded search
     (knn_svc_amd.dist.sharded_knn); in the debug dict ``iters_*`` are one-element tensors, or 0 without the Adam stage."""
+    resolve_f0_shift(f0_shift, transpose)     # one value each
     return match_features_many([query_seq], [query_f0], matching_list, matching_f0, harmonics_list, ckpt_type, post_opt,
                                nn32s=None if nn32 is None else [nn32], nan_flags=nan_flags, pool_prep=pool_prep,
-                               synth_list=synth_list, return_debug=return_debug, topk=topk)[0]
+                               synth_list=synth_list, return_debug=return_debug, topk=topk, f0_shift=f0_shift,
+                               transpose=transpose)[0]
 
 
 # How the match stage of SEVERAL items is put on the chip: "lanes" (one match_features per item on the lane streams, the default) or
@@ -422,7 +480,8 @@ def _stacked(ts):
 
 
 def match_features_many(query_seqs, query_f0s, matching_list, matching_f0, harmonics_list, ckpt_type, post_opt, nn32s=None,
-                        nan_flags=None, pool_prep=None, synth_list=None, return_debug=False, topk=None):
+                        nan_flags=None, pool_prep=None, synth_list=None, return_debug=False, topk=None, f0_shift=None,
+                        transpose=None):
     """The per-query body (ddsp_prematch_dataset.py:1189-1450) for several query utterances against one pool, run ONCE over their
     stacked frames -> a list of per-item tuples (out_feats, harm or None, shifted_f0[, debug dict]) (views of the stacked outputs).
     The row-wise stages (row norms, f0 re-rank, weighted sums) take the stacked rows as they are; the per-sequence stages (median,
@@ -432,8 +491,14 @@ def match_features_many(query_seqs, query_f0s, matching_list, matching_f0, harmo
     smoothness weights and the weighted sums on ``synth_list`` (:1260, 1347-1350).  ``nn32s``: per-item neighbour lists (or None: one
     search over the stacked frames).  ``nan_flags``: a list that receives the kNN NaN flag instead of the host checking it here
     (the caller then calls ``ops.raise_if_nan`` on each entry once everything is enqueued — keeps a stream pipeline free of syncs).
-    ``topk``: neighbours kept per frame out of the 32 found (1..8; None = 4, the specialised kernels)."""
+    ``topk``: neighbours kept per frame out of the 32 found (1..8; None = 4, the specialised kernels).
+    ``f0_shift`` / ``transpose``: how each item's f0 is moved (F0_SHIFT_MODES; a value for all items or a list with one per item;
+    None = "median" / 0).  The interval is chosen per item on the device (ops.shift_f0_seg with modes): no host read of the
+    medians.  With every item on the median shift and no transpose the stage launches exactly what it launches without the
+    arguments.  The debug dict carries ``shift_semitones``: the interval applied to the item (a one-element device tensor)."""
     topk = resolve_topk(topk)                 # before any device work
+    shift_modes, shift_ts = resolve_f0_shift(f0_shift, transpose, len(query_seqs))
+    plain_shift = f0_shift_is_default(shift_modes, shift_ts) and not return_debug
     lens = [int(q.shape[0]) for q in query_seqs]
     seg = [0]
     for n in lens:
@@ -463,7 +528,11 @@ def match_features_many(query_seqs, query_f0s, matching_list, matching_f0, harmo
     w = w2 = harm_w = None
     with torch.cuda.stream(side):
         qmed, pmed = ops.log_f0_median_seg(query_f0, seg), ops.log_f0_median(matching_f0)      # the pool's median once
-        shifted = ops.shift_f0_seg(query_f0, seg, qmed, pmed)
+        semis = None
+        if plain_shift:
+            shifted = ops.shift_f0_seg(query_f0, seg, qmed, pmed)
+        else:
+            shifted, semis = ops.shift_f0_seg(query_f0, seg, qmed, pmed, shift_modes, shift_ts, return_shift=True)
         ranked = ops.f0_rerank(nn32, shifted, matching_f0)
         idx2 = ranked[:, :topk].contiguous()
         if cw != -1:
@@ -480,7 +549,7 @@ def match_features_many(query_seqs, query_f0s, matching_list, matching_f0, harmo
         w, it1 = ops.smooth_weights_seg(idx, seg, Ps, 0.1, return_iters=True)
     out_feats = ops.weighted_gather(idx, w, Ps)                                      # without Adam: softmax(ones) (:1361-1364)
     main.wait_stream(side)
-    for t in (shifted, idx2, harm_w, w2, it2):
+    for t in (shifted, semis, idx2, harm_w, w2, it2):
         if t is not None:
             t.record_stream(main)
     if nan_flag is not None:
@@ -492,7 +561,8 @@ def match_features_many(query_seqs, query_f0s, matching_list, matching_f0, harmo
             except ops.KnnOverflow:         # the fused route's candidate buffer overflowed: once more on the dot-matrix route
                 with ops.fused_off():
                     return match_features_many(query_seqs, query_f0s, matching_list, matching_f0, harmonics_list, ckpt_type, post_opt,
-                                               pool_prep=pool_prep, synth_list=synth_list, return_debug=return_debug, topk=topk)
+                                               pool_prep=pool_prep, synth_list=synth_list, return_debug=return_debug, topk=topk,
+                                               f0_shift=f0_shift, transpose=transpose)
     parts = lambda t: t.split(lens) if t is not None else [None] * len(lens)
     out = []
     dbg = [parts(t) for t in (nn32, idx, w, idx2, w2)]
@@ -500,7 +570,8 @@ def match_features_many(query_seqs, query_f0s, matching_list, matching_f0, harmo
         if return_debug:
             out.append((of, hw, sf, dict(nn32=dbg[0][i], idx_wavlm=dbg[1][i], w_wavlm=dbg[2][i], idx_harm=dbg[3][i], w_harm=dbg[4][i],
                                          iters_wavlm=it1[i:i + 1] if it1 is not None else 0,
-                                         iters_harm=it2[i:i + 1] if it2 is not None else 0)))
+                                         iters_harm=it2[i:i + 1] if it2 is not None else 0,
+                                         shift_semitones=semis[i:i + 1])))
         else:
             out.append((of, hw, sf))
     return out
@@ -542,13 +613,17 @@ def match_at_inference_time(src_wav_file, ref_wav_file, wavlm: WavLMEncoder, mat
                             topk: int = 4, device="cuda", prioritize_f0=False, ckpt_type="wavlm_only",
                             src_dataset_path=None, tgt_dataset_path=None, cache_dir=None, required_subset=None,
                             post_opt="no_post_opt", duration_limit=None, vocode_fn=None, waves_out=None,
-                            pool_sharded=None, share_items=False, use_topk=False, use_vad=False, vad_trigger_level=7):
+                            pool_sharded=None, share_items=False, use_topk=False, use_vad=False, vad_trigger_level=7,
+                            f0_shift="median", transpose=0.0):
     """Same contract as the reference function (ddsp_prematch_dataset.py:1074).  ``topk`` is accepted and, as upstream
     (k = 32 -> 4 is hard-coded there, :1203,1246,1398), ignored UNLESS ``use_topk=True`` (an extension, off by default): the
     match stage then keeps ``topk`` (1..8) neighbours per frame.  ``cache_dir`` is ignored (the reference force-disables
     it, :1086-1087).  ``vad_trigger_level`` (upstream passes 7 for the target pool, :1131, to a function that drops it) takes
     effect only with ``use_vad=True`` (an extension, off by default): the TARGET pool's files, never the source, are trimmed of
     the silence at both ends (``get_complete_spk_pool``); output length and file names do not change.
+    ``f0_shift`` ("median", upstream's and the default; "octave", "semitone", "none": F0_SHIFT_MODES) and ``transpose`` (semitones,
+    |t| <= 36, default 0) steer the f0 shift of every item (an extension; the interval is chosen on the device, per item, on every
+    route below); with the defaults the stage launches what it always did.  File names do not change.
 
     Build extension (BASELINE cfg 5, many sources against one pool): ``vocode_fn(out_feats, shifted_f0, harm)`` is
     enqueued as the pipeline's tail stage right behind each item's match body and its waveform stored in
@@ -567,6 +642,8 @@ def match_at_inference_time(src_wav_file, ref_wav_file, wavlm: WavLMEncoder, mat
         own items: the returned dicts hold this rank's items."""
     import torch.distributed as tdist
     k_use = resolve_topk(topk) if use_topk else None        # refused before any file is read
+    # likewise; handed on only when it says something (as topk above: the bodies keep the call they always got)
+    pitch = {} if f0_shift_is_default(*resolve_f0_shift(f0_shift, transpose, 1)) else dict(f0_shift=f0_shift, transpose=transpose)
     vad_level = vad_trigger_level if use_vad else 0
     if pool_sharded is None:         # by environment: only when there is more than one rank to shard over
         pool_sharded = os.environ.get("KNNSVC_POOL_SHARD") == "1" and kdist.world()[1] > 1
@@ -670,13 +747,14 @@ def match_at_inference_time(src_wav_file, ref_wav_file, wavlm: WavLMEncoder, mat
             if k_use is not None:
                 extra["topk"] = k_use
             return match_features(query_pool[item], query_f0_pool[item], matching_list, matching_f0,
-                                  harmonics_list, ckpt_type, post_opt, nan_flags=flags, pool_prep=prep, nn32=nn.get(item), **extra)
+                                  harmonics_list, ckpt_type, post_opt, nan_flags=flags, pool_prep=prep, nn32=nn.get(item), **pitch,
+                                  **extra)
         def body_many(batch):
             for item in batch:
                 wait_for_neighbours(nn.get(item), nn_ready.get(item), matching_list.device)
             return match_features_many([query_pool[it] for it in batch], [query_f0_pool[it] for it in batch], matching_list, matching_f0,
                                        harmonics_list, ckpt_type, post_opt, nn32s=[nn.get(it) for it in batch], nan_flags=flags,
-                                       pool_prep=prep, synth_list=synth_list, topk=k_use)
+                                       pool_prep=prep, synth_list=synth_list, topk=k_use, **pitch)
         # match bodies in flight at once (each is a chain of single-workgroup recurrences: more lanes = more of them side by side);
         # KNNSVC_MATCH=segmented (unsharded pool, several items): batches of KNNSVC_MATCH_BATCH items, each one body_many on a lane
         lanes = min(int(os.environ.get("KNNSVC_MATCH_LANES", "3")), len(items))

@@ -902,14 +902,37 @@ def log_f0_median_seg(f0, seg):
     return res
 
 
-def shift_f0_seg(f0, seg, qmed, pmed):
-    """``qmed`` [n_seg, 2] from log_f0_median_seg, ``pmed`` [2] -> shifted f0 of the stacked rows."""
+F0_SHIFT_MEDIAN, F0_SHIFT_OCTAVE, F0_SHIFT_SEMITONE, F0_SHIFT_NONE = range(4)      # KNNSVC_F0_SHIFT_*
+
+
+def shift_f0_seg(f0, seg, qmed, pmed, modes=None, transposes=None, return_shift=False):
+    """``qmed`` [n_seg, 2] from log_f0_median_seg, ``pmed`` [2] -> shifted f0 of the stacked rows.
+    ``modes`` (per segment: 0 median, 1 octave, 2 semitone, 3 none) and ``transposes`` (per segment, semitones): the interval
+    is then chosen per segment on the device (knnsvc_shift_f0_seg_mode; include/knnsvc_hip.h "Pitch control"); with both None
+    this is the median shift through knnsvc_shift_f0_seg.  ``return_shift``: -> (shifted, [n_seg] applied interval in
+    semitones, on the device)."""
     _need(f0, name="f0"); seg = _segments(seg, "shift_f0_seg", f0)
     f0 = f0.contiguous()
     out = torch.empty_like(f0)
+    lib = _lib.load()
+    if modes is None and transposes is None and not return_shift:
+        for a, r0, tab in seg.chunks:
+            check(lib.knnsvc_shift_f0_seg(_p(f0[r0:]), tab, len(tab) - 1, _p(qmed[a:]), _p(pmed), _p(out[r0:]), _stream()), "shift_f0_seg")
+        return out
+    for name, t in (("modes", modes), ("transposes", transposes)):
+        if t is not None and len(t) != seg.n:
+            raise KnnSvcError(f"shift_f0_seg: {len(t)} {name} for {seg.n} segments")
+    _need(qmed, name="qmed"); _need(pmed, name="pmed")
+    if qmed.numel() != 2 * seg.n or not qmed.is_contiguous():
+        raise KnnSvcError(f"shift_f0_seg: qmed must be a contiguous [{seg.n}, 2] tensor, got {tuple(qmed.shape)}")
+    semis = torch.empty(seg.n, device=f0.device, dtype=torch.float32) if return_shift else None
     for a, r0, tab in seg.chunks:
-        check(_lib.load().knnsvc_shift_f0_seg(_p(f0[r0:]), tab, len(tab) - 1, _p(qmed[a:]), _p(pmed), _p(out[r0:]), _stream()), "shift_f0_seg")
-    return out
+        n = len(tab) - 1
+        mt = None if modes is None else (C.c_int32 * n)(*[int(m) for m in modes[a:a + n]])
+        tt = None if transposes is None else (C.c_float * n)(*[float(t) for t in transposes[a:a + n]])
+        check(lib.knnsvc_shift_f0_seg_mode(_p(f0[r0:]), tab, n, mt, tt, _p(qmed[a:]), _p(pmed), _p(out[r0:]),
+                                           _p(semis[a:]) if return_shift else None, _stream()), "shift_f0_seg_mode")
+    return (out, semis) if return_shift else out
 
 
 def concat_reselect_seg(idx4, seg, q, q_norm, pool, p_norm, shifted_f0=None, pool_f0=None, concat_weight=0.2):

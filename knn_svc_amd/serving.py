@@ -89,7 +89,8 @@ class TargetVoice:
 class BatchConverter:
     def __init__(self, vc, target: TargetVoice, ckpt_type: str = "mix", post_opt: str = "post_opt_0.2", lanes: int | None = None,
                  max_encode_batch: int = 32, match: str | None = None, match_batch: int | None = None,
-                 loudness_db: float | None = None, topk: int | None = None):
+                 loudness_db: float | None = None, topk: int | None = None, f0_shift: str | None = None,
+                 transpose: float | None = None):
         if "wavlm_only_original" in ckpt_type:
             raise NotImplementedError("wavlm_only_original needs hifigan/models.py, absent upstream")
         self.vc, self.target, self.ckpt_type, self.post_opt = vc, target, ckpt_type, post_opt
@@ -106,6 +107,10 @@ class BatchConverter:
         self.loudness_db = None if loudness_db is None else float(loudness_db)
         # neighbours mixed per frame out of the 32 found: 1..8; None: 4 (the released checkpoints' training condition)
         self.topk = None if topk is None else M.resolve_topk(topk)
+        # how every source's f0 is moved towards the target's unless a request says otherwise (matching.F0_SHIFT_MODES; None:
+        # "median" / 0 semitones, upstream's shift).  Kept as given, checked here.
+        M.resolve_f0_shift(f0_shift, transpose)
+        self.f0_shift, self.transpose = f0_shift, transpose
 
     def _load(self, src, check=False):
         """A request is a path, or (wav [L] float32 16 kHz mono as array / tensor, f0 [L // 320 + 1] or None).
@@ -144,9 +149,22 @@ class BatchConverter:
             raise ValueError(f"request: f0 has {len(f0)} frames for a waveform of {T} frames (expected {T} or {T + 1})")
         return w, f0
 
+    def pitch_of(self, f0_shift=None, transpose=None, n=None):
+        """Per-source ``f0_shift`` / ``transpose`` (a value for all, or one per source; None entries: this converter's defaults)
+        as checked lists of ``n`` values each; ``n`` None: one checked pair."""
+        fill = lambda v, d: [d if x is None else x for x in v] if isinstance(v, (list, tuple)) else (d if v is None else v)
+        f0_shift, transpose = fill(f0_shift, self.f0_shift), fill(transpose, self.transpose)
+        M.resolve_f0_shift(f0_shift, transpose, n)
+        if n is None:
+            return f0_shift, transpose
+        return [list(v) if isinstance(v, (list, tuple)) else [v] * n for v in (f0_shift, transpose)]
+
     @torch.inference_mode()
-    def convert(self, sources, loaded=None) -> list:
-        """-> one waveform tensor [T_i * 320] per source, in order.  ``loaded``: the sources already through load_checked."""
+    def convert(self, sources, loaded=None, f0_shift=None, transpose=None) -> list:
+        """-> one waveform tensor [T_i * 320] per source, in order.  ``loaded``: the sources already through load_checked.
+        ``f0_shift`` / ``transpose``: for all sources or one per source (None: the converter's defaults); one batch may mix
+        them on both match routes, each source's interval is chosen on the device."""
+        modes, semis = self.pitch_of(f0_shift, transpose, len(sources))        # refused before a file is read
         if len(sources) == 0:
             return []
         vc, tg = self.vc, self.target
@@ -178,12 +196,14 @@ class BatchConverter:
             def body(i):
                 M.wait_for_neighbours(nn.get(i), ready.get(i), dev)
                 return M.match_features(qpool[i], f0s[i], tg.feats, tg.f0, tg.harm, self.ckpt_type, post_opt,
-                                        nan_flags=flags, pool_prep=tg.prep, nn32=nn.get(i), topk=self.topk)
+                                        nan_flags=flags, pool_prep=tg.prep, nn32=nn.get(i), topk=self.topk,
+                                        f0_shift=modes[i], transpose=semis[i])
             def body_many(batch):
                 for i in batch:
                     M.wait_for_neighbours(nn.get(i), ready.get(i), dev)
                 return M.match_features_many([qpool[i] for i in batch], [f0s[i] for i in batch], tg.feats, tg.f0, tg.harm, self.ckpt_type,
-                                             post_opt, nn32s=[nn.get(i) for i in batch], nan_flags=flags, pool_prep=tg.prep, topk=self.topk)
+                                             post_opt, nn32s=[nn.get(i) for i in batch], nan_flags=flags, pool_prep=tg.prep, topk=self.topk,
+                                             f0_shift=[modes[i] for i in batch], transpose=[semis[i] for i in batch])
             tail = lambda i, r: voc(r[0], r[2], r[1])
             ys = M.run_match_bodies(items, body, body_many, tail, device=dev, lanes=max(1, min(self.lanes, len(items))),
                                     match=self.match, match_batch=self.match_batch)
@@ -208,7 +228,9 @@ class BatchConverter:
 
 
 class RequestQueue:
-    """Dynamic batching in front of a BatchConverter.  ``submit(src)`` -> Future of the waveform (a CPU tensor)."""
+    """Dynamic batching in front of a BatchConverter.  ``submit(src)`` -> Future of the waveform (a CPU tensor).
+    ``submit(src, transpose=, f0_shift=)``: the request's own transpose (semitones) / f0 shift mode instead of the converter's;
+    requests with different values share a batch."""
 
     def __init__(self, converter: BatchConverter, max_batch: int = 32, max_wait_ms: float = 5.0):
         self.conv, self.max_batch, self.max_wait = converter, int(max_batch), float(max_wait_ms) / 1e3
@@ -219,11 +241,14 @@ class RequestQueue:
         self._th = threading.Thread(target=self._loop, name="knnsvc-batcher", daemon=True)
         self._th.start()
 
-    def submit(self, src) -> Future:
+    def submit(self, src, transpose=None, f0_shift=None) -> Future:
         if self._stop:
             raise RuntimeError("RequestQueue is closed")
         fut = Future()
-        self._q.put((src, fut))
+        if transpose is None and f0_shift is None:
+            self._q.put((src, fut))
+        else:                                                # a bad value is refused here, not in the worker
+            self._q.put((src, fut, self.conv.pitch_of(f0_shift, transpose)))
         return fut
 
     def _loop(self):
@@ -251,19 +276,22 @@ class RequestQueue:
 
     def _run(self, batch):
         """One batch; a request that cannot be loaded, or whose data makes the conversion fail (a NaN source, an f0 track of the
-        wrong length), fails ALONE: the others of its batch are converted without it."""
+        wrong length), fails ALONE: the others of its batch are converted without it.  An entry is (source, Future) or (source,
+        Future, (f0_shift, transpose)); a batch in which no request carries values of its own is converted as it always was."""
         good, loaded = [], []
-        for s, fut in batch:
+        for s, fut, *own in batch:
             try:
                 loaded.append(self.conv.load_checked(s))
-                good.append((s, fut))
+                good.append((s, fut, own[0] if own else (None, None)))
             except BaseException as e:
                 fut.set_exception(e)
         if not good:
             return
+        plain = all(g[2] == (None, None) for g in good)
+        pitch = lambda gs: {} if plain else dict(f0_shift=[g[2][0] for g in gs], transpose=[g[2][1] for g in gs])
         try:
-            ys = self.conv.convert([s for s, _ in good], loaded=loaded)
-            for (_s, fut), y in zip(good, ys):
+            ys = self.conv.convert([g[0] for g in good], loaded=loaded, **pitch(good))
+            for (_s, fut, _p), y in zip(good, ys):
                 fut.set_result(y.detach().cpu())
             return
         except BaseException as e:
@@ -271,11 +299,11 @@ class RequestQueue:
                 good[0][1].set_exception(e)
                 return
         self.isolated += 1
-        for (s, fut), ld in zip(good, loaded):                # the batch failed as a whole: find the offender(s) one by one
+        for g, ld in zip(good, loaded):                       # the batch failed as a whole: find the offender(s) one by one
             try:
-                fut.set_result(self.conv.convert([s], loaded=[ld])[0].detach().cpu())
+                g[1].set_result(self.conv.convert([g[0]], loaded=[ld], **pitch([g]))[0].detach().cpu())
             except BaseException as e:
-                fut.set_exception(e)
+                g[1].set_exception(e)
 
     def close(self):
         self._stop = True
