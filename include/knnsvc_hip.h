@@ -701,6 +701,53 @@ int knnsvc_vad_trim_seg(const float* wav, const int64_t* host_seg_offsets, int32
                         double trigger_level, int64_t* out_strip, double* out_measures, void* workspace, size_t workspace_bytes,
                         void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Output dynamics (csrc/dynamics.hip): two stages behind the generator, both extensions without a counterpart in the reference.
+ * Their place in the tail is fixed: generator -> envelope mix -> loudness normalisation -> peak ceiling -> finiteness check.
+ * Both are restated in fp64 numpy in tests/dynamics_oracle.py; the text here is the specification.  All arithmetic between the
+ * fp32 samples and the fp32 result is fp64 in a fixed order (bit-stable from run to run).  n may not exceed 2^36 samples.
+ * ------------------------------------------------------------------------------------------ */
+/* Envelope mix: the SHAPE of the source's volume envelope put back on the generated waveform y[0..n), n = T hop.  x[0..nx) is the
+ * source as the encoder received it (16 kHz mono), zero-extended or cut to n samples; sample i of y corresponds to sample i of x.
+ *   block energies   bx[j] = sum of x[i]^2, by[j] = sum of y[i]^2 over i in [j hop, (j + 1) hop), j = 0 .. T - 1; 0 outside that range
+ *   frame RMS        rx[t] = sqrt((bx[t-1] + bx[t] + bx[t+1]) / (3 hop)), ry[t] likewise (the same divisor at the edges)
+ *   global RMS       Rx = sqrt(sum of bx / n), Ry likewise.  Rx == 0, Ry == 0 or either not finite: out = y bit for bit, G = 1
+ *   relative         px[t] = max(rx[t] / Rx, 1e-3), py[t] = max(ry[t] / Ry, 1e-3)          (floor: 60 dB under the average level)
+ *   frame gain       G[t] = min((px[t] / py[t])^a, 4)                                      (cap: +12 dB)
+ *   sample gain      linear between frame centres: p = (i - hop/2) / hop, t0 = clamp(floor p, 0, T-1), t1 = min(t0 + 1, T-1),
+ *                    f = clamp(p - t0, 0, 1), g[i] = G[t0] + f (G[t1] - G[t0]); constant before the first and after the last centre
+ *   result           out[i] = (float)(y[i] g[i]), rounded once.
+ * The division by the global RMS is deliberate: the envelope's shape is transferred, not the recording level (a source recorded
+ * 20 dB low gives the same result).  a in [0, 1] (0: G = 1).  hop: a positive multiple of 64, at most 1024; n a multiple of hop;
+ * anything else is KNNSVC_EINVAL before a launch.  x may be NULL when nx == 0.  gains (may be NULL): T device doubles, receives G.
+ * out may be y itself (no other overlap).  workspace: 8-byte aligned device memory of at least
+ * knnsvc_envelope_workspace_bytes(n, hop) bytes (a HOST function; 0 with knnsvc_last_error() set for bad arguments); a smaller one
+ * is refused before anything is launched.  Three launches, no floating-point atomics, asynchronous on `stream`, no allocation,
+ * no host synchronisation, capturable. */
+size_t knnsvc_envelope_workspace_bytes(int64_t n, int32_t hop);
+int knnsvc_envelope_mix(const float* y, int64_t n, const float* x, int64_t nx, int32_t hop, double a, float* out, double* gains,
+                        void* workspace, size_t workspace_bytes, void* stream);
+/* Peak ceiling: a look-ahead limiter without recursion on SAMPLE peaks (true-peak, i.e. oversampled, limiting is out of scope:
+ * the reconstructed signal between two samples may pass the ceiling).  It does not bring the loudness back: behind
+ * knnsvc_loudness_gain the integrated loudness can end below the target; the statistics say when the limiter engaged.
+ *   constants        c = 10^(peak_db / 20), L = floor(0.005 sample_rate + 0.5)             (80 at 16 kHz)
+ *   required gain    r[i] = c / |y[i]| where |y[i]| > c, else 1; 1 outside [0, n)
+ *   sliding minimum  m[j] = min r[j - L .. j + L]
+ *   weights          h[k] = (1 + cos(pi k / (L + 1))) / (2L + 2), k = -L .. L: a strictly positive Hann; the divisor is the sum
+ *   smoothed gain    s[i] = 1 - sum over k ascending of h[k] (1 - m[i + k])
+ *   result           out[i] = (float)(y[i] s[i]).
+ * Ceiling: every m[i + k] is a minimum over a window that contains i, so s[i] <= r[i] and |out[i]| <= c (1 + 2^-23) after the
+ * one fp32 rounding.  Identity: where nothing within 2L samples exceeds c, s[i] is exactly 1 and out[i] == y[i] bit for bit.
+ * A NaN sample stays NaN, an infinite one becomes NaN (its r is 0): the caller's finiteness check still fires.
+ * sample_rate 8000 .. 48000, peak_db finite and <= 0; anything else is KNNSVC_EINVAL before a launch.  stats (may be NULL): 16
+ * bytes of 8-byte aligned device memory = { int64 number of samples with s < 1, double smallest s (1 when none) }, reset by the
+ * call (integer atomics: order-independent).  out may be y itself (no other overlap); the aliased call runs ONE workgroup over
+ * the tiles in order (a parallel launch could overwrite a neighbour's look-ahead samples before they are read), same bits,
+ * slower.  One launch (two with stats), asynchronous on `stream`, no allocation, no host synchronisation, capturable. */
+int knnsvc_peak_limit(const float* y, int64_t n, int32_t sample_rate, double peak_db, float* out, void* stats, void* stream);
+/* HOST: samples per workgroup tile and L at 16 kHz; tests take their edge lengths from here; either pointer may be NULL. */
+void knnsvc_peak_limit_layout(int32_t* tile, int32_t* lookahead_at_16k);
+
 #ifdef __cplusplus
 }
 #endif

@@ -182,6 +182,10 @@ SIGNATURES = {
     "knnsvc_loudness_gain": (i32, [vp, i64, vp, f32, vp, vp]),
     "knnsvc_vad_workspace_bytes": (sz, [i64, i32, i32]),
     "knnsvc_vad_trim_seg": (i32, [vp, vp, i32, i32, f64, vp, vp, vp, sz, vp]),
+    "knnsvc_envelope_workspace_bytes": (sz, [i64, i32]),
+    "knnsvc_envelope_mix": (i32, [vp, i64, vp, i64, i32, f64, vp, vp, vp, sz, vp]),
+    "knnsvc_peak_limit": (i32, [vp, i64, i32, f64, vp, vp, vp]),
+    "knnsvc_peak_limit_layout": (None, [C.POINTER(i32), C.POINTER(i32)]),
 }
 
 _lib = None

@@ -23,7 +23,12 @@ source's f0 is moved towards the target's: by the difference of the log-f0 media
 arbitrary real interval), by that difference rounded to whole octaves (the pitch classes
 are kept) or to whole semitones (the result stays on the source's equal-tempered grid), or
 not at all; --transpose FLOAT (default 0, at most 36 either way) adds that many semitones
-in every mode.  File names do not change.  --dur_limit is
+in every mode.  File names do not change.  --envelope_mix FLOAT (an extension, 0..1,
+default 0 = off) puts that much of the SOURCE's volume envelope (its shape, not its
+recording level) back on every output, before the loudness stage; --peak_db FLOAT (an
+extension, dBFS <= 0, default none) holds the sample peaks of what is written under that
+ceiling, after the loudness stage, so a normalised file is no longer divided by its peak
+(where the limiter engages the loudness ends below the target).  --dur_limit is
 compared in seconds, as upstream (ddsp_prematch_dataset.py:408-411).
 """
 from __future__ import annotations
@@ -72,6 +77,10 @@ def build_parser() -> argparse.ArgumentParser:
                          "by that difference rounded to octaves or semitones, or not at all")
     ap.add_argument("--transpose", type=float, default=0.0,
                     help="(extension) semitones added to the f0 shift in every mode, at most 36 either way")
+    ap.add_argument("--envelope_mix", type=float, default=0.0,
+                    help="(extension) 0..1: how much of the source's volume envelope is put back on the output (0 = off)")
+    ap.add_argument("--peak_db", type=float, default=None,
+                    help="(extension) sample-peak ceiling of the output in dBFS, <= 0 (default: none)")
     ap.add_argument("--weights", default="auto", choices=["auto", "checkpoint", "seeded"],
                     help="(extension) 'seeded' runs with random weights when the released checkpoints are unavailable")
     return ap
@@ -88,9 +97,10 @@ def output_dir_for(src: str, tgt: str, ckpt_type: str, post_opt: str, dur_limit)
 def main(argv=None) -> int:
     ap = build_parser()
     a = ap.parse_args(argv)
-    from .matching import resolve_f0_shift
+    from .matching import resolve_dynamics, resolve_f0_shift
     try:
         resolve_f0_shift(a.f0_shift, a.transpose)          # before the models are loaded
+        resolve_dynamics(a.envelope_mix, a.peak_db)
     except ValueError as e:
         ap.error(str(e))
     from .hubconf import knn_vc
@@ -99,7 +109,7 @@ def main(argv=None) -> int:
     common = dict(topk=a.topk, device=a.device, prioritize_f0=a.prioritize_f0, ckpt_type=a.ckpt_type,
                   tgt_loudness_db=a.tgt_loudness_db, post_opt=a.post_opt, normalize_loudness=a.normalize_loudness,
                   use_topk=a.use_topk, use_vad=a.use_vad, vad_trigger_level=a.vad_trigger_level,
-                  f0_shift=a.f0_shift, transpose=a.transpose)
+                  f0_shift=a.f0_shift, transpose=a.transpose, envelope_mix=a.envelope_mix, peak_db=a.peak_db)
     if os.path.isfile(a.src) and os.path.isfile(a.tgt):
         knn.special_match(src_wav_file=a.src, ref_wav_file=a.tgt, **common)
         return 0

@@ -10,8 +10,8 @@ same argument names and output file naming.  ``topk`` is accepted and, as upstre
 then brought to that integrated loudness on the GPU (ops.normalize_loudness; what the reference
 documents for the argument, ddsp_matcher.py:533, 947, and does in its commented-out block
 :997-1003).  ``audio_io.save_audio`` keeps the reference's peak rule — a waveform whose peak
-exceeds 1 is divided by it — so a clip normalised past full scale is written lower than asked;
-there is no limiter.  ``vad_trigger_level`` is accepted and, as in upstream's pool builder
+exceeds 1 is divided by it — so a clip normalised past full scale is written lower than asked,
+unless ``peak_db`` (below) holds its peaks under a ceiling first.  ``vad_trigger_level`` is accepted and, as in upstream's pool builder
 (ddsp_prematch_dataset.py:1131 passes 7 to a function that drops it), ignored UNLESS ``use_vad=True``
 is passed (an extension, off by default): silence is then trimmed from both ends of every TARGET
 pool file on the GPU before it is encoded (ops.vad_trim: the sox `vad` effect with torchaudio's
@@ -21,7 +21,12 @@ file names do not change.  ``f0_shift`` ("median", the default and upstream's; "
 "none") and ``transpose`` (semitones, |t| <= 36, default 0) are an extension too: they choose how the
 source's f0 is moved towards the target's (matching.F0_SHIFT_MODES; the interval is chosen per
 utterance on the GPU) and take effect as passed; with the defaults nothing changes, and file names do
-not change with any value.  Other differences that are deliberate: ``special_match`` returns
+not change with any value.  ``envelope_mix`` (0..1, default 0 = off) and ``peak_db`` (dBFS <= 0, default
+None = off) are an extension as well (output dynamics, csrc/dynamics.hip): the tail behind the generator then puts
+the shape of the SOURCE's volume envelope back on the waveform (ops.envelope_mix: phrasing, fades and rests
+survive; level-invariant), normalises the loudness when asked, and last holds the sample peaks under the
+ceiling (ops.limit_peak), so that what is written respects it and ``save_audio``'s peak rule does not fire.
+With the defaults nothing new is launched; file names do not change.  Other differences that are deliberate: ``special_match`` returns
 the waveform instead of calling ``sys.exit()`` after saving (the CLI exits 0, the
 observable behaviour), and ``bulk_match`` does not ``rm -rf`` a hard-coded cache
 directory (ddsp_matcher.py:1066-1068).
@@ -35,7 +40,7 @@ from pathlib import Path
 import torch
 
 from . import audio_io, config as C, dist as kdist, ops
-from .matching import match_at_inference_time, resolve_f0_shift
+from .matching import load_utterance, match_at_inference_time, resolve_dynamics, resolve_f0_shift
 from .vocoder import Vocoder
 from .wavlm import WavLMEncoder
 
@@ -55,17 +60,24 @@ class KNeighborsVC:
         self.hop_length = 320
 
     @torch.inference_mode()
-    def vocode(self, c, f0=None, harmonics_out_feats_weighted=None, loudness_db=None):
+    def vocode(self, c, f0=None, harmonics_out_feats_weighted=None, loudness_db=None, src_wav=None, envelope_mix=0.0, peak_db=None):
         """c (bs, seq_len, c_dim), f0 (bs, seq_len, 1), harmonics (bs, seq_len, 49) -> (bs, seq_len*320).
-        ``loudness_db`` (extension): every waveform is normalised to that integrated loudness before the finiteness check."""
+        ``loudness_db`` (extension): every waveform is normalised to that integrated loudness before the finiteness check.
+        ``envelope_mix`` / ``peak_db`` (extension, matching.resolve_dynamics): the source's envelope is mixed in before the
+        loudness stage, the peak ceiling applied behind it.  ``src_wav``: the bs source waveforms (a [bs, L] tensor or a list of
+        [L_b] tensors, 16 kHz mono as the encoder received them); needed when ``envelope_mix`` > 0."""
+        a, p = resolve_dynamics(envelope_mix, peak_db)
+        if a > 0.0 and src_wav is None:
+            raise ValueError("vocode: envelope_mix > 0 needs src_wav, the source waveforms")
         if f0 is None:
             raise NotImplementedError("the f0-free 'wavlm_only_original' generator (hifigan/models.py) is missing "
                                       "from the reference snapshot and unsupported")
         outs = []
         for b in range(c.shape[0]):
             harm = harmonics_out_feats_weighted[b] if harmonics_out_feats_weighted is not None else None
+            src = src_wav[b].reshape(-1).float().to(self.device) if a > 0.0 else None
             outs.append(self._vocode_async(c[b].to(self.device), f0[b].to(self.device), None if harm is None else harm.to(self.device),
-                                           loudness_db=loudness_db))
+                                           loudness_db=loudness_db, src_wav=src, envelope_mix=a, peak_db=p))
         wav = torch.stack(outs, 0)
         self._check_finite(wav)
         return wav
@@ -76,26 +88,43 @@ class KNeighborsVC:
         if not bool(torch.isfinite(wav).all()):
             raise ops.KnnSvcError("vocode: non-finite waveform (non-finite features, f0, harmonics or weights)")
 
-    def _vocode_async(self, c, f0, harm=None, loudness_db=None):
-        """One utterance, enqueue only (no host sync): the tail stage of the dataset-mode pipeline.  ``loudness_db``: the
-        waveform is measured and scaled to that level on the same stream (in place: ``Vocoder.forward`` hands out a copy)."""
+    def _vocode_async(self, c, f0, harm=None, loudness_db=None, src_wav=None, envelope_mix=0.0, peak_db=None):
+        """One utterance, enqueue only (no host sync): the tail stage of the dataset-mode pipeline, in its fixed order:
+        generator; envelope mix (``envelope_mix`` > 0: the shape of ``src_wav``'s envelope, first because it changes the level);
+        loudness (``loudness_db``: measured and scaled to that level); peak ceiling (``peak_db``: last, so that what is written
+        respects it).  All on the same stream, the first two in place (``Vocoder.forward`` hands out a copy)."""
         y = self.hifigan.forward(c.float(), f0.reshape(-1).float(), None if harm is None else harm.float())
+        if envelope_mix:
+            ops.envelope_mix(y, src_wav, envelope_mix, hop=self.hop_length, out=y)
         if loudness_db is not None:
             ops.normalize_loudness(y, loudness_db, self.sr, out=y)
+        if peak_db is not None:
+            y = ops.limit_peak(y, peak_db, self.sr)          # out of place: the parallel launch
         return y
 
-    def _tail(self, f0only, loudness_db=None):
-        """``vocode_fn(out_feats, shifted_f0, harm)`` of the stream pipeline: generator, then loudness when asked for."""
+    def _tail(self, f0only, loudness_db=None, envelope_mix=0.0, peak_db=None):
+        """``vocode_fn`` of the stream pipeline: generator, then the stages asked for (``_vocode_async``).  With the envelope mix
+        it is the four-argument form ``(out_feats, shifted_f0, harm, src_wav)``, else the three-argument one."""
+        kw = dict(loudness_db=loudness_db, peak_db=peak_db)
+        if envelope_mix:
+            kw["envelope_mix"] = envelope_mix
+            if f0only:
+                return lambda c, f0, _h, src: self._vocode_async(c, f0, src_wav=src, **kw)
+            return lambda c, f0, h, src: self._vocode_async(c, f0, h, src_wav=src, **kw)
         if f0only:
-            return lambda c, f0, _h: self._vocode_async(c, f0, loudness_db=loudness_db)
-        return lambda c, f0, h: self._vocode_async(c, f0, h, loudness_db=loudness_db)
+            return lambda c, f0, _h: self._vocode_async(c, f0, **kw)
+        return lambda c, f0, h: self._vocode_async(c, f0, h, **kw)
 
     @torch.inference_mode()
     def special_match(self, src_wav_file, ref_wav_file, topk: int = 4, device=None, prioritize_f0=True,
                       ckpt_type="wavlm_only", tgt_loudness_db=-16, post_opt="no_post_opt", save=True, normalize_loudness=False,
-                      use_topk=False, use_vad=False, vad_trigger_level=7, f0_shift="median", transpose=0.0):
+                      use_topk=False, use_vad=False, vad_trigger_level=7, f0_shift="median", transpose=0.0, envelope_mix=0.0,
+                      peak_db=None):
         level = tgt_loudness_db if normalize_loudness else None
         resolve_f0_shift(f0_shift, transpose)            # refused before a file is read
+        mix, ceiling = resolve_dynamics(envelope_mix, peak_db)      # likewise
+        dyn = lambda: dict(src_wav=[torch.from_numpy(load_utterance(src_wav_file)[0])] if mix > 0.0 else None, envelope_mix=mix,
+                           peak_db=ceiling)
         f0only = "wavlm_only" in ckpt_type or "no_harm_no_amp" in ckpt_type
         if "wavlm_only_original" in ckpt_type:
             raise NotImplementedError("wavlm_only_original needs hifigan/models.py, absent upstream")
@@ -106,7 +135,7 @@ class KNeighborsVC:
                                                       prioritize_f0=prioritize_f0, ckpt_type=ckpt_type, post_opt=post_opt,
                                                       use_topk=use_topk, use_vad=use_vad, vad_trigger_level=vad_trigger_level,
                                                       f0_shift=f0_shift, transpose=transpose)
-            pred = self.vocode(of[key][None], sf0[key][None, :, None], hw[key][None], loudness_db=level).squeeze()
+            pred = self.vocode(of[key][None], sf0[key][None, :, None], hw[key][None], loudness_db=level, **dyn()).squeeze()
         else:
             # the reference does not forward post_opt on this branch (ddsp_matcher.py:970)
             of, _a, sf0 = match_at_inference_time(Path(src_wav_file), Path(ref_wav_file), self.wavlm,
@@ -114,7 +143,7 @@ class KNeighborsVC:
                                                   prioritize_f0=prioritize_f0, ckpt_type=ckpt_type, use_topk=use_topk,
                                                   use_vad=use_vad, vad_trigger_level=vad_trigger_level,
                                                   f0_shift=f0_shift, transpose=transpose)
-            pred = self.vocode(of[key][None], sf0[key][None, :, None], loudness_db=level).squeeze()
+            pred = self.vocode(of[key][None], sf0[key][None, :, None], loudness_db=level, **dyn()).squeeze()
         src_id = os.path.basename(src_wav_file).split(".")[0]
         ref_id = os.path.basename(ref_wav_file).split(".")[0]
         out_file = str(Path(src_wav_file).parent) + "/" + src_id + "_to_" + ref_id + f"_knn_{ckpt_type}_{post_opt}.wav"
@@ -126,7 +155,7 @@ class KNeighborsVC:
     @torch.inference_mode()
     def many_to_one(self, src_files, ref_wav_file, converted_audio_dir=None, ckpt_type="mix", post_opt="post_opt_0.2",
                     duration_limit=None, target=None, match=None, loudness_db=None, topk=None, vad_trigger_level=None,
-                    f0_shift=None, transpose=None):
+                    f0_shift=None, transpose=None, envelope_mix=None, peak_db=None):
         """BASELINE cfg 5 (no counterpart upstream: the reference would call ``special_match`` once per source and rebuild the
         target pool each time, ddsp_matcher.py:937-1023): MANY sources against ONE target pool that is built once and stays
         resident, all sources through the stream pipeline as one batch (knn_svc_amd/serving.py).  Under a process group the
@@ -135,24 +164,27 @@ class KNeighborsVC:
         from KNNSVC_MATCH).  ``loudness_db``: every waveform is normalised to that integrated loudness (None: left as generated).
         ``topk``: neighbours mixed per frame, 1..8 (None: 4).  ``vad_trigger_level``: the pool's files are trimmed of the silence
         at both ends with that trigger level (None: left whole; ignored when ``target`` is given).  ``f0_shift`` / ``transpose``:
-        the f0 shift mode and the transpose in semitones of every source (None: "median" / 0)."""
+        the f0 shift mode and the transpose in semitones of every source (None: "median" / 0).  ``envelope_mix`` / ``peak_db``: how
+        much of each source's volume envelope is put back on its output (0..1) and the sample-peak ceiling in dBFS (None: off)."""
         from . import serving
         resolve_f0_shift(f0_shift, transpose)            # refused before a file is read
+        resolve_dynamics(envelope_mix, peak_db)
         if target is None:
             target = serving.TargetVoice(self, ref_wav_file, duration_limit, vad_trigger_level=vad_trigger_level)
         mine = kdist.my_share([str(p) for p in src_files])
         written = serving.BatchConverter(self, target, ckpt_type, post_opt, match=match,
                                          loudness_db=loudness_db, topk=topk, f0_shift=f0_shift,
-                                         transpose=transpose).convert_files(mine, converted_audio_dir)
+                                         transpose=transpose, envelope_mix=envelope_mix, peak_db=peak_db).convert_files(mine, converted_audio_dir)
         return kdist.gather_paths(written)
 
     @torch.inference_mode()
     def bulk_match(self, src_dataset_path, tgt_dataset_path, converted_audio_dir, topk: int = 4, device=None,
                    prioritize_f0=True, ckpt_type="mix", tgt_loudness_db=-16, required_subset_file=None,
                    post_opt="no_post_opt", duration_limit=None, normalize_loudness=False, use_topk=False, use_vad=False,
-                   vad_trigger_level=7, f0_shift="median", transpose=0.0):
+                   vad_trigger_level=7, f0_shift="median", transpose=0.0, envelope_mix=0.0, peak_db=None):
         level = tgt_loudness_db if normalize_loudness else None
         resolve_f0_shift(f0_shift, transpose)            # refused before a file is read
+        mix, ceiling = resolve_dynamics(envelope_mix, peak_db)      # likewise
         assert os.path.isdir(src_dataset_path) and os.path.isdir(tgt_dataset_path)
         Path(converted_audio_dir).mkdir(parents=True, exist_ok=True)
         spk = lambda root: sorted([p for p in Path(root).iterdir() if p.is_dir() and "f0_cache" not in os.path.basename(p)])
@@ -194,15 +226,15 @@ class KNeighborsVC:
                               vad_trigger_level=vad_trigger_level, f0_shift=f0_shift, transpose=transpose)
                 # the generator of every utterance is the tail stage of the match pipeline (same kernels and inputs as
                 # `vocode` after the fact, ddsp_matcher.py:1114-1128, but enqueued under the next utterances' matching);
-                # one finiteness check per speaker pair instead of one host sync per utterance; with normalize_loudness the
-                # tail is generator + loudness, still enqueue-only
+                # one finiteness check per speaker pair instead of one host sync per utterance; with normalize_loudness,
+                # envelope_mix or peak_db the tail is generator + those stages, still enqueue-only
                 preds = {}
                 if not f0only:
                     match_at_inference_time(Path(s), Path(t), self.wavlm, self.weighting, self.weighting, post_opt=post_opt,
-                                            vocode_fn=self._tail(False, level), waves_out=preds, **common)
+                                            vocode_fn=self._tail(False, level, mix, ceiling), waves_out=preds, **common)
                 else:
                     match_at_inference_time(Path(s), Path(t), self.wavlm, self.weighting, self.weighting,
-                                            vocode_fn=self._tail(True, level), waves_out=preds, **common)
+                                            vocode_fn=self._tail(True, level, mix, ceiling), waves_out=preds, **common)
                 if preds:      # max |x| of a waveform is NaN / inf iff the waveform holds one
                     self._check_finite(torch.stack([p.abs().max() for p in preds.values()]))
                 for k, pred in preds.items():

@@ -437,6 +437,31 @@ def f0_shift_is_default(modes, transposes) -> bool:
     return all(m == ops.F0_SHIFT_MEDIAN for m in modes) and all(t == 0.0 for t in transposes)
 
 
+def resolve_dynamics(envelope_mix, peak_db):
+    """The two output-dynamics switches as the library takes them, refused before any device or file work when they are not
+    valid -> (a, p).  ``envelope_mix``: a number in [0, 1], None = 0 (off): how much of the source's volume envelope the tail
+    puts back on the generated waveform (ops.envelope_mix).  ``peak_db``: None (off) or a finite number <= 0: the sample-peak
+    ceiling in dBFS the tail holds the waveform under (ops.limit_peak)."""
+    num = lambda v: not isinstance(v, (bool, np.bool_)) and isinstance(v, (int, float, np.integer, np.floating))
+    a = 0.0 if envelope_mix is None else envelope_mix
+    if not num(a) or not 0.0 <= float(a) <= 1.0:                      # (NaN compares false)
+        raise ValueError(f"envelope_mix must be a number in [0, 1] (or None for 0 = off), got {envelope_mix!r}")
+    if peak_db is not None and (not num(peak_db) or not np.isfinite(float(peak_db)) or float(peak_db) > 0.0):
+        raise ValueError(f"peak_db must be a finite number of dBFS <= 0 (or None for no ceiling), got {peak_db!r}")
+    return float(a), None if peak_db is None else float(peak_db)
+
+
+def takes_source(vocode_fn) -> bool:
+    """Whether a ``vocode_fn`` wants the item's source waveform as a fourth argument (the three-argument form keeps working)."""
+    import inspect
+    try:
+        params = list(inspect.signature(vocode_fn).parameters.values())
+    except (TypeError, ValueError):
+        return False
+    pos = [p for p in params if p.kind in (p.POSITIONAL_ONLY, p.POSITIONAL_OR_KEYWORD)]
+    return len(pos) >= 4 or any(p.kind == p.VAR_POSITIONAL for p in params)
+
+
 def match_features(query_seq, query_f0, matching_list, matching_f0, harmonics_list, ckpt_type, post_opt,
                    return_debug=False, nn32=None, nan_flags=None, pool_prep=None, synth_list=None, topk=None,
                    f0_shift=None, transpose=None):
@@ -580,7 +605,8 @@ def match_features_many(query_seqs, query_f0s, matching_list, matching_f0, harmo
 def run_match_bodies(items, body, body_many, tail=None, *, device, lanes, match="lanes", match_batch=None):
     """The match bodies of ``items``, and ``tail(item, result)`` behind each, on the lane / tail streams of a pipeline.LanePipeline
     -> the results in item order.  ``match`` "lanes": ``body(item)`` per item; "segmented" (several items): the items in order, in
-    batches of ``match_batch``, each batch one ``body_many(batch)`` on a lane.  CPU tensors (the injected kernels of the gloo tests)
+    batches of ``match_batch``, each batch one ``body_many(batch)`` on a lane.  What a tail needs besides the match result (the
+    item's source waveform, for the envelope mix) it finds by ``item``: the callers' tails close over it.  CPU tensors (the injected kernels of the gloo tests)
     and a single lane without a tail run on the caller's stream, one after the other."""
     items = list(items)
     dev = torch.device(device)
@@ -628,7 +654,9 @@ def match_at_inference_time(src_wav_file, ref_wav_file, wavlm: WavLMEncoder, mat
     Build extension (BASELINE cfg 5, many sources against one pool): ``vocode_fn(out_feats, shifted_f0, harm)`` is
     enqueued as the pipeline's tail stage right behind each item's match body and its waveform stored in
     ``waves_out[item]`` — the generator of item i then runs underneath the kNN / recurrences of items i+1.., instead
-    of after all of them.  It must not synchronise with the host.
+    of after all of them.  It must not synchronise with the host.  A ``vocode_fn`` with a FOURTH positional parameter also
+    receives the item's source waveform (1-D fp32 on the device, 16 kHz mono as the encoder received it; ``takes_source``): the
+    envelope mix of the tail needs it (KNeighborsVC._tail).  The three-argument form keeps working and loads nothing.
 
     ``pool_sharded`` (default: environment KNNSVC_POOL_SHARD=1; needs a process group, one process per GPU; BASELINE
     cfg 4): EVERY rank must make this call with the same arguments.  The target pool's files are encoded in contiguous
@@ -761,7 +789,13 @@ def match_at_inference_time(src_wav_file, ref_wav_file, wavlm: WavLMEncoder, mat
         tail = None
         if vocode_fn is not None and len(items) > 0:
             assert waves_out is not None
-            tail = lambda item, r: r + (vocode_fn(r[0], r[2], r[1]),)
+            if takes_source(vocode_fn):
+                # the items' waveforms as the encoder received them (load_utterance: mono, 16 kHz), on the device before the
+                # pipeline starts: the tail only enqueues
+                src = {it: torch.from_numpy(load_utterance(it)[0]).to(matching_list.device) for it in items}
+                tail = lambda item, r: r + (vocode_fn(r[0], r[2], r[1], src[item]),)
+            else:
+                tail = lambda item, r: r + (vocode_fn(r[0], r[2], r[1]),)
         results = run_match_bodies(items, body, body_many, tail, device=matching_list.device, lanes=lanes,
                                    match=match_mode() if shard is None else "lanes")
         if tail is not None:

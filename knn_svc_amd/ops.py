@@ -1123,8 +1123,10 @@ def loudness(wav, sample_rate=16000, return_counts=False):
 def normalize_loudness(wav, target_db, sample_rate=16000, out=None):
     """wav scaled to ``target_db`` LKFS: out = wav * 10^((target_db - loudness(wav)) / 20) -> (out, lkfs of wav as a 0-d device
     tensor).  A signal without a measurable loudness (-inf: silence, or shorter than 400 ms) comes back unchanged.  ``out`` may
-    be ``wav`` itself (in place).  Enqueue only: no host read.  Nothing limits the result: a quiet, peaky signal can pass full
-    scale, and audio_io.save_audio then divides by the peak (the reference's rule), so the FILE is lower than asked."""
+    be ``wav`` itself (in place).  Enqueue only: no host read.  This op does not limit the result: a quiet, peaky signal can pass
+    full scale, and audio_io.save_audio then divides by the peak (the reference's rule), so the FILE is lower than asked —
+    unless ``limit_peak`` (below; the ``peak_db`` switch of the entry points) holds the peaks under a ceiling first, at the
+    price of a loudness that can end below ``target_db`` where the limiter engages."""
     _need(wav, name="normalize_loudness.wav")
     if not wav.is_contiguous():
         raise KnnSvcError("normalize_loudness: expected a contiguous waveform")
@@ -1135,6 +1137,64 @@ def normalize_loudness(wav, target_db, sample_rate=16000, out=None):
         raise KnnSvcError("normalize_loudness: out must be a contiguous fp32 tensor of wav's shape")
     check(_lib.load().knnsvc_loudness_gain(_p(wav), wav.numel(), _p(lkfs), float(target_db), _p(out), _stream()), "loudness_gain")
     return out, lkfs
+
+
+# ------------------------------------------------------------------ output dynamics
+def _dyn_out(name, y, out):
+    _need(y, name=f"{name}.y")
+    if y.dim() != 1 or not y.is_contiguous():
+        raise KnnSvcError(f"{name}: expected a contiguous mono waveform [L], got shape {tuple(y.shape)}")
+    if out is None:
+        return torch.empty_like(y)
+    if not (_need(out, name=f"{name}.out").is_contiguous() and out.shape == y.shape):
+        raise KnnSvcError(f"{name}: out must be a contiguous fp32 tensor of y's shape")
+    return out
+
+
+def envelope_mix(y, x, a, hop=320, out=None, return_gains=False):
+    """The shape of the source's volume envelope put back on a generated waveform: ``y`` [T hop] scaled frame by frame by
+    G[t] = min((px[t] / py[t])^a, 4), px / py the three-block RMS envelopes of the source ``x`` (zero-extended or cut to y's
+    length) and of y, each relative to its own global RMS and floored at 1e-3, G interpolated linearly between frame centres
+    (the definition in include/knnsvc_hip.h; fp64 on the device, csrc/dynamics.hip).  ``a`` in [0, 1]: 0 leaves y as it is, 1
+    transfers the envelope fully.  Level-invariant: scaling x changes nothing.  A silent x or y gives y back bit for bit.
+    -> out, or (out, G as [T] fp64 device tensor) with return_gains.  ``out`` may be ``y`` itself.  Enqueue only: no host read."""
+    out = _dyn_out("envelope_mix", y, out)
+    _need(x, name="envelope_mix.x")
+    if x.dim() != 1:
+        raise KnnSvcError(f"envelope_mix: expected a mono source waveform [L], got shape {tuple(x.shape)}")
+    x = x.contiguous()
+    lib = _lib.load()
+    n = y.numel()
+    nbytes = lib.knnsvc_envelope_workspace_bytes(n, int(hop))
+    if nbytes == 0:
+        check(1, "envelope_workspace_bytes")
+    ws = torch.empty((nbytes + 7) // 8, device=y.device, dtype=torch.float64)
+    gains = torch.empty(n // int(hop), device=y.device, dtype=torch.float64) if return_gains else None
+    check(lib.knnsvc_envelope_mix(_p(y), n, _p(x), x.numel(), int(hop), float(a), _p(out), _p(gains), _p(ws), ws.numel() * 8,
+                                  _stream()), "envelope_mix")
+    return (out, gains) if return_gains else out
+
+
+def peak_limit_layout():
+    """(samples per workgroup tile, look-ahead L at 16 kHz) as the library reports them (csrc/dynamics.hip: PK_TILE, and
+    L = floor(0.005 sample_rate + 0.5)): the lengths and positions at which ``limit_peak`` changes path."""
+    tile, look = C.c_int32(0), C.c_int32(0)
+    _lib.load().knnsvc_peak_limit_layout(C.byref(tile), C.byref(look))
+    return tile.value, look.value
+
+
+def limit_peak(y, peak_db, sample_rate=16000, out=None, return_stats=False):
+    """A sample-peak ceiling at ``peak_db`` dBFS (<= 0): a look-ahead limiter without recursion — the gain each sample needs, its
+    minimum over +-5 ms, smoothed by a 10 ms Hann (the definition in include/knnsvc_hip.h; fp64 on the device,
+    csrc/dynamics.hip).  |out| <= 10^(peak_db / 20) (1 + 2^-23) everywhere; samples further than 10 ms from anything over the
+    ceiling come back bit-identical.  Not a true-peak limiter, and it does not bring the loudness back.
+    -> out, or (out, (int64 0-d device tensor: samples whose gain is below 1, fp64 0-d device tensor: the smallest gain)) with
+    return_stats.  ``out`` may be ``y`` itself (one workgroup then walks the signal in order: same bits, slower).  Enqueue
+    only: no host read."""
+    out = _dyn_out("limit_peak", y, out)
+    stats = torch.empty(2, device=y.device, dtype=torch.int64) if return_stats else None
+    check(_lib.load().knnsvc_peak_limit(_p(y), y.numel(), int(sample_rate), float(peak_db), _p(out), _p(stats), _stream()), "peak_limit")
+    return (out, (stats[0], stats[1:].view(torch.float64)[0])) if return_stats else out
 
 
 # ------------------------------------------------------------------ pool-silence trimming

@@ -90,7 +90,11 @@ class BatchConverter:
     def __init__(self, vc, target: TargetVoice, ckpt_type: str = "mix", post_opt: str = "post_opt_0.2", lanes: int | None = None,
                  max_encode_batch: int = 32, match: str | None = None, match_batch: int | None = None,
                  loudness_db: float | None = None, topk: int | None = None, f0_shift: str | None = None,
-                 transpose: float | None = None):
+                 transpose: float | None = None, envelope_mix: float | None = None, peak_db: float | None = None):
+        # output dynamics, checked before anything else (matching.resolve_dynamics; None: off): how much of each source's volume
+        # envelope the tail puts back on its output, in front of the loudness stage (ops.envelope_mix), and the sample-peak ceiling
+        # in dBFS behind it (ops.limit_peak).  Part of the tail, on the tail's stream, enqueue-only; inherited by a RequestQueue.
+        self.envelope_mix, self.peak_db = M.resolve_dynamics(envelope_mix, peak_db)
         if "wavlm_only_original" in ckpt_type:
             raise NotImplementedError("wavlm_only_original needs hifigan/models.py, absent upstream")
         self.vc, self.target, self.ckpt_type, self.post_opt = vc, target, ckpt_type, post_opt
@@ -184,7 +188,7 @@ class BatchConverter:
         qpool = dict(enumerate(feats))
         # the reference does not forward post_opt to the f0-only generators (ddsp_matcher.py:970, 1102-1110)
         post_opt = "no_post_opt" if self.f0only else self.post_opt
-        voc = vc._tail(self.f0only, self.loudness_db)
+        voc = vc._tail(self.f0only, self.loudness_db, self.envelope_mix, self.peak_db)
 
         def run():
             flags = []
@@ -204,7 +208,8 @@ class BatchConverter:
                 return M.match_features_many([qpool[i] for i in batch], [f0s[i] for i in batch], tg.feats, tg.f0, tg.harm, self.ckpt_type,
                                              post_opt, nn32s=[nn.get(i) for i in batch], nan_flags=flags, pool_prep=tg.prep, topk=self.topk,
                                              f0_shift=[modes[i] for i in batch], transpose=[semis[i] for i in batch])
-            tail = lambda i, r: voc(r[0], r[2], r[1])
+            # with the envelope mix the tail also takes the source as the encoder received it
+            tail = (lambda i, r: voc(r[0], r[2], r[1], wavs[i])) if self.envelope_mix else (lambda i, r: voc(r[0], r[2], r[1]))
             ys = M.run_match_bodies(items, body, body_many, tail, device=dev, lanes=max(1, min(self.lanes, len(items))),
                                     match=self.match, match_batch=self.match_batch)
             peak = torch.stack([y.abs().max() for y in ys])
@@ -230,7 +235,8 @@ class BatchConverter:
 class RequestQueue:
     """Dynamic batching in front of a BatchConverter.  ``submit(src)`` -> Future of the waveform (a CPU tensor).
     ``submit(src, transpose=, f0_shift=)``: the request's own transpose (semitones) / f0 shift mode instead of the converter's;
-    requests with different values share a batch."""
+    requests with different values share a batch.  The converter's ``loudness_db``, ``envelope_mix`` and ``peak_db`` apply to every
+    request (per-request values of those are not supported)."""
 
     def __init__(self, converter: BatchConverter, max_batch: int = 32, max_wait_ms: float = 5.0):
         self.conv, self.max_batch, self.max_wait = converter, int(max_batch), float(max_wait_ms) / 1e3
