@@ -434,7 +434,8 @@ int knnsvc_knn_merge(const float* part_dist, const int64_t* part_idx, int32_t pa
  * result[0] = median, result[1] = voiced count (as float).  workspace: n floats. */
 int knnsvc_log_f0_median(const float* f0, int64_t n, float* result, float* workspace, void* stream);
 
-/* shifted[i] = f0[i] ? exp(log f0[i] + (pool_median - query_median)) : 0   (:1232-1233) */
+/* shifted[i] = f0[i] ? exp(log f0[i] + (pool_median - query_median)) : 0   (:1232-1233).  The one-segment case of
+ * knnsvc_shift_f0_seg_mode with MEDIAN / 0 ("Pitch control" below: the three entries share one kernel). */
 int knnsvc_shift_f0(const float* f0, int64_t n, const float* query_median, const float* pool_median,
                     float* shifted, void* stream);
 
@@ -479,12 +480,14 @@ int knnsvc_smooth_weights(const int64_t* idx, int64_t nq, const float* pool, int
  * log f0 over voiced rows — NaN if there is none —, voiced count); workspace: total floats. */
 int knnsvc_log_f0_median_seg(const float* f0, const int64_t* host_seg, int32_t n_seg, float* result, float* workspace, void* stream);
 
-/* knnsvc_shift_f0 per segment (:1232-1233).  query_median [n_seg][2] (the above), pool_median [2]. */
+/* knnsvc_shift_f0 per segment (:1232-1233).  query_median [n_seg][2] (the above), pool_median [2].
+ * knnsvc_shift_f0_seg_mode with NULL tables and a NULL shift_semitones, under this entry's name in the messages. */
 int knnsvc_shift_f0_seg(const float* f0, const int64_t* host_seg, int32_t n_seg, const float* query_median,
                         const float* pool_median, float* shifted, void* stream);
 
 /* Pitch control (an extension; upstream knows only the median shift): knnsvc_shift_f0_seg with a MODE and a TRANSPOSE t
- * (semitones, finite, |t| <= KNNSVC_F0_TRANSPOSE_MAX) per segment.  This restatement is the specification.
+ * (semitones, finite, |t| <= KNNSVC_F0_TRANSPOSE_MAX) per segment.  This restatement is the specification, and the one kernel
+ * and host path behind it also serve knnsvc_shift_f0 and knnsvc_shift_f0_seg (all MEDIAN, all 0).
  *   L = log_rn(f): the fp32 log evaluated in fp64 and rounded once, as in knnsvc_shift_f0; qm, pm: the fp32 lower medians
  *   (query_median[s][0], pool_median[0]); LN2 = fp64 ln 2, S = LN2 / 12, d = (double)pm - (double)qm; rint rounds half to
  *   even; no floating-point contraction anywhere.  Shifted log f0 of a voiced frame:
@@ -492,8 +495,8 @@ int knnsvc_shift_f0_seg(const float* f0, const int64_t* host_seg, int32_t n_seg,
  *     KNNSVC_F0_SHIFT_OCTAVE   (1)  L + (float)(LN2 * rint(d / LN2) + t * S)   pitch classes kept, register moved to the pool's
  *     KNNSVC_F0_SHIFT_SEMITONE (2)  L + (float)(S * rint(d / S) + t * S)       stays on the source's equal-tempered grid
  *     KNNSVC_F0_SHIFT_NONE     (3)  L + (float)(t * S)                         the medians are NOT READ
- *   shifted = exp_rn of that value; an unvoiced frame (f == 0) is copied bit for bit.  MEDIAN with t == 0 gives the bits of
- *   knnsvc_shift_f0_seg.  A NaN median (no voiced frame on either side) propagates in the three modes that read the medians.
+ *   shifted = exp_rn of that value; an unvoiced frame (f == 0) is copied bit for bit.  MEDIAN with t == 0 is upstream's
+ *   shift.  A NaN median (no voiced frame on either side) propagates in the three modes that read the medians.
  *   shift_semitones (device float [n_seg], may be NULL) receives the interval applied, in semitones: d / S + t (MEDIAN),
  *   (quantised + t * S) / S (OCTAVE, SEMITONE), t (NONE).
  * host_modes (int32 [n_seg]) and host_transposes (float [n_seg]) are HOST tables read by the call and handed to the kernel

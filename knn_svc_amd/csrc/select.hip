@@ -71,31 +71,16 @@ __global__ __launch_bounds__(1024) void log_f0_median_kernel(const float* __rest
     log_f0_median_body(f0 + o, seg.off[blockIdx.x + 1] - o, result + 2 * blockIdx.x, ws + o);
 }
 
-// row i of a sequence whose median is qmed[0]
-__device__ __forceinline__ void shift_f0_body(const float* __restrict__ f0, long n, const float* __restrict__ qmed,
-                                              const float* __restrict__ pmed, float* __restrict__ out, long i) {
-#pragma clang fp contract(off)
-    if (i >= n) return;
-    const float f = f0[i];
-    out[i] = f != 0.f ? exp_rn((log_rn(f) + pmed[0]) - qmed[0]) : f;
-}
-
-// blockIdx.y = segment, blockIdx.x covers the longest segment
-__global__ void shift_f0_kernel(const float* __restrict__ f0, const KnSegTable seg, const float* __restrict__ qmed,
-                                    const float* __restrict__ pmed, float* __restrict__ out) {
-    const long o = seg.off[blockIdx.y];
-    shift_f0_body(f0 + o, seg.off[blockIdx.y + 1] - o, qmed + 2 * blockIdx.y, pmed, out + o, (long)blockIdx.x * blockDim.x + threadIdx.x);
-}
-
-// Per-segment shift mode and transpose (semitones) of shift_f0_mode_kernel: host tables handed over by value like the segment table.
+// Per-segment shift mode and transpose (semitones) of shift_f0_kernel: host tables handed over by value like the segment table.
 struct KnShiftModes { int mode[KNNSVC_MAX_SEGMENTS]; float transpose[KNNSVC_MAX_SEGMENTS]; };
 
-// shift_f0_kernel with the interval chosen per segment on the device (include/knnsvc_hip.h, "Pitch control"): every thread derives
-// its segment's interval from the medians, so nothing is read back by the host; thread 0 of the segment's first block reports it.
-// KNNSVC_F0_SHIFT_NONE never reads the medians.
-__global__ void shift_f0_mode_kernel(const float* __restrict__ f0, const KnSegTable seg, const KnShiftModes pm,
-                                     const float* __restrict__ qmed, const float* __restrict__ pmed, float* __restrict__ out,
-                                     float* __restrict__ semis) {
+// The f0 shift of every entry point (include/knnsvc_hip.h, "Pitch control"); blockIdx.y = segment, blockIdx.x covers the longest
+// segment.  The interval is chosen per segment on the device: every thread derives what it adds from the medians, so nothing is
+// read back by the host; thread 0 of the segment's first block reports the interval when asked.  KNNSVC_F0_SHIFT_NONE never reads
+// the medians.
+__global__ void shift_f0_kernel(const float* __restrict__ f0, const KnSegTable seg, const KnShiftModes pm,
+                                const float* __restrict__ qmed, const float* __restrict__ pmed, float* __restrict__ out,
+                                float* __restrict__ semis) {
 #pragma clang fp contract(off)
     const double LN2 = 0.693147180559945309417232121458, S = LN2 / 12.0;
     const int s = blockIdx.y;
@@ -104,30 +89,27 @@ __global__ void shift_f0_mode_kernel(const float* __restrict__ f0, const KnSegTa
     if (i >= n) return;
     const int mode = pm.mode[s];
     const float t = pm.transpose[s];
-    const double ts = (double)t * S;
     float q = 0.f, p = 0.f;
-    float add = (float)ts;                   // what is added to log f0 (median: after its own two-step shift, when t != 0)
-    float applied = t;                       // the interval applied, in semitones
+    double d = 0.0, interval = (double)t * S;
+    float add = (float)interval;             // what is added to log f0 (median: after its own two-step shift, when t != 0)
     if (mode != KNNSVC_F0_SHIFT_NONE) {
         q = qmed[2 * s]; p = pmed[0];
-        const double d = (double)p - (double)q;
-        if (mode == KNNSVC_F0_SHIFT_MEDIAN) {
-            applied = (float)(d / S + (double)t);
-        } else {
+        d = (double)p - (double)q;
+        if (mode != KNNSVC_F0_SHIFT_MEDIAN) {
             const double step = mode == KNNSVC_F0_SHIFT_OCTAVE ? LN2 : S;
-            const double interval = step * rint(d / step) + ts;
+            interval = step * rint(d / step) + interval;
             add = (float)interval;
-            applied = (float)(interval / S);
         }
     }
-    if (i == 0 && semis) semis[s] = applied;
+    if (i == 0 && semis)                     // the interval applied, in semitones
+        semis[s] = mode == KNNSVC_F0_SHIFT_NONE ? t : mode == KNNSVC_F0_SHIFT_MEDIAN ? (float)(d / S + (double)t) : (float)(interval / S);
     const float f = f0[o + i];
     float r = f;
     if (f != 0.f) {
         const float L = log_rn(f);
         float v;
         if (mode == KNNSVC_F0_SHIFT_MEDIAN) {
-            v = (L + p) - q;                 // today's expression, today's bits
+            v = (L + p) - q;                 // upstream's expression
             if (t != 0.f) v = v + add;
         } else {
             v = L + add;
@@ -687,13 +669,27 @@ static int log_f0_median_launch(const KnSegTable& seg, const char* entry, const 
     return knnsvc_check_launch(entry);
 }
 
-static int shift_f0_launch(const KnSegTable& seg, const char* entry, const float* f0, const float* query_median,
-                           const float* pool_median, float* shifted, void* stream) {
+// NULL tables: median / 0.  Every check before the launch: the pointers, then each segment's mode and transpose.
+static int shift_f0_launch(const KnSegTable& seg, const char* entry, const float* f0, const int32_t* host_modes,
+                           const float* host_transposes, const float* query_median, const float* pool_median, float* shifted,
+                           float* shift_semitones, void* stream) {
     KN_REQUIRE(f0 && query_median && pool_median && shifted, "%s: null pointer", entry);
+    KnShiftModes pm;
+    for (int s = 0; s < KNNSVC_MAX_SEGMENTS; ++s) { pm.mode[s] = KNNSVC_F0_SHIFT_MEDIAN; pm.transpose[s] = 0.f; }
+    for (int s = 0; s < seg.n; ++s) {
+        const int m = host_modes ? host_modes[s] : KNNSVC_F0_SHIFT_MEDIAN;
+        const float t = host_transposes ? host_transposes[s] : 0.f;
+        KN_REQUIRE(m >= KNNSVC_F0_SHIFT_MEDIAN && m <= KNNSVC_F0_SHIFT_NONE, "%s: segment %d: unknown mode %d (0 median, 1 octave, 2 semitone, 3 none)",
+                   entry, s, m);
+        KN_REQUIRE(t == t && t >= -KNNSVC_F0_TRANSPOSE_MAX && t <= KNNSVC_F0_TRANSPOSE_MAX,
+                   "%s: segment %d: transpose %g is not a finite number of semitones within +-%g", entry, s, (double)t,
+                   (double)KNNSVC_F0_TRANSPOSE_MAX);
+        pm.mode[s] = m; pm.transpose[s] = t;
+    }
     long longest = 0;
     for (int s = 0; s < seg.n; ++s) longest = seg.off[s + 1] - seg.off[s] > longest ? seg.off[s + 1] - seg.off[s] : longest;
     hipLaunchKernelGGL(shift_f0_kernel, dim3((unsigned)cdiv64(longest, 256), (unsigned)seg.n), dim3(256), 0, (hipStream_t)stream,
-                       f0, seg, query_median, pool_median, shifted);
+                       f0, seg, pm, query_median, pool_median, shifted, shift_semitones);
     return knnsvc_check_launch(entry);
 }
 
@@ -757,7 +753,7 @@ extern "C" int knnsvc_shift_f0(const float* f0, int64_t n, const float* query_me
                                float* shifted, void* stream) {
     KnSegTable seg;
     if (const int rc = kn_seg_one(n, "shift_f0", &seg)) return rc;
-    return shift_f0_launch(seg, "shift_f0", f0, query_median, pool_median, shifted, stream);
+    return shift_f0_launch(seg, "shift_f0", f0, nullptr, nullptr, query_median, pool_median, shifted, nullptr, stream);
 }
 
 extern "C" int knnsvc_f0_rerank(const int64_t* nn_idx, int64_t nq, int32_t k, const float* shifted_f0,
@@ -792,34 +788,16 @@ extern "C" int knnsvc_shift_f0_seg(const float* f0, const int64_t* host_seg, int
                                    const float* pool_median, float* shifted, void* stream) {
     KnSegTable seg;
     if (const int rc = kn_seg_table(host_seg, n_seg, "shift_f0_seg", &seg)) return rc;
-    return shift_f0_launch(seg, "shift_f0_seg", f0, query_median, pool_median, shifted, stream);
+    return shift_f0_launch(seg, "shift_f0_seg", f0, nullptr, nullptr, query_median, pool_median, shifted, nullptr, stream);
 }
 
-// Every check before the launch: the table, the pointers, then each segment's mode and transpose (NULL tables: median / 0).
 extern "C" int knnsvc_shift_f0_seg_mode(const float* f0, const int64_t* host_seg, int32_t n_seg, const int32_t* host_modes,
                                         const float* host_transposes, const float* query_median, const float* pool_median,
                                         float* shifted, float* shift_semitones, void* stream) {
-    const char* entry = "shift_f0_seg_mode";
     KnSegTable seg;
-    if (const int rc = kn_seg_table(host_seg, n_seg, entry, &seg)) return rc;
-    KN_REQUIRE(f0 && query_median && pool_median && shifted, "%s: null pointer", entry);
-    KnShiftModes pm;
-    for (int s = 0; s < KNNSVC_MAX_SEGMENTS; ++s) { pm.mode[s] = KNNSVC_F0_SHIFT_MEDIAN; pm.transpose[s] = 0.f; }
-    for (int s = 0; s < seg.n; ++s) {
-        const int m = host_modes ? host_modes[s] : KNNSVC_F0_SHIFT_MEDIAN;
-        const float t = host_transposes ? host_transposes[s] : 0.f;
-        KN_REQUIRE(m >= KNNSVC_F0_SHIFT_MEDIAN && m <= KNNSVC_F0_SHIFT_NONE, "%s: segment %d: unknown mode %d (0 median, 1 octave, 2 semitone, 3 none)",
-                   entry, s, m);
-        KN_REQUIRE(t == t && t >= -KNNSVC_F0_TRANSPOSE_MAX && t <= KNNSVC_F0_TRANSPOSE_MAX,
-                   "%s: segment %d: transpose %g is not a finite number of semitones within +-%g", entry, s, (double)t,
-                   (double)KNNSVC_F0_TRANSPOSE_MAX);
-        pm.mode[s] = m; pm.transpose[s] = t;
-    }
-    long longest = 0;
-    for (int s = 0; s < seg.n; ++s) longest = seg.off[s + 1] - seg.off[s] > longest ? seg.off[s + 1] - seg.off[s] : longest;
-    hipLaunchKernelGGL(shift_f0_mode_kernel, dim3((unsigned)cdiv64(longest, 256), (unsigned)seg.n), dim3(256), 0, (hipStream_t)stream,
-                       f0, seg, pm, query_median, pool_median, shifted, shift_semitones);
-    return knnsvc_check_launch(entry);
+    if (const int rc = kn_seg_table(host_seg, n_seg, "shift_f0_seg_mode", &seg)) return rc;
+    return shift_f0_launch(seg, "shift_f0_seg_mode", f0, host_modes, host_transposes, query_median, pool_median, shifted,
+                           shift_semitones, stream);
 }
 
 extern "C" int knnsvc_concat_reselect_seg(const int64_t* idx_in, const float* q, const float* q_norm, const int64_t* host_seg,

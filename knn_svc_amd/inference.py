@@ -5,30 +5,13 @@
 SRC/TGT are both audio files (single conversion, output next to SRC as
 ``<src>_to_<tgt>_knn_<ckpt_type>_<post_opt>.wav``) or both dataset roots (folders of
 speaker folders; outputs under ``<tgt parent>/<src>_to_<tgt>_<ckpt_type>_post_opt_<post_opt>/``,
-prefixed ``duration_limit_<n>_`` when --dur_limit is given).  --topk is accepted and, as
-upstream, ignored unless --use_topk true is given (an extension, default false): the match
-stage then mixes that many (1..8) of the 32 neighbours per frame instead of the hard-coded 4;
-file names do not change.  --tgt_loudness_db (default -16) is accepted and, as upstream,
-ignored unless --normalize_loudness true is given (an extension, default false): every
-output is then brought to that integrated loudness (BS.1770) on the GPU before it is
-written; file names do not change, and a clip normalised past full scale is written
-lower than asked (save_audio divides by a peak above 1, as upstream).  --vad_trigger_level
-(default 7, what upstream passes for the target pool and then drops) is ignored unless
---use_vad true is given (an extension, default false): silence is then trimmed from both ends
-of every target pool file on the GPU (the sox `vad` effect with torchaudio's defaults as
-restated in include/knnsvc_hip.h; parity with torchaudio's own code is not pinned); the
-source, the output length and the file names do not change.  --f0_shift
-{median,octave,semitone,none} (an extension, default median = upstream) chooses how the
-source's f0 is moved towards the target's: by the difference of the log-f0 medians (an
-arbitrary real interval), by that difference rounded to whole octaves (the pitch classes
-are kept) or to whole semitones (the result stays on the source's equal-tempered grid), or
-not at all; --transpose FLOAT (default 0, at most 36 either way) adds that many semitones
-in every mode.  File names do not change.  --envelope_mix FLOAT (an extension, 0..1,
-default 0 = off) puts that much of the SOURCE's volume envelope (its shape, not its
-recording level) back on every output, before the loudness stage; --peak_db FLOAT (an
-extension, dBFS <= 0, default none) holds the sample peaks of what is written under that
-ceiling, after the loudness stage, so a normalised file is no longer divided by its peak
-(where the limiter engages the loudness ends below the target).  --dur_limit is
+prefixed ``duration_limit_<n>_`` when --dur_limit is given).  --topk / --use_topk,
+--tgt_loudness_db / --normalize_loudness, --vad_trigger_level / --use_vad, --f0_shift,
+--transpose, --envelope_mix and --peak_db are the extension knobs (knn_svc_amd/options.py has
+the table; the first three values are accepted and, as upstream, ignored unless their switch
+is true); no value changes a file name, and a clip normalised past full scale is written
+lower than asked (save_audio divides by a peak above 1, as upstream) unless --peak_db holds
+its peaks under a ceiling (where the limiter engages the loudness ends below the target).  --dur_limit is
 compared in seconds, as upstream (ddsp_prematch_dataset.py:408-411).
 """
 from __future__ import annotations
@@ -97,19 +80,18 @@ def output_dir_for(src: str, tgt: str, ckpt_type: str, post_opt: str, dur_limit)
 def main(argv=None) -> int:
     ap = build_parser()
     a = ap.parse_args(argv)
-    from .matching import resolve_dynamics, resolve_f0_shift
+    from .options import Extensions
+    knobs = dict(topk=a.topk, use_topk=a.use_topk, tgt_loudness_db=a.tgt_loudness_db, normalize_loudness=a.normalize_loudness,
+                 use_vad=a.use_vad, vad_trigger_level=a.vad_trigger_level, f0_shift=a.f0_shift, transpose=a.transpose,
+                 envelope_mix=a.envelope_mix, peak_db=a.peak_db)
     try:
-        resolve_f0_shift(a.f0_shift, a.transpose)          # before the models are loaded
-        resolve_dynamics(a.envelope_mix, a.peak_db)
+        Extensions.from_reference(**knobs)                 # before the models are loaded
     except ValueError as e:
         ap.error(str(e))
     from .hubconf import knn_vc
     knn = knn_vc(pretrained=True, progress=True, prematched=True, device=a.device, ckpt_type=a.ckpt_type,
                  local_ckpt_dir=a.ckpt_dir, weights=a.weights)
-    common = dict(topk=a.topk, device=a.device, prioritize_f0=a.prioritize_f0, ckpt_type=a.ckpt_type,
-                  tgt_loudness_db=a.tgt_loudness_db, post_opt=a.post_opt, normalize_loudness=a.normalize_loudness,
-                  use_topk=a.use_topk, use_vad=a.use_vad, vad_trigger_level=a.vad_trigger_level,
-                  f0_shift=a.f0_shift, transpose=a.transpose, envelope_mix=a.envelope_mix, peak_db=a.peak_db)
+    common = dict(device=a.device, prioritize_f0=a.prioritize_f0, ckpt_type=a.ckpt_type, post_opt=a.post_opt, **knobs)
     if os.path.isfile(a.src) and os.path.isfile(a.tgt):
         knn.special_match(src_wav_file=a.src, ref_wav_file=a.tgt, **common)
         return 0

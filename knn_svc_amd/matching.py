@@ -5,15 +5,8 @@ Host-side mirror of the reference's ``get_complete_spk_pool`` and
 arguments, same returned dict-of-tensors keyed by ``str(path)``, same quirks
 (k hard-coded to 32 -> first 4, ``--dur_limit`` in seconds overshooting by one file,
 ``post_opt`` parsing, ``prioritize_f0`` must be True, pool rebuilt per call).
-``topk`` is ignored as upstream unless ``use_topk=True`` (an extension, off by default): the
-match stage then keeps that many (1..8) of the 32 neighbours per frame instead of 4.
-``f0_shift`` / ``transpose`` (an extension; defaults "median" / 0 = upstream) choose how the source's f0 is moved towards the
-target's: by the difference of the log-f0 medians, by that difference rounded to whole octaves or semitones, or not at all, plus
-a transpose in semitones (F0_SHIFT_MODES; the kernel chooses the interval per item on the device).
-``vad_trigger_level`` is ignored as in upstream's ``get_complete_spk_pool`` unless ``use_vad=True`` (an extension, off by
-default): silence is then trimmed from both ends of every TARGET pool file on the GPU (ops.vad_trim: the sox `vad` effect with
-torchaudio's defaults as restated in include/knnsvc_hip.h — that restatement is the specification, parity with torchaudio's
-own code is not pinned), which is what the reference documents for the argument (ddsp_matcher.py:438-491).
+``topk``, ``vad_trigger_level`` (accepted and dropped upstream), ``f0_shift`` and ``transpose`` are extension knobs:
+knn_svc_amd/options.py has the table; ``resolve_topk`` / ``resolve_f0_shift`` / ``resolve_dynamics`` below are its checks.
 All arithmetic is done by libknnsvc_hip.so kernels on device-resident tensors; the
 only host work is file I/O and the chunk bookkeeping.
 """
@@ -27,6 +20,7 @@ import numpy as np
 import torch
 
 from . import audio_io, config as C, dist as kdist, features, ops, pipeline, pool_cache
+from .options import Extensions
 from .wavlm import WavLMEncoder, chunk_plan
 
 AUDIO_EXT = {".flac", ".wav", ".mp3"}
@@ -432,11 +426,6 @@ def resolve_f0_shift(mode, transpose, n_items=None):
     return [m for m, _ in pairs], [t for _, t in pairs]
 
 
-def f0_shift_is_default(modes, transposes) -> bool:
-    """True when every item takes upstream's median shift untransposed: the match stage then launches what it always did."""
-    return all(m == ops.F0_SHIFT_MEDIAN for m in modes) and all(t == 0.0 for t in transposes)
-
-
 def resolve_dynamics(envelope_mix, peak_db):
     """The two output-dynamics switches as the library takes them, refused before any device or file work when they are not
     valid -> (a, p).  ``envelope_mix``: a number in [0, 1], None = 0 (off): how much of the source's volume envelope the tail
@@ -449,17 +438,6 @@ def resolve_dynamics(envelope_mix, peak_db):
     if peak_db is not None and (not num(peak_db) or not np.isfinite(float(peak_db)) or float(peak_db) > 0.0):
         raise ValueError(f"peak_db must be a finite number of dBFS <= 0 (or None for no ceiling), got {peak_db!r}")
     return float(a), None if peak_db is None else float(peak_db)
-
-
-def takes_source(vocode_fn) -> bool:
-    """Whether a ``vocode_fn`` wants the item's source waveform as a fourth argument (the three-argument form keeps working)."""
-    import inspect
-    try:
-        params = list(inspect.signature(vocode_fn).parameters.values())
-    except (TypeError, ValueError):
-        return False
-    pos = [p for p in params if p.kind in (p.POSITIONAL_ONLY, p.POSITIONAL_OR_KEYWORD)]
-    return len(pos) >= 4 or any(p.kind == p.VAR_POSITIONAL for p in params)
 
 
 def match_features(query_seq, query_f0, matching_list, matching_f0, harmonics_list, ckpt_type, post_opt,
@@ -519,11 +497,10 @@ def match_features_many(query_seqs, query_f0s, matching_list, matching_f0, harmo
     ``topk``: neighbours kept per frame out of the 32 found (1..8; None = 4, the specialised kernels).
     ``f0_shift`` / ``transpose``: how each item's f0 is moved (F0_SHIFT_MODES; a value for all items or a list with one per item;
     None = "median" / 0).  The interval is chosen per item on the device (ops.shift_f0_seg with modes): no host read of the
-    medians.  With every item on the median shift and no transpose the stage launches exactly what it launches without the
-    arguments.  The debug dict carries ``shift_semitones``: the interval applied to the item (a one-element device tensor)."""
+    medians; the defaults are the same call with the median / 0 tables.  The debug dict carries ``shift_semitones``: the interval
+    applied to the item (a one-element device tensor)."""
     topk = resolve_topk(topk)                 # before any device work
     shift_modes, shift_ts = resolve_f0_shift(f0_shift, transpose, len(query_seqs))
-    plain_shift = f0_shift_is_default(shift_modes, shift_ts) and not return_debug
     lens = [int(q.shape[0]) for q in query_seqs]
     seg = [0]
     for n in lens:
@@ -553,11 +530,8 @@ def match_features_many(query_seqs, query_f0s, matching_list, matching_f0, harmo
     w = w2 = harm_w = None
     with torch.cuda.stream(side):
         qmed, pmed = ops.log_f0_median_seg(query_f0, seg), ops.log_f0_median(matching_f0)      # the pool's median once
-        semis = None
-        if plain_shift:
-            shifted = ops.shift_f0_seg(query_f0, seg, qmed, pmed)
-        else:
-            shifted, semis = ops.shift_f0_seg(query_f0, seg, qmed, pmed, shift_modes, shift_ts, return_shift=True)
+        shifted = ops.shift_f0_seg(query_f0, seg, qmed, pmed, shift_modes, shift_ts, return_shift=return_debug)
+        shifted, semis = shifted if return_debug else (shifted, None)
         ranked = ops.f0_rerank(nn32, shifted, matching_f0)
         idx2 = ranked[:, :topk].contiguous()
         if cw != -1:
@@ -621,6 +595,17 @@ def run_match_bodies(items, body, body_many, tail=None, *, device, lanes, match=
     return pipe.run(items, body, tail)
 
 
+def vocoding_tail(vocode_fn, items, source_of):
+    """The ``tail(item, result)`` of ``run_match_bodies`` around a ``vocode_fn(out_feats, shifted_f0, harm)`` -> the item's
+    waveform.  A ``vocode_fn`` whose ``needs_source`` attribute is true (matcher.Tail with the envelope mix)
+    also gets ``src_wav=source_of(item)``, the item's waveform as the encoder received it, on the device: all of them are fetched
+    here, before the pipeline starts, since the tail only enqueues.  Any other callable is called with the three arguments."""
+    if not getattr(vocode_fn, "needs_source", False):
+        return lambda item, r: vocode_fn(r[0], r[2], r[1])
+    src = {it: source_of(it) for it in items}
+    return lambda item, r: vocode_fn(r[0], r[2], r[1], src_wav=src[item])
+
+
 def _mix_of(weights, wavlm):
     """A layer weighting as the encoder takes it: None for the one-hot on its exit layer (the live path), else the tuple."""
     if weights is None:
@@ -640,23 +625,19 @@ def match_at_inference_time(src_wav_file, ref_wav_file, wavlm: WavLMEncoder, mat
                             src_dataset_path=None, tgt_dataset_path=None, cache_dir=None, required_subset=None,
                             post_opt="no_post_opt", duration_limit=None, vocode_fn=None, waves_out=None,
                             pool_sharded=None, share_items=False, use_topk=False, use_vad=False, vad_trigger_level=7,
-                            f0_shift="median", transpose=0.0):
-    """Same contract as the reference function (ddsp_prematch_dataset.py:1074).  ``topk`` is accepted and, as upstream
-    (k = 32 -> 4 is hard-coded there, :1203,1246,1398), ignored UNLESS ``use_topk=True`` (an extension, off by default): the
-    match stage then keeps ``topk`` (1..8) neighbours per frame.  ``cache_dir`` is ignored (the reference force-disables
-    it, :1086-1087).  ``vad_trigger_level`` (upstream passes 7 for the target pool, :1131, to a function that drops it) takes
-    effect only with ``use_vad=True`` (an extension, off by default): the TARGET pool's files, never the source, are trimmed of
-    the silence at both ends (``get_complete_spk_pool``); output length and file names do not change.
-    ``f0_shift`` ("median", upstream's and the default; "octave", "semitone", "none": F0_SHIFT_MODES) and ``transpose`` (semitones,
-    |t| <= 36, default 0) steer the f0 shift of every item (an extension; the interval is chosen on the device, per item, on every
-    route below); with the defaults the stage launches what it always did.  File names do not change.
+                            f0_shift="median", transpose=0.0, ext=None):
+    """Same contract as the reference function (ddsp_prematch_dataset.py:1074).  ``cache_dir`` is ignored (the reference
+    force-disables it, :1086-1087).  ``topk`` (k = 32 -> 4 is hard-coded upstream, :1203,1246,1398) / ``use_topk``,
+    ``vad_trigger_level`` (upstream passes 7 for the target pool, :1131, to a function that drops it) / ``use_vad``, ``f0_shift``
+    and ``transpose`` are the extension knobs of options.Extensions.from_reference, on every route below; ``ext``: that record
+    already built by the caller (``special_match``, ``bulk_match``), the six arguments are then not read.
 
     Build extension (BASELINE cfg 5, many sources against one pool): ``vocode_fn(out_feats, shifted_f0, harm)`` is
     enqueued as the pipeline's tail stage right behind each item's match body and its waveform stored in
     ``waves_out[item]`` — the generator of item i then runs underneath the kNN / recurrences of items i+1.., instead
-    of after all of them.  It must not synchronise with the host.  A ``vocode_fn`` with a FOURTH positional parameter also
-    receives the item's source waveform (1-D fp32 on the device, 16 kHz mono as the encoder received it; ``takes_source``): the
-    envelope mix of the tail needs it (KNeighborsVC._tail).  The three-argument form keeps working and loads nothing.
+    of after all of them.  It must not synchronise with the host.  A ``vocode_fn`` with a true ``needs_source`` attribute
+    (matcher.Tail with the envelope mix) also receives ``src_wav=``, the item's source waveform (``vocoding_tail``); a plain
+    three-argument callable loads nothing.
 
     ``pool_sharded`` (default: environment KNNSVC_POOL_SHARD=1; needs a process group, one process per GPU; BASELINE
     cfg 4): EVERY rank must make this call with the same arguments.  The target pool's files are encoded in contiguous
@@ -669,10 +650,9 @@ def match_at_inference_time(src_wav_file, ref_wav_file, wavlm: WavLMEncoder, mat
         rank the per-shard lists of its own items only, and each rank runs the match bodies (and ``vocode_fn``) of its
         own items: the returned dicts hold this rank's items."""
     import torch.distributed as tdist
-    k_use = resolve_topk(topk) if use_topk else None        # refused before any file is read
-    # likewise; handed on only when it says something (as topk above: the bodies keep the call they always got)
-    pitch = {} if f0_shift_is_default(*resolve_f0_shift(f0_shift, transpose, 1)) else dict(f0_shift=f0_shift, transpose=transpose)
-    vad_level = vad_trigger_level if use_vad else 0
+    if ext is None:                  # refused before any file is read
+        ext = Extensions.from_reference(topk=topk, use_topk=use_topk, use_vad=use_vad, vad_trigger_level=vad_trigger_level,
+                                        f0_shift=f0_shift, transpose=transpose)
     if pool_sharded is None:         # by environment: only when there is more than one rank to shard over
         pool_sharded = os.environ.get("KNNSVC_POOL_SHARD") == "1" and kdist.world()[1] > 1
     pool_sharded = bool(pool_sharded) and tdist.is_available() and tdist.is_initialized()   # explicit True: any group, even 1 rank
@@ -692,7 +672,7 @@ def match_at_inference_time(src_wav_file, ref_wav_file, wavlm: WavLMEncoder, mat
     if tgt_dataset_path is None:
         assert os.path.isfile(ref_wav_file)
     matching_pool, _synth, _audio, _spec, f0_pool, harm_pool = get_complete_spk_pool(
-        ref_wav_file, wavlm, device=device, duration_limit=duration_limit, shard_files=pool_sharded, vad_trigger_level=vad_level)
+        ref_wav_file, wavlm, device=device, duration_limit=duration_limit, shard_files=pool_sharded, vad_trigger_level=ext.vad_level)
     keys = list(matching_pool)
     E = wavlm.E
     cat = lambda pool, shape: (torch.cat([pool[k] for k in keys], 0).contiguous() if keys
@@ -705,7 +685,7 @@ def match_at_inference_time(src_wav_file, ref_wav_file, wavlm: WavLMEncoder, mat
             # (a sharded pool: this rank's share again, under the synthesis weighting; all-gathered below like the matching features —
             #  the search only ever sees the matching features, the gathers and the smoothness weights read the synthesis ones)
             _m, synth_pool, _a2, _s2, _f2, _h2 = get_complete_spk_pool(ref_wav_file, wavlm, device=device, duration_limit=duration_limit,
-                                                                       shard_files=pool_sharded, vad_trigger_level=vad_level)
+                                                                       shard_files=pool_sharded, vad_trigger_level=ext.vad_level)
         finally:
             wavlm.set_layer_mix(mix_m)
         assert list(synth_pool) == keys
@@ -771,31 +751,25 @@ def match_at_inference_time(src_wav_file, ref_wav_file, wavlm: WavLMEncoder, mat
             nn.update(g_nn); nn_ready.update(g_ready)
         def body(item):
             wait_for_neighbours(nn.get(item), nn_ready.get(item), matching_list.device)      # a group search on the kNN stream
-            extra = dict(synth_list=synth_list) if synth_list is not None else {}
-            if k_use is not None:
-                extra["topk"] = k_use
             return match_features(query_pool[item], query_f0_pool[item], matching_list, matching_f0,
-                                  harmonics_list, ckpt_type, post_opt, nan_flags=flags, pool_prep=prep, nn32=nn.get(item), **pitch,
-                                  **extra)
+                                  harmonics_list, ckpt_type, post_opt, nan_flags=flags, pool_prep=prep, nn32=nn.get(item),
+                                  synth_list=synth_list, topk=ext.topk, f0_shift=ext.f0_shift, transpose=ext.transpose)
         def body_many(batch):
             for item in batch:
                 wait_for_neighbours(nn.get(item), nn_ready.get(item), matching_list.device)
             return match_features_many([query_pool[it] for it in batch], [query_f0_pool[it] for it in batch], matching_list, matching_f0,
                                        harmonics_list, ckpt_type, post_opt, nn32s=[nn.get(it) for it in batch], nan_flags=flags,
-                                       pool_prep=prep, synth_list=synth_list, topk=k_use, **pitch)
+                                       pool_prep=prep, synth_list=synth_list, topk=ext.topk, f0_shift=ext.f0_shift,
+                                       transpose=ext.transpose)
         # match bodies in flight at once (each is a chain of single-workgroup recurrences: more lanes = more of them side by side);
         # KNNSVC_MATCH=segmented (unsharded pool, several items): batches of KNNSVC_MATCH_BATCH items, each one body_many on a lane
         lanes = min(int(os.environ.get("KNNSVC_MATCH_LANES", "3")), len(items))
         tail = None
         if vocode_fn is not None and len(items) > 0:
             assert waves_out is not None
-            if takes_source(vocode_fn):
-                # the items' waveforms as the encoder received them (load_utterance: mono, 16 kHz), on the device before the
-                # pipeline starts: the tail only enqueues
-                src = {it: torch.from_numpy(load_utterance(it)[0]).to(matching_list.device) for it in items}
-                tail = lambda item, r: r + (vocode_fn(r[0], r[2], r[1], src[item]),)
-            else:
-                tail = lambda item, r: r + (vocode_fn(r[0], r[2], r[1]),)
+            # (load_utterance: mono, 16 kHz — the waveform the encoder received)
+            wave = vocoding_tail(vocode_fn, items, lambda it: torch.from_numpy(load_utterance(it)[0]).to(matching_list.device))
+            tail = lambda item, r: r + (wave(item, r),)
         results = run_match_bodies(items, body, body_many, tail, device=matching_list.device, lanes=lanes,
                                    match=match_mode() if shard is None else "lanes")
         if tail is not None:

@@ -909,9 +909,12 @@ def shift_f0_seg(f0, seg, qmed, pmed, modes=None, transposes=None, return_shift=
     """``qmed`` [n_seg, 2] from log_f0_median_seg, ``pmed`` [2] -> shifted f0 of the stacked rows.
     ``modes`` (per segment: 0 median, 1 octave, 2 semitone, 3 none) and ``transposes`` (per segment, semitones): the interval
     is then chosen per segment on the device (knnsvc_shift_f0_seg_mode; include/knnsvc_hip.h "Pitch control"); with both None
-    this is the median shift through knnsvc_shift_f0_seg.  ``return_shift``: -> (shifted, [n_seg] applied interval in
+    this is the median shift through knnsvc_shift_f0_seg (the same kernel with median / 0).  ``return_shift``: -> (shifted, [n_seg] applied interval in
     semitones, on the device)."""
     _need(f0, name="f0"); seg = _segments(seg, "shift_f0_seg", f0)
+    _need(qmed, name="qmed"); _need(pmed, name="pmed")
+    if qmed.numel() != 2 * seg.n or not qmed.is_contiguous():
+        raise KnnSvcError(f"shift_f0_seg: qmed must be a contiguous [{seg.n}, 2] tensor, got {tuple(qmed.shape)}")
     f0 = f0.contiguous()
     out = torch.empty_like(f0)
     lib = _lib.load()
@@ -922,9 +925,6 @@ def shift_f0_seg(f0, seg, qmed, pmed, modes=None, transposes=None, return_shift=
     for name, t in (("modes", modes), ("transposes", transposes)):
         if t is not None and len(t) != seg.n:
             raise KnnSvcError(f"shift_f0_seg: {len(t)} {name} for {seg.n} segments")
-    _need(qmed, name="qmed"); _need(pmed, name="pmed")
-    if qmed.numel() != 2 * seg.n or not qmed.is_contiguous():
-        raise KnnSvcError(f"shift_f0_seg: qmed must be a contiguous [{seg.n}, 2] tensor, got {tuple(qmed.shape)}")
     semis = torch.empty(seg.n, device=f0.device, dtype=torch.float32) if return_shift else None
     for a, r0, tab in seg.chunks:
         n = len(tab) - 1

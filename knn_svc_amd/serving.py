@@ -34,6 +34,8 @@ import torch
 
 from . import audio_io, config as C, ops
 from . import matching as M
+from .matcher import Tail
+from .options import Extensions
 
 
 class TargetVoice:
@@ -90,11 +92,14 @@ class BatchConverter:
     def __init__(self, vc, target: TargetVoice, ckpt_type: str = "mix", post_opt: str = "post_opt_0.2", lanes: int | None = None,
                  max_encode_batch: int = 32, match: str | None = None, match_batch: int | None = None,
                  loudness_db: float | None = None, topk: int | None = None, f0_shift: str | None = None,
-                 transpose: float | None = None, envelope_mix: float | None = None, peak_db: float | None = None):
-        # output dynamics, checked before anything else (matching.resolve_dynamics; None: off): how much of each source's volume
-        # envelope the tail puts back on its output, in front of the loudness stage (ops.envelope_mix), and the sample-peak ceiling
-        # in dBFS behind it (ops.limit_peak).  Part of the tail, on the tail's stream, enqueue-only; inherited by a RequestQueue.
-        self.envelope_mix, self.peak_db = M.resolve_dynamics(envelope_mix, peak_db)
+                 transpose: float | None = None, envelope_mix: float | None = None, peak_db: float | None = None,
+                 ext: Extensions | None = None):
+        # the extension knobs, checked before anything else (options.py; None: off): ``loudness_db``, ``envelope_mix`` and
+        # ``peak_db`` are part of the tail, on the tail's stream, enqueue-only, and apply to every request of a RequestQueue in
+        # front of this converter; ``f0_shift`` / ``transpose`` are what a source gets unless a request says otherwise (pitch_of).
+        # ``ext``: the record already built by the caller (many_to_one); the six arguments are then not read.
+        self.ext = ext if ext is not None else Extensions.from_serving(loudness_db=loudness_db, topk=topk, f0_shift=f0_shift,
+                                                                       transpose=transpose, envelope_mix=envelope_mix, peak_db=peak_db)
         if "wavlm_only_original" in ckpt_type:
             raise NotImplementedError("wavlm_only_original needs hifigan/models.py, absent upstream")
         self.vc, self.target, self.ckpt_type, self.post_opt = vc, target, ckpt_type, post_opt
@@ -106,15 +111,6 @@ class BatchConverter:
         # KNNSVC_MATCH / KNNSVC_MATCH_BATCH.
         self.match = M.match_mode(match)
         self.match_batch = M.match_batch_size(match_batch)
-        # integrated loudness every waveform is brought to (ops.normalize_loudness as part of the tail, on the tail's stream,
-        # enqueue-only); None: the generator's own level.  A RequestQueue in front of this converter inherits it.
-        self.loudness_db = None if loudness_db is None else float(loudness_db)
-        # neighbours mixed per frame out of the 32 found: 1..8; None: 4 (the released checkpoints' training condition)
-        self.topk = None if topk is None else M.resolve_topk(topk)
-        # how every source's f0 is moved towards the target's unless a request says otherwise (matching.F0_SHIFT_MODES; None:
-        # "median" / 0 semitones, upstream's shift).  Kept as given, checked here.
-        M.resolve_f0_shift(f0_shift, transpose)
-        self.f0_shift, self.transpose = f0_shift, transpose
 
     def _load(self, src, check=False):
         """A request is a path, or (wav [L] float32 16 kHz mono as array / tensor, f0 [L // 320 + 1] or None).
@@ -157,7 +153,7 @@ class BatchConverter:
         """Per-source ``f0_shift`` / ``transpose`` (a value for all, or one per source; None entries: this converter's defaults)
         as checked lists of ``n`` values each; ``n`` None: one checked pair."""
         fill = lambda v, d: [d if x is None else x for x in v] if isinstance(v, (list, tuple)) else (d if v is None else v)
-        f0_shift, transpose = fill(f0_shift, self.f0_shift), fill(transpose, self.transpose)
+        f0_shift, transpose = fill(f0_shift, self.ext.f0_shift), fill(transpose, self.ext.transpose)
         M.resolve_f0_shift(f0_shift, transpose, n)
         if n is None:
             return f0_shift, transpose
@@ -188,7 +184,7 @@ class BatchConverter:
         qpool = dict(enumerate(feats))
         # the reference does not forward post_opt to the f0-only generators (ddsp_matcher.py:970, 1102-1110)
         post_opt = "no_post_opt" if self.f0only else self.post_opt
-        voc = vc._tail(self.f0only, self.loudness_db, self.envelope_mix, self.peak_db)
+        tail = M.vocoding_tail(Tail(vc, self.f0only, self.ext), items, wavs.__getitem__)
 
         def run():
             flags = []
@@ -200,16 +196,14 @@ class BatchConverter:
             def body(i):
                 M.wait_for_neighbours(nn.get(i), ready.get(i), dev)
                 return M.match_features(qpool[i], f0s[i], tg.feats, tg.f0, tg.harm, self.ckpt_type, post_opt,
-                                        nan_flags=flags, pool_prep=tg.prep, nn32=nn.get(i), topk=self.topk,
+                                        nan_flags=flags, pool_prep=tg.prep, nn32=nn.get(i), topk=self.ext.topk,
                                         f0_shift=modes[i], transpose=semis[i])
             def body_many(batch):
                 for i in batch:
                     M.wait_for_neighbours(nn.get(i), ready.get(i), dev)
                 return M.match_features_many([qpool[i] for i in batch], [f0s[i] for i in batch], tg.feats, tg.f0, tg.harm, self.ckpt_type,
-                                             post_opt, nn32s=[nn.get(i) for i in batch], nan_flags=flags, pool_prep=tg.prep, topk=self.topk,
+                                             post_opt, nn32s=[nn.get(i) for i in batch], nan_flags=flags, pool_prep=tg.prep, topk=self.ext.topk,
                                              f0_shift=[modes[i] for i in batch], transpose=[semis[i] for i in batch])
-            # with the envelope mix the tail also takes the source as the encoder received it
-            tail = (lambda i, r: voc(r[0], r[2], r[1], wavs[i])) if self.envelope_mix else (lambda i, r: voc(r[0], r[2], r[1]))
             ys = M.run_match_bodies(items, body, body_many, tail, device=dev, lanes=max(1, min(self.lanes, len(items))),
                                     match=self.match, match_batch=self.match_batch)
             peak = torch.stack([y.abs().max() for y in ys])

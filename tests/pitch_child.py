@@ -84,6 +84,24 @@ def case_kernel():
     note("kernel/median-t0-is-the-old-entry", same(old, new) and same(old, new2) and bool(np.isnan(q[1, 0]) and np.isnan(q[6, 0]))
          and q[3, 1] == 1 and bool(torch.isnan(old[seg[1]:seg[2]]).sum() == 0),
          f"{len(segs)} segments, {seg[-1]} rows; voiced counts {q[:, 1].tolist()}")
+    # the three entries share one kernel, so the table is also held against the oracle (fed the device's medians), and every
+    # segment alone through the single-sequence entry must give the stacked result
+    old_h, pm, bad = old.cpu().numpy(), np.float32(pmed[0].item()), []
+    for i, s in enumerate(segs):
+        got = old_h[seg[i]:seg[i + 1]]
+        want_i = O.shift(s, q[i, 0], pm, O.MEDIAN, 0)[0]
+        unv = s == 0
+        if unv.all():                                  # nothing to shift: the median is NaN and is not applied to anything
+            ok = bool(np.isnan(q[i, 0]))
+        else:
+            WORST.append(rel_err(got, want_i))
+            ok = WORST[-1] <= REL_TOL
+        ok = ok and np.array_equal(got[unv].view(np.uint32), s[unv].view(np.uint32)) \
+            and np.array_equal(np.isnan(got), np.isnan(want_i))          # (NaN wherever the oracle has one)
+        alone = ops.shift_f0(f0[seg[i]:seg[i + 1]].contiguous(), qmed[i].contiguous(), pmed)
+        if not (ok and same(alone, old[seg[i]:seg[i + 1]])):
+            bad.append(i)
+    note("kernel/median-t0-equals-the-oracle-and-each-segment-alone", not bad, f"segments that differ: {bad}")
     want = [(float(pmed[0]) - float(q[i, 0])) / O.S for i in range(len(segs))]
     got = semis.cpu().numpy()
     okm = all((np.isnan(w) and np.isnan(g)) or abs(w - g) <= SEMI_TOL for w, g in zip(want, got))

@@ -77,8 +77,10 @@ def _cpu_merge(part_dist, part_idx):
 
 
 def _cpu_match_features(query_seq, query_f0, matching_list, matching_f0, harmonics_list, ckpt_type, post_opt,
-                        return_debug=False, nn32=None, nan_flags=None, pool_prep=None):
+                        return_debug=False, nn32=None, nan_flags=None, pool_prep=None, synth_list=None, topk=None, f0_shift=None,
+                        transpose=None):
     from oracle import select_ref
+    assert synth_list is None and topk is None and f0_shift in (None, "median") and not transpose      # the defaults: k = 4, median shift
     if nn32 is None:
         nn32 = _cpu_local_topk(query_seq, matching_list, 32, 0)[0]
     sh = select_ref.shift_query_f0(query_f0, matching_f0)

@@ -193,8 +193,22 @@ def test_cli_defaults_are_off():
 
 
 def test_a_three_argument_vocode_fn_is_told_apart_from_a_four_argument_one():
-    from knn_svc_amd.matching import takes_source
+    """The tail asks for the source (``needs_source``) exactly when the envelope mix is on; a plain three-argument callable has
+    no such attribute and is called with the three arguments (matching.vocoding_tail)."""
+    from knn_svc_amd.matcher import Tail
+    from knn_svc_amd.matching import vocoding_tail
+    from knn_svc_amd.options import Extensions
     vc = _bare_vc()
-    assert not takes_source(lambda c, f0, h: None) and takes_source(lambda c, f0, h, src: None)
-    assert not takes_source(vc._tail(False)) and not takes_source(vc._tail(True, -16.0, 0.0, -1.0))
-    assert takes_source(vc._tail(False, None, 0.5)) and takes_source(vc._tail(True, None, 0.5, -1.0))
+    tail = lambda f0only, loudness_db=None, envelope_mix=0.0, peak_db=None: Tail(vc, f0only, Extensions.from_serving(
+        loudness_db=loudness_db, envelope_mix=envelope_mix, peak_db=peak_db))
+    assert not tail(False).needs_source and not tail(True, -16.0, 0.0, -1.0).needs_source
+    assert tail(False, None, 0.5).needs_source and tail(True, None, 0.5, -1.0).needs_source
+    loaded = []
+    plain = vocoding_tail(lambda c, f0, h: (c, f0, h), ["a"], loaded.append)
+    assert plain("a", (1, 2, 3)) == (1, 3, 2) and loaded == []
+
+    def wants(c, f0, h, src_wav=None):
+        return c, f0, h, src_wav
+    wants.needs_source = True
+    sourced = vocoding_tail(wants, ["a", "b"], lambda it: (loaded.append(it), it.upper())[1])
+    assert loaded == ["a", "b"] and sourced("b", (1, 2, 3)) == (1, 3, 2, "B")

@@ -9,7 +9,8 @@ the pytest process.
 
 Kernel cases (a few hundred to two thousand frames each):
   median-t0              a stacked table (three melodies, an all-unvoiced segment, a segment with one voiced frame, two 1-frame
-                         segments) through the new entry with median / 0 == the old entry, bit for bit
+                         segments) through the new entry with median / 0 == the old entry, bit for bit; the entries share one
+                         kernel, so the table is also held against the oracle and against each segment alone (knnsvc_shift_f0)
   up / down / near       every mode x transpose {0, +3, -12, 0.5}: one call per case, the source stacked sixteen times
   seventy-segments       mixed modes and transposes in one ops call (two library calls) == each segment alone, bit for bit
   unvoiced-pool          `none` gives finite output and never reads the NaN median; `median` gives NaN on voiced frames
@@ -59,6 +60,8 @@ def _check(report, prefix, at_least):
 def test_median_without_transpose_through_the_new_entry_is_the_old_entry_bit_for_bit(report):
     _check(report, "kernel/median-t0-is-the-old-entry", 1)
     _check(report, "kernel/median-t0-reports-the-interval", 1)
+    # the entries share one kernel: the same table against the oracle, and each segment alone through knnsvc_shift_f0
+    _check(report, "kernel/median-t0-equals-the-oracle-and-each-segment-alone", 1)
 
 
 @pytest.mark.parametrize("case", ["up", "down", "near"])

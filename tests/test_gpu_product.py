@@ -69,6 +69,52 @@ def test_many_to_one_equals_special_match_per_source(tmp_path, ckpt_type, kind):
         assert np.array_equal(ref, got), (stem, int(np.abs(ref.astype(np.int64) - got.astype(np.int64)).max()))
 
 
+@pytest.mark.parametrize("ckpt_type,kind", [("mix", "mix"), ("wavlm_only", "f0")])
+def test_every_knob_switched_on_gives_the_same_samples_on_every_route(tmp_path, ckpt_type, kind):
+    """topk 3, semitone shift + 2, loudness -20, envelope mix 0.5 and a -1 dBFS ceiling at once: ``special_match`` (upstream-style
+    arguments with their switches), the file ``many_to_one`` writes, ``BatchConverter.convert`` and a ``RequestQueue`` in front of
+    it give every source the same PCM32 samples — a knob dropped or misrouted on one route shows here.  And ``special_match`` with
+    the same values but every switch off equals the call without any of the arguments.  (The pool trimmer has its own product
+    tests, test_gpu_vad.py: synthetic clips have no silence to trim.)"""
+    from knn_svc_amd import serving
+    vc = _tiny_vc(kind)
+    pool = tmp_path / "tgt"
+    _write_pool(pool, n=1, secs=4)
+    ref = str(pool / "t0.wav")
+    files = []
+    for i, n in enumerate([16000 * 2 + 11, 9000, 16000 * 3]):
+        w, f = S.synth_clip(n, seed=700 + i)
+        p = tmp_path / f"s{i}.wav"
+        audio_io.write_wav_pcm16(str(p), w, 16000); np.save(tmp_path / f"s{i}_f0.npy", f * 1.2)
+        files.append(str(p))
+    post_opt = "post_opt_0.2"
+    sk = dict(ckpt_type=ckpt_type, post_opt=post_opt, save=False)
+    upstream = dict(topk=3, use_topk=True, tgt_loudness_db=-20, normalize_loudness=True, f0_shift="semitone", transpose=2,
+                    envelope_mix=0.5, peak_db=-1)
+    knobs = dict(topk=3, loudness_db=-20, f0_shift="semitone", transpose=2, envelope_mix=0.5, peak_db=-1)
+    pcm = lambda y: audio_io.to_pcm32(y.detach().cpu().numpy().reshape(1, -1))
+    single = [pcm(vc.special_match(p, ref, **upstream, **sk)) for p in files]
+    written = vc.many_to_one(files, ref, str(tmp_path / "out"), ckpt_type=ckpt_type, post_opt=post_opt, **knobs)
+    conv = serving.BatchConverter(vc, serving.TargetVoice(vc, ref), ckpt_type, post_opt, **knobs)
+    batch = [pcm(y) for y in conv.convert(files)]
+    rq = serving.RequestQueue(conv, max_batch=len(files), max_wait_ms=5000.0)      # the batch closes when it is full: nothing waits
+    try:
+        queued = [pcm(f.result(timeout=60)) for f in [rq.submit(p) for p in files]]
+    finally:
+        rq.close()
+    for i, o in enumerate(written):
+        x, sr = audio_io.read_wav(o)
+        assert sr == 16000 and x.shape == single[i].shape
+        for route, got in (("many_to_one", audio_io.to_pcm32(x)), ("convert", batch[i]), ("queue", queued[i])):
+            assert np.array_equal(single[i], got), (i, route, int(np.abs(single[i].astype(np.int64) - got.astype(np.int64)).max()))
+    p = files[0]
+    plain = pcm(vc.special_match(p, ref, **sk))
+    assert not np.array_equal(plain, single[0])                  # the knobs do something
+    off = dict(upstream, use_topk=False, normalize_loudness=False, use_vad=False, vad_trigger_level=7, f0_shift="median", transpose=0,
+               envelope_mix=0, peak_db=None)
+    assert np.array_equal(plain, pcm(vc.special_match(p, ref, **off, **sk)))
+
+
 def test_request_queue_batches_and_returns_each_request_its_own_waveform(tmp_path):
     """serving.RequestQueue: requests submitted from several threads are drained into batches (dynamic batching) and every
     Future gets the waveform of ITS request — equal to converting that request alone; in-memory requests with and without an

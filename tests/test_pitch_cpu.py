@@ -41,8 +41,6 @@ def test_resolve_f0_shift_values():
     assert M.resolve_f0_shift("octave", 0.0, 3) == ([1, 1, 1], [0.0, 0.0, 0.0])
     assert M.resolve_f0_shift(["median", "none", None], [1, None, -2.0], 3) == ([0, 3, 0], [1.0, 0.0, -2.0])
     assert M.resolve_f0_shift("none", [0, 12], 2) == ([3, 3], [0.0, 12.0])
-    assert M.f0_shift_is_default([0, 0], [0.0, 0.0]) and not M.f0_shift_is_default([0, 2], [0.0, 0.0])
-    assert not M.f0_shift_is_default([0, 0], [0.0, 1.0])
 
 
 @pytest.mark.parametrize("mode,t", [("fifth", 0), ("Median", 0), (4, 0), (0, 0), (True, 0), ("median", float("nan")),
