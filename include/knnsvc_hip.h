@@ -546,6 +546,37 @@ int knnsvc_smooth_weights_seg_k(const int64_t* idx, int32_t k, const int64_t* ho
                                 int32_t dim, int32_t ld, float scale, const float* row_scale, int32_t max_iter, float* out_w,
                                 int32_t* out_iters, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Time scale (makes upstream's target_duration work, ddsp_matcher.py:524-548): n_seg stacked query sequences re-timed
+ * along the frame axis, in front of the whole match stage.  x [seg_in[n_seg], dim] -> x_out [seg_out[n_seg], dim] and
+ * f0 [seg_in[n_seg]] -> f0_out [seg_out[n_seg]]; x / x_out may both be NULL (f0 only), f0 / f0_out may both be NULL
+ * (features only).  host_seg_in / host_seg_out are HOST row-offset tables as for the *_seg calls above (segment s: T =
+ * seg_in[s+1] - seg_in[s] >= 1 input rows, T' = seg_out[s+1] - seg_out[s] >= 1 output rows); host_inv_scale (HOST double
+ * [n_seg]) holds c = 1 / scale_factor per segment, finite and > 0.  The caller decides T' and c; the kernel applies them.
+ * This restatement is the specification.  All arithmetic is fp64 and no operation is contracted with another, with ONE
+ * stated exception: the source index is a single fused multiply-add, rounded once, because that is how PyTorch's CPU
+ * kernel evaluates the same expression (the two-rounding form differs from it wherever c * (j + 0.5) lies just above a
+ * power of two and r below it, by up to an ulp of the product).  For output row j of a segment:
+ *     r  = fma(c, (double)j + 0.5, -0.5);  r < 0 becomes 0
+ *     i0 = (int64)r;  i1 = i0 + (i0 < T-1 ? 1 : 0);  l1 = r - (double)i0;  l0 = 1.0 - l1
+ *     i0 > T-1 (possible only through rounding): i0 = i1 = T-1, l1 = 0
+ *   which is PyTorch's `linear`, align_corners=False, scale_factor-given source index with c = 1 / scale_factor, the call
+ *   upstream makes.
+ *   features  x_out[j][d] = (float)(l0 * (double)x[i0][d] + l1 * (double)x[i1][d]): two multiplies, one add, one rounding
+ *             to fp32.  With c == 1 every l1 is 0 and finite rows come back bit for bit.
+ *   f0        (upstream has no rule) voiced means > 0; near = (l1 > 0.5) ? i1 : i0, a tie goes left.  f0[near] <= 0 -> 0;
+ *             else both neighbours voiced -> (float)exp(l0 * log((double)f0[i0]) + l1 * log((double)f0[i1])) (interpolation
+ *             in log-frequency, the domain the match stage works in); else f0[near] unchanged.  Voicing follows the nearer
+ *             frame and a note's edge never glides towards 0 Hz.
+ * A row never reads across its segment's boundary, and the result of segment s does not depend on what else is in the call.
+ * One launch on `stream` (256-thread workgroups: four feature rows each, 16-byte accesses when dim % 4 == 0 and x, x_out are
+ * 16-byte aligned, else scalar; the f0 frames in a tail of the grid), no atomics, no workspace, hipGraph-capturable.
+ * Refused before the launch, with a message: a bad table, a null / non-finite / non-positive inv_scale, x without x_out
+ * (or f0 without f0_out) and the reverse, neither pair given, dim <= 0 with features.
+ * ------------------------------------------------------------------------------------------ */
+int knnsvc_time_scale_seg(const float* x, int32_t dim, const float* f0, const int64_t* host_seg_in, const int64_t* host_seg_out,
+                          const double* host_inv_scale, int32_t n_seg, float* x_out, float* f0_out, void* stream);
+
 /* out[i,:] = sum_k w[i,k] * pool[idx[i,k], :]   (ddsp_prematch_dataset.py:1358, 1444).  w NULL = uniform weights:
  * mean_mode 0 multiplies every row by 1.0f / k (softmax(ones), :1361-1364), mean_mode 1 sums in order and divides by k
  * (torch.mean, harmonics :1446); any k >= 1, the two are bit-identical when k is a power of two. */

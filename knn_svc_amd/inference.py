@@ -11,7 +11,9 @@ prefixed ``duration_limit_<n>_`` when --dur_limit is given).  --topk / --use_top
 the table; the first three values are accepted and, as upstream, ignored unless their switch
 is true); no value changes a file name, and a clip normalised past full scale is written
 lower than asked (save_audio divides by a peak above 1, as upstream) unless --peak_db holds
-its peaks under a ceiling (where the limiter engages the loudness ends below the target).  --dur_limit is
+its peaks under a ceiling (where the limiter engages the loudness ends below the target).  --target_duration
+SECONDS (file mode only; upstream documents the argument and never delivers it) re-times the conversion to
+that length (matching.duration_plan; the file name does not change).  --dur_limit is
 compared in seconds, as upstream (ddsp_prematch_dataset.py:408-411).
 """
 from __future__ import annotations
@@ -64,6 +66,9 @@ def build_parser() -> argparse.ArgumentParser:
                     help="(extension) 0..1: how much of the source's volume envelope is put back on the output (0 = off)")
     ap.add_argument("--peak_db", type=float, default=None,
                     help="(extension) sample-peak ceiling of the output in dBFS, <= 0 (default: none)")
+    ap.add_argument("--target_duration", type=float, default=None, metavar="SECONDS",
+                    help="(extension, file mode only) re-time the conversion to this length; between a quarter of and four "
+                         "times the source's; not together with --envelope_mix")
     ap.add_argument("--weights", default="auto", choices=["auto", "checkpoint", "seeded"],
                     help="(extension) 'seeded' runs with random weights when the released checkpoints are unavailable")
     return ap
@@ -85,15 +90,19 @@ def main(argv=None) -> int:
                  use_vad=a.use_vad, vad_trigger_level=a.vad_trigger_level, f0_shift=a.f0_shift, transpose=a.transpose,
                  envelope_mix=a.envelope_mix, peak_db=a.peak_db)
     try:
-        Extensions.from_reference(**knobs)                 # before the models are loaded
+        ext = Extensions.from_reference(**knobs)           # before the models are loaded
+        from .matching import refuse_duration_with_envelope, resolve_target_duration
+        refuse_duration_with_envelope([resolve_target_duration(a.target_duration)], ext)
     except ValueError as e:
         ap.error(str(e))
+    if a.target_duration is not None and os.path.isdir(a.src):
+        ap.error("--target_duration applies to a single source file: one duration for a dataset of utterances means nothing")
     from .hubconf import knn_vc
     knn = knn_vc(pretrained=True, progress=True, prematched=True, device=a.device, ckpt_type=a.ckpt_type,
                  local_ckpt_dir=a.ckpt_dir, weights=a.weights)
     common = dict(device=a.device, prioritize_f0=a.prioritize_f0, ckpt_type=a.ckpt_type, post_opt=a.post_opt, **knobs)
     if os.path.isfile(a.src) and os.path.isfile(a.tgt):
-        knn.special_match(src_wav_file=a.src, ref_wav_file=a.tgt, **common)
+        knn.special_match(src_wav_file=a.src, ref_wav_file=a.tgt, target_duration=a.target_duration, **common)
         return 0
     if os.path.isdir(a.src) and os.path.isdir(a.tgt):
         knn.bulk_match(src_dataset_path=a.src, tgt_dataset_path=a.tgt,

@@ -21,7 +21,7 @@ from pathlib import Path
 import torch
 
 from . import audio_io, config as C, dist as kdist, ops
-from .matching import load_utterance, match_at_inference_time
+from .matching import load_utterance, match_at_inference_time, refuse_duration_with_envelope, resolve_target_duration
 from .options import Extensions
 from .vocoder import Vocoder
 from .wavlm import WavLMEncoder
@@ -97,9 +97,12 @@ class KNeighborsVC:
     def special_match(self, src_wav_file, ref_wav_file, topk: int = 4, device=None, prioritize_f0=True,
                       ckpt_type="wavlm_only", tgt_loudness_db=-16, post_opt="no_post_opt", save=True, normalize_loudness=False,
                       use_topk=False, use_vad=False, vad_trigger_level=7, f0_shift="median", transpose=0.0, envelope_mix=0.0,
-                      peak_db=None):
+                      peak_db=None, target_duration=None):
+        """``target_duration`` (seconds, None: off): the conversion re-timed to that length — the waveform has
+        matching.duration_plan's T_out * 320 samples, the file name does not change; not with ``envelope_mix`` > 0."""
         ext = Extensions.from_reference(topk, use_topk, tgt_loudness_db, normalize_loudness, use_vad, vad_trigger_level, f0_shift,
                                         transpose, envelope_mix, peak_db)          # refused before a file is read
+        refuse_duration_with_envelope([resolve_target_duration(target_duration)], ext)
         f0only = "wavlm_only" in ckpt_type or "no_harm_no_amp" in ckpt_type
         if "wavlm_only_original" in ckpt_type:
             raise NotImplementedError("wavlm_only_original needs hifigan/models.py, absent upstream")
@@ -107,7 +110,7 @@ class KNeighborsVC:
         # the reference does not forward post_opt to the f0-only generators (ddsp_matcher.py:970)
         res = match_at_inference_time(Path(src_wav_file), Path(ref_wav_file), self.wavlm, self.weighting, self.weighting,
                                       device=self.device, prioritize_f0=prioritize_f0, ckpt_type=ckpt_type, ext=ext,
-                                      **({} if f0only else dict(post_opt=post_opt)))
+                                      target_duration=target_duration, **({} if f0only else dict(post_opt=post_opt)))
         tail = Tail(self, f0only, ext)
         src = [torch.from_numpy(load_utterance(src_wav_file)[0])] if tail.needs_source else None
         pred = self._vocode(tail, res[0][key][None], res[-1][key][None, :, None], None if f0only else res[1][key][None], src).squeeze()
@@ -122,20 +125,25 @@ class KNeighborsVC:
     @torch.inference_mode()
     def many_to_one(self, src_files, ref_wav_file, converted_audio_dir=None, ckpt_type="mix", post_opt="post_opt_0.2",
                     duration_limit=None, target=None, match=None, loudness_db=None, topk=None, vad_trigger_level=None,
-                    f0_shift=None, transpose=None, envelope_mix=None, peak_db=None):
+                    f0_shift=None, transpose=None, envelope_mix=None, peak_db=None, target_duration=None):
         """BASELINE cfg 5 (no counterpart upstream: the reference would call ``special_match`` once per source and rebuild the
         target pool each time, ddsp_matcher.py:937-1023): MANY sources against ONE target pool that is built once and stays
         resident, all sources through the stream pipeline as one batch (knn_svc_amd/serving.py).  Under a process group the
         sources are dealt over the ranks (no collective).  ``target``: a serving.TargetVoice to reuse.  -> written paths (all
         ranks' on every rank), named like ``special_match``'s outputs.  ``match``: "lanes" | "segmented" (serving.BatchConverter; default
         from KNNSVC_MATCH).  ``loudness_db`` ... ``peak_db``: the extension knobs, None = off (options.Extensions.from_serving;
-        ``vad_trigger_level`` is ignored when ``target`` is given)."""
+        ``vad_trigger_level`` is ignored when ``target`` is given).  ``target_duration``: seconds, one value for all sources or
+        a list with one entry per source (None entries: off; serving.BatchConverter.convert)."""
         from . import serving
         ext = Extensions.from_serving(loudness_db, topk, vad_trigger_level, f0_shift, transpose, envelope_mix, peak_db)   # before a file is read
+        refuse_duration_with_envelope(resolve_target_duration(target_duration, len(src_files)), ext)
         if target is None:
             target = serving.TargetVoice(self, ref_wav_file, duration_limit, vad_trigger_level=ext.vad_level)
         mine = kdist.my_share([str(p) for p in src_files])
-        written = serving.BatchConverter(self, target, ckpt_type, post_opt, match=match, ext=ext).convert_files(mine, converted_audio_dir)
+        if isinstance(target_duration, (list, tuple)):        # this rank's sources' own entries
+            target_duration = kdist.my_share(list(target_duration))
+        written = serving.BatchConverter(self, target, ckpt_type, post_opt, match=match, ext=ext).convert_files(
+            mine, converted_audio_dir, target_duration=target_duration)
         return kdist.gather_paths(written)
 
     @torch.inference_mode()

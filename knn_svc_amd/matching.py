@@ -13,6 +13,7 @@ only host work is file I/O and the chunk bookkeeping.
 from __future__ import annotations
 
 import contextlib
+import math
 import os
 from pathlib import Path
 
@@ -426,6 +427,87 @@ def resolve_f0_shift(mode, transpose, n_items=None):
     return [m for m, _ in pairs], [t for _, t in pairs]
 
 
+# ``target_duration`` (seconds; upstream's name, documented there and never delivered: ddsp_matcher.py:524-548 stretches the query
+# features only, then exits): the QUERY sequence — features and f0 — is re-timed right behind the encoder (ops.time_scale_seg;
+# include/knnsvc_hip.h "Time scale" is the specification), so every stage of the match sees the stretched sequence and the generator
+# emits T_out * hop samples.  A duration belongs to a source item, not to the options.Extensions record.
+DURATION_SCALE_MIN, DURATION_SCALE_MAX = 0.25, 4.0      # product bound on T_out / T: beyond it the pool's frames are repeated or
+                                                        # skipped further than the neighbour smoothing can hide
+
+
+def _one_target_duration(value):
+    if value is None:
+        return None
+    if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, float, np.integer, np.floating)):
+        raise ValueError(f"target_duration must be a number of seconds (or None for off), got {value!r}")
+    d = float(value)
+    if not np.isfinite(d) or d <= 0:
+        raise ValueError(f"target_duration must be finite and > 0 seconds (or None for off), got {value!r}")
+    return d
+
+
+def resolve_target_duration(value, n_items=None):
+    """``target_duration`` checked, refused before any device or file work when it is not valid.  ``n_items`` None: one number
+    of seconds, finite and > 0, or None (off) -> float or None.  ``n_items`` = the number of items of a batch: the value may
+    also be a list / tuple with one entry per item (None entries: off) -> list of n_items entries."""
+    if n_items is None:
+        if isinstance(value, (list, tuple)):
+            raise ValueError("target_duration: a single value expected here, not a list")
+        return _one_target_duration(value)
+    if isinstance(value, (list, tuple)):
+        if len(value) != n_items:
+            raise ValueError(f"target_duration: {len(value)} values for {n_items} items")
+        return [_one_target_duration(v) for v in value]
+    return [_one_target_duration(value)] * n_items
+
+
+def duration_plan(T, target_duration, sr=C.SAMPLE_RATE, hop=C.HOP, item=None):
+    """-> (T_out, inv_scale) for a query of ``T`` frames and a ``target_duration`` in seconds: upstream's arithmetic verbatim
+    (ddsp_matcher.py:546-548), T_out as F.interpolate computes it from its scale factor.  ValueError (naming ``item``) when the
+    result has no frame or the scale factor lies outside [DURATION_SCALE_MIN, DURATION_SCALE_MAX]."""
+    who = "" if item is None else f" for {item}"
+    if int(T) < 1:
+        raise ValueError(f"target_duration{who}: the source has no frame")
+    target_samples = int(target_duration * sr)
+    s = (target_samples / hop) / T
+    T_out = int(math.floor(float(T) * s))
+    if T_out < 1:
+        raise ValueError(f"target_duration{who}: {target_duration!r} s is shorter than one frame ({hop} samples at {sr} Hz)")
+    if not DURATION_SCALE_MIN <= s <= DURATION_SCALE_MAX:
+        raise ValueError(f"target_duration{who}: {target_duration!r} s for a source of {T} frames ({T * hop / sr:g} s) is a time scale "
+                         f"of {s:g}, outside [{DURATION_SCALE_MIN:g}, {DURATION_SCALE_MAX:g}]")
+    return T_out, 1.0 / s
+
+
+def refuse_duration_with_envelope(durations, ext):
+    """The envelope mix aligns the source waveform with the output sample for sample, so it cannot be combined with a re-timed
+    query (re-timing that envelope is left for later): ValueError when any of ``durations`` is set and ``ext.envelope_mix`` > 0."""
+    if ext.envelope_mix > 0 and any(d is not None for d in durations):
+        raise ValueError("target_duration cannot be combined with envelope_mix > 0: the envelope stage aligns the source waveform "
+                         "with the output sample for sample")
+
+
+def stretch_queries(feats, f0s, durations):
+    """The queries of a batch re-timed to their ``durations`` (seconds, None: left alone): ONE ops.time_scale_seg over the
+    stacked items that have one -> (feats', f0s'), per-item views of its outputs; the other items pass through as the very
+    same tensors, and without any duration nothing is launched."""
+    who = [i for i, d in enumerate(durations) if d is not None]
+    if not who:
+        return feats, f0s
+    plans = [duration_plan(feats[i].shape[0], durations[i], item=f"item {i}") for i in who]
+    seg = [0]
+    for i in who:
+        seg.append(seg[-1] + int(feats[i].shape[0]))
+    xo, fo = ops.time_scale_seg(_stacked([feats[i] for i in who]), _stacked([f0s[i] for i in who]), seg,
+                                [p[0] for p in plans], [p[1] for p in plans])
+    feats, f0s = list(feats), list(f0s)
+    o = 0
+    for i, (T_out, _c) in zip(who, plans):
+        feats[i], f0s[i] = xo[o:o + T_out], fo[o:o + T_out]
+        o += T_out
+    return feats, f0s
+
+
 def resolve_dynamics(envelope_mix, peak_db):
     """The two output-dynamics switches as the library takes them, refused before any device or file work when they are not
     valid -> (a, p).  ``envelope_mix``: a number in [0, 1], None = 0 (off): how much of the source's volume envelope the tail
@@ -625,12 +707,15 @@ def match_at_inference_time(src_wav_file, ref_wav_file, wavlm: WavLMEncoder, mat
                             src_dataset_path=None, tgt_dataset_path=None, cache_dir=None, required_subset=None,
                             post_opt="no_post_opt", duration_limit=None, vocode_fn=None, waves_out=None,
                             pool_sharded=None, share_items=False, use_topk=False, use_vad=False, vad_trigger_level=7,
-                            f0_shift="median", transpose=0.0, ext=None):
+                            f0_shift="median", transpose=0.0, ext=None, target_duration=None):
     """Same contract as the reference function (ddsp_prematch_dataset.py:1074).  ``cache_dir`` is ignored (the reference
     force-disables it, :1086-1087).  ``topk`` (k = 32 -> 4 is hard-coded upstream, :1203,1246,1398) / ``use_topk``,
     ``vad_trigger_level`` (upstream passes 7 for the target pool, :1131, to a function that drops it) / ``use_vad``, ``f0_shift``
     and ``transpose`` are the extension knobs of options.Extensions.from_reference, on every route below; ``ext``: that record
-    already built by the caller (``special_match``, ``bulk_match``), the six arguments are then not read.
+    already built by the caller (``special_match``, ``bulk_match``), the six arguments are then not read.  ``target_duration``
+    (seconds, None: off; single source file only — with ``src_dataset_path`` a value is refused): the source's features and f0
+    are re-timed to that length right behind the encoder (``stretch_queries``), in front of everything of the match stage, so
+    the returned tensors have ``duration_plan``'s T_out frames; not to be combined with ``envelope_mix`` > 0.
 
     Build extension (BASELINE cfg 5, many sources against one pool): ``vocode_fn(out_feats, shifted_f0, harm)`` is
     enqueued as the pipeline's tail stage right behind each item's match body and its waveform stored in
@@ -653,6 +738,10 @@ def match_at_inference_time(src_wav_file, ref_wav_file, wavlm: WavLMEncoder, mat
     if ext is None:                  # refused before any file is read
         ext = Extensions.from_reference(topk=topk, use_topk=use_topk, use_vad=use_vad, vad_trigger_level=vad_trigger_level,
                                         f0_shift=f0_shift, transpose=transpose)
+    target_duration = resolve_target_duration(target_duration)
+    if target_duration is not None and src_dataset_path is not None:
+        raise ValueError("target_duration applies to a single source file: one duration for a dataset of utterances means nothing")
+    refuse_duration_with_envelope([target_duration], ext)
     if pool_sharded is None:         # by environment: only when there is more than one rank to shard over
         pool_sharded = os.environ.get("KNNSVC_POOL_SHARD") == "1" and kdist.world()[1] > 1
     pool_sharded = bool(pool_sharded) and tdist.is_available() and tdist.is_initialized()   # explicit True: any group, even 1 rank
@@ -667,8 +756,14 @@ def match_at_inference_time(src_wav_file, ref_wav_file, wavlm: WavLMEncoder, mat
     wavlm.set_layer_mix(mix_m)
     if src_dataset_path is None:
         assert os.path.isfile(src_wav_file)
+    if target_duration is not None:  # the ratio is refused before anything is encoded
+        duration_plan(frames_of(len(load_utterance(src_wav_file)[0]), wavlm), target_duration, item=str(src_wav_file))
     query_pool, _, _, _, query_f0_pool, _ = get_complete_spk_pool(src_wav_file, wavlm, device=device,
                                                                   shard_files=share_items, gather=share_items)
+    if target_duration is not None:
+        (key,) = list(query_pool)
+        ft, f0 = stretch_queries([query_pool[key]], [query_f0_pool[key]], [target_duration])
+        query_pool, query_f0_pool = {key: ft[0]}, {key: f0[0]}      # (new dicts: the pool store's entries stay as they are)
     if tgt_dataset_path is None:
         assert os.path.isfile(ref_wav_file)
     matching_pool, _synth, _audio, _spec, f0_pool, harm_pool = get_complete_spk_pool(

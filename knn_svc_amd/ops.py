@@ -975,6 +975,66 @@ def smooth_weights_seg(idx4, seg, pool, scale, max_iter=100000, return_iters=Fal
     return (w, iters) if return_iters else w
 
 
+def time_scale_seg(x, f0, seg, out_frames, inv_scales, out=None):
+    """The stacked sequences of ``seg`` re-timed along the frame axis (knnsvc_time_scale_seg; include/knnsvc_hip.h "Time scale"
+    is the specification): segment s gets ``out_frames[s]`` >= 1 rows, read at the source positions ``inv_scales[s]`` (= 1 /
+    scale factor, finite and > 0) spaces.  ``x`` [total, dim] features and ``f0`` [total], either may be None -> (x_out, f0_out)
+    with None for None.  The caller decides the lengths and the scales (matching.duration_plan).  ``out``: (x_out, f0_out)
+    buffers to write into instead of new ones.  Enqueue only: nothing is read back."""
+    given = [(n, t) for n, t in (("x", x), ("f0", f0)) if t is not None]
+    if not given:
+        raise KnnSvcError("time_scale_seg: neither features nor f0 given")
+    for n, t in given:
+        _need(t, name=n)
+        if not t.is_contiguous():
+            raise KnnSvcError(f"time_scale_seg: {n} must be contiguous")
+    if x is not None and (x.dim() != 2 or x.shape[1] < 1):
+        raise KnnSvcError(f"time_scale_seg: x must be [rows, dim], got {tuple(x.shape)}")
+    if f0 is not None and f0.dim() != 1:
+        raise KnnSvcError(f"time_scale_seg: f0 must be [rows], got {tuple(f0.shape)}")
+    seg = _segments(seg, "time_scale_seg", *[t for _, t in given])
+    if len(out_frames) != seg.n or len(inv_scales) != seg.n:
+        raise KnnSvcError(f"time_scale_seg: {len(out_frames)} out_frames and {len(inv_scales)} inv_scales for {seg.n} segments")
+    oseg = [0]
+    for s, n in enumerate(out_frames):
+        if isinstance(n, bool) or int(n) != n or int(n) < 1:
+            raise KnnSvcError(f"time_scale_seg: segment {s}: out_frames must be an integer >= 1, got {n!r}")
+        oseg.append(oseg[-1] + int(n))
+    cs = [float(c) for c in inv_scales]
+    for s, c in enumerate(cs):
+        if not (math.isfinite(c) and c > 0):
+            raise KnnSvcError(f"time_scale_seg: segment {s}: inv_scale must be finite and > 0, got {inv_scales[s]!r}")
+    oseg = Segments(oseg)
+    dev = given[0][1].device
+    dim = 0 if x is None else int(x.shape[1])
+    xo, fo = out if out is not None else (None, None)
+    if x is not None and xo is None:
+        xo = torch.empty(oseg.total, dim, device=dev, dtype=torch.float32)
+    if f0 is not None and fo is None:
+        fo = torch.empty(oseg.total, device=dev, dtype=torch.float32)
+    for n, t, shape in (("x_out", xo, (oseg.total, dim)), ("f0_out", fo, (oseg.total,))):
+        if (t is None) != ((x if n == "x_out" else f0) is None):
+            raise KnnSvcError(f"time_scale_seg: {n} given without its input, or the reverse")
+        if t is not None:
+            _need(t, name=n)
+            if tuple(t.shape) != shape or not t.is_contiguous():
+                raise KnnSvcError(f"time_scale_seg: {n} must be a contiguous {shape} tensor, got {tuple(t.shape)}")
+    lib = _lib.load()
+    # a chunk of at most MAX_SEGMENTS segments has TWO row offsets: where its rows start in the input and in the output
+    for (a, r0, tab), (_a, o0, otab) in zip(seg.chunks, oseg.chunks):
+        n = len(tab) - 1
+        check(lib.knnsvc_time_scale_seg(_p(x[r0:]) if x is not None else _p(None), dim, _p(f0[r0:]) if f0 is not None else _p(None),
+                                        tab, otab, (C.c_double * n)(*cs[a:a + n]), n, _p(xo[o0:]) if x is not None else _p(None),
+                                        _p(fo[o0:]) if f0 is not None else _p(None), _stream()), "time_scale_seg")
+    return xo, fo
+
+
+def time_scale(x, f0, out_frames, inv_scale):
+    """``time_scale_seg`` of one sequence -> (x_out [out_frames, dim] or None, f0_out [out_frames] or None)."""
+    rows = (x if x is not None else f0).shape[0] if (x is not None or f0 is not None) else 0
+    return time_scale_seg(x, f0, [0, int(rows)], [out_frames], [inv_scale])
+
+
 def weighted_gather(idx4, w, pool, mean=False):
     """sum_k w[i, k] * pool[idx4[i, k]].  ``w`` None = uniform weights: each row times 1.0f / k (softmax(ones)), or with ``mean`` the
     sum in order divided by k (torch.mean); the same bits when k is a power of two."""

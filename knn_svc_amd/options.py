@@ -23,6 +23,11 @@ Two constructors, one per calling convention: ``from_reference`` takes the upstr
 ``bulk_match``, ``match_at_inference_time`` and the command line, where ``topk``, ``tgt_loudness_db`` and ``vad_trigger_level`` are
 accepted and, as upstream, IGNORED unless their switch (``use_topk``, ``normalize_loudness``, ``use_vad``) is on; ``from_serving``
 takes the "None = off" arguments of ``many_to_one``, ``TargetVoice`` and ``BatchConverter``.
+
+``target_duration`` is NOT a field of this record, and the promise above about lengths holds because of that: a duration is a
+property of a *source item*, like a request's own ``transpose``, and travels beside the record (``special_match``,
+``many_to_one``, ``BatchConverter.convert`` and ``RequestQueue.submit`` take it as an argument of its own).  Its checks are
+``matching.resolve_target_duration`` (the value) and ``matching.duration_plan`` (the ratio to the source's length).
 """
 from __future__ import annotations
 

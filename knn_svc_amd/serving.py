@@ -159,12 +159,28 @@ class BatchConverter:
             return f0_shift, transpose
         return [list(v) if isinstance(v, (list, tuple)) else [v] * n for v in (f0_shift, transpose)]
 
+    def duration_of(self, target_duration=None, n=None):
+        """``target_duration`` (seconds; a value for all sources, or one per source; None: off) checked
+        (matching.resolve_target_duration) and held against this converter's envelope mix, which excludes it -> a list of
+        ``n`` entries; ``n`` None: one checked value."""
+        d = M.resolve_target_duration(target_duration, n)
+        M.refuse_duration_with_envelope([d] if n is None else d, self.ext)
+        return d
+
+    def plan_duration(self, w, target_duration, item=None):
+        """matching.duration_plan of a loaded source waveform (its frame count follows from its length: nothing is encoded)."""
+        return M.duration_plan(M.frames_of(int(w.shape[0]), self.vc.wavlm), target_duration, item=item)
+
     @torch.inference_mode()
-    def convert(self, sources, loaded=None, f0_shift=None, transpose=None) -> list:
+    def convert(self, sources, loaded=None, f0_shift=None, transpose=None, target_duration=None) -> list:
         """-> one waveform tensor [T_i * 320] per source, in order.  ``loaded``: the sources already through load_checked.
         ``f0_shift`` / ``transpose``: for all sources or one per source (None: the converter's defaults); one batch may mix
-        them on both match routes, each source's interval is chosen on the device."""
+        them on both match routes, each source's interval is chosen on the device.  ``target_duration`` (seconds): for all
+        sources or one per source (None: off): that source's features and f0 are re-timed behind the encoder
+        (matching.stretch_queries, one launch for the batch) and its waveform has matching.duration_plan's T_out * 320
+        samples; sources with and without one share a batch."""
         modes, semis = self.pitch_of(f0_shift, transpose, len(sources))        # refused before a file is read
+        durs = self.duration_of(target_duration, len(sources))
         if len(sources) == 0:
             return []
         vc, tg = self.vc, self.target
@@ -172,6 +188,9 @@ class BatchConverter:
         vc.wavlm.set_layer_mix(M._mix_of(vc.weighting, vc.wavlm))      # the shared encoder may have been left in another mix
         loaded = loaded if loaded is not None else [self._load(s) for s in sources]
         wavs = [w for w, _ in loaded]
+        for i, d in enumerate(durs):                                   # a ratio out of bounds is refused before anything is encoded
+            if d is not None:
+                self.plan_duration(wavs[i], d, item=f"source {i}")
         feats = vc.wavlm.encode_many(wavs, max_batch=self.max_encode_batch, pow2_batches=True)
         f0s = []
         for (w, f0), ft in zip(loaded, feats):
@@ -180,6 +199,7 @@ class BatchConverter:
                 raise ValueError(f"f0 has {len(f0)} frames for {T} feature frames")
             f0s.append(f0[:T].contiguous().to(dev) if isinstance(f0, torch.Tensor)
                        else torch.from_numpy(np.ascontiguousarray(f0[:T])).to(dev, non_blocking=True))
+        feats, f0s = M.stretch_queries(feats, f0s, durs)               # in front of everything of the match stage
         items = list(range(len(sources)))
         qpool = dict(enumerate(feats))
         # the reference does not forward post_opt to the f0-only generators (ddsp_matcher.py:970, 1102-1110)
@@ -213,10 +233,10 @@ class BatchConverter:
             return ys
         return ops.retry_on_overflow(run)
 
-    def convert_files(self, src_files, converted_audio_dir=None) -> list:
+    def convert_files(self, src_files, converted_audio_dir=None, target_duration=None) -> list:
         """Paths in, files out: ``<dir or the source's folder>/<src>_to_<ref>_knn_<ckpt_type>_<post_opt>.wav`` (the single-file
-        naming, ddsp_matcher.py:1015), PCM_32 16 kHz mono.  -> the written paths."""
-        ys = self.convert([str(p) for p in src_files])
+        naming, ddsp_matcher.py:1015), PCM_32 16 kHz mono.  -> the written paths.  ``target_duration``: as ``convert``."""
+        ys = self.convert([str(p) for p in src_files], target_duration=target_duration)
         out = []
         for p, y in zip(src_files, ys):
             d = converted_audio_dir if converted_audio_dir is not None else str(Path(p).parent)
@@ -229,6 +249,7 @@ class BatchConverter:
 class RequestQueue:
     """Dynamic batching in front of a BatchConverter.  ``submit(src)`` -> Future of the waveform (a CPU tensor).
     ``submit(src, transpose=, f0_shift=)``: the request's own transpose (semitones) / f0 shift mode instead of the converter's;
+    ``submit(src, target_duration=)``: the length in seconds the request's conversion is re-timed to (BatchConverter.convert);
     requests with different values share a batch.  The converter's ``loudness_db``, ``envelope_mix`` and ``peak_db`` apply to every
     request (per-request values of those are not supported)."""
 
@@ -241,14 +262,18 @@ class RequestQueue:
         self._th = threading.Thread(target=self._loop, name="knnsvc-batcher", daemon=True)
         self._th.start()
 
-    def submit(self, src, transpose=None, f0_shift=None) -> Future:
+    def submit(self, src, transpose=None, f0_shift=None, target_duration=None) -> Future:
         if self._stop:
             raise RuntimeError("RequestQueue is closed")
         fut = Future()
-        if transpose is None and f0_shift is None:
+        # a bad value is refused here, not in the worker
+        pitch = (None, None) if transpose is None and f0_shift is None else self.conv.pitch_of(f0_shift, transpose)
+        if target_duration is not None:
+            self._q.put((src, fut, pitch, self.conv.duration_of(target_duration)))
+        elif pitch != (None, None):
+            self._q.put((src, fut, pitch))
+        else:
             self._q.put((src, fut))
-        else:                                                # a bad value is refused here, not in the worker
-            self._q.put((src, fut, self.conv.pitch_of(f0_shift, transpose)))
         return fut
 
     def _loop(self):
@@ -276,22 +301,32 @@ class RequestQueue:
 
     def _run(self, batch):
         """One batch; a request that cannot be loaded, or whose data makes the conversion fail (a NaN source, an f0 track of the
-        wrong length), fails ALONE: the others of its batch are converted without it.  An entry is (source, Future) or (source,
-        Future, (f0_shift, transpose)); a batch in which no request carries values of its own is converted as it always was."""
+        wrong length, a target duration out of proportion to its length), fails ALONE: the others of its batch are converted
+        without it.  An entry is (source, Future), (source, Future, (f0_shift, transpose)) or (source, Future, (f0_shift,
+        transpose), target_duration); a batch in which no request carries values of its own is converted as it always was, and
+        ``target_duration`` is passed on only when a request of the batch has one."""
         good, loaded = [], []
         for s, fut, *own in batch:
             try:
-                loaded.append(self.conv.load_checked(s))
-                good.append((s, fut, own[0] if own else (None, None)))
+                ld = self.conv.load_checked(s)
+                dur = own[1] if len(own) > 1 else None
+                if dur is not None:                          # needs the loaded source: refused here, before the batch is formed
+                    self.conv.plan_duration(ld[0], dur, item="request")
+                loaded.append(ld)
+                good.append((s, fut, own[0] if own else (None, None), dur))
             except BaseException as e:
                 fut.set_exception(e)
         if not good:
             return
         plain = all(g[2] == (None, None) for g in good)
-        pitch = lambda gs: {} if plain else dict(f0_shift=[g[2][0] for g in gs], transpose=[g[2][1] for g in gs])
+        timed = any(g[3] is not None for g in good)
+
+        def pitch(gs):
+            kw = {} if plain else dict(f0_shift=[g[2][0] for g in gs], transpose=[g[2][1] for g in gs])
+            return dict(kw, target_duration=[g[3] for g in gs]) if timed else kw
         try:
             ys = self.conv.convert([g[0] for g in good], loaded=loaded, **pitch(good))
-            for (_s, fut, _p), y in zip(good, ys):
+            for (_s, fut, _p, _d), y in zip(good, ys):
                 fut.set_result(y.detach().cpu())
             return
         except BaseException as e:
