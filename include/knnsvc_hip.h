@@ -577,6 +577,50 @@ int knnsvc_smooth_weights_seg_k(const int64_t* idx, int32_t k, const int64_t* ho
 int knnsvc_time_scale_seg(const float* x, int32_t dim, const float* f0, const int64_t* host_seg_in, const int64_t* host_seg_out,
                           const double* host_inv_scale, int32_t n_seg, float* x_out, float* f0_out, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Voice blend (an extension; upstream converts towards one pool): a conversion towards a weighted mix of V voices,
+ * 2 <= V <= KNNSVC_BLEND_MAX_VOICES, with weights a_0 .. a_{V-1} per segment (source item).  This restatement is the
+ * specification.
+ *   1. Per voice the match stage runs exactly as for a single target, against that voice's pool with the item's f0 shift
+ *      mode, transpose and k: voice v's features x_v and harmonics are bit-identical to the single-target conversion
+ *      towards v.  The per-voice shifted f0 is used inside that voice's match only.
+ *   2. Features and harmonics are mixed linearly in fp64 and rounded once:
+ *          out[i][c] = (float)( sum_v a_v * (double)x_v[i][c] )
+ *      over the voices in ascending order.  Every product and every sum is an fp64 operation of its own (no contraction);
+ *      the sum starts with the first product (nothing is added to a zero).  A voice whose weight is exactly 0 is NOT READ:
+ *      a NaN in it does not reach the output.  When only one weight of the row is non-zero, that voice's values are copied
+ *      bit for bit.
+ *   3. The output f0 is ONE shift towards the blended register, not a mix of shifted tracks: the pool median of the segment
+ *      is pm = (float)( sum_v a_v * (double)pm_v ) over the voices' fp32 lower medians of log f0 (pool_medians[v][0]), with
+ *      the zero-skip and single-term-copy rules of 2.  After that the arithmetic of "Pitch control" applies unchanged, in
+ *      all four modes and with the transpose: OCTAVE and SEMITONE keep their grid guarantee under a blend, MEDIAN moves
+ *      the source to the weighted mean of the voices' log medians, NONE reads no median.  A NaN median of a voice with a
+ *      non-zero weight propagates.  (Mixing the per-voice shifted tracks instead would put an OCTAVE blend of two voices
+ *      an octave apart half an octave — a tritone — off the source's pitch classes.)
+ *   4. Weights: every entry finite and >= 0, at least one > 0, |sum - 1| <= 1e-6 (summed in order in fp64).  The library
+ *      does not normalise: the caller divides by the sum, so that a one-hot row stays exactly one-hot.
+ * knnsvc_blend_seg: point 2 for n_seg stacked segments.  host_x: a HOST array of n_voices device pointers, each to the
+ * stacked [host_seg[n_seg], dim] rows of one voice; host_weights: HOST double [n_seg][n_voices]; both tables are read by
+ * the call and reach the kernel by value like host_seg.  out [host_seg[n_seg], dim] may be one of the inputs, and may not
+ * overlap one otherwise.  One launch on `stream` (256-thread workgroups, four rows each; 16-byte accesses when dim % 4 == 0
+ * and every pointer is 16-byte aligned, else scalar), no device table, no allocation, no synchronisation,
+ * hipGraph-capturable; the result of segment s does not depend on what else is in the call.
+ * knnsvc_shift_f0_seg_blend: knnsvc_shift_f0_seg_mode with pool_medians (device float [n_voices][2], the results of
+ * knnsvc_log_f0_median per voice), n_voices and host_weights [n_seg][n_voices] in place of pool_median: point 3.  The same
+ * kernel and host path as the other three shift entries; the blended median is formed by every thread of the segment
+ * from the device medians: no host read, no extra launch.
+ * Both refuse before the first HIP call, with a message: a null pointer, n_voices outside 2..KNNSVC_BLEND_MAX_VOICES, a bad
+ * segment table, a weight row that breaks point 4 (naming the segment), dim <= 0; the shift entry also what
+ * knnsvc_shift_f0_seg_mode refuses.
+ * ------------------------------------------------------------------------------------------ */
+#define KNNSVC_BLEND_MAX_VOICES 4
+int knnsvc_blend_seg(const float* const* host_x, int32_t n_voices, int32_t dim, const int64_t* host_seg, int32_t n_seg,
+                     const double* host_weights, float* out, void* stream);
+int knnsvc_shift_f0_seg_blend(const float* f0, const int64_t* host_seg, int32_t n_seg, const int32_t* host_modes,
+                              const float* host_transposes, const float* query_median, const float* pool_medians,
+                              int32_t n_voices, const double* host_weights, float* shifted, float* shift_semitones,
+                              void* stream);
+
 /* out[i,:] = sum_k w[i,k] * pool[idx[i,k], :]   (ddsp_prematch_dataset.py:1358, 1444).  w NULL = uniform weights:
  * mean_mode 0 multiplies every row by 1.0f / k (softmax(ones), :1361-1364), mean_mode 1 sums in order and divides by k
  * (torch.mean, harmonics :1446); any k >= 1, the two are bit-identical when k is a power of two. */

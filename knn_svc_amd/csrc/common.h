@@ -55,6 +55,67 @@ static inline int kn_seg_one(int64_t n, const char* entry, KnSegTable* out) {
     return kn_seg_table(one, 1, entry, out);
 }
 
+// Voice blend (include/knnsvc_hip.h, "Voice blend"): the per-segment weight rows of knnsvc_blend_seg (blend.hip) and
+// knnsvc_shift_f0_seg_blend (select.hip), a host table validated here and handed to the kernels by value (2 KiB beside the
+// segment table).  Unused rows and voices hold 0.
+struct KnBlendWeights { int nv; double w[KNNSVC_MAX_SEGMENTS][KNNSVC_BLEND_MAX_VOICES]; };
+
+static inline int kn_blend_weights(const double* host_weights, int32_t n_seg, int32_t n_voices, const char* entry, KnBlendWeights* out) {
+    if (n_voices < 2 || n_voices > KNNSVC_BLEND_MAX_VOICES)
+        return knnsvc_fail(KNNSVC_EINVAL, "%s: n_voices %d outside 2..%d", entry, (int)n_voices, KNNSVC_BLEND_MAX_VOICES);
+    if (!host_weights) return knnsvc_fail(KNNSVC_EINVAL, "%s: null weight table", entry);
+    out->nv = n_voices;
+    for (int s = 0; s < KNNSVC_MAX_SEGMENTS; ++s)
+        for (int v = 0; v < KNNSVC_BLEND_MAX_VOICES; ++v) out->w[s][v] = 0.0;
+    for (int s = 0; s < n_seg; ++s) {
+        double sum = 0.0;
+        bool positive = false;
+        for (int v = 0; v < n_voices; ++v) {
+            const double a = host_weights[(size_t)s * n_voices + v];
+            if (!(a >= 0.0 && a <= 1.79769313486231570815e308))
+                return knnsvc_fail(KNNSVC_EINVAL, "%s: segment %d: weight %d is %g, not finite and >= 0", entry, s, v, a);
+            positive = positive || a > 0.0;
+            sum += a;
+            out->w[s][v] = a;
+        }
+        if (!positive) return knnsvc_fail(KNNSVC_EINVAL, "%s: segment %d: no positive weight", entry, s);
+        if (!(sum - 1.0 <= 1e-6 && 1.0 - sum <= 1e-6))
+            return knnsvc_fail(KNNSVC_EINVAL, "%s: segment %d: the weights sum to %.9g, not 1 (the caller normalises)", entry, s, sum);
+    }
+    return KNNSVC_OK;
+}
+
+// One segment's row of the table as the mixing code wants it: w[v] (0 beyond nv) and how many are non-zero.
+struct KnBlendRow { double w[KNNSVC_BLEND_MAX_VOICES]; int live; };
+__device__ __forceinline__ KnBlendRow kn_blend_row(const KnBlendWeights& bw, int s) {
+    KnBlendRow r;
+    r.live = 0;
+#pragma unroll
+    for (int v = 0; v < KNNSVC_BLEND_MAX_VOICES; ++v) {
+        r.w[v] = v < bw.nv ? bw.w[s][v] : 0.0;
+        if (r.w[v] != 0.0) ++r.live;
+    }
+    return r;
+}
+// (float)(sum_v w[v] * (double)x[v]) over the voices with a non-zero weight, in ascending order, every operation on its own; the
+// sum starts with the first product.  x[v] of a zero-weight voice is not looked at; a single non-zero weight hands its x on as it is.
+__device__ __forceinline__ float kn_blend_mix(const KnBlendRow& r, const float (&x)[KNNSVC_BLEND_MAX_VOICES]) {
+#pragma clang fp contract(off)
+    double acc = 0.0;
+    float one = 0.f;
+    bool first = true;
+#pragma unroll
+    for (int v = 0; v < KNNSVC_BLEND_MAX_VOICES; ++v) {
+        if (r.w[v] != 0.0) {
+            const double p = r.w[v] * (double)x[v];
+            acc = first ? p : acc + p;
+            first = false;
+            one = x[v];
+        }
+    }
+    return r.live == 1 ? one : (float)acc;
+}
+
 // KNNSVC_MATCH_GENERIC_K=1: the match stage at k = 4 skips its fast paths and runs the K kernels as any other k (select.hip)
 bool knnsvc_match_generic_k();
 

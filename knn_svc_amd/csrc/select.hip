@@ -77,10 +77,25 @@ struct KnShiftModes { int mode[KNNSVC_MAX_SEGMENTS]; float transpose[KNNSVC_MAX_
 // The f0 shift of every entry point (include/knnsvc_hip.h, "Pitch control"); blockIdx.y = segment, blockIdx.x covers the longest
 // segment.  The interval is chosen per segment on the device: every thread derives what it adds from the medians, so nothing is
 // read back by the host; thread 0 of the segment's first block reports the interval when asked.  KNNSVC_F0_SHIFT_NONE never reads
-// the medians.
+// the medians.  POOL says where a segment's pool median comes from: the one pool's (every entry but the blend), or the voices'
+// medians mixed with the segment's weights ("Voice blend", point 3) — after that line the arithmetic is the same.
+struct KnOnePool {
+    __device__ __forceinline__ float median(const float* __restrict__ pmed, int) const { return pmed[0]; }
+};
+struct KnBlendedPools {
+    KnBlendWeights bw;
+    __device__ __forceinline__ float median(const float* __restrict__ pmed, int s) const {
+        const KnBlendRow row = kn_blend_row(bw, s);
+        float m[KNNSVC_BLEND_MAX_VOICES];
+#pragma unroll
+        for (int v = 0; v < KNNSVC_BLEND_MAX_VOICES; ++v) m[v] = row.w[v] != 0.0 ? pmed[2 * v] : 0.f;
+        return kn_blend_mix(row, m);
+    }
+};
+template <class POOL>
 __global__ void shift_f0_kernel(const float* __restrict__ f0, const KnSegTable seg, const KnShiftModes pm,
-                                const float* __restrict__ qmed, const float* __restrict__ pmed, float* __restrict__ out,
-                                float* __restrict__ semis) {
+                                const float* __restrict__ qmed, const float* __restrict__ pmed, const POOL pool,
+                                float* __restrict__ out, float* __restrict__ semis) {
 #pragma clang fp contract(off)
     const double LN2 = 0.693147180559945309417232121458, S = LN2 / 12.0;
     const int s = blockIdx.y;
@@ -93,7 +108,7 @@ __global__ void shift_f0_kernel(const float* __restrict__ f0, const KnSegTable s
     double d = 0.0, interval = (double)t * S;
     float add = (float)interval;             // what is added to log f0 (median: after its own two-step shift, when t != 0)
     if (mode != KNNSVC_F0_SHIFT_NONE) {
-        q = qmed[2 * s]; p = pmed[0];
+        q = qmed[2 * s]; p = pool.median(pmed, s);
         d = (double)p - (double)q;
         if (mode != KNNSVC_F0_SHIFT_MEDIAN) {
             const double step = mode == KNNSVC_F0_SHIFT_OCTAVE ? LN2 : S;
@@ -670,9 +685,10 @@ static int log_f0_median_launch(const KnSegTable& seg, const char* entry, const 
 }
 
 // NULL tables: median / 0.  Every check before the launch: the pointers, then each segment's mode and transpose.
+// `blend` (NULL for the single-pool entries): the validated weight rows; pool_median is then the voices' [n_voices][2].
 static int shift_f0_launch(const KnSegTable& seg, const char* entry, const float* f0, const int32_t* host_modes,
                            const float* host_transposes, const float* query_median, const float* pool_median, float* shifted,
-                           float* shift_semitones, void* stream) {
+                           float* shift_semitones, void* stream, const KnBlendWeights* blend = nullptr) {
     KN_REQUIRE(f0 && query_median && pool_median && shifted, "%s: null pointer", entry);
     KnShiftModes pm;
     for (int s = 0; s < KNNSVC_MAX_SEGMENTS; ++s) { pm.mode[s] = KNNSVC_F0_SHIFT_MEDIAN; pm.transpose[s] = 0.f; }
@@ -688,8 +704,13 @@ static int shift_f0_launch(const KnSegTable& seg, const char* entry, const float
     }
     long longest = 0;
     for (int s = 0; s < seg.n; ++s) longest = seg.off[s + 1] - seg.off[s] > longest ? seg.off[s + 1] - seg.off[s] : longest;
-    hipLaunchKernelGGL(shift_f0_kernel, dim3((unsigned)cdiv64(longest, 256), (unsigned)seg.n), dim3(256), 0, (hipStream_t)stream,
-                       f0, seg, pm, query_median, pool_median, shifted, shift_semitones);
+    const dim3 grid((unsigned)cdiv64(longest, 256), (unsigned)seg.n);
+    if (blend)
+        hipLaunchKernelGGL(shift_f0_kernel<KnBlendedPools>, grid, dim3(256), 0, (hipStream_t)stream, f0, seg, pm, query_median,
+                           pool_median, KnBlendedPools{*blend}, shifted, shift_semitones);
+    else
+        hipLaunchKernelGGL(shift_f0_kernel<KnOnePool>, grid, dim3(256), 0, (hipStream_t)stream, f0, seg, pm, query_median,
+                           pool_median, KnOnePool{}, shifted, shift_semitones);
     return knnsvc_check_launch(entry);
 }
 
@@ -798,6 +819,19 @@ extern "C" int knnsvc_shift_f0_seg_mode(const float* f0, const int64_t* host_seg
     if (const int rc = kn_seg_table(host_seg, n_seg, "shift_f0_seg_mode", &seg)) return rc;
     return shift_f0_launch(seg, "shift_f0_seg_mode", f0, host_modes, host_transposes, query_median, pool_median, shifted,
                            shift_semitones, stream);
+}
+
+// "Voice blend", point 3: the pool median of segment s is the voices' medians mixed with row s of host_weights
+extern "C" int knnsvc_shift_f0_seg_blend(const float* f0, const int64_t* host_seg, int32_t n_seg, const int32_t* host_modes,
+                                         const float* host_transposes, const float* query_median, const float* pool_medians,
+                                         int32_t n_voices, const double* host_weights, float* shifted, float* shift_semitones,
+                                         void* stream) {
+    KnSegTable seg;
+    KnBlendWeights bw;
+    if (const int rc = kn_seg_table(host_seg, n_seg, "shift_f0_seg_blend", &seg)) return rc;
+    if (const int rc = kn_blend_weights(host_weights, n_seg, n_voices, "shift_f0_seg_blend", &bw)) return rc;
+    return shift_f0_launch(seg, "shift_f0_seg_blend", f0, host_modes, host_transposes, query_median, pool_medians, shifted,
+                           shift_semitones, stream, &bw);
 }
 
 extern "C" int knnsvc_concat_reselect_seg(const int64_t* idx_in, const float* q, const float* q_norm, const int64_t* host_seg,

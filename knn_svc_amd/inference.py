@@ -13,7 +13,9 @@ is true); no value changes a file name, and a clip normalised past full scale is
 lower than asked (save_audio divides by a peak above 1, as upstream) unless --peak_db holds
 its peaks under a ceiling (where the limiter engages the loudness ends below the target).  --target_duration
 SECONDS (file mode only; upstream documents the argument and never delivers it) re-times the conversion to
-that length (matching.duration_plan; the file name does not change).  --dur_limit is
+that length (matching.duration_plan; the file name does not change).  --blend_tgt PATH (file mode only, up to
+three times) adds target voices and --blend W0,W1[,...] weighs TGT and them: the conversion goes towards that mix
+(matcher.KNeighborsVC.blend_voices; the output is named <src>_to_<tgt>+<blend_tgt>..., without the weights).  --dur_limit is
 compared in seconds, as upstream (ddsp_prematch_dataset.py:408-411).
 """
 from __future__ import annotations
@@ -40,6 +42,13 @@ def _bool(v: str) -> bool:
     if v in ("no", "false", "f", "0", "n"):
         return False
     raise argparse.ArgumentTypeError("boolean value expected")
+
+
+def _weights(v: str) -> list:
+    try:
+        return [float(w) for w in v.split(",")]
+    except ValueError:
+        raise argparse.ArgumentTypeError("comma-separated numbers expected, e.g. 0.7,0.3")
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -69,6 +78,12 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--target_duration", type=float, default=None, metavar="SECONDS",
                     help="(extension, file mode only) re-time the conversion to this length; between a quarter of and four "
                          "times the source's; not together with --envelope_mix")
+    ap.add_argument("--blend_tgt", action="append", default=None, metavar="PATH",
+                    help="(extension, file mode only; up to three times) a further target voice: the conversion goes towards a "
+                         "weighted mix of TGT and these")
+    ap.add_argument("--blend", type=_weights, default=None, metavar="W0,W1[,...]",
+                    help="(extension, with --blend_tgt) the weights of TGT and of each --blend_tgt in order; normalised to sum "
+                         "1 (default: equal)")
     ap.add_argument("--weights", default="auto", choices=["auto", "checkpoint", "seeded"],
                     help="(extension) 'seeded' runs with random weights when the released checkpoints are unavailable")
     return ap
@@ -95,6 +110,13 @@ def main(argv=None) -> int:
         refuse_duration_with_envelope([resolve_target_duration(a.target_duration)], ext)
     except ValueError as e:
         ap.error(str(e))
+    if (a.blend_tgt is not None or a.blend is not None) and os.path.isdir(a.src):
+        ap.error("--blend_tgt / --blend apply to a single conversion: a dataset run pairs speakers, a blend has no meaning there")
+    try:                                                   # the count of voices and of weights, before the models are loaded
+        from .matcher import KNeighborsVC
+        KNeighborsVC.blend_voices(a.tgt, a.blend_tgt, a.blend)
+    except ValueError as e:
+        ap.error(str(e))
     if a.target_duration is not None and os.path.isdir(a.src):
         ap.error("--target_duration applies to a single source file: one duration for a dataset of utterances means nothing")
     from .hubconf import knn_vc
@@ -102,7 +124,8 @@ def main(argv=None) -> int:
                  local_ckpt_dir=a.ckpt_dir, weights=a.weights)
     common = dict(device=a.device, prioritize_f0=a.prioritize_f0, ckpt_type=a.ckpt_type, post_opt=a.post_opt, **knobs)
     if os.path.isfile(a.src) and os.path.isfile(a.tgt):
-        knn.special_match(src_wav_file=a.src, ref_wav_file=a.tgt, target_duration=a.target_duration, **common)
+        knn.special_match(src_wav_file=a.src, ref_wav_file=a.tgt, target_duration=a.target_duration, blend_with=a.blend_tgt,
+                          blend=a.blend, **common)
         return 0
     if os.path.isdir(a.src) and os.path.isdir(a.tgt):
         knn.bulk_match(src_dataset_path=a.src, tgt_dataset_path=a.tgt,

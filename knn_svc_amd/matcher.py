@@ -93,19 +93,51 @@ class KNeighborsVC:
         if not bool(torch.isfinite(wav).all()):
             raise ops.KnnSvcError("vocode: non-finite waveform (non-finite features, f0, harmonics or weights)")
 
+    @staticmethod
+    def blend_voices(ref_wav_file, blend_with=None, blend=None):
+        """The references of a voice blend, checked before a file is read: ``[ref_wav_file, *blend_with]`` (``blend_with``: one
+        path or a sequence of one to three) with ``blend`` as their weights (matching.resolve_blend; None: equal), or None
+        without ``blend_with`` — ``blend`` alone is refused, as are more than four voices, a wrong count of weights and a blend
+        under KNNSVC_POOL_SHARD=1."""
+        from .matching import refuse_blend_when_sharded, resolve_blend
+        if blend_with is None:
+            if blend is not None:
+                raise ValueError("blend needs several target voices: give the further references as blend_with")
+            return None
+        more = [blend_with] if isinstance(blend_with, (str, os.PathLike)) else list(blend_with)
+        if not 1 <= len(more) <= 3:
+            raise ValueError(f"blend_with takes one to three further references (four voices in all), got {len(more)}")
+        resolve_blend(blend, 1 + len(more))
+        refuse_blend_when_sharded()
+        return [ref_wav_file] + more
+
     @torch.inference_mode()
     def special_match(self, src_wav_file, ref_wav_file, topk: int = 4, device=None, prioritize_f0=True,
                       ckpt_type="wavlm_only", tgt_loudness_db=-16, post_opt="no_post_opt", save=True, normalize_loudness=False,
                       use_topk=False, use_vad=False, vad_trigger_level=7, f0_shift="median", transpose=0.0, envelope_mix=0.0,
-                      peak_db=None, target_duration=None):
+                      peak_db=None, target_duration=None, blend_with=None, blend=None):
         """``target_duration`` (seconds, None: off): the conversion re-timed to that length — the waveform has
-        matching.duration_plan's T_out * 320 samples, the file name does not change; not with ``envelope_mix`` > 0."""
+        matching.duration_plan's T_out * 320 samples, the file name does not change; not with ``envelope_mix`` > 0.
+        ``blend_with`` (one to three further reference files or folders) / ``blend`` (weights for ``[ref_wav_file, *blend_with]``,
+        None: equal): the conversion goes towards that weighted mix of voices (``blend_voices``), through serving.TargetVoice and
+        serving.BatchConverter; ``use_vad`` trims every voice's pool; the file is named ``<src>_to_<idA>+<idB>[+...]_knn_...``."""
         ext = Extensions.from_reference(topk, use_topk, tgt_loudness_db, normalize_loudness, use_vad, vad_trigger_level, f0_shift,
                                         transpose, envelope_mix, peak_db)          # refused before a file is read
         refuse_duration_with_envelope([resolve_target_duration(target_duration)], ext)
+        refs = self.blend_voices(ref_wav_file, blend_with, blend)
         f0only = "wavlm_only" in ckpt_type or "no_harm_no_amp" in ckpt_type
         if "wavlm_only_original" in ckpt_type:
             raise NotImplementedError("wavlm_only_original needs hifigan/models.py, absent upstream")
+        if refs is not None:
+            from . import serving
+            voices = [serving.TargetVoice(self, r, vad_trigger_level=ext.vad_level) for r in refs]
+            conv = serving.BatchConverter(self, voices, ckpt_type, post_opt, ext=ext, blend=blend)
+            pred = conv.convert([str(src_wav_file)], target_duration=target_duration)[0]
+            if save:
+                out_file = conv.output_path(src_wav_file)
+                print("->", out_file)
+                audio_io.save_audio(out_file, pred.detach().cpu().numpy(), sample_rate=16000)
+            return pred
         key = str(src_wav_file)
         # the reference does not forward post_opt to the f0-only generators (ddsp_matcher.py:970)
         res = match_at_inference_time(Path(src_wav_file), Path(ref_wav_file), self.wavlm, self.weighting, self.weighting,
@@ -125,7 +157,8 @@ class KNeighborsVC:
     @torch.inference_mode()
     def many_to_one(self, src_files, ref_wav_file, converted_audio_dir=None, ckpt_type="mix", post_opt="post_opt_0.2",
                     duration_limit=None, target=None, match=None, loudness_db=None, topk=None, vad_trigger_level=None,
-                    f0_shift=None, transpose=None, envelope_mix=None, peak_db=None, target_duration=None):
+                    f0_shift=None, transpose=None, envelope_mix=None, peak_db=None, target_duration=None, blend_with=None,
+                    blend=None):
         """BASELINE cfg 5 (no counterpart upstream: the reference would call ``special_match`` once per source and rebuild the
         target pool each time, ddsp_matcher.py:937-1023): MANY sources against ONE target pool that is built once and stays
         resident, all sources through the stream pipeline as one batch (knn_svc_amd/serving.py).  Under a process group the
@@ -133,16 +166,22 @@ class KNeighborsVC:
         ranks' on every rank), named like ``special_match``'s outputs.  ``match``: "lanes" | "segmented" (serving.BatchConverter; default
         from KNNSVC_MATCH).  ``loudness_db`` ... ``peak_db``: the extension knobs, None = off (options.Extensions.from_serving;
         ``vad_trigger_level`` is ignored when ``target`` is given).  ``target_duration``: seconds, one value for all sources or
-        a list with one entry per source (None entries: off; serving.BatchConverter.convert)."""
+        a list with one entry per source (None entries: off; serving.BatchConverter.convert).  ``blend_with`` (one to three
+        further reference files or folders) / ``blend`` (weights for ``[ref_wav_file, *blend_with]``, None: equal): every source is
+        converted towards that weighted mix of voices (``blend_voices``; each voice's pool is trimmed when ``vad_trigger_level``
+        is given); ``target`` is then a sequence of TargetVoice to reuse, and the outputs are named ``<src>_to_<idA>+<idB>[+...]``."""
         from . import serving
         ext = Extensions.from_serving(loudness_db, topk, vad_trigger_level, f0_shift, transpose, envelope_mix, peak_db)   # before a file is read
         refuse_duration_with_envelope(resolve_target_duration(target_duration, len(src_files)), ext)
+        # (voices handed in as ``target``: the converter checks the weights against them)
+        refs = None if isinstance(target, (list, tuple)) else self.blend_voices(ref_wav_file, blend_with, blend)
         if target is None:
-            target = serving.TargetVoice(self, ref_wav_file, duration_limit, vad_trigger_level=ext.vad_level)
+            target = serving.TargetVoice(self, ref_wav_file, duration_limit, vad_trigger_level=ext.vad_level) if refs is None else \
+                [serving.TargetVoice(self, r, duration_limit, vad_trigger_level=ext.vad_level) for r in refs]
         mine = kdist.my_share([str(p) for p in src_files])
         if isinstance(target_duration, (list, tuple)):        # this rank's sources' own entries
             target_duration = kdist.my_share(list(target_duration))
-        written = serving.BatchConverter(self, target, ckpt_type, post_opt, match=match, ext=ext).convert_files(
+        written = serving.BatchConverter(self, target, ckpt_type, post_opt, match=match, ext=ext, blend=blend).convert_files(
             mine, converted_audio_dir, target_duration=target_duration)
         return kdist.gather_paths(written)
 

@@ -508,6 +508,65 @@ def stretch_queries(feats, f0s, durations):
     return feats, f0s
 
 
+# Voice blend (an extension; include/knnsvc_hip.h "Voice blend" is the specification): a conversion towards a weighted mix of 2 to
+# BLEND_MAX_VOICES target voices.  Each voice is matched as if it were the only target, the matched features and harmonics are
+# mixed (ops.blend_seg), and the source's f0 is shifted ONCE, towards the weighted mean of the voices' log-f0 medians
+# (ops.shift_f0_seg_blend).  A weight vector belongs to a source item, like a request's own ``transpose``: it travels beside the
+# options.Extensions record.  The library does not normalise; ``resolve_blend`` does, in fp64.
+BLEND_MAX_VOICES = ops.BLEND_MAX_VOICES
+
+
+def _one_blend(value, n_voices):
+    if value is None:
+        return (1.0 / n_voices,) * n_voices
+    if isinstance(value, (str, bytes)) or not isinstance(value, (list, tuple, np.ndarray)):
+        raise ValueError(f"blend must be a sequence of {n_voices} weights (or None for equal weights), got {value!r}")
+    if len(value) != n_voices:
+        raise ValueError(f"blend: {len(value)} weights for {n_voices} voices")
+    a = []
+    for w in value:
+        if isinstance(w, (bool, np.bool_)) or not isinstance(w, (int, float, np.integer, np.floating)):
+            raise ValueError(f"blend: a weight must be a number, got {w!r}")
+        w = float(w)
+        if not math.isfinite(w) or w < 0:
+            raise ValueError(f"blend: a weight must be finite and >= 0, got {w!r}")
+        a.append(w + 0.0)                              # (-0.0 becomes 0.0)
+    try:
+        total = math.fsum(a)
+    except OverflowError:
+        total = math.inf
+    if not total > 0 or not math.isfinite(total):
+        raise ValueError(f"blend: at least one weight must be > 0 and their sum finite, got {value!r}")
+    return tuple(w / total for w in a)
+
+
+def resolve_blend(weights, n_voices, n_items=None):
+    """Blend weights as the library takes them, refused (ValueError) before any device or file work when they are not valid:
+    ``n_voices`` numbers, finite and >= 0, at least one > 0 (None: equal weights), normalised in fp64 as ``a / math.fsum(a)``
+    — a one-hot vector stays exactly one-hot.  ``n_items`` None: one vector -> a tuple.  ``n_items`` = the number of items of a
+    batch: one vector for all items, or a list / tuple with one entry per item (a vector, or None for equal weights)
+    -> a list of n_items tuples.  ``n_voices`` outside 2..BLEND_MAX_VOICES is refused as well."""
+    if isinstance(n_voices, bool) or int(n_voices) != n_voices or not 2 <= int(n_voices) <= BLEND_MAX_VOICES:
+        raise ValueError(f"a blend takes 2..{BLEND_MAX_VOICES} voices, got {n_voices!r}")
+    n_voices = int(n_voices)
+    if n_items is None:
+        return _one_blend(weights, n_voices)
+    per_item = isinstance(weights, (list, tuple)) and (len(weights) == 0 or
+                                                       any(w is None or isinstance(w, (list, tuple, np.ndarray)) for w in weights))
+    if not per_item:
+        return [_one_blend(weights, n_voices)] * n_items
+    if len(weights) != n_items:
+        raise ValueError(f"blend: {len(weights)} weight vectors for {n_items} items")
+    return [_one_blend(w, n_voices) for w in weights]
+
+
+def refuse_blend_when_sharded():
+    """A blend matches every voice's whole pool on one GPU: under KNNSVC_POOL_SHARD=1 (pool rows sharded over the ranks) it is
+    refused, before a file is read."""
+    if os.environ.get("KNNSVC_POOL_SHARD") == "1":
+        raise ValueError("a voice blend cannot be combined with KNNSVC_POOL_SHARD=1 (the pools of a blend are not sharded)")
+
+
 def resolve_dynamics(envelope_mix, peak_db):
     """The two output-dynamics switches as the library takes them, refused before any device or file work when they are not
     valid -> (a, p).  ``envelope_mix``: a number in [0, 1], None = 0 (off): how much of the source's volume envelope the tail
@@ -656,6 +715,60 @@ def match_features_many(query_seqs, query_f0s, matching_list, matching_f0, harmo
         else:
             out.append((of, hw, sf))
     return out
+
+
+def _voice_parts(voice):
+    """A voice of a blend as (matching_list, matching_f0, harmonics_list, pool_prep or None, synth_list or None): a
+    serving.TargetVoice (or anything with ``feats`` / ``f0`` / ``harm`` and optionally ``prep`` / ``synth``), or such a tuple
+    of three to five entries."""
+    if isinstance(voice, (list, tuple)):
+        if not 3 <= len(voice) <= 5:
+            raise ValueError(f"a voice given as a tuple is (pool, f0, harmonics[, pool_prep[, synth_list]]), got {len(voice)} entries")
+        return tuple(voice) + (None,) * (5 - len(voice))
+    return voice.feats, voice.f0, voice.harm, getattr(voice, "prep", None), getattr(voice, "synth", None)
+
+
+def match_features_blend(query_seqs, query_f0s, voices, weights, ckpt_type, post_opt, nn32s=None, nan_flags=None, topk=None,
+                         f0_shift=None, transpose=None):
+    """``match_features_many`` towards a weighted mix of 2..BLEND_MAX_VOICES ``voices`` (``_voice_parts``) -> the same list of
+    per-item tuples (out_feats, harm or None, shifted_f0).  ``weights``: ``resolve_blend``'s argument (one vector for all items or
+    one per item; None: equal).  One ``match_features_many`` per voice — its pool, f0, harmonics, ``pool_prep``, ``synth_list``
+    and the items' own ``f0_shift`` / ``transpose`` / ``topk``, so every voice's frames are bit-identical to the single-target
+    conversion towards it —, then ONE ops.blend_seg for the features and one for the harmonics (none when the checkpoint type has
+    no harmonics), then ONE ops.shift_f0_seg_blend: the returned f0 is the source's, shifted once towards the weighted mean of the
+    voices' log medians (the per-voice shifted tracks are used inside each voice's match only).  A voice whose weight is 0 for
+    every item is not matched.  ``nn32s``: per voice, the per-item neighbour lists of ``match_features_many`` (or None).  NaN
+    flags and the overflow retry work per voice, as there."""
+    voices = [_voice_parts(v) for v in voices]
+    rows = resolve_blend(weights, len(voices), len(query_seqs))      # before any device work
+    resolve_topk(topk)
+    shift_modes, shift_ts = resolve_f0_shift(f0_shift, transpose, len(query_seqs))
+    live = [v for v in range(len(voices)) if any(r[v] != 0.0 for r in rows)]
+    per = {}
+    for v in live:
+        P, Pf0, Ph, prep, synth = voices[v]
+        per[v] = match_features_many(query_seqs, query_f0s, P, Pf0, Ph, ckpt_type, post_opt, nn32s=None if nn32s is None else nn32s[v],
+                                     nan_flags=nan_flags, pool_prep=prep, synth_list=synth, topk=topk, f0_shift=f0_shift,
+                                     transpose=transpose)
+    lens = [int(q.shape[0]) for q in query_seqs]
+    seg = [0]
+    for n in lens:
+        seg.append(seg[-1] + n)
+    seg = ops.Segments(seg)
+    # a voice that was not matched has weight 0 in every row: its pointer is never read, any live voice's stands in
+    def stacked(k):
+        got = {v: _stacked([r[k] for r in per[v]]) for v in live}
+        return [got.get(v, got[live[0]]) for v in range(len(voices))]
+    out_feats = ops.blend_seg(stacked(0), seg, rows)
+    with_harm = per[live[0]][0][1] is not None
+    harm = ops.blend_seg(stacked(1), seg, rows) if with_harm else None
+    query_f0 = _stacked([t.reshape(-1) for t in query_f0s])
+    qmed = ops.log_f0_median_seg(query_f0, seg)
+    meds = {v: ops.log_f0_median(voices[v][1]) for v in live}
+    pmeds = torch.stack([meds.get(v, meds[live[0]]) for v in range(len(voices))]).contiguous()
+    shifted = ops.shift_f0_seg_blend(query_f0, seg, qmed, pmeds, rows, shift_modes, shift_ts)
+    parts = lambda t: t.split(lens) if t is not None else [None] * len(lens)
+    return list(zip(parts(out_feats), parts(harm), parts(shifted)))
 
 
 def run_match_bodies(items, body, body_many, tail=None, *, device, lanes, match="lanes", match_batch=None):

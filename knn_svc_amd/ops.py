@@ -1035,6 +1035,80 @@ def time_scale(x, f0, out_frames, inv_scale):
     return time_scale_seg(x, f0, [0, int(rows)], [out_frames], [inv_scale])
 
 
+BLEND_MAX_VOICES = 4         # KNNSVC_BLEND_MAX_VOICES
+
+
+def _blend_rows(name, weights, n_seg, n_voices):
+    """``weights`` ([n_seg][n_voices] numbers, one row per segment) as a list of tuples of floats, shape-checked; what the
+    values have to satisfy (include/knnsvc_hip.h "Voice blend", point 4) the library checks before it launches."""
+    if not 2 <= n_voices <= BLEND_MAX_VOICES:
+        raise KnnSvcError(f"{name}: {n_voices} voices, expected 2..{BLEND_MAX_VOICES}")
+    rows = [tuple(float(a) for a in row) for row in weights]
+    if len(rows) != n_seg or any(len(r) != n_voices for r in rows):
+        raise KnnSvcError(f"{name}: weights must be [{n_seg}][{n_voices}] (a row per segment), got {len(rows)} rows of "
+                          f"{sorted(set(len(r) for r in rows))} entries")
+    return rows
+
+
+def blend_seg(xs, seg, weights, out=None):
+    """The stacked rows of 2..4 voices (``xs``: contiguous [total, dim] fp32 tensors of one shape) mixed per segment with
+    ``weights[s]`` (normalised by the caller: matching.resolve_blend) -> [total, dim] (knnsvc_blend_seg; include/knnsvc_hip.h
+    "Voice blend" is the specification: fp64 products and sums in voice order, one rounding, a zero-weight voice not read, a
+    single non-zero weight a copy).  ``out``: a buffer to write into.  One launch per 64 segments; enqueue only."""
+    xs = list(xs)
+    for v, x in enumerate(xs):
+        _need(x, name=f"xs[{v}]")
+        if x.dim() != 2 or x.shape[1] < 1 or not x.is_contiguous() or x.shape != xs[0].shape:
+            raise KnnSvcError(f"blend_seg: xs[{v}] must be a contiguous [rows, dim] tensor of the voices' common shape, got {tuple(x.shape)}")
+    if not xs:
+        raise KnnSvcError("blend_seg: no voices")
+    seg = _segments(seg, "blend_seg", *xs)
+    rows = _blend_rows("blend_seg", weights, seg.n, len(xs))
+    if out is None:
+        out = torch.empty_like(xs[0])
+    _need(out, name="out")
+    if out.shape != xs[0].shape or not out.is_contiguous():
+        raise KnnSvcError(f"blend_seg: out must be a contiguous {tuple(xs[0].shape)} tensor, got {tuple(out.shape)}")
+    lib = _lib.load()
+    nv, dim = len(xs), int(xs[0].shape[1])
+    for a, r0, tab in seg.chunks:
+        n = len(tab) - 1
+        ptrs = (C.c_void_p * nv)(*[x[r0:].data_ptr() for x in xs])
+        wt = (C.c_double * (n * nv))(*[w for row in rows[a:a + n] for w in row])
+        check(lib.knnsvc_blend_seg(ptrs, nv, dim, tab, n, wt, _p(out[r0:]), _stream()), "blend_seg")
+    return out
+
+
+def shift_f0_seg_blend(f0, seg, qmed, pmeds, weights, modes=None, transposes=None, return_shift=False):
+    """``shift_f0_seg`` towards a blend of voices: ``pmeds`` [n_voices, 2] (log_f0_median of each voice's pool, stacked) and
+    ``weights`` [n_seg][n_voices] in place of the single ``pmed``; segment s is shifted towards the weighted mean of the voices'
+    log medians, formed on the device (knnsvc_shift_f0_seg_blend; include/knnsvc_hip.h "Voice blend", point 3), after which modes
+    and transposes act as in ``shift_f0_seg``."""
+    _need(f0, name="f0"); seg = _segments(seg, "shift_f0_seg_blend", f0)
+    _need(qmed, name="qmed"); _need(pmeds, name="pmeds")
+    if qmed.numel() != 2 * seg.n or not qmed.is_contiguous():
+        raise KnnSvcError(f"shift_f0_seg_blend: qmed must be a contiguous [{seg.n}, 2] tensor, got {tuple(qmed.shape)}")
+    if pmeds.dim() != 2 or pmeds.shape[1] != 2 or not pmeds.is_contiguous():
+        raise KnnSvcError(f"shift_f0_seg_blend: pmeds must be a contiguous [n_voices, 2] tensor, got {tuple(pmeds.shape)}")
+    nv = int(pmeds.shape[0])
+    rows = _blend_rows("shift_f0_seg_blend", weights, seg.n, nv)
+    for name, t in (("modes", modes), ("transposes", transposes)):
+        if t is not None and len(t) != seg.n:
+            raise KnnSvcError(f"shift_f0_seg_blend: {len(t)} {name} for {seg.n} segments")
+    f0 = f0.contiguous()
+    out = torch.empty_like(f0)
+    semis = torch.empty(seg.n, device=f0.device, dtype=torch.float32) if return_shift else None
+    lib = _lib.load()
+    for a, r0, tab in seg.chunks:
+        n = len(tab) - 1
+        mt = None if modes is None else (C.c_int32 * n)(*[int(m) for m in modes[a:a + n]])
+        tt = None if transposes is None else (C.c_float * n)(*[float(t) for t in transposes[a:a + n]])
+        wt = (C.c_double * (n * nv))(*[w for row in rows[a:a + n] for w in row])
+        check(lib.knnsvc_shift_f0_seg_blend(_p(f0[r0:]), tab, n, mt, tt, _p(qmed[a:]), _p(pmeds), nv, wt, _p(out[r0:]),
+                                            _p(semis[a:]) if return_shift else None, _stream()), "shift_f0_seg_blend")
+    return (out, semis) if return_shift else out
+
+
 def weighted_gather(idx4, w, pool, mean=False):
     """sum_k w[i, k] * pool[idx4[i, k]].  ``w`` None = uniform weights: each row times 1.0f / k (softmax(ones)), or with ``mean`` the
     sum in order divided by k (torch.mean); the same bits when k is a power of two."""

@@ -28,6 +28,13 @@ takes the "None = off" arguments of ``many_to_one``, ``TargetVoice`` and ``Batch
 property of a *source item*, like a request's own ``transpose``, and travels beside the record (``special_match``,
 ``many_to_one``, ``BatchConverter.convert`` and ``RequestQueue.submit`` take it as an argument of its own).  Its checks are
 ``matching.resolve_target_duration`` (the value) and ``matching.duration_plan`` (the ratio to the source's length).
+
+The weights of a voice blend (``blend``: a conversion towards a weighted mix of 2 to 4 target voices; include/knnsvc_hip.h "Voice
+blend") are NOT a field either, for the same reason: a weight vector is a property of a source item and travels beside the record
+(``special_match`` / ``many_to_one`` take ``blend_with`` and ``blend``, ``BatchConverter`` a sequence of ``TargetVoice`` and a
+default ``blend``, ``BatchConverter.convert`` and ``RequestQueue.submit`` a ``blend`` per source).  Its check is
+``matching.resolve_blend``, which also normalises; every knob of the record acts on a blend as on a single target (the pitch knobs
+and ``topk`` inside every voice's match and in the one f0 shift, the tail on the blended frames).
 """
 from __future__ import annotations
 

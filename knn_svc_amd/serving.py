@@ -11,6 +11,8 @@ for bit with the small test models and on most full-size sources, <= 1e-6 otherw
                    features, kNN searches over the frames of several sources at a time on a stream of their own
                    (matching.grouped_knn), match bodies on lane streams, the generator as the tail stage (pipeline.LanePipeline).
                    No host synchronisation between the first launch and the last; the deferred kNN flags are read once.
+                   Given 2 to 4 TargetVoice it converts towards a weighted mix of them (matching.match_features_blend), with
+                   weights per converter, per source or per request.
   RequestQueue     dynamic batching for a serving process: ``submit`` returns a Future; one worker thread drains the queue into
                    batches (up to ``max_batch`` requests, waiting at most ``max_wait_ms`` for the batch to fill) and runs them
                    through a BatchConverter.  One worker per GPU: a hipGraph owns its buffers, so the same encoder / generator
@@ -93,7 +95,19 @@ class BatchConverter:
                  max_encode_batch: int = 32, match: str | None = None, match_batch: int | None = None,
                  loudness_db: float | None = None, topk: int | None = None, f0_shift: str | None = None,
                  transpose: float | None = None, envelope_mix: float | None = None, peak_db: float | None = None,
-                 ext: Extensions | None = None):
+                 ext: Extensions | None = None, blend=None):
+        # ``target``: one TargetVoice, or a sequence of 2 to 4 of them: the sources are then converted towards a weighted mix of
+        # those voices (matching.match_features_blend; include/knnsvc_hip.h "Voice blend"), ``blend`` being the weights a source
+        # gets unless a request says otherwise (blend_of; None: equal weights).  Refused before anything else: a sequence of
+        # another length, ``blend`` with a single voice, a blend under KNNSVC_POOL_SHARD=1.
+        self.voices = list(target) if isinstance(target, (list, tuple)) else None
+        if self.voices is None:
+            if blend is not None:
+                raise ValueError("blend needs several target voices: pass a sequence of 2 to 4 TargetVoice as the target")
+            self.blend = None
+        else:
+            self.blend = M.resolve_blend(blend, len(self.voices))
+            M.refuse_blend_when_sharded()
         # the extension knobs, checked before anything else (options.py; None: off): ``loudness_db``, ``envelope_mix`` and
         # ``peak_db`` are part of the tail, on the tail's stream, enqueue-only, and apply to every request of a RequestQueue in
         # front of this converter; ``f0_shift`` / ``transpose`` are what a source gets unless a request says otherwise (pitch_of).
@@ -167,20 +181,41 @@ class BatchConverter:
         M.refuse_duration_with_envelope([d] if n is None else d, self.ext)
         return d
 
+    def blend_of(self, blend=None, n=None):
+        """Per-source blend weights (a vector for all sources, or one entry per source; None entries: this converter's default)
+        checked and normalised (matching.resolve_blend) -> a list of ``n`` tuples; ``n`` None: one tuple.  With a single target
+        voice there is nothing to blend: None (or ``n`` Nones) when no weights are given, ValueError when some are."""
+        if self.voices is None:
+            if blend is not None and not (isinstance(blend, (list, tuple)) and all(b is None for b in blend)):
+                raise ValueError("blend needs several target voices: this converter has a single TargetVoice")
+            return None
+        if n is None:
+            return self.blend if blend is None else M.resolve_blend(blend, len(self.voices))
+        if blend is None:
+            return [self.blend] * n
+        if isinstance(blend, (list, tuple)) and (len(blend) == 0 or any(b is None or isinstance(b, (list, tuple, np.ndarray)) for b in blend)):
+            if len(blend) != n:
+                raise ValueError(f"blend: {len(blend)} weight vectors for {n} sources")
+            return [self.blend if b is None else M.resolve_blend(b, len(self.voices)) for b in blend]
+        return [M.resolve_blend(blend, len(self.voices))] * n
+
     def plan_duration(self, w, target_duration, item=None):
         """matching.duration_plan of a loaded source waveform (its frame count follows from its length: nothing is encoded)."""
         return M.duration_plan(M.frames_of(int(w.shape[0]), self.vc.wavlm), target_duration, item=item)
 
     @torch.inference_mode()
-    def convert(self, sources, loaded=None, f0_shift=None, transpose=None, target_duration=None) -> list:
+    def convert(self, sources, loaded=None, f0_shift=None, transpose=None, target_duration=None, blend=None) -> list:
         """-> one waveform tensor [T_i * 320] per source, in order.  ``loaded``: the sources already through load_checked.
         ``f0_shift`` / ``transpose``: for all sources or one per source (None: the converter's defaults); one batch may mix
         them on both match routes, each source's interval is chosen on the device.  ``target_duration`` (seconds): for all
         sources or one per source (None: off): that source's features and f0 are re-timed behind the encoder
         (matching.stretch_queries, one launch for the batch) and its waveform has matching.duration_plan's T_out * 320
-        samples; sources with and without one share a batch."""
+        samples; sources with and without one share a batch.  ``blend`` (a converter with several target voices): the
+        weights of the voices, for all sources or one vector per source (None: the converter's default); one batch may mix
+        weight vectors on both match routes ("lanes": one blend per source, "segmented": one blend launch per batch)."""
         modes, semis = self.pitch_of(f0_shift, transpose, len(sources))        # refused before a file is read
         durs = self.duration_of(target_duration, len(sources))
+        mixes = self.blend_of(blend, len(sources))
         if len(sources) == 0:
             return []
         vc, tg = self.vc, self.target
@@ -205,6 +240,32 @@ class BatchConverter:
         # the reference does not forward post_opt to the f0-only generators (ddsp_matcher.py:970, 1102-1110)
         post_opt = "no_post_opt" if self.f0only else self.post_opt
         tail = M.vocoding_tail(Tail(vc, self.f0only, self.ext), items, wavs.__getitem__)
+
+        def run_blend():
+            # every voice that some source of the batch gives weight to is searched (grouped_knn) and matched on its own; the
+            # blend sits between the match bodies and the tail
+            flags = []
+            vs = self.voices
+            used = [v for v in range(len(vs)) if any(m[v] != 0.0 for m in mixes)]
+            found = {v: M.grouped_knn(items, qpool, vs[v].feats, vs[v].prep, flags) for v in used} if len(items) > 1 else {}
+
+            def body_many(batch):
+                for nn, ready in found.values():
+                    for i in batch:
+                        M.wait_for_neighbours(nn.get(i), ready.get(i), dev)
+                nn32s = [[found[v][0].get(i) for i in batch] if v in found else None for v in range(len(vs))]
+                return M.match_features_blend([qpool[i] for i in batch], [f0s[i] for i in batch], vs, [mixes[i] for i in batch],
+                                              self.ckpt_type, post_opt, nn32s=nn32s, nan_flags=flags, topk=self.ext.topk,
+                                              f0_shift=[modes[i] for i in batch], transpose=[semis[i] for i in batch])
+            ys = M.run_match_bodies(items, lambda i: body_many([i])[0], body_many, tail, device=dev,
+                                    lanes=max(1, min(self.lanes, len(items))), match=self.match, match_batch=self.match_batch)
+            peak = torch.stack([y.abs().max() for y in ys])
+            for f in flags:
+                ops.raise_if_nan(f)
+            vc._check_finite(peak)
+            return ys
+        if self.voices is not None:
+            return ops.retry_on_overflow(run_blend)
 
         def run():
             flags = []
@@ -233,25 +294,32 @@ class BatchConverter:
             return ys
         return ops.retry_on_overflow(run)
 
-    def convert_files(self, src_files, converted_audio_dir=None, target_duration=None) -> list:
+    def convert_files(self, src_files, converted_audio_dir=None, target_duration=None, blend=None) -> list:
         """Paths in, files out: ``<dir or the source's folder>/<src>_to_<ref>_knn_<ckpt_type>_<post_opt>.wav`` (the single-file
-        naming, ddsp_matcher.py:1015), PCM_32 16 kHz mono.  -> the written paths.  ``target_duration``: as ``convert``."""
-        ys = self.convert([str(p) for p in src_files], target_duration=target_duration)
+        naming, ddsp_matcher.py:1015), PCM_32 16 kHz mono.  -> the written paths.  ``target_duration`` / ``blend``: as ``convert``.
+        With several target voices ``<ref>`` is their ids joined by ``+`` (``<idA>+<idB>[+...]``); the weights are not in the name."""
+        ys = self.convert([str(p) for p in src_files], target_duration=target_duration, **({} if blend is None else dict(blend=blend)))
         out = []
         for p, y in zip(src_files, ys):
-            d = converted_audio_dir if converted_audio_dir is not None else str(Path(p).parent)
-            Path(d).mkdir(parents=True, exist_ok=True)
-            name = os.path.basename(str(p)).split(".")[0] + "_to_" + self.target.ref_id + f"_knn_{self.ckpt_type}_{self.post_opt}.wav"
-            out.append(audio_io.save_audio(os.path.join(d, name), y.detach().cpu().numpy(), sample_rate=16000))
+            path = self.output_path(p, converted_audio_dir)
+            Path(path).parent.mkdir(parents=True, exist_ok=True)
+            out.append(audio_io.save_audio(path, y.detach().cpu().numpy(), sample_rate=16000))
         return out
+
+    def output_path(self, src_file, converted_audio_dir=None) -> str:
+        """Where ``convert_files`` writes the conversion of ``src_file``."""
+        d = converted_audio_dir if converted_audio_dir is not None else str(Path(src_file).parent)
+        ref_id = self.target.ref_id if self.voices is None else "+".join(v.ref_id for v in self.voices)
+        return os.path.join(d, os.path.basename(str(src_file)).split(".")[0] + "_to_" + ref_id + f"_knn_{self.ckpt_type}_{self.post_opt}.wav")
 
 
 class RequestQueue:
     """Dynamic batching in front of a BatchConverter.  ``submit(src)`` -> Future of the waveform (a CPU tensor).
     ``submit(src, transpose=, f0_shift=)``: the request's own transpose (semitones) / f0 shift mode instead of the converter's;
     ``submit(src, target_duration=)``: the length in seconds the request's conversion is re-timed to (BatchConverter.convert);
-    requests with different values share a batch.  The converter's ``loudness_db``, ``envelope_mix`` and ``peak_db`` apply to every
-    request (per-request values of those are not supported)."""
+    ``submit(src, blend=)`` (a converter with several target voices): the request's own blend weights; a bad vector is refused
+    at the door and fails alone.  Requests with different values share a batch.  The converter's ``loudness_db``, ``envelope_mix``
+    and ``peak_db`` apply to every request (per-request values of those are not supported)."""
 
     def __init__(self, converter: BatchConverter, max_batch: int = 32, max_wait_ms: float = 5.0):
         self.conv, self.max_batch, self.max_wait = converter, int(max_batch), float(max_wait_ms) / 1e3
@@ -262,13 +330,16 @@ class RequestQueue:
         self._th = threading.Thread(target=self._loop, name="knnsvc-batcher", daemon=True)
         self._th.start()
 
-    def submit(self, src, transpose=None, f0_shift=None, target_duration=None) -> Future:
+    def submit(self, src, transpose=None, f0_shift=None, target_duration=None, blend=None) -> Future:
         if self._stop:
             raise RuntimeError("RequestQueue is closed")
         fut = Future()
         # a bad value is refused here, not in the worker
         pitch = (None, None) if transpose is None and f0_shift is None else self.conv.pitch_of(f0_shift, transpose)
-        if target_duration is not None:
+        if blend is not None:
+            self._q.put((src, fut, pitch, None if target_duration is None else self.conv.duration_of(target_duration),
+                         self.conv.blend_of(blend)))
+        elif target_duration is not None:
             self._q.put((src, fut, pitch, self.conv.duration_of(target_duration)))
         elif pitch != (None, None):
             self._q.put((src, fut, pitch))
@@ -303,8 +374,9 @@ class RequestQueue:
         """One batch; a request that cannot be loaded, or whose data makes the conversion fail (a NaN source, an f0 track of the
         wrong length, a target duration out of proportion to its length), fails ALONE: the others of its batch are converted
         without it.  An entry is (source, Future), (source, Future, (f0_shift, transpose)) or (source, Future, (f0_shift,
-        transpose), target_duration); a batch in which no request carries values of its own is converted as it always was, and
-        ``target_duration`` is passed on only when a request of the batch has one."""
+        transpose), target_duration) or (source, Future, (f0_shift, transpose), target_duration or None, blend weights); a batch
+        in which no request carries values of its own is converted as it always was, and ``target_duration`` / ``blend`` are
+        passed on only when a request of the batch has one."""
         good, loaded = [], []
         for s, fut, *own in batch:
             try:
@@ -313,20 +385,22 @@ class RequestQueue:
                 if dur is not None:                          # needs the loaded source: refused here, before the batch is formed
                     self.conv.plan_duration(ld[0], dur, item="request")
                 loaded.append(ld)
-                good.append((s, fut, own[0] if own else (None, None), dur))
+                good.append((s, fut, own[0] if own else (None, None), dur, own[2] if len(own) > 2 else None))
             except BaseException as e:
                 fut.set_exception(e)
         if not good:
             return
         plain = all(g[2] == (None, None) for g in good)
         timed = any(g[3] is not None for g in good)
+        mixed = any(g[4] is not None for g in good)
 
         def pitch(gs):
             kw = {} if plain else dict(f0_shift=[g[2][0] for g in gs], transpose=[g[2][1] for g in gs])
-            return dict(kw, target_duration=[g[3] for g in gs]) if timed else kw
+            kw = dict(kw, target_duration=[g[3] for g in gs]) if timed else kw
+            return dict(kw, blend=[g[4] for g in gs]) if mixed else kw
         try:
             ys = self.conv.convert([g[0] for g in good], loaded=loaded, **pitch(good))
-            for (_s, fut, _p, _d), y in zip(good, ys):
+            for (_s, fut, _p, _d, _b), y in zip(good, ys):
                 fut.set_result(y.detach().cpu())
             return
         except BaseException as e:
