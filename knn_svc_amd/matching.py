@@ -15,13 +15,14 @@ from __future__ import annotations
 import contextlib
 import math
 import os
+import types
 from pathlib import Path
 
 import numpy as np
 import torch
 
 from . import audio_io, config as C, dist as kdist, features, ops, pipeline, pool_cache
-from .options import Extensions
+from .options import Extensions, SourceKnobs, per_item
 from .wavlm import WavLMEncoder, chunk_plan
 
 AUDIO_EXT = {".flac", ".wav", ".mp3"}
@@ -415,15 +416,7 @@ def resolve_f0_shift(mode, transpose, n_items=None):
         if isinstance(mode, (list, tuple)) or isinstance(transpose, (list, tuple)):
             raise ValueError("f0_shift / transpose: a single value expected here, not a list")
         return _one_f0_shift(mode, transpose)
-    per = []
-    for name, v in (("f0_shift", mode), ("transpose", transpose)):
-        if isinstance(v, (list, tuple)):
-            if len(v) != n_items:
-                raise ValueError(f"{name}: {len(v)} values for {n_items} items")
-            per.append(list(v))
-        else:
-            per.append([v] * n_items)
-    pairs = [_one_f0_shift(m, t) for m, t in zip(*per)]
+    pairs = [_one_f0_shift(m, t) for m, t in zip(per_item(mode, n_items, "f0_shift"), per_item(transpose, n_items, "transpose"))]
     return [m for m, _ in pairs], [t for _, t in pairs]
 
 
@@ -454,11 +447,7 @@ def resolve_target_duration(value, n_items=None):
         if isinstance(value, (list, tuple)):
             raise ValueError("target_duration: a single value expected here, not a list")
         return _one_target_duration(value)
-    if isinstance(value, (list, tuple)):
-        if len(value) != n_items:
-            raise ValueError(f"target_duration: {len(value)} values for {n_items} items")
-        return [_one_target_duration(v) for v in value]
-    return [_one_target_duration(value)] * n_items
+    return per_item(value, n_items, "target_duration", _one_target_duration)
 
 
 def duration_plan(T, target_duration, sr=C.SAMPLE_RATE, hop=C.HOP, item=None):
@@ -495,11 +484,8 @@ def stretch_queries(feats, f0s, durations):
     if not who:
         return feats, f0s
     plans = [duration_plan(feats[i].shape[0], durations[i], item=f"item {i}") for i in who]
-    seg = [0]
-    for i in who:
-        seg.append(seg[-1] + int(feats[i].shape[0]))
-    xo, fo = ops.time_scale_seg(_stacked([feats[i] for i in who]), _stacked([f0s[i] for i in who]), seg,
-                                [p[0] for p in plans], [p[1] for p in plans])
+    xo, fo = ops.time_scale_seg(_stacked([feats[i] for i in who]), _stacked([f0s[i] for i in who]),
+                                ops.Segments.of_lengths(feats[i].shape[0] for i in who), [p[0] for p in plans], [p[1] for p in plans])
     feats, f0s = list(feats), list(f0s)
     o = 0
     for i, (T_out, _c) in zip(who, plans):
@@ -511,8 +497,8 @@ def stretch_queries(feats, f0s, durations):
 # Voice blend (an extension; include/knnsvc_hip.h "Voice blend" is the specification): a conversion towards a weighted mix of 2 to
 # BLEND_MAX_VOICES target voices.  Each voice is matched as if it were the only target, the matched features and harmonics are
 # mixed (ops.blend_seg), and the source's f0 is shifted ONCE, towards the weighted mean of the voices' log-f0 medians
-# (ops.shift_f0_seg_blend).  A weight vector belongs to a source item, like a request's own ``transpose``: it travels beside the
-# options.Extensions record.  The library does not normalise; ``resolve_blend`` does, in fp64.
+# (ops.shift_f0_seg_blend).  A weight vector belongs to a source item, like a request's own ``transpose``: it is a field of
+# options.SourceKnobs, not of options.Extensions.  The library does not normalise; ``resolve_blend`` does, in fp64.
 BLEND_MAX_VOICES = ops.BLEND_MAX_VOICES
 
 
@@ -540,6 +526,12 @@ def _one_blend(value, n_voices):
     return tuple(w / total for w in a)
 
 
+def blend_per_item(weights) -> bool:
+    """Whether ``weights`` is a list with one entry per item (vectors or Nones; the empty list too), not one weight vector."""
+    return isinstance(weights, (list, tuple)) and (len(weights) == 0 or
+                                                   any(w is None or isinstance(w, (list, tuple, np.ndarray)) for w in weights))
+
+
 def resolve_blend(weights, n_voices, n_items=None):
     """Blend weights as the library takes them, refused (ValueError) before any device or file work when they are not valid:
     ``n_voices`` numbers, finite and >= 0, at least one > 0 (None: equal weights), normalised in fp64 as ``a / math.fsum(a)``
@@ -551,13 +543,8 @@ def resolve_blend(weights, n_voices, n_items=None):
     n_voices = int(n_voices)
     if n_items is None:
         return _one_blend(weights, n_voices)
-    per_item = isinstance(weights, (list, tuple)) and (len(weights) == 0 or
-                                                       any(w is None or isinstance(w, (list, tuple, np.ndarray)) for w in weights))
-    if not per_item:
-        return [_one_blend(weights, n_voices)] * n_items
-    if len(weights) != n_items:
-        raise ValueError(f"blend: {len(weights)} weight vectors for {n_items} items")
-    return [_one_blend(w, n_voices) for w in weights]
+    one = lambda w: _one_blend(w, n_voices)
+    return per_item(weights, n_items, "blend", one, default=one(None), is_list=blend_per_item, unit="weight vectors")
 
 
 def refuse_blend_when_sharded():
@@ -623,6 +610,11 @@ def _stacked(ts):
     return ts[0].contiguous() if len(ts) == 1 else torch.cat([t.contiguous() for t in ts], 0).contiguous()
 
 
+def _split(t, lens):
+    """The stacked rows of ``t`` per item again (views); None: a None per item."""
+    return t.split(lens) if t is not None else [None] * len(lens)
+
+
 def match_features_many(query_seqs, query_f0s, matching_list, matching_f0, harmonics_list, ckpt_type, post_opt, nn32s=None,
                         nan_flags=None, pool_prep=None, synth_list=None, return_debug=False, topk=None, f0_shift=None,
                         transpose=None):
@@ -643,10 +635,7 @@ def match_features_many(query_seqs, query_f0s, matching_list, matching_f0, harmo
     topk = resolve_topk(topk)                 # before any device work
     shift_modes, shift_ts = resolve_f0_shift(f0_shift, transpose, len(query_seqs))
     lens = [int(q.shape[0]) for q in query_seqs]
-    seg = [0]
-    for n in lens:
-        seg.append(seg[-1] + n)
-    seg = ops.Segments(seg)                   # the host tables once for the six segmented calls
+    seg = ops.Segments.of_lengths(lens)       # the host tables once for the six segmented calls
     q = _stacked(query_seqs)
     query_f0 = _stacked([t.reshape(-1) for t in query_f0s])
     P = matching_list
@@ -703,10 +692,9 @@ def match_features_many(query_seqs, query_f0s, matching_list, matching_f0, harmo
                     return match_features_many(query_seqs, query_f0s, matching_list, matching_f0, harmonics_list, ckpt_type, post_opt,
                                                pool_prep=pool_prep, synth_list=synth_list, return_debug=return_debug, topk=topk,
                                                f0_shift=f0_shift, transpose=transpose)
-    parts = lambda t: t.split(lens) if t is not None else [None] * len(lens)
     out = []
-    dbg = [parts(t) for t in (nn32, idx, w, idx2, w2)]
-    for i, (of, hw, sf) in enumerate(zip(parts(out_feats), parts(harm_w), parts(shifted))):
+    dbg = [_split(t, lens) for t in (nn32, idx, w, idx2, w2)]
+    for i, (of, hw, sf) in enumerate(zip(_split(out_feats, lens), _split(harm_w, lens), _split(shifted, lens))):
         if return_debug:
             out.append((of, hw, sf, dict(nn32=dbg[0][i], idx_wavlm=dbg[1][i], w_wavlm=dbg[2][i], idx_harm=dbg[3][i], w_harm=dbg[4][i],
                                          iters_wavlm=it1[i:i + 1] if it1 is not None else 0,
@@ -717,20 +705,10 @@ def match_features_many(query_seqs, query_f0s, matching_list, matching_f0, harmo
     return out
 
 
-def _voice_parts(voice):
-    """A voice of a blend as (matching_list, matching_f0, harmonics_list, pool_prep or None, synth_list or None): a
-    serving.TargetVoice (or anything with ``feats`` / ``f0`` / ``harm`` and optionally ``prep`` / ``synth``), or such a tuple
-    of three to five entries."""
-    if isinstance(voice, (list, tuple)):
-        if not 3 <= len(voice) <= 5:
-            raise ValueError(f"a voice given as a tuple is (pool, f0, harmonics[, pool_prep[, synth_list]]), got {len(voice)} entries")
-        return tuple(voice) + (None,) * (5 - len(voice))
-    return voice.feats, voice.f0, voice.harm, getattr(voice, "prep", None), getattr(voice, "synth", None)
-
-
 def match_features_blend(query_seqs, query_f0s, voices, weights, ckpt_type, post_opt, nn32s=None, nan_flags=None, topk=None,
                          f0_shift=None, transpose=None):
-    """``match_features_many`` towards a weighted mix of 2..BLEND_MAX_VOICES ``voices`` (``_voice_parts``) -> the same list of
+    """``match_features_many`` towards a weighted mix of 2..BLEND_MAX_VOICES ``voices`` (serving.TargetVoice, or anything with
+    ``feats`` / ``f0`` / ``harm`` and optionally ``prep`` / ``synth``: ``match_bodies``) -> the same list of
     per-item tuples (out_feats, harm or None, shifted_f0).  ``weights``: ``resolve_blend``'s argument (one vector for all items or
     one per item; None: equal).  One ``match_features_many`` per voice — its pool, f0, harmonics, ``pool_prep``, ``synth_list``
     and the items' own ``f0_shift`` / ``transpose`` / ``topk``, so every voice's frames are bit-identical to the single-target
@@ -739,22 +717,18 @@ def match_features_blend(query_seqs, query_f0s, voices, weights, ckpt_type, post
     voices' log medians (the per-voice shifted tracks are used inside each voice's match only).  A voice whose weight is 0 for
     every item is not matched.  ``nn32s``: per voice, the per-item neighbour lists of ``match_features_many`` (or None).  NaN
     flags and the overflow retry work per voice, as there."""
-    voices = [_voice_parts(v) for v in voices]
     rows = resolve_blend(weights, len(voices), len(query_seqs))      # before any device work
     resolve_topk(topk)
     shift_modes, shift_ts = resolve_f0_shift(f0_shift, transpose, len(query_seqs))
     live = [v for v in range(len(voices)) if any(r[v] != 0.0 for r in rows)]
     per = {}
     for v in live:
-        P, Pf0, Ph, prep, synth = voices[v]
-        per[v] = match_features_many(query_seqs, query_f0s, P, Pf0, Ph, ckpt_type, post_opt, nn32s=None if nn32s is None else nn32s[v],
-                                     nan_flags=nan_flags, pool_prep=prep, synth_list=synth, topk=topk, f0_shift=f0_shift,
-                                     transpose=transpose)
+        vo = voices[v]
+        per[v] = match_features_many(query_seqs, query_f0s, vo.feats, vo.f0, vo.harm, ckpt_type, post_opt,
+                                     nn32s=None if nn32s is None else nn32s[v], nan_flags=nan_flags, pool_prep=getattr(vo, "prep", None),
+                                     synth_list=getattr(vo, "synth", None), topk=topk, f0_shift=f0_shift, transpose=transpose)
     lens = [int(q.shape[0]) for q in query_seqs]
-    seg = [0]
-    for n in lens:
-        seg.append(seg[-1] + n)
-    seg = ops.Segments(seg)
+    seg = ops.Segments.of_lengths(lens)
     # a voice that was not matched has weight 0 in every row: its pointer is never read, any live voice's stands in
     def stacked(k):
         got = {v: _stacked([r[k] for r in per[v]]) for v in live}
@@ -764,11 +738,41 @@ def match_features_blend(query_seqs, query_f0s, voices, weights, ckpt_type, post
     harm = ops.blend_seg(stacked(1), seg, rows) if with_harm else None
     query_f0 = _stacked([t.reshape(-1) for t in query_f0s])
     qmed = ops.log_f0_median_seg(query_f0, seg)
-    meds = {v: ops.log_f0_median(voices[v][1]) for v in live}
+    meds = {v: ops.log_f0_median(voices[v].f0) for v in live}
     pmeds = torch.stack([meds.get(v, meds[live[0]]) for v in range(len(voices))]).contiguous()
     shifted = ops.shift_f0_seg_blend(query_f0, seg, qmed, pmeds, rows, shift_modes, shift_ts)
-    parts = lambda t: t.split(lens) if t is not None else [None] * len(lens)
-    return list(zip(parts(out_feats), parts(harm), parts(shifted)))
+    return list(zip(_split(out_feats, lens), _split(harm, lens), _split(shifted, lens)))
+
+
+def match_bodies(query_of, voices, ckpt_type, post_opt, found, flags, knobs, topk=None):
+    """-> the ``(body, body_many)`` pair of ``run_match_bodies``: the match of one item, and of a batch of items stacked.
+    ``query_of(item)`` -> (features, f0) of the item's query.  ``voices``: a list of one voice (serving.TargetVoice, or anything
+    with ``feats`` / ``f0`` / ``harm`` and optionally ``prep`` / ``synth``), or of 2..BLEND_MAX_VOICES for a blend
+    (``match_features_blend``, on both routes).  ``found``: per voice, ``(nn: item -> neighbour list, ready: item -> event)`` of the
+    searches already enqueued (``grouped_knn``); an item not in ``nn`` is searched inside its match.  ``flags``: receives the
+    deferred NaN flags.  ``knobs(item)`` -> the item's options.SourceKnobs: its ``f0_shift`` / ``transpose`` and, for a blend, its
+    weight row."""
+    dev = voices[0].feats.device
+
+    def match(batch, alone):
+        for nn, ready in found:
+            for i in batch:
+                wait_for_neighbours(nn.get(i), ready.get(i), dev)      # a group search on the kNN stream
+        nn32s = [[nn.get(i) for i in batch] for nn, _ready in found]
+        qs, f0s = (list(t) for t in zip(*(query_of(i) for i in batch)))
+        ks = [knobs(i) for i in batch]
+        modes, semis = [k.f0_shift for k in ks], [k.transpose for k in ks]
+        if len(voices) > 1:
+            return match_features_blend(qs, f0s, voices, [k.blend for k in ks], ckpt_type, post_opt, nn32s=nn32s, nan_flags=flags,
+                                        topk=topk, f0_shift=modes, transpose=semis)
+        vo = voices[0]
+        pool = dict(nan_flags=flags, pool_prep=getattr(vo, "prep", None), synth_list=getattr(vo, "synth", None), topk=topk)
+        if alone:              # (through the module global: the CPU tests put their stand-in there)
+            return [match_features(qs[0], f0s[0], vo.feats, vo.f0, vo.harm, ckpt_type, post_opt, nn32=nn32s[0][0], f0_shift=modes[0],
+                                   transpose=semis[0], **pool)]
+        return match_features_many(qs, f0s, vo.feats, vo.f0, vo.harm, ckpt_type, post_opt, nn32s=nn32s[0], f0_shift=modes,
+                                   transpose=semis, **pool)
+    return (lambda item: match([item], True)[0]), (lambda batch: match(batch, False))
 
 
 def run_match_bodies(items, body, body_many, tail=None, *, device, lanes, match="lanes", match_batch=None):
@@ -957,18 +961,10 @@ def match_at_inference_time(src_wav_file, ref_wav_file, wavlm: WavLMEncoder, mat
             # 3-4 x as efficiently as one ~300-row search per utterance
             g_nn, g_ready = grouped_knn(items, query_pool, matching_list, prep, flags)
             nn.update(g_nn); nn_ready.update(g_ready)
-        def body(item):
-            wait_for_neighbours(nn.get(item), nn_ready.get(item), matching_list.device)      # a group search on the kNN stream
-            return match_features(query_pool[item], query_f0_pool[item], matching_list, matching_f0,
-                                  harmonics_list, ckpt_type, post_opt, nan_flags=flags, pool_prep=prep, nn32=nn.get(item),
-                                  synth_list=synth_list, topk=ext.topk, f0_shift=ext.f0_shift, transpose=ext.transpose)
-        def body_many(batch):
-            for item in batch:
-                wait_for_neighbours(nn.get(item), nn_ready.get(item), matching_list.device)
-            return match_features_many([query_pool[it] for it in batch], [query_f0_pool[it] for it in batch], matching_list, matching_f0,
-                                       harmonics_list, ckpt_type, post_opt, nn32s=[nn.get(it) for it in batch], nan_flags=flags,
-                                       pool_prep=prep, synth_list=synth_list, topk=ext.topk, f0_shift=ext.f0_shift,
-                                       transpose=ext.transpose)
+        voice = types.SimpleNamespace(feats=matching_list, f0=matching_f0, harm=harmonics_list, prep=prep, synth=synth_list)
+        own = SourceKnobs(f0_shift=ext.f0_shift, transpose=ext.transpose)          # (checked with the record)
+        body, body_many = match_bodies(lambda it: (query_pool[it], query_f0_pool[it]), [voice], ckpt_type, post_opt, [(nn, nn_ready)],
+                                       flags, lambda it: own, topk=ext.topk)
         # match bodies in flight at once (each is a chain of single-workgroup recurrences: more lanes = more of them side by side);
         # KNNSVC_MATCH=segmented (unsharded pool, several items): batches of KNNSVC_MATCH_BATCH items, each one body_many on a lane
         lanes = min(int(os.environ.get("KNNSVC_MATCH_LANES", "3")), len(items))

@@ -879,7 +879,18 @@ class Segments:
     """Row offsets prepared once (the host tables of _seg_chunks) for any number of *_seg calls; each takes the Python list or this."""
 
     def __init__(self, seg):
-        self.chunks, self.n, self.total = _seg_chunks(seg), len(seg) - 1, int(seg[-1])
+        self.chunks, self.n, self.total, self.offsets = _seg_chunks(seg), len(seg) - 1, int(seg[-1]), list(seg)
+
+    def __iter__(self):
+        return iter(self.offsets)
+
+    @classmethod
+    def of_lengths(cls, lens):
+        """The table of sequences of ``lens`` rows stacked one after the other."""
+        seg = [0]
+        for n in lens:
+            seg.append(seg[-1] + int(n))
+        return cls(seg)
 
 
 def _segments(seg, name, *stacked):
@@ -911,27 +922,41 @@ def shift_f0_seg(f0, seg, qmed, pmed, modes=None, transposes=None, return_shift=
     is then chosen per segment on the device (knnsvc_shift_f0_seg_mode; include/knnsvc_hip.h "Pitch control"); with both None
     this is the median shift through knnsvc_shift_f0_seg (the same kernel with median / 0).  ``return_shift``: -> (shifted, [n_seg] applied interval in
     semitones, on the device)."""
-    _need(f0, name="f0"); seg = _segments(seg, "shift_f0_seg", f0)
-    _need(qmed, name="qmed"); _need(pmed, name="pmed")
+    return _shift_f0_seg("shift_f0_seg", f0, seg, qmed, pmed, modes, transposes, return_shift)
+
+
+def _shift_f0_seg(fn, f0, seg, qmed, pmed, modes, transposes, return_shift, weights=None):
+    """``shift_f0_seg`` and, with ``weights`` (``pmed`` is then its ``pmeds``), ``shift_f0_seg_blend``."""
+    _need(f0, name="f0"); seg = _segments(seg, fn, f0)
+    _need(qmed, name="qmed"); _need(pmed, name="pmed" if weights is None else "pmeds")
     if qmed.numel() != 2 * seg.n or not qmed.is_contiguous():
-        raise KnnSvcError(f"shift_f0_seg: qmed must be a contiguous [{seg.n}, 2] tensor, got {tuple(qmed.shape)}")
-    f0 = f0.contiguous()
-    out = torch.empty_like(f0)
-    lib = _lib.load()
-    if modes is None and transposes is None and not return_shift:
-        for a, r0, tab in seg.chunks:
-            check(lib.knnsvc_shift_f0_seg(_p(f0[r0:]), tab, len(tab) - 1, _p(qmed[a:]), _p(pmed), _p(out[r0:]), _stream()), "shift_f0_seg")
-        return out
+        raise KnnSvcError(f"{fn}: qmed must be a contiguous [{seg.n}, 2] tensor, got {tuple(qmed.shape)}")
+    if weights is not None:
+        if pmed.dim() != 2 or pmed.shape[1] != 2 or not pmed.is_contiguous():
+            raise KnnSvcError(f"{fn}: pmeds must be a contiguous [n_voices, 2] tensor, got {tuple(pmed.shape)}")
+        nv = int(pmed.shape[0])
+        rows = _blend_rows(fn, weights, seg.n, nv)
     for name, t in (("modes", modes), ("transposes", transposes)):
         if t is not None and len(t) != seg.n:
-            raise KnnSvcError(f"shift_f0_seg: {len(t)} {name} for {seg.n} segments")
+            raise KnnSvcError(f"{fn}: {len(t)} {name} for {seg.n} segments")
+    f0 = f0.contiguous()
+    out = torch.empty_like(f0)
     semis = torch.empty(seg.n, device=f0.device, dtype=torch.float32) if return_shift else None
+    plain = weights is None and modes is None and transposes is None and not return_shift
+    lib = _lib.load()
     for a, r0, tab in seg.chunks:
         n = len(tab) - 1
+        if plain:
+            check(lib.knnsvc_shift_f0_seg(_p(f0[r0:]), tab, n, _p(qmed[a:]), _p(pmed), _p(out[r0:]), _stream()), "shift_f0_seg")
+            continue
         mt = None if modes is None else (C.c_int32 * n)(*[int(m) for m in modes[a:a + n]])
         tt = None if transposes is None else (C.c_float * n)(*[float(t) for t in transposes[a:a + n]])
-        check(lib.knnsvc_shift_f0_seg_mode(_p(f0[r0:]), tab, n, mt, tt, _p(qmed[a:]), _p(pmed), _p(out[r0:]),
-                                           _p(semis[a:]) if return_shift else None, _stream()), "shift_f0_seg_mode")
+        dst = (_p(out[r0:]), _p(semis[a:]) if return_shift else None, _stream())
+        if weights is None:
+            check(lib.knnsvc_shift_f0_seg_mode(_p(f0[r0:]), tab, n, mt, tt, _p(qmed[a:]), _p(pmed), *dst), "shift_f0_seg_mode")
+        else:
+            wt = (C.c_double * (n * nv))(*[w for row in rows[a:a + n] for w in row])
+            check(lib.knnsvc_shift_f0_seg_blend(_p(f0[r0:]), tab, n, mt, tt, _p(qmed[a:]), _p(pmed), nv, wt, *dst), fn)
     return (out, semis) if return_shift else out
 
 
@@ -995,16 +1020,14 @@ def time_scale_seg(x, f0, seg, out_frames, inv_scales, out=None):
     seg = _segments(seg, "time_scale_seg", *[t for _, t in given])
     if len(out_frames) != seg.n or len(inv_scales) != seg.n:
         raise KnnSvcError(f"time_scale_seg: {len(out_frames)} out_frames and {len(inv_scales)} inv_scales for {seg.n} segments")
-    oseg = [0]
     for s, n in enumerate(out_frames):
         if isinstance(n, bool) or int(n) != n or int(n) < 1:
             raise KnnSvcError(f"time_scale_seg: segment {s}: out_frames must be an integer >= 1, got {n!r}")
-        oseg.append(oseg[-1] + int(n))
     cs = [float(c) for c in inv_scales]
     for s, c in enumerate(cs):
         if not (math.isfinite(c) and c > 0):
             raise KnnSvcError(f"time_scale_seg: segment {s}: inv_scale must be finite and > 0, got {inv_scales[s]!r}")
-    oseg = Segments(oseg)
+    oseg = Segments.of_lengths(out_frames)
     dev = given[0][1].device
     dim = 0 if x is None else int(x.shape[1])
     xo, fo = out if out is not None else (None, None)
@@ -1084,29 +1107,7 @@ def shift_f0_seg_blend(f0, seg, qmed, pmeds, weights, modes=None, transposes=Non
     ``weights`` [n_seg][n_voices] in place of the single ``pmed``; segment s is shifted towards the weighted mean of the voices'
     log medians, formed on the device (knnsvc_shift_f0_seg_blend; include/knnsvc_hip.h "Voice blend", point 3), after which modes
     and transposes act as in ``shift_f0_seg``."""
-    _need(f0, name="f0"); seg = _segments(seg, "shift_f0_seg_blend", f0)
-    _need(qmed, name="qmed"); _need(pmeds, name="pmeds")
-    if qmed.numel() != 2 * seg.n or not qmed.is_contiguous():
-        raise KnnSvcError(f"shift_f0_seg_blend: qmed must be a contiguous [{seg.n}, 2] tensor, got {tuple(qmed.shape)}")
-    if pmeds.dim() != 2 or pmeds.shape[1] != 2 or not pmeds.is_contiguous():
-        raise KnnSvcError(f"shift_f0_seg_blend: pmeds must be a contiguous [n_voices, 2] tensor, got {tuple(pmeds.shape)}")
-    nv = int(pmeds.shape[0])
-    rows = _blend_rows("shift_f0_seg_blend", weights, seg.n, nv)
-    for name, t in (("modes", modes), ("transposes", transposes)):
-        if t is not None and len(t) != seg.n:
-            raise KnnSvcError(f"shift_f0_seg_blend: {len(t)} {name} for {seg.n} segments")
-    f0 = f0.contiguous()
-    out = torch.empty_like(f0)
-    semis = torch.empty(seg.n, device=f0.device, dtype=torch.float32) if return_shift else None
-    lib = _lib.load()
-    for a, r0, tab in seg.chunks:
-        n = len(tab) - 1
-        mt = None if modes is None else (C.c_int32 * n)(*[int(m) for m in modes[a:a + n]])
-        tt = None if transposes is None else (C.c_float * n)(*[float(t) for t in transposes[a:a + n]])
-        wt = (C.c_double * (n * nv))(*[w for row in rows[a:a + n] for w in row])
-        check(lib.knnsvc_shift_f0_seg_blend(_p(f0[r0:]), tab, n, mt, tt, _p(qmed[a:]), _p(pmeds), nv, wt, _p(out[r0:]),
-                                            _p(semis[a:]) if return_shift else None, _stream()), "shift_f0_seg_blend")
-    return (out, semis) if return_shift else out
+    return _shift_f0_seg("shift_f0_seg_blend", f0, seg, qmed, pmeds, modes, transposes, return_shift, weights)
 
 
 def weighted_gather(idx4, w, pool, mean=False):
@@ -1353,13 +1354,10 @@ def vad_trim(wavs, trigger_level, sample_rate=16000, return_measures=False):
         raise KnnSvcError(f"vad_trim: trigger_level must be finite and positive, got {trigger_level!r}")
     lib = _lib.load()
     dev = wavs[0].device
-    seg = [0]
-    for w in wavs:
-        seg.append(seg[-1] + w.numel())
     x = wavs[0].contiguous() if len(wavs) == 1 else torch.cat([w.contiguous() for w in wavs])
     strip = torch.empty(len(wavs), 2, device=dev, dtype=torch.int64)
     measures = []
-    for a, r0, tab in _seg_chunks(seg):
+    for a, r0, tab in Segments.of_lengths(w.numel() for w in wavs).chunks:
         n, total = len(tab) - 1, int(tab[len(tab) - 1])
         nbytes = lib.knnsvc_vad_workspace_bytes(total, n, int(sample_rate))
         if nbytes == 0:

@@ -37,7 +37,7 @@ import torch
 from . import audio_io, config as C, ops
 from . import matching as M
 from .matcher import Tail
-from .options import Extensions
+from .options import Extensions, SourceKnobs, per_item
 
 
 class TargetVoice:
@@ -166,12 +166,13 @@ class BatchConverter:
     def pitch_of(self, f0_shift=None, transpose=None, n=None):
         """Per-source ``f0_shift`` / ``transpose`` (a value for all, or one per source; None entries: this converter's defaults)
         as checked lists of ``n`` values each; ``n`` None: one checked pair."""
-        fill = lambda v, d: [d if x is None else x for x in v] if isinstance(v, (list, tuple)) else (d if v is None else v)
-        f0_shift, transpose = fill(f0_shift, self.ext.f0_shift), fill(transpose, self.ext.transpose)
-        M.resolve_f0_shift(f0_shift, transpose, n)
         if n is None:
-            return f0_shift, transpose
-        return [list(v) if isinstance(v, (list, tuple)) else [v] * n for v in (f0_shift, transpose)]
+            per = (self.ext.f0_shift if f0_shift is None else f0_shift, self.ext.transpose if transpose is None else transpose)
+        else:
+            per = [per_item(f0_shift, n, "f0_shift", default=self.ext.f0_shift),
+                   per_item(transpose, n, "transpose", default=self.ext.transpose)]
+        M.resolve_f0_shift(*per, n)
+        return per
 
     def duration_of(self, target_duration=None, n=None):
         """``target_duration`` (seconds; a value for all sources, or one per source; None: off) checked
@@ -189,15 +190,10 @@ class BatchConverter:
             if blend is not None and not (isinstance(blend, (list, tuple)) and all(b is None for b in blend)):
                 raise ValueError("blend needs several target voices: this converter has a single TargetVoice")
             return None
+        one = lambda b: M.resolve_blend(b, len(self.voices))
         if n is None:
-            return self.blend if blend is None else M.resolve_blend(blend, len(self.voices))
-        if blend is None:
-            return [self.blend] * n
-        if isinstance(blend, (list, tuple)) and (len(blend) == 0 or any(b is None or isinstance(b, (list, tuple, np.ndarray)) for b in blend)):
-            if len(blend) != n:
-                raise ValueError(f"blend: {len(blend)} weight vectors for {n} sources")
-            return [self.blend if b is None else M.resolve_blend(b, len(self.voices)) for b in blend]
-        return [M.resolve_blend(blend, len(self.voices))] * n
+            return self.blend if blend is None else one(blend)
+        return per_item(blend, n, "blend", one, default=self.blend, is_list=M.blend_per_item, unit="weight vectors")
 
     def plan_duration(self, w, target_duration, item=None):
         """matching.duration_plan of a loaded source waveform (its frame count follows from its length: nothing is encoded)."""
@@ -216,9 +212,10 @@ class BatchConverter:
         modes, semis = self.pitch_of(f0_shift, transpose, len(sources))        # refused before a file is read
         durs = self.duration_of(target_duration, len(sources))
         mixes = self.blend_of(blend, len(sources))
+        knobs = [SourceKnobs(*k) for k in zip(modes, semis, durs, mixes or [None] * len(sources))]
         if len(sources) == 0:
             return []
-        vc, tg = self.vc, self.target
+        vc, voices = self.vc, self.voices or [self.target]
         dev = vc.device
         vc.wavlm.set_layer_mix(M._mix_of(vc.weighting, vc.wavlm))      # the shared encoder may have been left in another mix
         loaded = loaded if loaded is not None else [self._load(s) for s in sources]
@@ -241,50 +238,14 @@ class BatchConverter:
         post_opt = "no_post_opt" if self.f0only else self.post_opt
         tail = M.vocoding_tail(Tail(vc, self.f0only, self.ext), items, wavs.__getitem__)
 
-        def run_blend():
-            # every voice that some source of the batch gives weight to is searched (grouped_knn) and matched on its own; the
-            # blend sits between the match bodies and the tail
-            flags = []
-            vs = self.voices
-            used = [v for v in range(len(vs)) if any(m[v] != 0.0 for m in mixes)]
-            found = {v: M.grouped_knn(items, qpool, vs[v].feats, vs[v].prep, flags) for v in used} if len(items) > 1 else {}
-
-            def body_many(batch):
-                for nn, ready in found.values():
-                    for i in batch:
-                        M.wait_for_neighbours(nn.get(i), ready.get(i), dev)
-                nn32s = [[found[v][0].get(i) for i in batch] if v in found else None for v in range(len(vs))]
-                return M.match_features_blend([qpool[i] for i in batch], [f0s[i] for i in batch], vs, [mixes[i] for i in batch],
-                                              self.ckpt_type, post_opt, nn32s=nn32s, nan_flags=flags, topk=self.ext.topk,
-                                              f0_shift=[modes[i] for i in batch], transpose=[semis[i] for i in batch])
-            ys = M.run_match_bodies(items, lambda i: body_many([i])[0], body_many, tail, device=dev,
-                                    lanes=max(1, min(self.lanes, len(items))), match=self.match, match_batch=self.match_batch)
-            peak = torch.stack([y.abs().max() for y in ys])
-            for f in flags:
-                ops.raise_if_nan(f)
-            vc._check_finite(peak)
-            return ys
-        if self.voices is not None:
-            return ops.retry_on_overflow(run_blend)
-
         def run():
+            # every voice that some source of the batch gives weight to (a single target: that one) is searched over the frames
+            # of several sources at a time (grouped_knn) and matched on its own; a blend sits between the match bodies and the tail
             flags = []
-            if len(items) > 1:
-                nn, ready = M.grouped_knn(items, qpool, tg.feats, tg.prep, flags)
-            else:
-                nn, ready = {}, {}
-
-            def body(i):
-                M.wait_for_neighbours(nn.get(i), ready.get(i), dev)
-                return M.match_features(qpool[i], f0s[i], tg.feats, tg.f0, tg.harm, self.ckpt_type, post_opt,
-                                        nan_flags=flags, pool_prep=tg.prep, nn32=nn.get(i), topk=self.ext.topk,
-                                        f0_shift=modes[i], transpose=semis[i])
-            def body_many(batch):
-                for i in batch:
-                    M.wait_for_neighbours(nn.get(i), ready.get(i), dev)
-                return M.match_features_many([qpool[i] for i in batch], [f0s[i] for i in batch], tg.feats, tg.f0, tg.harm, self.ckpt_type,
-                                             post_opt, nn32s=[nn.get(i) for i in batch], nan_flags=flags, pool_prep=tg.prep, topk=self.ext.topk,
-                                             f0_shift=[modes[i] for i in batch], transpose=[semis[i] for i in batch])
+            used = [len(items) > 1 and (mixes is None or any(m[v] != 0.0 for m in mixes)) for v in range(len(voices))]
+            found = [M.grouped_knn(items, qpool, vo.feats, vo.prep, flags) if u else ({}, {}) for vo, u in zip(voices, used)]
+            body, body_many = M.match_bodies(lambda i: (qpool[i], f0s[i]), voices, self.ckpt_type, post_opt, found, flags,
+                                             knobs.__getitem__, topk=self.ext.topk)
             ys = M.run_match_bodies(items, body, body_many, tail, device=dev, lanes=max(1, min(self.lanes, len(items))),
                                     match=self.match, match_batch=self.match_batch)
             peak = torch.stack([y.abs().max() for y in ys])
@@ -334,17 +295,14 @@ class RequestQueue:
         if self._stop:
             raise RuntimeError("RequestQueue is closed")
         fut = Future()
-        # a bad value is refused here, not in the worker
-        pitch = (None, None) if transpose is None and f0_shift is None else self.conv.pitch_of(f0_shift, transpose)
+        own = {}                                             # a bad value is refused here, not in the worker
+        if transpose is not None or f0_shift is not None:
+            own["f0_shift"], own["transpose"] = self.conv.pitch_of(f0_shift, transpose)
+        if target_duration is not None:
+            own["target_duration"] = self.conv.duration_of(target_duration)
         if blend is not None:
-            self._q.put((src, fut, pitch, None if target_duration is None else self.conv.duration_of(target_duration),
-                         self.conv.blend_of(blend)))
-        elif target_duration is not None:
-            self._q.put((src, fut, pitch, self.conv.duration_of(target_duration)))
-        elif pitch != (None, None):
-            self._q.put((src, fut, pitch))
-        else:
-            self._q.put((src, fut))
+            own["blend"] = self.conv.blend_of(blend)
+        self._q.put((src, fut, SourceKnobs(**own)))
         return fut
 
     def _loop(self):
@@ -373,34 +331,27 @@ class RequestQueue:
     def _run(self, batch):
         """One batch; a request that cannot be loaded, or whose data makes the conversion fail (a NaN source, an f0 track of the
         wrong length, a target duration out of proportion to its length), fails ALONE: the others of its batch are converted
-        without it.  An entry is (source, Future), (source, Future, (f0_shift, transpose)) or (source, Future, (f0_shift,
-        transpose), target_duration) or (source, Future, (f0_shift, transpose), target_duration or None, blend weights); a batch
-        in which no request carries values of its own is converted as it always was, and ``target_duration`` / ``blend`` are
-        passed on only when a request of the batch has one."""
+        without it.  An entry is (source, Future, SourceKnobs: the request's own values, None where it has none); a knob is
+        passed on to ``convert`` only when a request of the batch carries it (``f0_shift`` and ``transpose`` together), so a batch
+        in which no request carries values of its own is converted as it always was."""
         good, loaded = [], []
-        for s, fut, *own in batch:
+        for s, fut, own in batch:
             try:
                 ld = self.conv.load_checked(s)
-                dur = own[1] if len(own) > 1 else None
-                if dur is not None:                          # needs the loaded source: refused here, before the batch is formed
-                    self.conv.plan_duration(ld[0], dur, item="request")
+                if own.target_duration is not None:          # needs the loaded source: refused here, before the batch is formed
+                    self.conv.plan_duration(ld[0], own.target_duration, item="request")
                 loaded.append(ld)
-                good.append((s, fut, own[0] if own else (None, None), dur, own[2] if len(own) > 2 else None))
+                good.append((s, fut, own))
             except BaseException as e:
                 fut.set_exception(e)
         if not good:
             return
-        plain = all(g[2] == (None, None) for g in good)
-        timed = any(g[3] is not None for g in good)
-        mixed = any(g[4] is not None for g in good)
-
-        def pitch(gs):
-            kw = {} if plain else dict(f0_shift=[g[2][0] for g in gs], transpose=[g[2][1] for g in gs])
-            kw = dict(kw, target_duration=[g[3] for g in gs]) if timed else kw
-            return dict(kw, blend=[g[4] for g in gs]) if mixed else kw
+        carried = [names for names in (("f0_shift", "transpose"), ("target_duration",), ("blend",))
+                   if any(getattr(own, k) is not None for _s, _f, own in good for k in names)]
+        kwargs = lambda gs: {k: [getattr(own, k) for _s, _f, own in gs] for names in carried for k in names}
         try:
-            ys = self.conv.convert([g[0] for g in good], loaded=loaded, **pitch(good))
-            for (_s, fut, _p, _d, _b), y in zip(good, ys):
+            ys = self.conv.convert([g[0] for g in good], loaded=loaded, **kwargs(good))
+            for (_s, fut, _own), y in zip(good, ys):
                 fut.set_result(y.detach().cpu())
             return
         except BaseException as e:
@@ -410,7 +361,7 @@ class RequestQueue:
         self.isolated += 1
         for g, ld in zip(good, loaded):                       # the batch failed as a whole: find the offender(s) one by one
             try:
-                g[1].set_result(self.conv.convert([g[0]], loaded=[ld], **pitch([g]))[0].detach().cpu())
+                g[1].set_result(self.conv.convert([g[0]], loaded=[ld], **kwargs([g]))[0].detach().cpu())
             except BaseException as e:
                 g[1].set_exception(e)
 

@@ -58,6 +58,7 @@ def test_request_queue_isolates_a_batch_that_fails_as_a_whole():
     import torch
     from concurrent.futures import Future
     from knn_svc_amd import serving
+    from knn_svc_amd.options import SourceKnobs
 
     class Conv:
         class vc:
@@ -77,7 +78,7 @@ def test_request_queue_isolates_a_batch_that_fails_as_a_whole():
 
     rq = serving.RequestQueue.__new__(serving.RequestQueue)
     rq.conv, rq.isolated = Conv(), 0
-    batch = [(s, Future()) for s in ("a", "unloadable", "poison", "bcd")]
+    batch = [(s, Future(), SourceKnobs()) for s in ("a", "unloadable", "poison", "bcd")]
     rq._run(batch)
     assert rq.isolated == 1 and Conv.calls == [["a", "poison", "bcd"], ["a"], ["poison"], ["bcd"]]
     assert float(batch[0][1].result()) == 1.0 and float(batch[3][1].result()) == 3.0
