@@ -8,11 +8,8 @@ one answer, so the blended features are BIT-IDENTICAL to the oracle; the blended
 ops.shift_f0_seg (pinned to tests/pitch_oracle.py by its own tests) called with the oracle's blended fp32 median; everything else
 (a segment alone against its slice of a stacked call, a batch against single conversions, the product against the same steps by
 hand, identities) is bit equality as well."""
-import json
 import os
 import sys
-import tempfile
-import traceback
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (ROOT, os.path.join(ROOT, "tests")):
@@ -23,48 +20,10 @@ import numpy as np
 import torch
 
 import blend_oracle as O
-from knn_svc_amd import audio_io, config as C, matching as M, ops, synthetic as S
+from knn_svc_amd import audio_io, config as C, matching as M, ops
+from tests.gpu_child import DEV, dev, guarded, misaligned, note, run_cases, same, tiny_vc, write_clip, x_equal
 
-DEV = "cuda"
-REPORT = {}
-SENTINEL = -7.25e11
 NAN = float("nan")
-
-
-def note(name, ok, detail=""):
-    REPORT[name] = {"ok": bool(ok), "detail": str(detail)}
-    print(("ok   " if ok else "FAIL ") + name + (f"  [{detail}]" if detail else ""), flush=True)
-
-
-def bits(t):
-    t = t.detach().cpu().contiguous()
-    return t.view(torch.int32) if t.dtype == torch.float32 else t
-
-
-def same(a, b):
-    return a.shape == b.shape and torch.equal(bits(a), bits(b))
-
-
-def dev(x):
-    return torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(DEV)
-
-
-def x_equal(got, want):
-    """(bit-identical?, number of differing elements)"""
-    got = got.cpu().numpy()
-    if got.shape != want.shape:
-        return False, -1
-    bad = int((got.view(np.uint32) != want.view(np.uint32)).sum())
-    return bad == 0, bad
-
-
-def off_by_one_float(xh):
-    """The rows on the device, contiguous, one float off a 16-byte boundary."""
-    flat = torch.empty(xh.size + 1, device=DEV, dtype=torch.float32)
-    x = flat[1:].reshape(xh.shape)
-    x.copy_(dev(xh))
-    assert x.data_ptr() % 16 == 4 and x.is_contiguous()
-    return x
 
 
 # ------------------------------------------------------------------ 1. the kernels
@@ -81,7 +40,7 @@ def case_kernel():
             okx, nbad = x_equal(ops.blend_seg([dev(x) for x in xh], [0, T], [vectors[V]]), want)
             note(f"kernel/dims/{dim}/v{V}", okx, f"{nbad} elements differ")
             xs = [dev(x) for x in xh]
-            xs[V - 1] = off_by_one_float(xh[V - 1])
+            xs[V - 1] = misaligned(xh[V - 1])
             okx, nbad = x_equal(ops.blend_seg(xs, [0, T], [vectors[V]]), want)
             note(f"kernel/dims/{dim}/v{V}-offset-pointer", okx, f"{nbad} elements differ")
 
@@ -124,11 +83,11 @@ def case_kernel():
         seg = O.table(lens); N = seg[-1]
         xh = [O.feats(N, dim, 50 + v) for v in range(4)]
         rows = [vectors[4], (0.0, 0.0, 0.0, 1.0), O.normalise([1, 0, 1, 0]), vectors[4][::-1], O.normalise([0, 1, 1, 1])]
-        buf = torch.full((N + 128, dim), SENTINEL, device=DEV)
-        got = ops.blend_seg([dev(x) for x in xh], seg, rows, out=buf[64:64 + N])
-        guards = bool((buf[:64] == SENTINEL).all()) and bool((buf[64 + N:] == SENTINEL).all())
+        out, untouched = guarded(N, dim)
+        got = ops.blend_seg([dev(x) for x in xh], seg, rows, out=out)
+        guards = untouched()
         okx, nbad = x_equal(got, O.blend_seg(xh, seg, rows))
-        note(f"kernel/canary/{dim}", guards and okx and got.data_ptr() == buf[64:].data_ptr(), f"guards untouched {guards}; {nbad} differ")
+        note(f"kernel/canary/{dim}", guards and okx and got.data_ptr() == out.data_ptr(), f"guards untouched {guards}; {nbad} differ")
 
     # (e) refusals through ops (the library's own are in tests/test_blend_cpu.py)
     x = dev(O.feats(10, 8, 9))
@@ -232,15 +191,6 @@ def case_shift():
 
 
 # ------------------------------------------------------------------ 2. product
-def tiny_vc(kind="mix"):
-    from knn_svc_amd.matcher import KNeighborsVC
-    from knn_svc_amd.vocoder import Vocoder
-    from knn_svc_amd.wavlm import WavLMEncoder
-    cfg, h = C.WAVLM_TINY, C.HIFIGAN_TINY
-    enc = WavLMEncoder(S.seeded_state(S.wavlm_param_spec(cfg), seed=11), cfg, DEV, n_layers=2)
-    return KNeighborsVC(enc, Vocoder(S.seeded_state(S.generator_param_spec(h, kind), 63 if kind == "mix" else 64), h, kind, DEV), h, DEV)
-
-
 def case_product(tmp):
     from knn_svc_amd import serving
     from knn_svc_amd.matcher import Tail
@@ -249,15 +199,13 @@ def case_product(tmp):
     for name, hz, seed in (("A", 233.0, 900), ("B", 147.0, 910), ("C", 330.0, 920)):
         pools[name] = os.path.join(tmp, name); os.makedirs(pools[name])
         for i in range(2):
-            w, _f = S.synth_clip(3 * 16000 + 37 * i, seed=seed + i)
-            audio_io.write_wav_pcm16(os.path.join(pools[name], f"t{i}.wav"), w, 16000)
-            np.save(os.path.join(pools[name], f"t{i}_f0.npy"), O.track(len(w) // 320 + 1, hz, seed + 40 + i))
+            n = 3 * 16000 + 37 * i
+            write_clip(os.path.join(pools[name], f"t{i}.wav"), n, seed + i, f0=O.track(n // 320 + 1, hz, seed + 40 + i))
     reqs, files = [], []
     for i, n in enumerate([16000 * 2 + 11, 9000, 16000 + 641, 16000 + 2000]):
-        w, _f = S.synth_clip(n, seed=700 + i)
         f = O.track(n // 320 + 1, 110.0, 50 + i)
         p = os.path.join(tmp, f"s{i}.wav")
-        audio_io.write_wav_pcm16(p, w, 16000); np.save(p[:-4] + "_f0.npy", f)
+        write_clip(p, n, 700 + i, f0=f)
         files.append(p); reqs.append((M.load_utterance(p)[0], f))
     vc = tiny_vc()
     A, B, Cv = (serving.TargetVoice(vc, pools[k]) for k in "ABC")
@@ -355,24 +303,5 @@ def case_product(tmp):
          f"{out}; {m2o}; special_match equals the converter {same(ys, y37)}")
 
 
-def main(out_path):
-    torch.cuda.set_device(0)
-    rc = 0
-    with torch.inference_mode(), tempfile.TemporaryDirectory() as tmp:
-        for name, fn in (("kernel", case_kernel), ("shift", case_shift), ("product", lambda: case_product(tmp))):
-            try:
-                fn()
-                torch.cuda.synchronize()
-            except Exception:          # nothing more is started on the GPU after an error: report what ran and stop
-                note(f"{name}/ran", False, traceback.format_exc()[-1500:])
-                print(traceback.format_exc(), file=sys.stderr)
-                rc = 1
-                break
-            note(f"{name}/ran", True)
-    with open(out_path, "w") as f:
-        json.dump(REPORT, f, indent=1)
-    return rc
-
-
 if __name__ == "__main__":
-    sys.exit(main(sys.argv[1]))
+    sys.exit(run_cases([("kernel", case_kernel), ("shift", case_shift), ("product", case_product)], sys.argv[1]))

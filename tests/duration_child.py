@@ -12,11 +12,8 @@ The reference is tests/duration_oracle.py.  What is asked, none of it taken from
              how many frames differ at all
 Everything else (a segment alone against its slice of a stacked call, a batch against single conversions, the product chain
 against the same steps by hand) is bit equality."""
-import json
 import os
 import sys
-import tempfile
-import traceback
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (ROOT, os.path.join(ROOT, "tests")):
@@ -27,46 +24,10 @@ import numpy as np
 import torch
 
 import duration_oracle as O
-from knn_svc_amd import audio_io, config as C, matching as M, ops, synthetic as S
+from knn_svc_amd import audio_io, config as C, matching as M, ops
+from tests.gpu_child import dev, guarded, misaligned, note, run_cases, same, table, tiny_vc, write_clip, x_equal
 
-DEV = "cuda"
-REPORT = {}
 F0_FRAMES = [0, 0]            # voiced frames compared / frames that differ from the oracle at all
-SENTINEL = -7.25e11
-
-
-def note(name, ok, detail=""):
-    REPORT[name] = {"ok": bool(ok), "detail": str(detail)}
-    print(("ok   " if ok else "FAIL ") + name + (f"  [{detail}]" if detail else ""), flush=True)
-
-
-def bits(t):
-    t = t.detach().cpu().contiguous()
-    return t.view(torch.int32) if t.dtype == torch.float32 else t
-
-
-def same(a, b):
-    return a.shape == b.shape and torch.equal(bits(a), bits(b))
-
-
-def dev(x):
-    return torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(DEV)
-
-
-def table(lens):
-    seg = [0]
-    for n in lens:
-        seg.append(seg[-1] + int(n))
-    return seg
-
-
-def x_equal(got, want):
-    """(bit-identical?, number of differing elements)"""
-    got = got.cpu().numpy()
-    if got.shape != want.shape:
-        return False, -1
-    bad = int((got.view(np.uint32) != want.view(np.uint32)).sum())
-    return bad == 0, bad
 
 
 def f0_equal(got, want):
@@ -122,9 +83,7 @@ def case_kernel():
         gx, _ = ops.time_scale(dev(xh), None, To, c)
         okx, nbad = x_equal(gx, want)
         note(f"kernel/dims/{dim}", okx, f"{nbad} elements differ")
-        flat = torch.empty(T * dim + 1, device=DEV, dtype=torch.float32)
-        xo = flat[1:].reshape(T, dim)
-        xo.copy_(dev(xh))
+        xo = misaligned(xh)
         gx, _ = ops.time_scale(xo, None, To, c)
         okx, nbad = x_equal(gx, want)
         note(f"kernel/dims/{dim}-offset-pointer", okx and xo.data_ptr() % 16 == 4 and xo.is_contiguous(), f"{nbad} elements differ")
@@ -173,13 +132,13 @@ def case_kernel():
         outs, cs = plans(lens, [2.0, 4.0, 0.25, 1.37, 0.73])
         seg = table(lens); N = sum(outs)
         xh, fh = O.feats(seg[-1], dim, 7), O.track(seg[-1], 200.0, 8, run=6)
-        xb = torch.full((N + 128, dim), SENTINEL, device=DEV); fb = torch.full((N + 128,), SENTINEL, device=DEV)
-        gx, gf = ops.time_scale_seg(dev(xh), dev(fh), seg, outs, cs, out=(xb[64:64 + N], fb[64:64 + N]))
+        (xo, x_untouched), (fo, f_untouched) = guarded(N, dim), guarded(N)
+        gx, gf = ops.time_scale_seg(dev(xh), dev(fh), seg, outs, cs, out=(xo, fo))
         wx, wf = O.time_scale_seg(xh, fh, seg, outs, cs)
-        guards = all(bool((t == SENTINEL).all()) for t in (xb[:64], xb[64 + N:], fb[:64], fb[64 + N:]))
+        guards = x_untouched() and f_untouched()
         okx, nbad = x_equal(gx, wx)
         okf, df = f0_equal(gf, wf)
-        note(f"kernel/canary/{dim}", guards and okx and okf and gx.data_ptr() == xb[64:].data_ptr(), f"guards untouched {guards}; {nbad} differ; {df}")
+        note(f"kernel/canary/{dim}", guards and okx and okf and gx.data_ptr() == xo.data_ptr(), f"guards untouched {guards}; {nbad} differ; {df}")
 
     # (f) refusals through ops
     refused = 0
@@ -218,15 +177,6 @@ def case_kernel():
 
 
 # ------------------------------------------------------------------ 2. product
-def tiny_vc(kind="mix"):
-    from knn_svc_amd.matcher import KNeighborsVC
-    from knn_svc_amd.vocoder import Vocoder
-    from knn_svc_amd.wavlm import WavLMEncoder
-    cfg, h = C.WAVLM_TINY, C.HIFIGAN_TINY
-    enc = WavLMEncoder(S.seeded_state(S.wavlm_param_spec(cfg), seed=11), cfg, DEV, n_layers=2)
-    return KNeighborsVC(enc, Vocoder(S.seeded_state(S.generator_param_spec(h, kind), 63 if kind == "mix" else 64), h, kind, DEV), h, DEV)
-
-
 def seconds_for(T, s):
     """A target_duration that upstream's arithmetic turns into round(T * s) frames for a source of T frames (half a sample
     above the frame boundary, so that int() cannot fall one sample short of it)."""
@@ -239,15 +189,13 @@ def case_product(tmp):
     from knn_svc_amd.options import Extensions
     pool = os.path.join(tmp, "tgt"); os.makedirs(pool)
     for i in range(2):
-        w, _f = S.synth_clip(3 * 16000 + 37 * i, seed=900 + i)
-        audio_io.write_wav_pcm16(os.path.join(pool, f"t{i}.wav"), w, 16000)
-        np.save(os.path.join(pool, f"t{i}_f0.npy"), O.track(len(w) // 320 + 1, 233.0, 40 + i))
+        n = 3 * 16000 + 37 * i
+        write_clip(os.path.join(pool, f"t{i}.wav"), n, 900 + i, f0=O.track(n // 320 + 1, 233.0, 40 + i))
     reqs, files = [], []
     for i, n in enumerate([16000 * 2 + 11, 9000, 16000 + 641, 16000 + 2000]):
-        w, _f = S.synth_clip(n, seed=700 + i)
         f = O.track(n // 320 + 1, 110.0, 50 + i)
         p = os.path.join(tmp, f"s{i}.wav")
-        audio_io.write_wav_pcm16(p, w, 16000); np.save(p[:-4] + "_f0.npy", f)
+        write_clip(p, n, 700 + i, f0=f)
         files.append(p); reqs.append((M.load_utterance(p)[0], f))
     vc = tiny_vc()
     src, ref = files[0], os.path.join(pool, "t0.wav")
@@ -357,24 +305,5 @@ def case_product(tmp):
     note("product/refusals", n == 16, f"{n} of 16 refused with ValueError")
 
 
-def main(out_path):
-    torch.cuda.set_device(0)
-    rc = 0
-    with torch.inference_mode(), tempfile.TemporaryDirectory() as tmp:
-        for name, fn in (("kernel", case_kernel), ("product", lambda: case_product(tmp))):
-            try:
-                fn()
-                torch.cuda.synchronize()
-            except Exception:          # nothing more is started on the GPU after an error: report what ran and stop
-                note(f"{name}/ran", False, traceback.format_exc()[-1500:])
-                print(traceback.format_exc(), file=sys.stderr)
-                rc = 1
-                break
-            note(f"{name}/ran", True)
-    with open(out_path, "w") as f:
-        json.dump(REPORT, f, indent=1)
-    return rc
-
-
 if __name__ == "__main__":
-    sys.exit(main(sys.argv[1]))
+    sys.exit(run_cases([("kernel", case_kernel), ("product", case_product)], sys.argv[1]))

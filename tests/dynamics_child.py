@@ -12,12 +12,9 @@ The reference is tests/dynamics_oracle.py (fp64 numpy).  Tolerances, none of the
   ceiling property     max |out| <= c (1 + 2^-23), on the device output itself
 Everything else is bit equality.  The largest observed errors go into the report ("envelope/max-error", "ceiling/max-error")."""
 import ctypes
-import json
 import math
 import os
 import sys
-import tempfile
-import traceback
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (ROOT, os.path.join(ROOT, "tests")):
@@ -28,26 +25,12 @@ import numpy as np
 import torch
 
 import dynamics_oracle as O
-from knn_svc_amd import _lib, audio_io, config as C, ops, synthetic as S
+from knn_svc_amd import _lib, audio_io, ops
+from tests.gpu_child import DEV, dev, misaligned, note, run_cases, same, tiny_vc, write_clip
 
-DEV = "cuda"
-REPORT = {}
 HOP = 320
 TOL_G, TOL_MIN = 1e-9, 1e-13
 WORST = {"G": 0.0, "env_ulp": 0, "lim_ulp": 0, "min_gain": 0.0}
-
-
-def same(a, b):
-    if a.shape != b.shape or a.dtype != b.dtype:
-        return False
-    if a.dtype == torch.float32:
-        return torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
-    return torch.equal(a, b)
-
-
-def note(name, ok, detail=""):
-    REPORT[name] = {"ok": bool(ok), "detail": str(detail)}
-    print(("ok   " if ok else "FAIL ") + name + (f"  [{detail}]" if detail else ""), flush=True)
 
 
 def ulps(a, b):
@@ -63,25 +46,11 @@ def ulps(a, b):
     return int(np.abs(key(a) - key(b)).max())
 
 
-def gpu(v):
-    return torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32)).to(DEV)
-
-
-def off_by_4(v):
-    """The array on the device, starting 4 bytes past a 16-byte boundary."""
-    big = torch.zeros(v.size + 8, device=DEV)
-    off = next(o for o in range(1, 5) if (big.data_ptr() + 4 * o) % 16 == 4)
-    big[off:off + v.size] = gpu(v)
-    view = big[off:off + v.size]
-    assert view.data_ptr() % 16 == 4
-    return view
-
-
 # ------------------------------------------------------------------ 1. envelope mix against the oracle
 def env_check(name, y, x, a, hop=HOP, got=None):
     want, wG = O.envelope_mix(y, x, a, hop)
     if got is None:
-        got = ops.envelope_mix(gpu(y), gpu(x), a, hop=hop, return_gains=True)
+        got = ops.envelope_mix(dev(y), dev(x), a, hop=hop, return_gains=True)
     out, G = got[0].cpu().numpy(), got[1].cpu().numpy()
     eG = float(np.abs(G / wG - 1).max()) if G.shape == wG.shape else float("inf")
     eu = ulps(out, want)
@@ -104,9 +73,9 @@ def case_envelope():
         env_check(f"phrased-a{a}", y, x[:N], a)
     for tag, yy, xx in (("silent-source", y, np.zeros(N, np.float32)), ("silent-output", np.zeros(N, np.float32), x[:N])):
         out, G = env_check(tag, yy, xx, 0.7)
-        note(f"envelope/{tag}-is-y-bit-for-bit", same(out, gpu(yy)) and bool((G == 1).all()), "")
-    out, G = ops.envelope_mix(gpu(y), torch.zeros(0, device=DEV), 0.7, return_gains=True)
-    note("envelope/empty-source-is-y-bit-for-bit", same(out, gpu(y)) and bool((G == 1).all()), "")
+        note(f"envelope/{tag}-is-y-bit-for-bit", same(out, dev(yy)) and bool((G == 1).all()), "")
+    out, G = ops.envelope_mix(dev(y), torch.zeros(0, device=DEV), 0.7, return_gains=True)
+    note("envelope/empty-source-is-y-bit-for-bit", same(out, dev(y)) and bool((G == 1).all()), "")
     # level invariance: the same source 40 dB lower, the scaling exact in fp32 (multiples of 2^-20 below 2^-3, times 100)
     m = np.round(x[:N].astype(np.float64) * 0.1 * 2 ** 20)
     lo, hi = (m / 2 ** 20).astype(np.float32), (100 * m / 2 ** 20).astype(np.float32)
@@ -118,12 +87,12 @@ def case_envelope():
          f"source rms {float(np.sqrt((lo.astype(np.float64) ** 2).mean())):.4f} against {float(np.sqrt((hi.astype(np.float64) ** 2).mean())):.4f}: "
          f"G rel diff {eG:.2e}, waveform {eu} ulp")
     # in place, gains = NULL, misaligned pointers: the same bits as the plain call
-    ref_out, ref_G = ops.envelope_mix(gpu(y), gpu(x[:N]), 0.5, return_gains=True)
-    buf = gpu(y)
-    r = ops.envelope_mix(buf, gpu(x[:N]), 0.5, out=buf, return_gains=True)
+    ref_out, ref_G = ops.envelope_mix(dev(y), dev(x[:N]), 0.5, return_gains=True)
+    buf = dev(y)
+    r = ops.envelope_mix(buf, dev(x[:N]), 0.5, out=buf, return_gains=True)
     note("envelope/in-place", r[0] is buf and same(buf, ref_out) and same(r[1], ref_G), "")
-    note("envelope/gains-null", same(ops.envelope_mix(gpu(y), gpu(x[:N]), 0.5), ref_out), "")
-    ym, xm, om = off_by_4(y), off_by_4(x[:N]), off_by_4(np.zeros(N, np.float32))
+    note("envelope/gains-null", same(ops.envelope_mix(dev(y), dev(x[:N]), 0.5), ref_out), "")
+    ym, xm, om = misaligned(y), misaligned(x[:N]), misaligned(np.zeros(N, np.float32))
     r = ops.envelope_mix(ym, xm, 0.5, out=om, return_gains=True)
     note("envelope/pointers-4-bytes-off-alignment", same(om, ref_out) and same(r[1], ref_G), f"y % 16 = {ym.data_ptr() % 16}, out % 16 = {om.data_ptr() % 16}")
     # a workspace of exactly the reported size between sentinel bytes
@@ -131,7 +100,7 @@ def case_envelope():
     lead, trail, mark = 64, 4096, 0xA5
     ws = torch.full((lead + need + trail,), mark, device=DEV, dtype=torch.uint8)
     assert (ws.data_ptr() + lead) % 8 == 0
-    yg, xg, og, Gg = gpu(y), gpu(x[:N]), torch.zeros(N, device=DEV), torch.zeros(T, device=DEV, dtype=torch.float64)
+    yg, xg, og, Gg = dev(y), dev(x[:N]), torch.zeros(N, device=DEV), torch.zeros(T, device=DEV, dtype=torch.float64)
     call = lambda n, hop, nbytes: lib.knnsvc_envelope_mix(ops._p(yg), n, ops._p(xg), N, hop, 0.5, ops._p(og), ops._p(Gg),
                                                           ctypes.c_void_p(ws.data_ptr() + lead), nbytes, ops._stream())
     rc = call(N, HOP, need)
@@ -158,7 +127,7 @@ def lim_check(name, y, p=P6, sr=16000, got=None):
     y = np.ascontiguousarray(y, dtype=np.float32)
     want, wcount, wmin = O.limit_peak(y, p, sr)
     if got is None:
-        got = ops.limit_peak(gpu(y), p, sr, return_stats=True)
+        got = ops.limit_peak(dev(y), p, sr, return_stats=True)
     out, count, smin = got[0].cpu().numpy(), int(got[1][0]), float(got[1][1])
     c = 10.0 ** (p / 20.0)
     eu, emin = ulps(out, want), abs(smin / wmin - 1)
@@ -201,20 +170,20 @@ def case_ceiling():
     for p in (0.0, -1.0, -6.0):
         lim_check(f"p{p:g}", loud, p=p)
     # identity: a signal under the ceiling comes back bit-identical, with empty statistics
-    out, (count, smin) = ops.limit_peak(gpu(quiet), P6, return_stats=True)
-    note("ceiling/identity", same(out, gpu(quiet)) and int(count) == 0 and float(smin) == 1.0, f"count {int(count)}, min gain {float(smin)!r}")
+    out, (count, smin) = ops.limit_peak(dev(quiet), P6, return_stats=True)
+    note("ceiling/identity", same(out, dev(quiet)) and int(count) == 0 and float(smin) == 1.0, f"count {int(count)}, min gain {float(smin)!r}")
     # in place, misaligned, stats = NULL: the same bits as the plain call
     y = peaks(5, tile - 1, tile + 2 * L, 2 * tile + 9, n - 3)
     y[tile + 900:tile + 1400] *= 2.5
     (ref, rstats), _ = lim_check("several", y)
-    buf = gpu(y)
+    buf = dev(y)
     r = ops.limit_peak(buf, P6, out=buf, return_stats=True)
     note("ceiling/in-place", r[0] is buf and same(buf, ref) and same(r[1][0], rstats[0]) and same(r[1][1], rstats[1]), "")
-    ym, om = off_by_4(y), off_by_4(np.zeros(n, np.float32))
+    ym, om = misaligned(y), misaligned(np.zeros(n, np.float32))
     r = ops.limit_peak(ym, P6, out=om, return_stats=True)
     note("ceiling/pointers-4-bytes-off-alignment", same(om, ref) and same(r[1][0], rstats[0]), f"y % 16 = {ym.data_ptr() % 16}")
-    note("ceiling/stats-null", same(ops.limit_peak(gpu(y), P6), ref), "")
-    yg, og = gpu(y), torch.full((n,), 7.0, device=DEV)
+    note("ceiling/stats-null", same(ops.limit_peak(dev(y), P6), ref), "")
+    yg, og = dev(y), torch.full((n,), 7.0, device=DEV)
     call = lambda sr, p: lib.knnsvc_peak_limit(ops._p(yg), n, sr, p, ops._p(og), None, ops._stream())
     rcs = [call(4000, -6.0), call(16000, 1.0), call(16000, float("nan")), call(16000, float("-inf"))]
     torch.cuda.synchronize()
@@ -227,7 +196,7 @@ def case_determinism():
     n = 480000
     t = np.arange(n) / 16000.0
     y = ((0.3 + 0.6 * np.sin(2 * np.pi * 0.21 * t) ** 2) * np.sin(2 * np.pi * (150.0 * t + 7.5 * t * t))).astype(np.float32) + O.noise(n, 51, 0.01)
-    yg, xg = gpu(y), gpu(O.phrased(n // HOP, 52))
+    yg, xg = dev(y), dev(O.phrased(n // HOP, 52))
 
     def both():
         e, G = ops.envelope_mix(yg, xg, 0.7, return_gains=True)
@@ -245,15 +214,6 @@ def case_determinism():
 
 
 # ------------------------------------------------------------------ 4. product
-def tiny_vc(kind="mix"):
-    from knn_svc_amd.matcher import KNeighborsVC
-    from knn_svc_amd.vocoder import Vocoder
-    from knn_svc_amd.wavlm import WavLMEncoder
-    cfg, h = C.WAVLM_TINY, C.HIFIGAN_TINY
-    enc = WavLMEncoder(S.seeded_state(S.wavlm_param_spec(cfg), seed=11), cfg, DEV, n_layers=2)
-    return KNeighborsVC(enc, Vocoder(S.seeded_state(S.generator_param_spec(h, kind), 63 if kind == "mix" else 64), h, kind, DEV), h, DEV)
-
-
 def phrase_gain(n, seed):
     """A phrased envelope for a clip: stretches of 0.2 .. 0.5 s, alternately at a level of their own (0.15 .. 1) and silent."""
     rng = np.random.default_rng(seed)
@@ -267,14 +227,6 @@ def phrase_gain(n, seed):
     return g
 
 
-def write_clip(path, n, seed, f0_mul=1.0, phrased=False):
-    w, f = S.synth_clip(n, seed=seed)
-    if phrased:
-        w = (w * phrase_gain(n, seed + 5000)).astype(np.float32)
-    audio_io.write_wav_pcm16(path, w, 16000)
-    np.save(path[:-4] + "_f0.npy", (f * f0_mul).astype(np.float32))
-
-
 def case_product(tmp):
     from knn_svc_amd import matching as M, serving
     pool = os.path.join(tmp, "tgt"); os.makedirs(pool)
@@ -285,8 +237,8 @@ def case_product(tmp):
     files = []
     for i, n in enumerate(lens):
         files.append(os.path.join(srcd, f"s{i}.wav"))
-        write_clip(files[-1], n, 700 + i, 1.2, phrased=True)
-    srcs = [gpu(M.load_utterance(f)[0]) for f in files]
+        write_clip(files[-1], n, 700 + i, f0_mul=1.2, gain=phrase_gain(n, 700 + i + 5000))
+    srcs = [dev(M.load_utterance(f)[0]) for f in files]
     vc = tiny_vc("mix")
     tv = serving.TargetVoice(vc, pool)
     mk = lambda **kw: serving.BatchConverter(vc, tv, "mix", "post_opt_0.2", **kw)
@@ -361,7 +313,8 @@ def case_product(tmp):
     for s, spk in enumerate(("spkA", "spkB")):
         os.makedirs(os.path.join(root, spk))
         for u in range(2):
-            write_clip(os.path.join(root, spk, f"u{u}.wav"), 3 * 16000 + 500 * u + 77 * s, 1000 * s + u + 40, 1.25 if s == 0 else 1.0, phrased=True)
+            n, seed = 3 * 16000 + 500 * u + 77 * s, 1000 * s + u + 40
+            write_clip(os.path.join(root, spk, f"u{u}.wav"), n, seed, f0_mul=1.25 if s == 0 else 1.0, gain=phrase_gain(n, seed + 5000))
     read = lambda p: audio_io.read_wav(p)[0][0].astype(np.float64)
     off_files = vc.bulk_match(root, root, os.path.join(tmp, "bulk_off"), ckpt_type="mix", post_opt="post_opt_0.2")
     off_peaks = [float(np.abs(read(p)).max()) for p in off_files]
@@ -380,25 +333,6 @@ def case_product(tmp):
     note("product/bulk_match/same-file-names", names(on_files, "bulk_on") == names(off_files, "bulk_off") == names(mix_files, "bulk_mix"), "")
 
 
-def main(out_path):
-    torch.cuda.set_device(0)
-    cases = [("envelope", case_envelope), ("ceiling", case_ceiling), ("determinism", case_determinism), ("product", None)]
-    rc = 0
-    with torch.inference_mode(), tempfile.TemporaryDirectory() as tmp:
-        for name, fn in cases:
-            try:
-                fn() if fn is not None else case_product(tmp)
-                torch.cuda.synchronize()
-            except Exception:          # nothing more is started on the GPU after an error: report what ran and stop
-                note(f"{name}/ran", False, traceback.format_exc()[-1500:])
-                print(traceback.format_exc(), file=sys.stderr)
-                rc = 1
-                break
-            note(f"{name}/ran", True)
-    with open(out_path, "w") as f:
-        json.dump(REPORT, f, indent=1)
-    return rc
-
-
 if __name__ == "__main__":
-    sys.exit(main(sys.argv[1]))
+    sys.exit(run_cases([("envelope", case_envelope), ("ceiling", case_ceiling), ("determinism", case_determinism), ("product", case_product)],
+                       sys.argv[1]))

@@ -12,12 +12,9 @@ The reference is tests/loudness_oracle.py (fp64 numpy).  Tolerances, none of the
   files                     within 1e-3 dB of the target by the oracle on the samples read back
 Everything else is bit equality."""
 import ctypes
-import json
 import math
 import os
 import sys
-import tempfile
-import traceback
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (ROOT, os.path.join(ROOT, "tests")):
@@ -28,25 +25,11 @@ import numpy as np
 import torch
 
 import loudness_oracle as O
-from knn_svc_amd import _lib, audio_io, config as C, ops, synthetic as S
+from knn_svc_amd import _lib, audio_io, ops
+from tests.gpu_child import DEV, misaligned, note, run_cases, same, tiny_vc, write_clip
 
-DEV = "cuda"
-REPORT = {}
 TOL_DB = 1e-4
 MARGIN_DB = 0.01
-
-
-def same(a, b):
-    if a.shape != b.shape or a.dtype != b.dtype:
-        return False
-    if a.dtype == torch.float32:
-        return torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
-    return torch.equal(a, b)
-
-
-def note(name, ok, detail=""):
-    REPORT[name] = {"ok": bool(ok), "detail": str(detail)}
-    print(("ok   " if ok else "FAIL ") + name + (f"  [{detail}]" if detail else ""), flush=True)
 
 
 def close_db(got, want, tol):
@@ -123,10 +106,7 @@ def case_oracle():
     xg = torch.from_numpy(x).to(DEV)
     note("oracle/counts-null", close_db(float(ops.loudness(xg)), want, TOL_DB), "")
     # a waveform that starts 4 bytes off a 16-byte boundary
-    big = torch.zeros(x.size + 8, device=DEV)
-    off = next(o for o in range(1, 5) if (big.data_ptr() + 4 * o) % 16 == 4)
-    big[off:off + x.size] = xg
-    view = big[off:off + x.size]
+    view = misaligned(x)
     got, gcounts = measure(view)
     note("oracle/wav-4-bytes-off-alignment", view.data_ptr() % 16 == 4 and close_db(got, want, TOL_DB) and gcounts == wcounts,
          f"pointer % 16 = {view.data_ptr() % 16}, lkfs {got!r} / {want!r}, counts {gcounts}")
@@ -185,21 +165,6 @@ def case_gain():
 
 
 # ------------------------------------------------------------------ 4. product
-def tiny_vc(kind="mix"):
-    from knn_svc_amd.matcher import KNeighborsVC
-    from knn_svc_amd.vocoder import Vocoder
-    from knn_svc_amd.wavlm import WavLMEncoder
-    cfg, h = C.WAVLM_TINY, C.HIFIGAN_TINY
-    enc = WavLMEncoder(S.seeded_state(S.wavlm_param_spec(cfg), seed=11), cfg, DEV, n_layers=2)
-    return KNeighborsVC(enc, Vocoder(S.seeded_state(S.generator_param_spec(h, kind), 63 if kind == "mix" else 64), h, kind, DEV), h, DEV)
-
-
-def write_clip(path, n, seed, f0_mul=1.0):
-    w, f = S.synth_clip(n, seed=seed)
-    audio_io.write_wav_pcm16(path, w, 16000)
-    np.save(path[:-4] + "_f0.npy", (f * f0_mul).astype(np.float32))
-
-
 def case_product(tmp):
     from knn_svc_amd import serving
     pool = os.path.join(tmp, "tgt"); os.makedirs(pool)
@@ -210,7 +175,7 @@ def case_product(tmp):
     files = []
     for i, n in enumerate(lens):
         files.append(os.path.join(srcd, f"s{i}.wav"))
-        write_clip(files[-1], n, 700 + i, 1.2)
+        write_clip(files[-1], n, 700 + i, f0_mul=1.2)
     vc = tiny_vc("mix")
     tv = serving.TargetVoice(vc, pool)
     mk = lambda **kw: serving.BatchConverter(vc, tv, "mix", "post_opt_0.2", **kw)
@@ -246,7 +211,7 @@ def case_product(tmp):
     for s, spk in enumerate(("spkA", "spkB")):
         os.makedirs(os.path.join(root, spk))
         for u in range(2):
-            write_clip(os.path.join(root, spk, f"u{u}.wav"), 3 * 16000 + 500 * u + 77 * s, 1000 * s + u + 40, 1.25 if s == 0 else 1.0)
+            write_clip(os.path.join(root, spk, f"u{u}.wav"), 3 * 16000 + 500 * u + 77 * s, 1000 * s + u + 40, f0_mul=1.25 if s == 0 else 1.0)
     read = lambda p: audio_io.read_wav(p)[0][0].astype(np.float64)
     off_files = vc.bulk_match(root, root, os.path.join(tmp, "bulk_off"), ckpt_type="mix", post_opt="post_opt_0.2")
     # precondition, by the oracle on the off run: -16 stays below full scale for every file (the peak rule of to_pcm32 must not fire)
@@ -266,25 +231,5 @@ def case_product(tmp):
     note("product/bulk_match/same-file-names", names(on_files, "bulk_on") == names(off_files, "bulk_off"), "")
 
 
-def main(out_path):
-    torch.cuda.set_device(0)
-    cases = [("oracle", case_oracle), ("determinism", case_determinism), ("gain", case_gain), ("product", None)]
-    rc = 0
-    with torch.inference_mode(), tempfile.TemporaryDirectory() as tmp:
-        for name, fn in cases:
-            try:
-                fn() if fn is not None else case_product(tmp)
-                torch.cuda.synchronize()
-            except Exception:          # nothing more is started on the GPU after an error: report what ran and stop
-                note(f"{name}/ran", False, traceback.format_exc()[-1500:])
-                print(traceback.format_exc(), file=sys.stderr)
-                rc = 1
-                break
-            note(f"{name}/ran", True)
-    with open(out_path, "w") as f:
-        json.dump(REPORT, f, indent=1)
-    return rc
-
-
 if __name__ == "__main__":
-    sys.exit(main(sys.argv[1]))
+    sys.exit(run_cases([("oracle", case_oracle), ("determinism", case_determinism), ("gain", case_gain), ("product", case_product)], sys.argv[1]))

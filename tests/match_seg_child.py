@@ -4,46 +4,17 @@
     python tests/match_seg_child.py REPORT.json
 
 Every comparison is exact: torch.equal on int64, the int32 view for floats (NaN medians compare too)."""
-import json
 import os
 import sys
-import tempfile
-import traceback
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-import numpy as np
 import torch
 
-from knn_svc_amd import audio_io, config as C, matching as M, ops, synthetic as S
-
-DEV = "cuda"
-REPORT = {}
-
-
-def same(a, b):
-    """Bit equality of two tensors (or of two None)."""
-    if a is None or b is None:
-        return a is None and b is None
-    if a.shape != b.shape or a.dtype != b.dtype:
-        return False
-    if a.dtype == torch.float32:
-        return torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
-    return torch.equal(a, b)
-
-
-def note(name, ok, detail=""):
-    REPORT[name] = {"ok": bool(ok), "detail": str(detail)}
-    print(("ok   " if ok else "FAIL ") + name + (f"  [{detail}]" if detail else ""), flush=True)
-
-
-def offsets(lens):
-    seg = [0]
-    for n in lens:
-        seg.append(seg[-1] + n)
-    return seg
+from knn_svc_amd import matching as M, ops, synthetic as S
+from tests.gpu_child import DEV, note, run_cases, same, table, tiny_vc, write_clip
 
 
 def f0_track(n, gen, zero_every=5):
@@ -69,7 +40,7 @@ def walk_inputs(lens, npool, dim):
 
 def case_walk():
     lens = [1, 2, 3, 5, 64, 257, 1]
-    seg = offsets(lens)
+    seg = table(lens)
     for npool in (40, 300):
         for dim in (64, 1000, 1024, 1280):
             q, p, idx4, sf0, pf0 = walk_inputs(lens, npool, dim)
@@ -87,7 +58,7 @@ def case_walk():
                 # swap segments 3 (5 rows) and 4 (64 rows): a segment's output moves with it and with nothing else
                 order = [0, 1, 2, 4, 3, 5, 6]
                 rows = torch.cat([torch.arange(seg[s], seg[s + 1]) for s in order]).to(DEV)
-                seg2 = offsets([lens[s] for s in order])
+                seg2 = table([lens[s] for s in order])
                 got2 = ops.concat_reselect_seg(idx4[rows].contiguous(), seg2, q[rows].contiguous(), qn[rows].contiguous(), p, pn,
                                                sf0[rows].contiguous() if use_f0 else None, pf0 if use_f0 else None, concat_weight=0.2)
                 bad2 = [s for k, s in enumerate(order) if not same(got2[seg2[k]:seg2[k + 1]], alone[s])]
@@ -97,7 +68,7 @@ def case_walk():
 # ------------------------------------------------------------------ 2. medians and shift
 def case_median():
     lens = [1, 7, 1024, 1025, 3000]
-    seg = offsets(lens)
+    seg = table(lens)
     gen = torch.Generator().manual_seed(5)
     f0 = f0_track(sum(lens), gen)
     f0[seg[0]:seg[1]] = 150.0                         # one row, voiced
@@ -137,7 +108,7 @@ def case_smooth():
     gen = torch.Generator().manual_seed(13)
     pools = {"dim64-scale0.1": (smooth_pool(64, 1.0, 3), 0.1), "dim49-ld64-scale1000": (smooth_pool(49, 0.02, 4, ld=64), 1000.0)}
     for lens in ([1, 2, 37, 512, 513, 1024, 1025, 1536, 1537], [4700, 3]):
-        seg = offsets(lens)
+        seg = table(lens)
         n = sum(lens)
         idx = torch.randint(0, 400, (n, 4), generator=gen)
         idx[::50] = torch.tensor([0, 399, 1, 398])                                # clamped +-1 neighbours
@@ -200,7 +171,7 @@ def case_single_workspace():
 # ------------------------------------------------------------------ 4. wrapper chunking
 def case_chunking():
     lens = [1 + i % 3 for i in range(70)]
-    seg = offsets(lens)
+    seg = table(lens)
     q, p, idx4, sf0, pf0 = walk_inputs(lens, 300, 64)
     qn, _ = ops.row_norms(q); pn, _ = ops.row_norms(p)
     got = ops.concat_reselect_seg(idx4, seg, q, qn, p, pn, sf0, pf0, concat_weight=0.2)
@@ -261,30 +232,17 @@ def case_match_many():
 
 
 # ------------------------------------------------------------------ 6. product
-def tiny_vc(kind):
-    from knn_svc_amd.matcher import KNeighborsVC
-    from knn_svc_amd.vocoder import Vocoder
-    from knn_svc_amd.wavlm import WavLMEncoder
-    cfg, h = C.WAVLM_TINY, C.HIFIGAN_TINY
-    enc = WavLMEncoder(S.seeded_state(S.wavlm_param_spec(cfg), seed=11), cfg, DEV, n_layers=2)
-    return KNeighborsVC(enc, Vocoder(S.seeded_state(S.generator_param_spec(h, kind), 63 if kind == "mix" else 64), h, kind, DEV), h, DEV)
-
-
 def case_product(tmp):
     from knn_svc_amd import serving
     pool = os.path.join(tmp, "tgt"); os.makedirs(pool)
     for i in range(4):
-        w, f = S.synth_clip(3 * 16000 + 37 * i, seed=900 + i)
-        audio_io.write_wav_pcm16(os.path.join(pool, f"t{i}.wav"), w, 16000)
-        np.save(os.path.join(pool, f"t{i}_f0.npy"), f)
+        write_clip(os.path.join(pool, f"t{i}.wav"), 3 * 16000 + 37 * i, 900 + i)
     srcd = os.path.join(tmp, "src"); os.makedirs(srcd)
     lens = [16000 * 2 + 11, 16000 * 3, 9000, 16000 * 2 + 11, 16000 + 641, 40000]
     files = []
     for i, n in enumerate(lens):
-        w, f = S.synth_clip(n, seed=700 + i)
-        p = os.path.join(srcd, f"s{i}.wav")
-        audio_io.write_wav_pcm16(p, w, 16000); np.save(os.path.join(srcd, f"s{i}_f0.npy"), f * 1.2)
-        files.append(p)
+        files.append(os.path.join(srcd, f"s{i}.wav"))
+        write_clip(files[-1], n, 700 + i, f0_mul=1.2)
     for ckpt_type, kind in (("mix", "mix"), ("wavlm_only", "f0")):
         vc = tiny_vc(kind)
         tv = serving.TargetVoice(vc, pool)
@@ -305,27 +263,7 @@ def case_product(tmp):
         note(f"product/{ckpt_type}/many_to_one-files", not bad and len(a) == len(b) == len(files), f"files that differ: {bad}")
 
 
-def main(out_path):
-    torch.cuda.set_device(0)
-    cases = [("walk", case_walk), ("median", case_median), ("smooth", case_smooth), ("single_ws", case_single_workspace),
-             ("chunking", case_chunking),
-             ("match_many", case_match_many), ("product", None)]
-    rc = 0
-    with torch.inference_mode(), tempfile.TemporaryDirectory() as tmp:
-        for name, fn in cases:
-            try:
-                fn() if fn is not None else case_product(tmp)
-                torch.cuda.synchronize()
-            except Exception:          # nothing more is started on the GPU after an error: report what ran and stop
-                note(f"{name}/ran", False, traceback.format_exc()[-1500:])
-                print(traceback.format_exc(), file=sys.stderr)
-                rc = 1
-                break
-            note(f"{name}/ran", True)
-    with open(out_path, "w") as f:
-        json.dump(REPORT, f, indent=1)
-    return rc
-
-
 if __name__ == "__main__":
-    sys.exit(main(sys.argv[1]))
+    cases = [("walk", case_walk), ("median", case_median), ("smooth", case_smooth), ("single_ws", case_single_workspace), ("chunking", case_chunking),
+             ("match_many", case_match_many), ("product", case_product)]
+    sys.exit(run_cases(cases, sys.argv[1]))

@@ -10,11 +10,8 @@ interval and the shift).  Tolerances, none taken from what the kernel gives:
                    near 6 is 4.8e-7 of the result)
   shift_semitones  within 1e-5 of the oracle's; minus the transpose (in fp32) a multiple of 12 (octave) / an integer (semitone)
 Everything else is bit equality (NaN patterns included: compared as integers)."""
-import json
 import os
 import sys
-import tempfile
-import traceback
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (ROOT, os.path.join(ROOT, "tests")):
@@ -25,38 +22,12 @@ import numpy as np
 import torch
 
 import pitch_oracle as O
-from knn_svc_amd import audio_io, config as C, matching as M, ops, synthetic as S
+from knn_svc_amd import matching as M, ops
+from tests.gpu_child import DEV, dev, note, run_cases, same, table, tiny_vc, write_clip
 
-DEV = "cuda"
-REPORT = {}
 REL_TOL, SEMI_TOL = 5e-6, 1e-5
 TRANSPOSES = (0.0, 3.0, -12.0, 0.5)
 WORST = []
-
-
-def note(name, ok, detail=""):
-    REPORT[name] = {"ok": bool(ok), "detail": str(detail)}
-    print(("ok   " if ok else "FAIL ") + name + (f"  [{detail}]" if detail else ""), flush=True)
-
-
-def bits(t):
-    t = t.detach().cpu().contiguous()
-    return t.view(torch.int32) if t.dtype == torch.float32 else t
-
-
-def same(a, b):
-    return a.shape == b.shape and torch.equal(bits(a), bits(b))
-
-
-def dev(x):
-    return torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(DEV)
-
-
-def table(lens):
-    seg = [0]
-    for n in lens:
-        seg.append(seg[-1] + int(n))
-    return seg
 
 
 def rel_err(got, want):
@@ -172,28 +143,17 @@ def case_kernel():
 
 
 # ------------------------------------------------------------------ 2. product
-def tiny_vc(kind="mix"):
-    from knn_svc_amd.matcher import KNeighborsVC
-    from knn_svc_amd.vocoder import Vocoder
-    from knn_svc_amd.wavlm import WavLMEncoder
-    cfg, h = C.WAVLM_TINY, C.HIFIGAN_TINY
-    enc = WavLMEncoder(S.seeded_state(S.wavlm_param_spec(cfg), seed=11), cfg, DEV, n_layers=2)
-    return KNeighborsVC(enc, Vocoder(S.seeded_state(S.generator_param_spec(h, kind), 63 if kind == "mix" else 64), h, kind, DEV), h, DEV)
-
-
 def case_product(tmp):
     from knn_svc_amd import serving
     pool = os.path.join(tmp, "tgt"); os.makedirs(pool)
     for i in range(2):
-        w, _f = S.synth_clip(3 * 16000 + 37 * i, seed=900 + i)
-        audio_io.write_wav_pcm16(os.path.join(pool, f"t{i}.wav"), w, 16000)
-        np.save(os.path.join(pool, f"t{i}_f0.npy"), O.track(len(w) // 320 + 1, 233.0, 40 + i))
+        n = 3 * 16000 + 37 * i
+        write_clip(os.path.join(pool, f"t{i}.wav"), n, 900 + i, f0=O.track(n // 320 + 1, 233.0, 40 + i))
     reqs, files = [], []
     for i, n in enumerate([16000 * 2 + 11, 9000, 16000 + 641, 16000 + 2000]):
-        w, _f = S.synth_clip(n, seed=700 + i)
         f = O.track(n // 320 + 1, 110.0, 50 + i)
         p = os.path.join(tmp, f"s{i}.wav")
-        audio_io.write_wav_pcm16(p, w, 16000); np.save(p[:-4] + "_f0.npy", f)
+        write_clip(p, n, 700 + i, f0=f)
         files.append(p); reqs.append((M.load_utterance(p)[0], f))
     vc = tiny_vc()
     src = files[0]
@@ -275,24 +235,5 @@ def case_product(tmp):
     note("product/largest-oracle-error", max(WORST) <= REL_TOL, f"{max(WORST):.3e}")
 
 
-def main(out_path):
-    torch.cuda.set_device(0)
-    rc = 0
-    with torch.inference_mode(), tempfile.TemporaryDirectory() as tmp:
-        for name, fn in (("kernel", case_kernel), ("product", lambda: case_product(tmp))):
-            try:
-                fn()
-                torch.cuda.synchronize()
-            except Exception:          # nothing more is started on the GPU after an error: report what ran and stop
-                note(f"{name}/ran", False, traceback.format_exc()[-1500:])
-                print(traceback.format_exc(), file=sys.stderr)
-                rc = 1
-                break
-            note(f"{name}/ran", True)
-    with open(out_path, "w") as f:
-        json.dump(REPORT, f, indent=1)
-    return rc
-
-
 if __name__ == "__main__":
-    sys.exit(main(sys.argv[1]))
+    sys.exit(run_cases([("kernel", case_kernel), ("product", case_product)], sys.argv[1]))

@@ -22,121 +22,91 @@ single-target conversions, (A, B, [.3, .7]) == (B, A, [.7, .3]), a single Target
 by hand and different from both single conversions, a batch of four with per-source weights on both match routes == the single
 conversions, queue requests with different weights in one batch and a bad vector failing alone, the blend together with
 target_duration, the written files' names.  They fail without the feature: the arguments and entries do not exist."""
-import json
-import os
-import subprocess
-import sys
-
 import pytest
 import torch
 
+from tests.gpu_child import check, report_fixture
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CHILD_TIMEOUT_S = 240        # the GPU work takes seconds; the rest is for a cold torch import
-
-
-@pytest.fixture(scope="module")
-def report(tmp_path_factory):
-    if torch.cuda.is_initialized():
-        pytest.skip("ranks are spawned from a process that has not initialised the GPU: run this module first / on its own")
-    out = str(tmp_path_factory.mktemp("blend") / "report.json")
-    try:
-        r = subprocess.run([sys.executable, "tests/blend_child.py", out], timeout=CHILD_TIMEOUT_S, cwd=ROOT,
-                           capture_output=True, text=True)
-    except subprocess.TimeoutExpired as e:
-        return {"__failed__": f"child timed out after {CHILD_TIMEOUT_S} s\n" + str(e.stderr or "")[-3000:]}
-    print(r.stdout[-12000:])
-    rep = {}
-    if os.path.isfile(out):
-        rep = json.load(open(out))
-    if r.returncode != 0:
-        rep["__failed__"] = f"child exited with {r.returncode}\n" + r.stderr[-3000:]
-    return rep
-
-
-def _check(report, prefix, at_least):
-    assert "__failed__" not in report, report["__failed__"]
-    mine = {k: v for k, v in report.items() if k.startswith(prefix)}
-    assert len(mine) >= at_least, (prefix, sorted(mine))
-    bad = {k: v["detail"] for k, v in mine.items() if not v["ok"]}
-    assert not bad, bad
+report = report_fixture("blend_child.py", "blend", CHILD_TIMEOUT_S)
 
 
 @pytest.mark.parametrize("V", [2, 3, 4])
 @pytest.mark.parametrize("dim", [1024, 49, 7])
 def test_vector_scalar_and_unaligned_paths_are_bit_identical_to_the_oracle(report, dim, V):
-    _check(report, f"kernel/dims/{dim}/v{V}", 2)
+    check(report, f"kernel/dims/{dim}/v{V}", 2)
 
 
 def test_edge_segments_in_one_call_equal_the_oracle_and_each_segment_alone(report):
-    _check(report, "kernel/edges/bit-identical", 1)
-    _check(report, "kernel/edges/each-segment-alone", 1)
+    check(report, "kernel/edges/bit-identical", 1)
+    check(report, "kernel/edges/each-segment-alone", 1)
 
 
 def test_a_one_hot_segment_is_its_input_and_a_zero_weight_voice_is_not_read(report):
-    _check(report, "kernel/edges/one-hot-segment-is-its-input", 1)
-    _check(report, "kernel/edges/single-term-copies-bit-for-bit", 1)
-    _check(report, "kernel/edges/a-positive-weight-lets-nan-through", 1)
+    check(report, "kernel/edges/one-hot-segment-is-its-input", 1)
+    check(report, "kernel/edges/single-term-copies-bit-for-bit", 1)
+    check(report, "kernel/edges/a-positive-weight-lets-nan-through", 1)
 
 
 def test_seventy_segments_in_one_call_equal_each_alone_bit_for_bit(report):
-    _check(report, "kernel/seventy-segments-equal-each-alone", 1)
+    check(report, "kernel/seventy-segments-equal-each-alone", 1)
 
 
 @pytest.mark.parametrize("dim", [1024, 7])
 def test_guard_rows_around_the_output_are_untouched(report, dim):
-    _check(report, f"kernel/canary/{dim}", 1)
+    check(report, f"kernel/canary/{dim}", 1)
 
 
 def test_ops_refuses_bad_tables_and_the_kernel_cases_ran(report):
-    _check(report, "kernel/ops-refuses", 1)
-    _check(report, "kernel/ran", 1)
+    check(report, "kernel/ops-refuses", 1)
+    check(report, "kernel/ran", 1)
     print("kernel time:", report["kernel/timing-1500x1024-v2"]["detail"])
 
 
 def test_blended_shift_equals_the_existing_shift_towards_the_blended_median(report):
-    _check(report, "shift/equals-the-existing-shift-towards-the-blended-median", 1)
-    _check(report, "shift/default-tables-are-the-median-shift", 1)
-    _check(report, "shift/seventy-segments-equal-each-alone", 1)
+    check(report, "shift/equals-the-existing-shift-towards-the-blended-median", 1)
+    check(report, "shift/default-tables-are-the-median-shift", 1)
+    check(report, "shift/seventy-segments-equal-each-alone", 1)
 
 
 def test_one_hot_shift_and_nan_medians(report):
-    _check(report, "shift/one-hot-is-the-shift-towards-that-voice", 1)
-    _check(report, "shift/nan-median-ignored-at-weight-zero-propagates-above", 1)
-    _check(report, "shift/ran", 1)
+    check(report, "shift/one-hot-is-the-shift-towards-that-voice", 1)
+    check(report, "shift/nan-median-ignored-at-weight-zero-propagates-above", 1)
+    check(report, "shift/ran", 1)
 
 
 def test_a_single_target_voice_without_blend_is_unchanged(report):
-    _check(report, "product/single-voice-is-unchanged", 1)
+    check(report, "product/single-voice-is-unchanged", 1)
 
 
 @pytest.mark.parametrize("case", ["one-zero-is-towards-A", "zero-one-is-towards-B", "half-half-of-A-and-A-is-A", "swapping-voices-and-weights"])
 def test_identities_are_bit_identical_to_the_single_target_conversion(report, case):
-    _check(report, f"product/identity/{case}", 1)
+    check(report, f"product/identity/{case}", 1)
 
 
 def test_half_half_equals_the_chain_by_hand_and_differs_from_both_voices(report):
-    _check(report, "product/chain-by-hand", 1)
-    _check(report, "product/half-half-differs-from-both", 1)
+    check(report, "product/chain-by-hand", 1)
+    check(report, "product/half-half-differs-from-both", 1)
 
 
 @pytest.mark.parametrize("route", ["lanes", "segmented"])
 def test_a_batch_with_per_source_weights_equals_the_single_conversions(report, route):
-    _check(report, "product/converter/single-conversions", 1)
-    _check(report, f"product/converter/{route}-batch-equals-single", 1)
+    check(report, "product/converter/single-conversions", 1)
+    check(report, f"product/converter/{route}-batch-equals-single", 1)
 
 
 def test_requests_with_different_weights_share_a_batch_and_a_bad_vector_fails_alone(report):
-    _check(report, "product/queue/", 1)
+    check(report, "product/queue/", 1)
 
 
 def test_the_blend_works_together_with_target_duration(report):
-    _check(report, "product/with-target-duration", 1)
+    check(report, "product/with-target-duration", 1)
 
 
 def test_the_written_files_are_named_after_the_voices(report):
-    _check(report, "product/files", 1)
-    _check(report, "product/ran", 1)
+    check(report, "product/files", 1)
+    check(report, "product/ran", 1)
 
 
 def test_parent_process_left_the_gpu_alone(report):

@@ -31,18 +31,12 @@ Every row kept all five properties in that run but one: W64-shorter-than-halo (m
 the lean epilogues compute and leave to the buffer range check — in the range slot (3.6204 against max |out| = 3.5084); the
 epilogues now leave them out (row_keep in conv_gemm.hip).
 """
-import json
-import os
-import subprocess
-import sys
-
 import pytest
 import torch
 
-from tests import conv_routes_common as R
+from tests import conv_routes_common as R, gpu_child
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CHILD_TIMEOUT_S = 300        # measured: 15 s for the child on a warm machine, 9 s of it the references on the CPU; the rest is for a cold torch import
 
 # F per family = twice the worst err / e32 measured over the table on an MI355X, rounded up (cap 16: see the table above)
@@ -64,19 +58,7 @@ def report(tmp_path_factory):
     if torch.cuda.is_initialized():
         from tests import conv_routes_child
         return conv_routes_child.run_all(print)
-    out = str(tmp_path_factory.mktemp("conv_routes") / "report.json")
-    try:
-        r = subprocess.run([sys.executable, "tests/conv_routes_child.py", out], timeout=CHILD_TIMEOUT_S, cwd=ROOT,
-                           capture_output=True, text=True)
-    except subprocess.TimeoutExpired as e:
-        return {"__failed__": f"child timed out after {CHILD_TIMEOUT_S} s\n" + str(e.stderr or "")[-3000:]}
-    print(r.stdout[-12000:])
-    rep = {}
-    if os.path.isfile(out):
-        rep = json.load(open(out))
-    if r.returncode != 0:
-        rep["__failed__"] = f"child exited with {r.returncode}\n" + r.stderr[-3000:]
-    return rep
+    return gpu_child.run_child("conv_routes_child.py", str(tmp_path_factory.mktemp("conv_routes") / "report.json"), CHILD_TIMEOUT_S)
 
 
 def _record(report, id_):

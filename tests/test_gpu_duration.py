@@ -21,108 +21,78 @@ argument does not exist), s = 1 bit-identical to the plain conversion, s = 1.25 
 -> match_features -> Tail by hand with T_out * 320 samples, a batch with [None, shorter, longer, None] on both match routes ==
 the four single conversions, requests with different durations in one queue batch and a bad ratio failing alone, the written
 file's length and name, refusals before a file is read."""
-import json
-import os
-import subprocess
-import sys
-
 import pytest
 import torch
 
+from tests.gpu_child import check, report_fixture
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CHILD_TIMEOUT_S = 180        # the GPU work takes seconds; the rest is for a cold torch import
-
-
-@pytest.fixture(scope="module")
-def report(tmp_path_factory):
-    if torch.cuda.is_initialized():
-        pytest.skip("ranks are spawned from a process that has not initialised the GPU: run this module first / on its own")
-    out = str(tmp_path_factory.mktemp("duration") / "report.json")
-    try:
-        r = subprocess.run([sys.executable, "tests/duration_child.py", out], timeout=CHILD_TIMEOUT_S, cwd=ROOT,
-                           capture_output=True, text=True)
-    except subprocess.TimeoutExpired as e:
-        return {"__failed__": f"child timed out after {CHILD_TIMEOUT_S} s\n" + str(e.stderr or "")[-3000:]}
-    print(r.stdout[-12000:])
-    rep = {}
-    if os.path.isfile(out):
-        rep = json.load(open(out))
-    if r.returncode != 0:
-        rep["__failed__"] = f"child exited with {r.returncode}\n" + r.stderr[-3000:]
-    return rep
-
-
-def _check(report, prefix, at_least):
-    assert "__failed__" not in report, report["__failed__"]
-    mine = {k: v for k, v in report.items() if k.startswith(prefix)}
-    assert len(mine) >= at_least, (prefix, sorted(mine))
-    bad = {k: v["detail"] for k, v in mine.items() if not v["ok"]}
-    assert not bad, bad
+report = report_fixture("duration_child.py", "duration", CHILD_TIMEOUT_S)
 
 
 def test_edge_segments_in_one_call_equal_the_oracle_and_each_segment_alone(report):
-    _check(report, "kernel/edges/features-bit-identical", 1)
-    _check(report, "kernel/edges/f0", 1)
-    _check(report, "kernel/edges/each-segment-alone", 1)
-    _check(report, "kernel/edges/scale-one-is-the-input", 1)
+    check(report, "kernel/edges/features-bit-identical", 1)
+    check(report, "kernel/edges/f0", 1)
+    check(report, "kernel/edges/each-segment-alone", 1)
+    check(report, "kernel/edges/scale-one-is-the-input", 1)
 
 
 @pytest.mark.parametrize("dim", [1024, 128, 7])
 def test_vector_scalar_and_unaligned_paths_are_bit_identical_to_the_oracle(report, dim):
-    _check(report, f"kernel/dims/{dim}", 2)
+    check(report, f"kernel/dims/{dim}", 2)
 
 
 def test_seventy_segments_in_one_call_equal_each_alone_bit_for_bit(report):
-    _check(report, "kernel/seventy-segments-equal-each-alone", 1)
+    check(report, "kernel/seventy-segments-equal-each-alone", 1)
 
 
 def test_f0_edges_in_the_features_null_and_the_f0_null_form(report):
-    _check(report, "kernel/f0-edges/", 2)
+    check(report, "kernel/f0-edges/", 2)
     print("f0 frames that differ from the oracle:", report["kernel/f0-frames-that-differ-from-the-oracle"]["detail"])
 
 
 @pytest.mark.parametrize("dim", [1024, 7])
 def test_guard_rows_around_the_outputs_are_untouched(report, dim):
-    _check(report, f"kernel/canary/{dim}", 1)
+    check(report, f"kernel/canary/{dim}", 1)
 
 
 def test_ops_refuses_bad_tables_and_the_kernel_cases_ran(report):
-    _check(report, "kernel/ops-refuses", 1)
-    _check(report, "kernel/ran", 1)
+    check(report, "kernel/ops-refuses", 1)
+    check(report, "kernel/ran", 1)
     print("kernel time:", report["kernel/timing-1500x1024-s1.25"]["detail"])
 
 
 def test_defaults_reproduce_the_call_without_the_argument_bit_for_bit(report):
-    _check(report, "product/defaults-are-bit-identical", 1)
+    check(report, "product/defaults-are-bit-identical", 1)
 
 
 def test_the_sources_own_length_is_the_plain_conversion_bit_for_bit(report):
-    _check(report, "product/identity", 1)
+    check(report, "product/identity", 1)
 
 
 @pytest.mark.parametrize("tag", ["longer", "shorter"])
 def test_the_product_equals_the_chain_by_hand_and_has_the_planned_length(report, tag):
-    _check(report, f"product/chain/{tag}", 1)
+    check(report, f"product/chain/{tag}", 1)
 
 
 @pytest.mark.parametrize("route", ["lanes", "segmented"])
 def test_a_batch_with_mixed_durations_equals_the_single_conversions(report, route):
-    _check(report, "product/converter/lengths", 1)
-    _check(report, f"product/converter/{route}-batch-equals-single", 1)
+    check(report, "product/converter/lengths", 1)
+    check(report, f"product/converter/{route}-batch-equals-single", 1)
 
 
 def test_requests_with_different_durations_share_a_batch_and_a_bad_ratio_fails_alone(report):
-    _check(report, "product/queue/", 2)
+    check(report, "product/queue/", 2)
 
 
 def test_the_written_file_has_the_planned_length_under_the_unchanged_name(report):
-    _check(report, "product/files", 1)
+    check(report, "product/files", 1)
 
 
 def test_bad_values_are_refused_before_a_file_is_read(report):
-    _check(report, "product/refusals", 1)
-    _check(report, "product/ran", 1)
+    check(report, "product/refusals", 1)
+    check(report, "product/ran", 1)
 
 
 def test_parent_process_left_the_gpu_alone(report):

@@ -21,112 +21,82 @@ read from the library: ops.peak_limit_layout):
   product      tiny models, pool of 4 x 3 s, six phrased sources: BatchConverter off twice; on (0.7, ceiling at half the off run's
                peak) == the ops by hand on both match routes; with loudness -20 the order mix, loudness, ceiling; a RequestQueue;
                special_match's file on / defaults / normalised past full scale under the ceiling; bulk_match's files."""
-import json
-import os
-import subprocess
-import sys
-
 import pytest
 import torch
 
+from tests.gpu_child import check, report_fixture
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CHILD_TIMEOUT_S = 240        # the child's own work is a few seconds; the rest is for a cold torch import
-
-
-@pytest.fixture(scope="module")
-def report(tmp_path_factory):
-    if torch.cuda.is_initialized():
-        pytest.skip("ranks are spawned from a process that has not initialised the GPU: run this module first / on its own")
-    out = str(tmp_path_factory.mktemp("dynamics") / "report.json")
-    try:
-        r = subprocess.run([sys.executable, "tests/dynamics_child.py", out], timeout=CHILD_TIMEOUT_S, cwd=ROOT,
-                           capture_output=True, text=True)
-    except subprocess.TimeoutExpired as e:
-        return {"__failed__": f"child timed out after {CHILD_TIMEOUT_S} s\n" + str(e.stderr or "")[-3000:]}
-    print(r.stdout[-12000:])
-    rep = {}
-    if os.path.isfile(out):
-        rep = json.load(open(out))
-    if r.returncode != 0:
-        rep["__failed__"] = f"child exited with {r.returncode}\n" + r.stderr[-3000:]
-    return rep
-
-
-def _check(report, prefix, at_least):
-    assert "__failed__" not in report, report["__failed__"]
-    mine = {k: v for k, v in report.items() if k.startswith(prefix)}
-    assert len(mine) >= at_least, (prefix, sorted(mine))
-    bad = {k: v["detail"] for k, v in mine.items() if not v["ok"]}
-    assert not bad, bad
+report = report_fixture("dynamics_child.py", "dynamics", CHILD_TIMEOUT_S)
 
 
 def test_envelope_mix_equals_the_fp64_oracle(report):
-    _check(report, "envelope/T", 5)
-    _check(report, "envelope/source-", 4)
-    _check(report, "envelope/phrased-", 3)
-    _check(report, "envelope/max-error", 1)
+    check(report, "envelope/T", 5)
+    check(report, "envelope/source-", 4)
+    check(report, "envelope/phrased-", 3)
+    check(report, "envelope/max-error", 1)
     print(report["envelope/max-error"]["detail"])
 
 
 def test_envelope_mix_leaves_y_alone_when_a_signal_is_silent(report):
-    _check(report, "envelope/silent-", 4)
-    _check(report, "envelope/empty-source", 1)
+    check(report, "envelope/silent-", 4)
+    check(report, "envelope/empty-source", 1)
 
 
 def test_envelope_mix_does_not_depend_on_the_source_level(report):
-    _check(report, "envelope/level/", 3)
+    check(report, "envelope/level/", 3)
 
 
 def test_envelope_mix_call_forms_and_refusals(report):
     for name in ("in-place", "gains-null", "pointers-4-bytes-off-alignment", "exact-workspace", "short-workspace-refused",
                  "bad-length-and-bad-hop-are-error-codes"):
-        _check(report, "envelope/" + name, 1)
-    _check(report, "envelope/ran", 1)
+        check(report, "envelope/" + name, 1)
+    check(report, "envelope/ran", 1)
 
 
 def test_peak_ceiling_equals_the_fp64_oracle_and_holds_the_ceiling(report):
-    _check(report, "ceiling/length/", 11)
-    _check(report, "ceiling/peak-at/", 12)
-    _check(report, "ceiling/two-peaks/", 2)
+    check(report, "ceiling/length/", 11)
+    check(report, "ceiling/peak-at/", 12)
+    check(report, "ceiling/two-peaks/", 2)
     for name in ("negative-peak", "plateau-across-a-tile-boundary", "everything-over", "44100-Hz", "p0", "p-1", "p-6", "several", "max-error"):
-        _check(report, "ceiling/" + name, 1)
+        check(report, "ceiling/" + name, 1)
     print(report["ceiling/max-error"]["detail"])
 
 
 def test_peak_ceiling_returns_a_signal_under_it_bit_identical(report):
-    _check(report, "ceiling/identity", 1)
+    check(report, "ceiling/identity", 1)
 
 
 def test_peak_ceiling_call_forms_and_refusals(report):
     for name in ("in-place", "pointers-4-bytes-off-alignment", "stats-null", "bad-rate-and-bad-level-are-error-codes", "ran"):
-        _check(report, "ceiling/" + name, 1)
+        check(report, "ceiling/" + name, 1)
 
 
 def test_both_ops_are_bit_stable_from_run_to_run_and_across_streams(report):
-    _check(report, "determinism/", 1 + 1)
+    check(report, "determinism/", 1 + 1)
 
 
 def test_batch_converter_with_dynamics_equals_the_ops_applied_to_its_own_output(report):
-    _check(report, "product/off-twice", 1)
-    _check(report, "product/on/", 3)
+    check(report, "product/off-twice", 1)
+    check(report, "product/on/", 3)
 
 
 def test_the_tail_runs_mix_then_loudness_then_ceiling(report):
-    _check(report, "product/order/", 2)
+    check(report, "product/order/", 2)
 
 
 def test_request_queue_inherits_the_converters_dynamics(report):
-    _check(report, "product/request-queue", 1)
+    check(report, "product/request-queue", 1)
 
 
 def test_special_match_writes_the_processed_waveform_only_when_asked(report):
-    _check(report, "product/special_match/", 4)
+    check(report, "product/special_match/", 4)
 
 
 def test_bulk_match_writes_every_file_under_the_ceiling(report):
-    _check(report, "product/bulk_match/", 3)
-    _check(report, "product/ran", 1)
+    check(report, "product/bulk_match/", 3)
+    check(report, "product/ran", 1)
 
 
 def test_parent_process_left_the_gpu_alone(report):

@@ -19,70 +19,40 @@ library: ops.loudness_layout):
   gain         targets -16 and -23, out of place and in place; inputs without a loudness come back bit-identical.
   product      tiny models, pool of 4 x 3 s, six sources: BatchConverter off twice, on (-20) == ops.normalize_loudness of the off
                run on both match routes, special_match's file on / level None / switch off, bulk_match's files at -16."""
-import json
-import os
-import subprocess
-import sys
-
 import pytest
 import torch
 
+from tests.gpu_child import check, report_fixture
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CHILD_TIMEOUT_S = 180        # measured: the child takes 3.4 s on a warm machine (1 s of it the oracle on the 30 s clip); the rest is for a cold torch import
-
-
-@pytest.fixture(scope="module")
-def report(tmp_path_factory):
-    if torch.cuda.is_initialized():
-        pytest.skip("ranks are spawned from a process that has not initialised the GPU: run this module first / on its own")
-    out = str(tmp_path_factory.mktemp("loudness") / "report.json")
-    try:
-        r = subprocess.run([sys.executable, "tests/loudness_child.py", out], timeout=CHILD_TIMEOUT_S, cwd=ROOT,
-                           capture_output=True, text=True)
-    except subprocess.TimeoutExpired as e:
-        return {"__failed__": f"child timed out after {CHILD_TIMEOUT_S} s\n" + str(e.stderr or "")[-3000:]}
-    print(r.stdout[-8000:])
-    rep = {}
-    if os.path.isfile(out):
-        rep = json.load(open(out))
-    if r.returncode != 0:
-        rep["__failed__"] = f"child exited with {r.returncode}\n" + r.stderr[-3000:]
-    return rep
-
-
-def _check(report, prefix, at_least):
-    assert "__failed__" not in report, report["__failed__"]
-    mine = {k: v for k, v in report.items() if k.startswith(prefix)}
-    assert len(mine) >= at_least, (prefix, sorted(mine))
-    bad = {k: v["detail"] for k, v in mine.items() if not v["ok"]}
-    assert not bad, bad
+report = report_fixture("loudness_child.py", "loudness", CHILD_TIMEOUT_S, stdout_tail=8000)
 
 
 def test_loudness_equals_the_fp64_oracle(report):
-    _check(report, "oracle/", 7 + 7 + 4 + 3 + 2 + 2 * 2 + 1)
+    check(report, "oracle/", 7 + 7 + 4 + 3 + 2 + 2 * 2 + 1)
 
 
 def test_loudness_is_bit_stable_from_run_to_run_and_across_streams(report):
-    _check(report, "determinism/", 1 + 1)
+    check(report, "determinism/", 1 + 1)
 
 
 def test_gain_reaches_the_target_and_leaves_silence_alone(report):
-    _check(report, "gain/", 2 * 2 + 2 + 1)
+    check(report, "gain/", 2 * 2 + 2 + 1)
 
 
 def test_batch_converter_with_loudness_equals_normalising_its_own_output(report):
-    _check(report, "product/off-twice", 1)
-    _check(report, "product/on/", 2)
+    check(report, "product/off-twice", 1)
+    check(report, "product/on/", 2)
 
 
 def test_special_match_writes_the_normalised_waveform_only_when_asked(report):
-    _check(report, "product/special_match/", 4)
+    check(report, "product/special_match/", 4)
 
 
 def test_bulk_match_writes_every_file_at_the_target_level(report):
-    _check(report, "product/bulk_match/", 3)
-    _check(report, "product/ran", 1)
+    check(report, "product/bulk_match/", 3)
+    check(report, "product/ran", 1)
 
 
 def test_parent_process_left_the_gpu_alone(report):

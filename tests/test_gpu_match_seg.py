@@ -19,77 +19,47 @@ Cases (the smallest sizes that reach every kernel variant and boundary):
   match_many six items of 1 / 2 / 31 / 150 / 151 / 600 frames, "mix" and "wavlm_only", with and without post_opt, synth_list once.
   product    BatchConverter(match="segmented", match_batch=4) against match="lanes", both generator kinds, three runs; many_to_one
              files under KNNSVC_MATCH=segmented."""
-import json
-import os
-import subprocess
-import sys
-
 import pytest
 import torch
 
+from tests.gpu_child import check, report_fixture
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CHILD_TIMEOUT_S = 300        # the child takes well under a minute of GPU work plus the imports and the tiny models' graph captures
-
-
-@pytest.fixture(scope="module")
-def report(tmp_path_factory):
-    if torch.cuda.is_initialized():
-        pytest.skip("ranks are spawned from a process that has not initialised the GPU: run this module first / on its own")
-    out = str(tmp_path_factory.mktemp("match_seg") / "report.json")
-    try:
-        r = subprocess.run([sys.executable, "tests/match_seg_child.py", out], timeout=CHILD_TIMEOUT_S, cwd=ROOT,
-                           capture_output=True, text=True)
-    except subprocess.TimeoutExpired as e:
-        return {"__failed__": f"child timed out after {CHILD_TIMEOUT_S} s\n" + str(e.stderr or "")[-3000:]}
-    print(r.stdout[-6000:])
-    rep = {}
-    if os.path.isfile(out):
-        rep = json.load(open(out))
-    if r.returncode != 0:
-        rep["__failed__"] = f"child exited with {r.returncode}\n" + r.stderr[-3000:]
-    return rep
-
-
-def _check(report, prefix, at_least):
-    assert "__failed__" not in report, report["__failed__"]
-    mine = {k: v for k, v in report.items() if k.startswith(prefix)}
-    assert len(mine) >= at_least, (prefix, sorted(mine))
-    bad = {k: v["detail"] for k, v in mine.items() if not v["ok"]}
-    assert not bad, bad
+report = report_fixture("match_seg_child.py", "match_seg", CHILD_TIMEOUT_S, stdout_tail=6000)
 
 
 def test_walk_segments_equal_single_sequences(report):
-    _check(report, "walk/", 2 * 4 * 2 + 1)
+    check(report, "walk/", 2 * 4 * 2 + 1)
 
 
 def test_walk_segment_output_does_not_depend_on_position(report):
-    _check(report, "walk-swapped/", 2 * 4 * 2)
+    check(report, "walk-swapped/", 2 * 4 * 2)
 
 
 def test_median_and_shift_segments_equal_single_sequences(report):
-    _check(report, "median/", 3)
-    _check(report, "shift/", 1)
+    check(report, "median/", 3)
+    check(report, "shift/", 1)
 
 
 def test_smooth_weights_segments_equal_single_sequences(report):
-    _check(report, "smooth/", 2 * 2 * 2 * 3 + 1)
+    check(report, "smooth/", 2 * 2 * 2 * 3 + 1)
 
 
 def test_single_smooth_weights_fits_its_own_workspace_size(report):
-    _check(report, "single_ws/", 5 * 2 + 1)
+    check(report, "single_ws/", 5 * 2 + 1)
 
 
 def test_wrappers_split_more_than_64_segments(report):
-    _check(report, "chunking/", 2)
+    check(report, "chunking/", 2)
 
 
 def test_match_features_many_equals_match_features(report):
-    _check(report, "match_many/", 5 + 1)
+    check(report, "match_many/", 5 + 1)
 
 
 def test_segmented_product_route_equals_lanes(report):
-    _check(report, "product/", 2 * (3 + 1) + 1)
+    check(report, "product/", 2 * (3 + 1) + 1)
 
 
 def test_parent_process_left_the_gpu_alone(report):

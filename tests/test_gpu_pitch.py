@@ -17,101 +17,71 @@ Kernel cases (a few hundred to two thousand frames each):
 Product cases (seeded small models): defaults bit-identical to the call without the arguments (fails without the feature: the
 arguments do not exist), semitone against the oracle, none + 12 doubles f0, a mixed batch of four on both match routes == the
 four single conversions, two requests with different transposes in one queue batch, refusals before a file is read."""
-import json
-import os
-import subprocess
-import sys
-
 import pytest
 import torch
 
+from tests.gpu_child import check, report_fixture
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CHILD_TIMEOUT_S = 180        # the GPU work takes seconds; the rest is for a cold torch import
-
-
-@pytest.fixture(scope="module")
-def report(tmp_path_factory):
-    if torch.cuda.is_initialized():
-        pytest.skip("ranks are spawned from a process that has not initialised the GPU: run this module first / on its own")
-    out = str(tmp_path_factory.mktemp("pitch") / "report.json")
-    try:
-        r = subprocess.run([sys.executable, "tests/pitch_child.py", out], timeout=CHILD_TIMEOUT_S, cwd=ROOT,
-                           capture_output=True, text=True)
-    except subprocess.TimeoutExpired as e:
-        return {"__failed__": f"child timed out after {CHILD_TIMEOUT_S} s\n" + str(e.stderr or "")[-3000:]}
-    print(r.stdout[-12000:])
-    rep = {}
-    if os.path.isfile(out):
-        rep = json.load(open(out))
-    if r.returncode != 0:
-        rep["__failed__"] = f"child exited with {r.returncode}\n" + r.stderr[-3000:]
-    return rep
-
-
-def _check(report, prefix, at_least):
-    assert "__failed__" not in report, report["__failed__"]
-    mine = {k: v for k, v in report.items() if k.startswith(prefix)}
-    assert len(mine) >= at_least, (prefix, sorted(mine))
-    bad = {k: v["detail"] for k, v in mine.items() if not v["ok"]}
-    assert not bad, bad
+report = report_fixture("pitch_child.py", "pitch", CHILD_TIMEOUT_S)
 
 
 def test_median_without_transpose_through_the_new_entry_is_the_old_entry_bit_for_bit(report):
-    _check(report, "kernel/median-t0-is-the-old-entry", 1)
-    _check(report, "kernel/median-t0-reports-the-interval", 1)
+    check(report, "kernel/median-t0-is-the-old-entry", 1)
+    check(report, "kernel/median-t0-reports-the-interval", 1)
     # the entries share one kernel: the same table against the oracle, and each segment alone through knnsvc_shift_f0
-    _check(report, "kernel/median-t0-equals-the-oracle-and-each-segment-alone", 1)
+    check(report, "kernel/median-t0-equals-the-oracle-and-each-segment-alone", 1)
 
 
 @pytest.mark.parametrize("case", ["up", "down", "near"])
 def test_every_mode_and_transpose_equals_the_oracle(report, case):
-    _check(report, f"kernel/{case}/precondition", 1)
-    _check(report, f"kernel/{case}/mode", 16)
+    check(report, f"kernel/{case}/precondition", 1)
+    check(report, f"kernel/{case}/mode", 16)
     print("largest relative error against the oracle:", report["kernel/largest-oracle-error"]["detail"])
 
 
 def test_largest_oracle_error_is_within_the_bound(report):
-    _check(report, "kernel/largest-oracle-error", 1)
+    check(report, "kernel/largest-oracle-error", 1)
 
 
 def test_seventy_segments_in_one_call_equal_each_alone_bit_for_bit(report):
-    _check(report, "kernel/seventy-segments-equal-each-alone", 1)
+    check(report, "kernel/seventy-segments-equal-each-alone", 1)
 
 
 def test_none_never_reads_the_medians_and_median_propagates_nan(report):
-    _check(report, "kernel/unvoiced-pool", 1)
-    _check(report, "kernel/ops-refuses", 1)
-    _check(report, "kernel/ran", 1)
+    check(report, "kernel/unvoiced-pool", 1)
+    check(report, "kernel/ops-refuses", 1)
+    check(report, "kernel/ran", 1)
 
 
 def test_defaults_reproduce_the_call_without_the_arguments_bit_for_bit(report):
-    _check(report, "product/defaults-are-bit-identical", 1)
+    check(report, "product/defaults-are-bit-identical", 1)
 
 
 def test_semitone_mode_equals_the_oracle_and_changes_the_waveform(report):
-    _check(report, "product/precondition", 1)
-    _check(report, "product/semitone", 2)
+    check(report, "product/precondition", 1)
+    check(report, "product/semitone", 2)
 
 
 def test_transpose_12_without_a_shift_doubles_every_voiced_f0(report):
-    _check(report, "product/none-plus-12-doubles", 1)
+    check(report, "product/none-plus-12-doubles", 1)
 
 
 @pytest.mark.parametrize("route", ["lanes", "segmented"])
 def test_a_batch_of_four_settings_equals_the_four_single_conversions(report, route):
-    _check(report, "product/converter/settings-change-the-output", 1)
-    _check(report, f"product/converter/{route}-batch-equals-single", 1)
+    check(report, "product/converter/settings-change-the-output", 1)
+    check(report, f"product/converter/{route}-batch-equals-single", 1)
 
 
 def test_two_requests_with_different_transposes_share_a_batch(report):
-    _check(report, "product/queue", 1)
+    check(report, "product/queue", 1)
 
 
 def test_bad_values_are_refused_before_a_file_is_read(report):
-    _check(report, "product/refusals", 1)
-    _check(report, "product/largest-oracle-error", 1)
-    _check(report, "product/ran", 1)
+    check(report, "product/refusals", 1)
+    check(report, "product/largest-oracle-error", 1)
+    check(report, "product/ran", 1)
 
 
 def test_parent_process_left_the_gpu_alone(report):

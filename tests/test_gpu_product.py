@@ -8,18 +8,10 @@ import pytest
 import torch
 
 from knn_svc_amd import audio_io, config as C, synthetic as S
+from tests.gpu_child import tiny_vc
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
-
-
-def _tiny_vc(kind="mix"):
-    from knn_svc_amd.matcher import KNeighborsVC
-    from knn_svc_amd.vocoder import Vocoder
-    from knn_svc_amd.wavlm import WavLMEncoder
-    cfg, h = C.WAVLM_TINY, C.HIFIGAN_TINY
-    enc = WavLMEncoder(S.seeded_state(S.wavlm_param_spec(cfg), seed=11), cfg, DEV, n_layers=2)
-    return KNeighborsVC(enc, Vocoder(S.seeded_state(S.generator_param_spec(h, kind), 63 if kind == "mix" else 64), h, kind, DEV), h, DEV)
 
 
 def _write_pool(d, n=4, secs=3):
@@ -36,7 +28,7 @@ def test_many_to_one_equals_special_match_per_source(tmp_path, ckpt_type, kind):
     generator as the tail stage) writes, for every source, the samples ``special_match`` writes for that source alone — both
     generator variants, ragged source lengths incl. one shorter than a chunk bucket."""
     from knn_svc_amd.matching import match_at_inference_time
-    vc = _tiny_vc(kind)
+    vc = tiny_vc(kind)
     pool = tmp_path / "tgt"
     _write_pool(pool)
     srcd = tmp_path / "src"; srcd.mkdir()
@@ -77,7 +69,7 @@ def test_every_knob_switched_on_gives_the_same_samples_on_every_route(tmp_path, 
     the same values but every switch off equals the call without any of the arguments.  (The pool trimmer has its own product
     tests, test_gpu_vad.py: synthetic clips have no silence to trim.)"""
     from knn_svc_amd import serving
-    vc = _tiny_vc(kind)
+    vc = tiny_vc(kind)
     pool = tmp_path / "tgt"
     _write_pool(pool, n=1, secs=4)
     ref = str(pool / "t0.wav")
@@ -121,7 +113,7 @@ def test_request_queue_batches_and_returns_each_request_its_own_waveform(tmp_pat
     f0 track (Harvest on the GPU when it is missing)."""
     import threading
     from knn_svc_amd import serving
-    vc = _tiny_vc()
+    vc = tiny_vc()
     pool = tmp_path / "tgt"
     _write_pool(pool)
     tv = serving.TargetVoice(vc, str(pool))
@@ -155,7 +147,7 @@ def test_request_queue_a_bad_request_fails_alone_and_one_deadline_per_batch(tmp_
     arrivals spaced closer than max_wait cannot hold the first request for max_batch x max_wait."""
     import time
     from knn_svc_amd import ops, serving
-    vc = _tiny_vc()
+    vc = tiny_vc()
     pool = tmp_path / "tgt"
     _write_pool(pool)
     tv = serving.TargetVoice(vc, str(pool))

@@ -25,88 +25,58 @@ Cases (the smallest shapes that reach every boundary; the bars and their CPU-che
                   wavlm_only / no_post_opt; topk=4 is topk=None and many is single (k = 8), bit for bit.
   product         tiny models: BatchConverter(topk=8) lanes == segmented, != default, finite; special_match ignores topk
                   without use_topk, honours it with, and use_topk with topk=4 is the default, bit for bit."""
-import json
-import os
-import subprocess
-import sys
-
 import pytest
 import torch
 
+from tests.gpu_child import check, report_fixture
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CHILD_TIMEOUT_S = 600        # a few seconds of GPU work per case; most of the time is the CPU oracle's frame-by-frame walks
-
-
-@pytest.fixture(scope="module")
-def report(tmp_path_factory):
-    if torch.cuda.is_initialized():
-        pytest.skip("ranks are spawned from a process that has not initialised the GPU: run this module first / on its own")
-    out = str(tmp_path_factory.mktemp("topk") / "report.json")
-    try:
-        r = subprocess.run([sys.executable, "tests/topk_child.py", out], timeout=CHILD_TIMEOUT_S, cwd=ROOT,
-                           capture_output=True, text=True)
-    except subprocess.TimeoutExpired as e:
-        return {"__failed__": f"child timed out after {CHILD_TIMEOUT_S} s\n" + str(e.stderr or "")[-3000:]}
-    print(r.stdout[-20000:])
-    rep = {}
-    if os.path.isfile(out):
-        rep = json.load(open(out))
-    if r.returncode != 0:
-        rep["__failed__"] = f"child exited with {r.returncode}\n" + r.stderr[-3000:]
-    return rep
-
-
-def _check(report, prefix, exactly):
-    assert "__failed__" not in report, report["__failed__"]
-    mine = {k: v for k, v in report.items() if k.startswith(prefix)}
-    assert len(mine) == exactly, (prefix, sorted(mine))
-    bad = {k: v["detail"] for k, v in mine.items() if not v["ok"]}
-    assert not bad, bad
+report = report_fixture("topk_child.py", "topk", CHILD_TIMEOUT_S, stdout_tail=20000)
 
 
 def test_walk_for_every_k_equals_the_oracle(report):
-    _check(report, "walk/", 7 * 5 * 2 + 1)
+    check(report, "walk/", exactly=7 * 5 * 2 + 1)
 
 
 def test_generic_walk_at_k4_equals_the_oracle(report):
-    _check(report, "walk-k4/", 2 * 2)
+    check(report, "walk-k4/", exactly=2 * 2)
 
 
 def test_walk_segments_equal_single_sequences_at_k8(report):
-    _check(report, "walk-seg/", 2)
+    check(report, "walk-seg/", exactly=2)
 
 
 def test_generic_walk_at_k4_matches_the_reference_fixture(report):
-    _check(report, "walk-generic4/", 2 + 1)
+    check(report, "walk-generic4/", exactly=2 + 1)
 
 
 def test_smooth_weights_for_every_k_equal_the_oracle(report):
-    _check(report, "smooth/", 2 * 5 + 1 + 1)
+    check(report, "smooth/", exactly=2 * 5 + 1 + 1)
 
 
 def test_long_smooth_weights_at_k4_equal_the_oracle(report):
-    _check(report, "smooth-k4/", 1 + 1)
+    check(report, "smooth-k4/", exactly=1 + 1)
 
 
 def test_smooth_weights_segments_equal_single_sequences(report):
-    _check(report, "smooth-seg/", 2 + 1)
+    check(report, "smooth-seg/", exactly=2 + 1)
 
 
 def test_generic_smooth_weights_at_k4_match_the_reference_fixture(report):
-    _check(report, "smooth-generic4/", 2 + 1)
+    check(report, "smooth-generic4/", exactly=2 + 1)
 
 
 def test_uniform_gather_both_modes(report):
-    _check(report, "gather/", 4 * 2 + 1 + 1)
+    check(report, "gather/", exactly=4 * 2 + 1 + 1)
 
 
 def test_match_features_many_with_topk(report):
-    _check(report, "chain/", 2 * (3 * 3 + 2) + 1)
+    check(report, "chain/", exactly=2 * (3 * 3 + 2) + 1)
 
 
 def test_product_entry_points_honour_topk(report):
-    _check(report, "product/", 6 + 1)
+    check(report, "product/", exactly=6 + 1)
 
 
 def test_parent_process_left_the_gpu_alone(report):

@@ -24,85 +24,55 @@ to flipping, so measures that agree within 1e-6 must give the oracle's cut point
                      at level 0 (fails without the feature), features / spectrum / harmonics of the hand-trimmed waveform, f0 = the
                      untrimmed file's track sliced, special_match(use_vad=True) keeps the source's length, the level is ignored
                      without the switch, serving.TargetVoice takes the level, a pool without speech is refused"""
-import json
-import os
-import subprocess
-import sys
-
 import pytest
 import torch
 
+from tests.gpu_child import check, report_fixture
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CHILD_TIMEOUT_S = 180        # measured: the GPU work takes under 3 s; the rest is for a cold torch import
-
-
-@pytest.fixture(scope="module")
-def report(tmp_path_factory):
-    if torch.cuda.is_initialized():
-        pytest.skip("ranks are spawned from a process that has not initialised the GPU: run this module first / on its own")
-    out = str(tmp_path_factory.mktemp("vad") / "report.json")
-    try:
-        r = subprocess.run([sys.executable, "tests/vad_child.py", out], timeout=CHILD_TIMEOUT_S, cwd=ROOT,
-                           capture_output=True, text=True)
-    except subprocess.TimeoutExpired as e:
-        return {"__failed__": f"child timed out after {CHILD_TIMEOUT_S} s\n" + str(e.stderr or "")[-3000:]}
-    print(r.stdout[-8000:])
-    rep = {}
-    if os.path.isfile(out):
-        rep = json.load(open(out))
-    if r.returncode != 0:
-        rep["__failed__"] = f"child exited with {r.returncode}\n" + r.stderr[-3000:]
-    return rep
-
-
-def _check(report, prefix, at_least):
-    assert "__failed__" not in report, report["__failed__"]
-    mine = {k: v for k, v in report.items() if k.startswith(prefix)}
-    assert len(mine) >= at_least, (prefix, sorted(mine))
-    bad = {k: v["detail"] for k, v in mine.items() if not v["ok"]}
-    assert not bad, bad
+report = report_fixture("vad_child.py", "vad", CHILD_TIMEOUT_S, stdout_tail=8000)
 
 
 def test_cut_points_equal_the_oracle_exactly(report):
-    _check(report, "cut/", 4 + 3 + 1 + 2 + 1 + 1 + 1 + 1)          # the twelve 16 kHz cases, the 8 kHz case, the plain call
+    check(report, "cut/", 4 + 3 + 1 + 2 + 1 + 1 + 1 + 1)          # the twelve 16 kHz cases, the 8 kHz case, the plain call
 
 
 def test_measures_equal_the_oracle_within_the_margin(report):
-    _check(report, "measures/", 12 + 1 + 1)
+    check(report, "measures/", 12 + 1 + 1)
     print("largest |measure - oracle| over all cases:", report["measures/largest-error"]["detail"])
 
 
 def test_five_recordings_in_one_call_equal_each_alone_bit_for_bit(report):
-    _check(report, "stacked/", 5)
+    check(report, "stacked/", 5)
 
 
 def test_ops_refuses_bad_levels_shapes_and_rates(report):
-    _check(report, "refuse/", 3)
-    _check(report, "oracle/ran", 1)
+    check(report, "refuse/", 3)
+    check(report, "oracle/ran", 1)
 
 
 def test_pool_of_a_trimmed_target_has_fewer_frames(report):
-    _check(report, "product/pool/fewer-frames", 1)
+    check(report, "product/pool/fewer-frames", 1)
 
 
 def test_trimmed_pool_is_the_pool_of_the_hand_trimmed_waveform(report):
-    _check(report, "product/pool/precondition", 1)
-    _check(report, "product/pool/features-of-the-hand-trimmed-waveform", 1)
-    _check(report, "product/pool/f0-is-the-sliced-track", 1)
+    check(report, "product/pool/precondition", 1)
+    check(report, "product/pool/features-of-the-hand-trimmed-waveform", 1)
+    check(report, "product/pool/f0-is-the-sliced-track", 1)
 
 
 def test_a_pool_without_speech_is_refused(report):
-    _check(report, "product/pool/empty-pool-refused", 1)
+    check(report, "product/pool/empty-pool-refused", 1)
 
 
 def test_special_match_keeps_the_source_length_and_ignores_the_level_without_the_switch(report):
-    _check(report, "product/special_match/", 2)
+    check(report, "product/special_match/", 2)
 
 
 def test_target_voice_takes_the_level(report):
-    _check(report, "product/target-voice", 1)
-    _check(report, "product/ran", 1)
+    check(report, "product/target-voice", 1)
+    check(report, "product/ran", 1)
 
 
 def test_parent_process_left_the_gpu_alone(report):

@@ -7,12 +7,8 @@ The references are the CPU oracle (oracle/select_ref.py, oracle/smooth_ref.py, w
 Every bar's precondition is asserted on the CPU before the device result is looked at (tests/topk_oracle.py): the oracle's walk
 must keep consecutive costs of distinct candidates >= 1e-5 apart, its optimiser must move < 2e-4 under a change of summation
 order.  The first exception ends the run: nothing more is started on the GPU after it."""
-import contextlib
-import json
 import os
 import sys
-import tempfile
-import traceback
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (ROOT, os.path.join(ROOT, "tests")):
@@ -23,30 +19,14 @@ import numpy as np
 import torch
 
 import topk_oracle as T
-from knn_svc_amd import audio_io, config as C, matching as M, ops, synthetic as S
+from knn_svc_amd import matching as M, ops, synthetic as S
 from oracle import select_ref
+from tests.gpu_child import DEV, note, run_cases, same, table, tiny_vc, write_clip
 
-DEV = "cuda"
-REPORT = {}
 KNOB = "KNNSVC_MATCH_GENERIC_K"
 WALK_GAP = 1e-5          # ~8 x the 1.2e-6 distance error of the four-wave walk (DESIGN)
 W_BAR = 4e-4             # the project's k = 4 bar (test_smooth_weights)
 SPREAD_BAR = 2e-4
-
-
-def same(a, b):
-    if a is None or b is None:
-        return a is None and b is None
-    if a.shape != b.shape or a.dtype != b.dtype:
-        return False
-    if a.dtype == torch.float32:
-        return torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
-    return torch.equal(a, b)
-
-
-def note(name, ok, detail=""):
-    REPORT[name] = {"ok": bool(ok), "detail": str(detail)}
-    print(("ok   " if ok else "FAIL ") + name + (f"  [{detail}]" if detail else ""), flush=True)
 
 
 class generic_k:
@@ -57,13 +37,6 @@ class generic_k:
 
     def __exit__(self, *a):
         del os.environ[KNOB]
-
-
-def offsets(lens):
-    seg = [0]
-    for n in lens:
-        seg.append(seg[-1] + n)
-    return seg
 
 
 def compare_walk(got, ref, idx_in, npool, ordered):
@@ -117,7 +90,7 @@ def case_walk():
         walk_case(4, shape, "walk-k4")
     # one segmented call over [1, 2, 3, 64] at k = 8: bit-identical to the single calls
     lens = [1, 2, 3, 64]
-    seg = offsets(lens)
+    seg = table(lens)
     q, p, idx, sf0, pf0 = T.walk_inputs(sum(lens), 48, 1024, 8, 8100)
     q, p, idx, sf0, pf0 = (t.to(DEV) for t in (q, p, idx, sf0, pf0))
     qn, _ = ops.row_norms(q); pn, _ = ops.row_norms(p)
@@ -201,7 +174,7 @@ def case_smooth_seg():
     _, pool, scale = T.smooth_inputs("feat", 8)
     pool = pool.to(DEV)
     for k, lens in ((8, [1, 2, 2304, 2305]), (3, [1, 2, 37, 6144, 6145])):
-        seg = offsets(lens)
+        seg = table(lens)
         n = sum(lens)
         idx = torch.randint(0, pool.shape[0], (n, k), generator=gen)
         idx[::50, 0] = 0; idx[::50, -1] = pool.shape[0] - 1
@@ -355,29 +328,16 @@ def case_chain():
 
 
 # ------------------------------------------------------------------ 5. product
-def tiny_vc(kind):
-    from knn_svc_amd.matcher import KNeighborsVC
-    from knn_svc_amd.vocoder import Vocoder
-    from knn_svc_amd.wavlm import WavLMEncoder
-    cfg, h = C.WAVLM_TINY, C.HIFIGAN_TINY
-    enc = WavLMEncoder(S.seeded_state(S.wavlm_param_spec(cfg), seed=11), cfg, DEV, n_layers=2)
-    return KNeighborsVC(enc, Vocoder(S.seeded_state(S.generator_param_spec(h, kind), 63 if kind == "mix" else 64), h, kind, DEV), h, DEV)
-
-
 def case_product(tmp):
     from knn_svc_amd import serving
     pool = os.path.join(tmp, "tgt"); os.makedirs(pool)
     for i in range(3):
-        w, f = S.synth_clip(3 * 16000 + 37 * i, seed=900 + i)
-        audio_io.write_wav_pcm16(os.path.join(pool, f"t{i}.wav"), w, 16000)
-        np.save(os.path.join(pool, f"t{i}_f0.npy"), f)
+        write_clip(os.path.join(pool, f"t{i}.wav"), 3 * 16000 + 37 * i, 900 + i)
     srcd = os.path.join(tmp, "src"); os.makedirs(srcd)
     files = []
     for i, n in enumerate([16000 * 2 + 11, 9000, 16000 + 641]):
-        w, f = S.synth_clip(n, seed=700 + i)
-        p = os.path.join(srcd, f"s{i}.wav")
-        audio_io.write_wav_pcm16(p, w, 16000); np.save(os.path.join(srcd, f"s{i}_f0.npy"), f * 1.2)
-        files.append(p)
+        files.append(os.path.join(srcd, f"s{i}.wav"))
+        write_clip(files[-1], n, 700 + i, f0_mul=1.2)
     vc = tiny_vc("mix")
     tv = serving.TargetVoice(vc, pool)
     conv = lambda **kw: [y.cpu() for y in serving.BatchConverter(vc, tv, "mix", "post_opt_0.2", **kw).convert(files)]
@@ -403,28 +363,8 @@ def case_product(tmp):
     note("product/special_match/use_topk-4-is-default", same(y_four, y0), "")
 
 
-def main(out_path):
-    torch.cuda.set_device(0)
-    cases = [("walk", case_walk), ("walk-generic4", case_walk_generic4), ("smooth", case_smooth), ("smooth-k4", case_smooth_long4),
-             ("smooth-seg", case_smooth_seg),
-             ("smooth-generic4", case_smooth_generic4), ("gather", case_gather), ("chain", case_chain), ("product", None)]
-    rc = 0
-    with tempfile.TemporaryDirectory() as tmp:
-        for name, fn in cases:
-            try:
-                with contextlib.nullcontext() if name in ("smooth", "smooth-k4", "chain") else torch.inference_mode():  # the oracle's Adam needs autograd
-                    fn() if fn is not None else case_product(tmp)
-                torch.cuda.synchronize()
-            except Exception:          # nothing more is started on the GPU after an error: report what ran and stop
-                note(f"{name}/ran", False, traceback.format_exc()[-1500:])
-                print(traceback.format_exc(), file=sys.stderr)
-                rc = 1
-                break
-            note(f"{name}/ran", True)
-    with open(out_path, "w") as f:
-        json.dump(REPORT, f, indent=1)
-    return rc
-
-
 if __name__ == "__main__":
-    sys.exit(main(sys.argv[1]))
+    cases = [("walk", case_walk), ("walk-generic4", case_walk_generic4), ("smooth", case_smooth), ("smooth-k4", case_smooth_long4),
+             ("smooth-seg", case_smooth_seg), ("smooth-generic4", case_smooth_generic4), ("gather", case_gather), ("chain", case_chain),
+             ("product", case_product)]
+    sys.exit(run_cases(cases, sys.argv[1], autograd=("smooth", "smooth-k4", "chain")))          # the oracle's Adam needs autograd

@@ -10,11 +10,8 @@ kernels give:
   measures      within 1e-6 of the oracle's — the margin inside which no decision can flip (fp64 on both sides: rounding stays far
                 below it); the exact zeros are the same entries
 Everything else is bit equality."""
-import json
 import os
 import sys
-import tempfile
-import traceback
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (ROOT, os.path.join(ROOT, "tests")):
@@ -26,16 +23,10 @@ import torch
 
 import vad_cases as VC
 import vad_oracle as O
-from knn_svc_amd import audio_io, config as C, ops, synthetic as S
+from knn_svc_amd import audio_io, ops, synthetic as S
+from tests.gpu_child import DEV, note, run_cases, tiny_vc, write_clip
 
-DEV = "cuda"
-REPORT = {}
 TOL = 1e-6
-
-
-def note(name, ok, detail=""):
-    REPORT[name] = {"ok": bool(ok), "detail": str(detail)}
-    print(("ok   " if ok else "FAIL ") + name + (f"  [{detail}]" if detail else ""), flush=True)
 
 
 def refused(fn):
@@ -106,15 +97,6 @@ def case_oracle():
 
 
 # ------------------------------------------------------------------ 2. product
-def tiny_vc(kind="mix"):
-    from knn_svc_amd.matcher import KNeighborsVC
-    from knn_svc_amd.vocoder import Vocoder
-    from knn_svc_amd.wavlm import WavLMEncoder
-    cfg, h = C.WAVLM_TINY, C.HIFIGAN_TINY
-    enc = WavLMEncoder(S.seeded_state(S.wavlm_param_spec(cfg), seed=11), cfg, DEV, n_layers=2)
-    return KNeighborsVC(enc, Vocoder(S.seeded_state(S.generator_param_spec(h, kind), 63 if kind == "mix" else 64), h, kind, DEV), h, DEV)
-
-
 def case_product(tmp):
     """A target whose recording starts and ends with 1 s of digital silence plus faint noise, one source, the small models."""
     from knn_svc_amd import matching, serving
@@ -123,10 +105,8 @@ def case_product(tmp):
     tgt = os.path.join(tmp, "tgt.wav")
     audio_io.write_wav_pcm16(tgt, np.concatenate([quiet(1), w, quiet(2)]), 16000)
     np.save(tgt[:-4] + "_f0.npy", (150.0 + np.arange((4 * 16000 + 123) // 320 + 1)).astype(np.float32))     # every frame its own value
-    ws, fs = S.synth_clip(16000 + 641, seed=700)
     src = os.path.join(tmp, "src.wav")
-    audio_io.write_wav_pcm16(src, ws, 16000)
-    np.save(src[:-4] + "_f0.npy", fs * 1.2)
+    write_clip(src, 16000 + 641, 700, f0_mul=1.2)
     vc = tiny_vc()
     vc.wavlm.set_layer_mix(matching._mix_of(vc.weighting, vc.wavlm))
     whole = matching.get_complete_spk_pool(tgt, vc.wavlm, vad_trigger_level=0)
@@ -172,24 +152,5 @@ def case_product(tmp):
          and serving.TargetVoice(vc, tgt).frames == n_whole)
 
 
-def main(out_path):
-    torch.cuda.set_device(0)
-    rc = 0
-    with torch.inference_mode(), tempfile.TemporaryDirectory() as tmp:
-        for name, fn in (("oracle", case_oracle), ("product", lambda: case_product(tmp))):
-            try:
-                fn()
-                torch.cuda.synchronize()
-            except Exception:          # nothing more is started on the GPU after an error: report what ran and stop
-                note(f"{name}/ran", False, traceback.format_exc()[-1500:])
-                print(traceback.format_exc(), file=sys.stderr)
-                rc = 1
-                break
-            note(f"{name}/ran", True)
-    with open(out_path, "w") as f:
-        json.dump(REPORT, f, indent=1)
-    return rc
-
-
 if __name__ == "__main__":
-    sys.exit(main(sys.argv[1]))
+    sys.exit(run_cases([("oracle", case_oracle), ("product", case_product)], sys.argv[1]))
