@@ -621,6 +621,53 @@ int knnsvc_shift_f0_seg_blend(const float* f0, const int64_t* host_seg, int32_t 
                               int32_t n_voices, const double* host_weights, float* shifted, float* shift_semitones,
                               void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Pitch correction (an extension; upstream has none): the shifted f0 of n_seg stacked segments snapped towards the notes of
+ * a key, behind knnsvc_shift_f0_seg[_mode|_blend] and in front of everything that reads the shifted track (f0 re-rank,
+ * pitched concat re-selection, vocoder).  This restatement is the specification.
+ * Per segment s:  x[i] fp32, the f0 as the shift returns it;  mask (int) 12 bits, bit k = pitch class k is allowed, C = 0;
+ * sigma (fp64) in [0, 1], the strength;  a (fp64) in (0, 1], the retune coefficient per frame;  log_ref (fp64), the natural
+ * log of the tuning frequency of A4.  mask == 0 or sigma == 0: the segment is OFF, its output is the input bit for bit and
+ * its notes are -1.  Constants: S = LN2 / 12 (the fp64 LN2 of "Pitch control"), H = 5, HYST = 0.25.  All arithmetic is fp64
+ * with contraction off, every step rounded on its own; the output is rounded once.
+ *   1. Pitched frames.  A frame is pitched iff 0 < x[i] < +inf.  Every other frame (0, NaN, negative, inf) keeps its bits,
+ *      gets note -1 and ends a run.  A run is a maximal stretch of consecutive pitched frames WITHIN ONE SEGMENT; nothing
+ *      below looks across a run's ends or a segment's ends.
+ *   2. Pitch in semitones.  l[i] = log((double)x[i]);  m[i] = (l[i] - log_ref) / S + 69.0.
+ *   3. Centre.  c[i] = the lower median (element (cnt - 1) / 2 of the sorted values) of m[lo..hi], lo = max(b, i - H),
+ *      hi = min(e - 1, i + H) for the run [b, e): selection only, no arithmetic.  It follows note steps and rides through
+ *      vibrato.
+ *   4. Note, sequential along the run.  near(c) = the integer k with bit ((k mod 12) + 12) mod 12 of mask set that minimises
+ *      |(double)k - c|; of two equally near, the lower.  n[b] = near(c[b]); for i > b, with cand = near(c[i]):
+ *      n[i] = cand if |c[i] - cand| + HYST < |c[i] - n[i-1]|, else n[i-1].  The hysteresis keeps vibrato from flipping
+ *      between two notes.
+ *   5. Correction, sequential along the run.  e[i] = (double)n[i] - m[i] (the raw pitch, not the centre);  g[b] = e[b],
+ *      g[i] = g[i-1] + a * (e[i] - g[i-1]).
+ *   6. Output.  y[i] = (float)exp(l[i] + (sigma * g[i]) * S);  notes[i] = n[i] (int32).
+ * a = 1 is a hard snap: every pitched frame lands on its note and vibrato is gone.  A small a (slow retune) moves each
+ * note's centre onto the grid and leaves vibrato alone.  A caller that thinks in milliseconds uses
+ * a = -expm1(-20 / retune_ms) in fp64 (20 ms frames; retune_ms = 0: a = 1).  The tie rules make the specification total; an
+ * exact tie cannot be reached from fp32 inputs through a log.
+ * knnsvc_tune_f0_seg: host_mask (int32), host_sigma, host_alpha, host_log_ref (double), each [n_seg], are HOST tables read
+ * by the call and handed to the kernel by value like host_seg (64 x 28 bytes beside the segment table).  out [total] may not
+ * be f0; notes (int32 [total]) may be NULL.  ws: knnsvc_tune_f0_workspace_bytes(total, n_seg) bytes, 8-byte aligned (32
+ * bytes per frame: m, c, g and the note between the phases).  One launch on `stream`, one workgroup per segment in three
+ * phases separated by workgroup barriers: (A) a thread per frame: m, the centre, near(c) and its distance; (B) the thread
+ * whose frame starts a run walks that run alone through 4 and 5 — runs side by side, the order inside a run is the
+ * specification's, so nothing depends on scheduling; (C) a thread per frame: the exponential.  No allocation, no
+ * synchronisation, no floating-point atomics, hipGraph-capturable.  A segment's output is bit-identical whether it is
+ * launched alone or stacked with others, and from call to call; an off segment is never read beyond copying its bits; rows
+ * outside the table are not written.
+ * Refused before the first HIP call, with a message: a bad table, a null table, a mask outside 0..0xFFF, a sigma that is not
+ * a number in [0, 1], an alpha that is not a number in (0, 1], a log_ref that is not finite (on and off segments alike), a
+ * null f0 / out / ws, out == f0, a misaligned workspace, a workspace below the size (KNNSVC_EWORKSPACE).  The size is 0,
+ * with a message, for n_seg outside 1..KNNSVC_MAX_SEGMENTS or fewer rows than segments.
+ * ------------------------------------------------------------------------------------------ */
+size_t knnsvc_tune_f0_workspace_bytes(int64_t n_total, int32_t n_seg);
+int knnsvc_tune_f0_seg(const float* f0, const int64_t* host_seg, int32_t n_seg, const int32_t* host_mask,
+                       const double* host_sigma, const double* host_alpha, const double* host_log_ref, float* out,
+                       int32_t* notes, void* ws, size_t ws_bytes, void* stream);
+
 /* out[i,:] = sum_k w[i,k] * pool[idx[i,k], :]   (ddsp_prematch_dataset.py:1358, 1444).  w NULL = uniform weights:
  * mean_mode 0 multiplies every row by 1.0f / k (softmax(ones), :1361-1364), mean_mode 1 sums in order and divides by k
  * (torch.mean, harmonics :1446); any k >= 1, the two are bit-identical when k is a power of two. */

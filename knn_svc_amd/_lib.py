@@ -165,6 +165,8 @@ SIGNATURES = {
     "knnsvc_time_scale_seg": (i32, [vp, i32, vp, vp, vp, vp, i32, vp, vp, vp]),
     "knnsvc_blend_seg": (i32, [vp, i32, i32, vp, i32, vp, vp, vp]),
     "knnsvc_shift_f0_seg_blend": (i32, [vp, vp, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp]),
+    "knnsvc_tune_f0_workspace_bytes": (sz, [i64, i32]),
+    "knnsvc_tune_f0_seg": (i32, [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
     "knnsvc_weighted_gather": (i32, [vp, vp, i64, i32, vp, i32, i32, i32, vp, vp]),
     "knnsvc_round_f16": (i32, [vp, i64, vp, vp]),
     "knnsvc_amp_ratio": (i32, [vp, i32, vp, i32, i64, vp, i64, i32, i32, vp, vp]),

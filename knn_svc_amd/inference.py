@@ -15,7 +15,10 @@ its peaks under a ceiling (where the limiter engages the loudness ends below the
 SECONDS (file mode only; upstream documents the argument and never delivers it) re-times the conversion to
 that length (matching.duration_plan; the file name does not change).  --blend_tgt PATH (file mode only, up to
 three times) adds target voices and --blend W0,W1[,...] weighs TGT and them: the conversion goes towards that mix
-(matcher.KNeighborsVC.blend_voices; the output is named <src>_to_<tgt>+<blend_tgt>..., without the weights).  --dur_limit is
+(matcher.KNeighborsVC.blend_voices; the output is named <src>_to_<tgt>+<blend_tgt>..., without the weights).  --tune SCALE
+("chromatic", "A:minor", "D:101011010101"; options.Tuning) snaps the converted f0 towards the notes of that key — the key of the
+OUTPUT —, with --tune_strength S (0..1), --retune_ms MS (0..2000; 0: hard snap) and --tuning_hz HZ (400..480) as its
+refinements, refused without --tune; no file name changes.  --dur_limit is
 compared in seconds, as upstream (ddsp_prematch_dataset.py:408-411).
 """
 from __future__ import annotations
@@ -84,6 +87,15 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--blend", type=_weights, default=None, metavar="W0,W1[,...]",
                     help="(extension, with --blend_tgt) the weights of TGT and of each --blend_tgt in order; normalised to sum "
                          "1 (default: equal)")
+    ap.add_argument("--tune", type=str, default=None, metavar="SCALE",
+                    help="(extension) pitch correction: snap the converted f0 towards the notes of this key, the key of the output: "
+                         "'chromatic', '<tonic>:<major|minor|harmonic_minor|pentatonic|minor_pentatonic|blues>' or "
+                         "'<tonic>:<twelve 0/1 from the tonic>'")
+    ap.add_argument("--tune_strength", type=float, default=None, metavar="S", help="(extension, with --tune) 0..1, default 1")
+    ap.add_argument("--retune_ms", type=float, default=None, metavar="MS",
+                    help="(extension, with --tune) time constant of the glide onto a note, 0..2000, default 80; 0 is a hard snap")
+    ap.add_argument("--tuning_hz", type=float, default=None, metavar="HZ",
+                    help="(extension, with --tune) the frequency of A4, 400..480, default 440")
     ap.add_argument("--weights", default="auto", choices=["auto", "checkpoint", "seeded"],
                     help="(extension) 'seeded' runs with random weights when the released checkpoints are unavailable")
     return ap
@@ -97,6 +109,18 @@ def output_dir_for(src: str, tgt: str, ckpt_type: str, post_opt: str, dur_limit)
     return out
 
 
+def tuning_of(a):
+    """The command line's --tune flags as an options.Tuning (None without --tune); ValueError for a bad value or a refinement
+    without --tune."""
+    from .options import Tuning
+    more = {k: v for k, v in (("strength", a.tune_strength), ("retune_ms", a.retune_ms), ("tuning_hz", a.tuning_hz)) if v is not None}
+    if a.tune is None:
+        if more:
+            raise ValueError("--tune_strength / --retune_ms / --tuning_hz refine --tune SCALE: give a scale")
+        return None
+    return Tuning(scale=a.tune, **more)
+
+
 def main(argv=None) -> int:
     ap = build_parser()
     a = ap.parse_args(argv)
@@ -108,6 +132,7 @@ def main(argv=None) -> int:
         ext = Extensions.from_reference(**knobs)           # before the models are loaded
         from .matching import refuse_duration_with_envelope, resolve_target_duration
         refuse_duration_with_envelope([resolve_target_duration(a.target_duration)], ext)
+        tune = tuning_of(a)
     except ValueError as e:
         ap.error(str(e))
     if (a.blend_tgt is not None or a.blend is not None) and os.path.isdir(a.src):
@@ -122,7 +147,8 @@ def main(argv=None) -> int:
     from .hubconf import knn_vc
     knn = knn_vc(pretrained=True, progress=True, prematched=True, device=a.device, ckpt_type=a.ckpt_type,
                  local_ckpt_dir=a.ckpt_dir, weights=a.weights)
-    common = dict(device=a.device, prioritize_f0=a.prioritize_f0, ckpt_type=a.ckpt_type, post_opt=a.post_opt, **knobs)
+    common = dict(device=a.device, prioritize_f0=a.prioritize_f0, ckpt_type=a.ckpt_type, post_opt=a.post_opt, **knobs,
+                  **({} if tune is None else dict(tune=tune)))
     if os.path.isfile(a.src) and os.path.isfile(a.tgt):
         knn.special_match(src_wav_file=a.src, ref_wav_file=a.tgt, target_duration=a.target_duration, blend_with=a.blend_tgt,
                           blend=a.blend, **common)

@@ -3,7 +3,7 @@
 Mirror of ddsp_matcher.py:303-1155 restricted to its live methods: ``vocode``
 (:375-406), ``special_match`` (:937-1023) and ``bulk_match`` (:1027-1155), with the
 same argument names and output file naming.  The arguments upstream accepts and drops (``topk``, ``tgt_loudness_db``,
-``vad_trigger_level``) and the ones it does not have (``f0_shift``, ``transpose``, ``envelope_mix``, ``peak_db``) are the
+``vad_trigger_level``) and the ones it does not have (``f0_shift``, ``transpose``, ``envelope_mix``, ``peak_db``, ``tune``) are the
 extension knobs: knn_svc_amd/options.py has the table of what each does and when it is ignored; every entry point below folds
 them into one ``options.Extensions`` first.  ``audio_io.save_audio`` keeps the reference's peak rule — a waveform whose peak
 exceeds 1 is divided by it — so a clip normalised past full scale is written lower than asked unless ``peak_db`` holds its
@@ -21,7 +21,7 @@ from pathlib import Path
 import torch
 
 from . import audio_io, config as C, dist as kdist, ops
-from .matching import load_utterance, match_at_inference_time, refuse_duration_with_envelope, resolve_target_duration
+from .matching import load_utterance, match_at_inference_time, refuse_duration_with_envelope, resolve_target_duration, resolve_tune
 from .options import Extensions
 from .vocoder import Vocoder
 from .wavlm import WavLMEncoder
@@ -115,8 +115,12 @@ class KNeighborsVC:
     def special_match(self, src_wav_file, ref_wav_file, topk: int = 4, device=None, prioritize_f0=True,
                       ckpt_type="wavlm_only", tgt_loudness_db=-16, post_opt="no_post_opt", save=True, normalize_loudness=False,
                       use_topk=False, use_vad=False, vad_trigger_level=7, f0_shift="median", transpose=0.0, envelope_mix=0.0,
-                      peak_db=None, target_duration=None, blend_with=None, blend=None):
-        """``target_duration`` (seconds, None: off): the conversion re-timed to that length — the waveform has
+                      peak_db=None, target_duration=None, blend_with=None, blend=None, tune=None):
+        """``tune`` (an options.Tuning, a scale such as "A:minor" or "chromatic", None: off): pitch correction — the shifted f0
+        is snapped towards the notes of that key, the OUTPUT's key, on the GPU inside the match stage (matching.resolve_tune;
+        options.py has the semantics); the file name does not change.  ``vocode`` does not take it: it starts behind the match
+        stage, where ops.tune_f0_seg serves such callers.
+        ``target_duration`` (seconds, None: off): the conversion re-timed to that length — the waveform has
         matching.duration_plan's T_out * 320 samples, the file name does not change; not with ``envelope_mix`` > 0.
         ``blend_with`` (one to three further reference files or folders) / ``blend`` (weights for ``[ref_wav_file, *blend_with]``,
         None: equal): the conversion goes towards that weighted mix of voices (``blend_voices``), through serving.TargetVoice and
@@ -124,6 +128,7 @@ class KNeighborsVC:
         ext = Extensions.from_reference(topk, use_topk, tgt_loudness_db, normalize_loudness, use_vad, vad_trigger_level, f0_shift,
                                         transpose, envelope_mix, peak_db)          # refused before a file is read
         refuse_duration_with_envelope([resolve_target_duration(target_duration)], ext)
+        tune = resolve_tune(tune)
         refs = self.blend_voices(ref_wav_file, blend_with, blend)
         f0only = "wavlm_only" in ckpt_type or "no_harm_no_amp" in ckpt_type
         if "wavlm_only_original" in ckpt_type:
@@ -131,7 +136,7 @@ class KNeighborsVC:
         if refs is not None:
             from . import serving
             voices = [serving.TargetVoice(self, r, vad_trigger_level=ext.vad_level) for r in refs]
-            conv = serving.BatchConverter(self, voices, ckpt_type, post_opt, ext=ext, blend=blend)
+            conv = serving.BatchConverter(self, voices, ckpt_type, post_opt, ext=ext, blend=blend, tune=tune)
             pred = conv.convert([str(src_wav_file)], target_duration=target_duration)[0]
             if save:
                 out_file = conv.output_path(src_wav_file)
@@ -142,7 +147,7 @@ class KNeighborsVC:
         # the reference does not forward post_opt to the f0-only generators (ddsp_matcher.py:970)
         res = match_at_inference_time(Path(src_wav_file), Path(ref_wav_file), self.wavlm, self.weighting, self.weighting,
                                       device=self.device, prioritize_f0=prioritize_f0, ckpt_type=ckpt_type, ext=ext,
-                                      target_duration=target_duration, **({} if f0only else dict(post_opt=post_opt)))
+                                      target_duration=target_duration, tune=tune, **({} if f0only else dict(post_opt=post_opt)))
         tail = Tail(self, f0only, ext)
         src = [torch.from_numpy(load_utterance(src_wav_file)[0])] if tail.needs_source else None
         pred = self._vocode(tail, res[0][key][None], res[-1][key][None, :, None], None if f0only else res[1][key][None], src).squeeze()
@@ -158,7 +163,7 @@ class KNeighborsVC:
     def many_to_one(self, src_files, ref_wav_file, converted_audio_dir=None, ckpt_type="mix", post_opt="post_opt_0.2",
                     duration_limit=None, target=None, match=None, loudness_db=None, topk=None, vad_trigger_level=None,
                     f0_shift=None, transpose=None, envelope_mix=None, peak_db=None, target_duration=None, blend_with=None,
-                    blend=None):
+                    blend=None, tune=None):
         """BASELINE cfg 5 (no counterpart upstream: the reference would call ``special_match`` once per source and rebuild the
         target pool each time, ddsp_matcher.py:937-1023): MANY sources against ONE target pool that is built once and stays
         resident, all sources through the stream pipeline as one batch (knn_svc_amd/serving.py).  Under a process group the
@@ -169,10 +174,13 @@ class KNeighborsVC:
         a list with one entry per source (None entries: off; serving.BatchConverter.convert).  ``blend_with`` (one to three
         further reference files or folders) / ``blend`` (weights for ``[ref_wav_file, *blend_with]``, None: equal): every source is
         converted towards that weighted mix of voices (``blend_voices``; each voice's pool is trimmed when ``vad_trigger_level``
-        is given); ``target`` is then a sequence of TargetVoice to reuse, and the outputs are named ``<src>_to_<idA>+<idB>[+...]``."""
+        is given); ``target`` is then a sequence of TargetVoice to reuse, and the outputs are named ``<src>_to_<idA>+<idB>[+...]``.
+        ``tune``: the pitch correction, one value for all sources or a list with one entry per source (an options.Tuning, a
+        scale, None / "off": none; serving.BatchConverter.convert)."""
         from . import serving
         ext = Extensions.from_serving(loudness_db, topk, vad_trigger_level, f0_shift, transpose, envelope_mix, peak_db)   # before a file is read
         refuse_duration_with_envelope(resolve_target_duration(target_duration, len(src_files)), ext)
+        resolve_tune(tune, len(src_files))
         # (voices handed in as ``target``: the converter checks the weights against them)
         refs = None if isinstance(target, (list, tuple)) else self.blend_voices(ref_wav_file, blend_with, blend)
         if target is None:
@@ -181,17 +189,22 @@ class KNeighborsVC:
         mine = kdist.my_share([str(p) for p in src_files])
         if isinstance(target_duration, (list, tuple)):        # this rank's sources' own entries
             target_duration = kdist.my_share(list(target_duration))
+        if isinstance(tune, (list, tuple)):
+            tune = kdist.my_share(list(tune))
         written = serving.BatchConverter(self, target, ckpt_type, post_opt, match=match, ext=ext, blend=blend).convert_files(
-            mine, converted_audio_dir, target_duration=target_duration)
+            mine, converted_audio_dir, target_duration=target_duration, tune=tune)
         return kdist.gather_paths(written)
 
     @torch.inference_mode()
     def bulk_match(self, src_dataset_path, tgt_dataset_path, converted_audio_dir, topk: int = 4, device=None,
                    prioritize_f0=True, ckpt_type="mix", tgt_loudness_db=-16, required_subset_file=None,
                    post_opt="no_post_opt", duration_limit=None, normalize_loudness=False, use_topk=False, use_vad=False,
-                   vad_trigger_level=7, f0_shift="median", transpose=0.0, envelope_mix=0.0, peak_db=None):
+                   vad_trigger_level=7, f0_shift="median", transpose=0.0, envelope_mix=0.0, peak_db=None, tune=None):
+        """``tune`` (an options.Tuning, a scale, None: off): pitch correction of every utterance's shifted f0 towards that key
+        (``special_match``)."""
         ext = Extensions.from_reference(topk, use_topk, tgt_loudness_db, normalize_loudness, use_vad, vad_trigger_level, f0_shift,
                                         transpose, envelope_mix, peak_db)          # refused before a file is read
+        tune = resolve_tune(tune)
         assert os.path.isdir(src_dataset_path) and os.path.isdir(tgt_dataset_path)
         Path(converted_audio_dir).mkdir(parents=True, exist_ok=True)
         spk = lambda root: sorted([p for p in Path(root).iterdir() if p.is_dir() and "f0_cache" not in os.path.basename(p)])
@@ -236,7 +249,7 @@ class KNeighborsVC:
                                         prioritize_f0=prioritize_f0, ckpt_type=ckpt_type, src_dataset_path=src_dataset_path,
                                         tgt_dataset_path=tgt_dataset_path, required_subset=required, duration_limit=duration_limit,
                                         pool_sharded=shard, share_items=shard, ext=ext, vocode_fn=Tail(self, f0only, ext),
-                                        waves_out=preds, **({} if f0only else dict(post_opt=post_opt)))
+                                        waves_out=preds, tune=tune, **({} if f0only else dict(post_opt=post_opt)))
                 if preds:      # max |x| of a waveform is NaN / inf iff the waveform holds one
                     self._check_finite(torch.stack([p.abs().max() for p in preds.values()]))
                 for k, pred in preds.items():

@@ -5,8 +5,9 @@ Host-side mirror of the reference's ``get_complete_spk_pool`` and
 arguments, same returned dict-of-tensors keyed by ``str(path)``, same quirks
 (k hard-coded to 32 -> first 4, ``--dur_limit`` in seconds overshooting by one file,
 ``post_opt`` parsing, ``prioritize_f0`` must be True, pool rebuilt per call).
-``topk``, ``vad_trigger_level`` (accepted and dropped upstream), ``f0_shift`` and ``transpose`` are extension knobs:
-knn_svc_amd/options.py has the table; ``resolve_topk`` / ``resolve_f0_shift`` / ``resolve_dynamics`` below are its checks.
+``topk``, ``vad_trigger_level`` (accepted and dropped upstream), ``f0_shift``, ``transpose`` and ``tune`` are extension knobs:
+knn_svc_amd/options.py has the tables; ``resolve_topk`` / ``resolve_f0_shift`` / ``resolve_dynamics`` / ``resolve_tune`` below are
+their checks.
 All arithmetic is done by libknnsvc_hip.so kernels on device-resident tensors; the
 only host work is file I/O and the chunk bookkeeping.
 """
@@ -22,7 +23,7 @@ import numpy as np
 import torch
 
 from . import audio_io, config as C, dist as kdist, features, ops, pipeline, pool_cache
-from .options import Extensions, SourceKnobs, per_item
+from .options import TUNE_OFF, Extensions, SourceKnobs, Tuning, per_item
 from .wavlm import WavLMEncoder, chunk_plan
 
 AUDIO_EXT = {".flac", ".wav", ".mp3"}
@@ -554,6 +555,39 @@ def refuse_blend_when_sharded():
         raise ValueError("a voice blend cannot be combined with KNNSVC_POOL_SHARD=1 (the pools of a blend are not sharded)")
 
 
+# Pitch correction (an extension; include/knnsvc_hip.h "Pitch correction" is the specification): the SHIFTED f0 of an item snapped
+# towards the notes of a key (ops.tune_f0_seg), right behind the f0 shift and in front of the f0 re-rank, so that the neighbour
+# selection, the pitched re-selection and the vocoder all see the corrected contour.  The key is the key of the OUTPUT: correction
+# follows the shift, ``transpose``, a blend's one shift and ``target_duration``'s re-timing (``retune_ms`` runs in output time).  With
+# "median" the interval is an arbitrary real number and correction is what puts the result on a grid; with "semitone" / "octave" /
+# "none" plus a whole ``transpose`` the output's key is the source's key moved by that interval.  A key belongs to a song, that is,
+# to a source item: a field of options.SourceKnobs, not of options.Extensions.
+def _one_tune(value):
+    if value is None or isinstance(value, Tuning):        # (a Tuning is checked when it is built)
+        return value
+    if isinstance(value, str):
+        return TUNE_OFF if value.strip().lower() == "off" else Tuning(scale=value)
+    raise ValueError(f"tune must be an options.Tuning, a scale such as 'chromatic' or 'A:minor', 'off' or None, got {value!r}")
+
+
+def resolve_tune(value, n_items=None):
+    """``tune`` checked, refused (ValueError) before any file or device work when it is not valid.  None -> None (nothing of its
+    own: the converter's default, or off); "off" -> options.TUNE_OFF, an explicit off for that item; any other string ->
+    ``Tuning(scale=...)`` with the default strength, retune time and tuning frequency; a ``Tuning`` -> itself.  ``n_items`` None:
+    one value.  ``n_items`` = the number of items of a batch: one value for all items or a list / tuple with one entry per item
+    -> a list of n_items entries."""
+    if n_items is None:
+        if isinstance(value, (list, tuple)):
+            raise ValueError("tune: a single value expected here, not a list")
+        return _one_tune(value)
+    return per_item(value, n_items, "tune", _one_tune)
+
+
+def tune_active(tunings) -> bool:
+    """Whether any entry of a resolved ``tune`` list asks for a correction (an entry that is None or off does not)."""
+    return any(t is not None and t.on for t in tunings)
+
+
 def resolve_dynamics(envelope_mix, peak_db):
     """The two output-dynamics switches as the library takes them, refused before any device or file work when they are not
     valid -> (a, p).  ``envelope_mix``: a number in [0, 1], None = 0 (off): how much of the source's volume envelope the tail
@@ -570,15 +604,16 @@ def resolve_dynamics(envelope_mix, peak_db):
 
 def match_features(query_seq, query_f0, matching_list, matching_f0, harmonics_list, ckpt_type, post_opt,
                    return_debug=False, nn32=None, nan_flags=None, pool_prep=None, synth_list=None, topk=None,
-                   f0_shift=None, transpose=None):
+                   f0_shift=None, transpose=None, tune=None):
     """The per-query body (ddsp_prematch_dataset.py:1189-1450) on device tensors: ``match_features_many`` (below, where the
     arguments are described) of one utterance.  ``nn32`` may carry neighbours already found by the pool-sharded search
     (knn_svc_amd.dist.sharded_knn); in the debug dict ``iters_*`` are one-element tensors, or 0 without the Adam stage."""
     resolve_f0_shift(f0_shift, transpose)     # one value each
+    resolve_tune(tune)
     return match_features_many([query_seq], [query_f0], matching_list, matching_f0, harmonics_list, ckpt_type, post_opt,
                                nn32s=None if nn32 is None else [nn32], nan_flags=nan_flags, pool_prep=pool_prep,
                                synth_list=synth_list, return_debug=return_debug, topk=topk, f0_shift=f0_shift,
-                               transpose=transpose)[0]
+                               transpose=transpose, tune=tune)[0]
 
 
 # How the match stage of SEVERAL items is put on the chip: "lanes" (one match_features per item on the lane streams, the default) or
@@ -617,7 +652,7 @@ def _split(t, lens):
 
 def match_features_many(query_seqs, query_f0s, matching_list, matching_f0, harmonics_list, ckpt_type, post_opt, nn32s=None,
                         nan_flags=None, pool_prep=None, synth_list=None, return_debug=False, topk=None, f0_shift=None,
-                        transpose=None):
+                        transpose=None, tune=None):
     """The per-query body (ddsp_prematch_dataset.py:1189-1450) for several query utterances against one pool, run ONCE over their
     stacked frames -> a list of per-item tuples (out_feats, harm or None, shifted_f0[, debug dict]) (views of the stacked outputs).
     The row-wise stages (row norms, f0 re-rank, weighted sums) take the stacked rows as they are; the per-sequence stages (median,
@@ -631,9 +666,15 @@ def match_features_many(query_seqs, query_f0s, matching_list, matching_f0, harmo
     ``f0_shift`` / ``transpose``: how each item's f0 is moved (F0_SHIFT_MODES; a value for all items or a list with one per item;
     None = "median" / 0).  The interval is chosen per item on the device (ops.shift_f0_seg with modes): no host read of the
     medians; the defaults are the same call with the median / 0 tables.  The debug dict carries ``shift_semitones``: the interval
-    applied to the item (a one-element device tensor)."""
+    applied to the item (a one-element device tensor).
+    ``tune``: the pitch correction of each item (``resolve_tune``'s argument: a value for all items or one per item; None / "off":
+    none).  When any item has one, the shifted f0 goes through ops.tune_f0_seg right behind the shift, on the side stream, so the
+    re-rank, the pitched concat re-selection and the returned f0 (the vocoder's) all see the corrected contour; otherwise nothing
+    is launched.  The debug dict carries ``tuned_notes``: the item's int32 note per frame (-1: not corrected), None when off;
+    ``shift_semitones`` stays the shift's interval."""
     topk = resolve_topk(topk)                 # before any device work
     shift_modes, shift_ts = resolve_f0_shift(f0_shift, transpose, len(query_seqs))
+    tunings = resolve_tune(tune, len(query_seqs))
     lens = [int(q.shape[0]) for q in query_seqs]
     seg = ops.Segments.of_lengths(lens)       # the host tables once for the six segmented calls
     q = _stacked(query_seqs)
@@ -662,6 +703,10 @@ def match_features_many(query_seqs, query_f0s, matching_list, matching_f0, harmo
         qmed, pmed = ops.log_f0_median_seg(query_f0, seg), ops.log_f0_median(matching_f0)      # the pool's median once
         shifted = ops.shift_f0_seg(query_f0, seg, qmed, pmed, shift_modes, shift_ts, return_shift=return_debug)
         shifted, semis = shifted if return_debug else (shifted, None)
+        notes = None
+        if tune_active(tunings):
+            shifted = ops.tune_f0_seg(shifted, seg, tunings, return_notes=return_debug)
+            shifted, notes = shifted if return_debug else (shifted, None)
         ranked = ops.f0_rerank(nn32, shifted, matching_f0)
         idx2 = ranked[:, :topk].contiguous()
         if cw != -1:
@@ -678,7 +723,7 @@ def match_features_many(query_seqs, query_f0s, matching_list, matching_f0, harmo
         w, it1 = ops.smooth_weights_seg(idx, seg, Ps, 0.1, return_iters=True)
     out_feats = ops.weighted_gather(idx, w, Ps)                                      # without Adam: softmax(ones) (:1361-1364)
     main.wait_stream(side)
-    for t in (shifted, semis, idx2, harm_w, w2, it2):
+    for t in (shifted, semis, notes, idx2, harm_w, w2, it2):
         if t is not None:
             t.record_stream(main)
     if nan_flag is not None:
@@ -691,22 +736,22 @@ def match_features_many(query_seqs, query_f0s, matching_list, matching_f0, harmo
                 with ops.fused_off():
                     return match_features_many(query_seqs, query_f0s, matching_list, matching_f0, harmonics_list, ckpt_type, post_opt,
                                                pool_prep=pool_prep, synth_list=synth_list, return_debug=return_debug, topk=topk,
-                                               f0_shift=f0_shift, transpose=transpose)
+                                               f0_shift=f0_shift, transpose=transpose, tune=tune)
     out = []
-    dbg = [_split(t, lens) for t in (nn32, idx, w, idx2, w2)]
+    dbg = [_split(t, lens) for t in (nn32, idx, w, idx2, w2, notes)]
     for i, (of, hw, sf) in enumerate(zip(_split(out_feats, lens), _split(harm_w, lens), _split(shifted, lens))):
         if return_debug:
             out.append((of, hw, sf, dict(nn32=dbg[0][i], idx_wavlm=dbg[1][i], w_wavlm=dbg[2][i], idx_harm=dbg[3][i], w_harm=dbg[4][i],
                                          iters_wavlm=it1[i:i + 1] if it1 is not None else 0,
                                          iters_harm=it2[i:i + 1] if it2 is not None else 0,
-                                         shift_semitones=semis[i:i + 1])))
+                                         shift_semitones=semis[i:i + 1], tuned_notes=dbg[5][i])))
         else:
             out.append((of, hw, sf))
     return out
 
 
 def match_features_blend(query_seqs, query_f0s, voices, weights, ckpt_type, post_opt, nn32s=None, nan_flags=None, topk=None,
-                         f0_shift=None, transpose=None):
+                         f0_shift=None, transpose=None, tune=None):
     """``match_features_many`` towards a weighted mix of 2..BLEND_MAX_VOICES ``voices`` (serving.TargetVoice, or anything with
     ``feats`` / ``f0`` / ``harm`` and optionally ``prep`` / ``synth``: ``match_bodies``) -> the same list of
     per-item tuples (out_feats, harm or None, shifted_f0).  ``weights``: ``resolve_blend``'s argument (one vector for all items or
@@ -716,9 +761,12 @@ def match_features_blend(query_seqs, query_f0s, voices, weights, ckpt_type, post
     no harmonics), then ONE ops.shift_f0_seg_blend: the returned f0 is the source's, shifted once towards the weighted mean of the
     voices' log medians (the per-voice shifted tracks are used inside each voice's match only).  A voice whose weight is 0 for
     every item is not matched.  ``nn32s``: per voice, the per-item neighbour lists of ``match_features_many`` (or None).  NaN
-    flags and the overflow retry work per voice, as there."""
+    flags and the overflow retry work per voice, as there.  ``tune``: as there, inside every voice's match (each on that voice's
+    shifted track) and, through one more ops.tune_f0_seg, on the returned f0: the blend's one shift, corrected."""
     rows = resolve_blend(weights, len(voices), len(query_seqs))      # before any device work
     resolve_topk(topk)
+    tunings = resolve_tune(tune, len(query_seqs))
+    tuned = dict(tune=tunings) if tune_active(tunings) else {}
     shift_modes, shift_ts = resolve_f0_shift(f0_shift, transpose, len(query_seqs))
     live = [v for v in range(len(voices)) if any(r[v] != 0.0 for r in rows)]
     per = {}
@@ -726,7 +774,7 @@ def match_features_blend(query_seqs, query_f0s, voices, weights, ckpt_type, post
         vo = voices[v]
         per[v] = match_features_many(query_seqs, query_f0s, vo.feats, vo.f0, vo.harm, ckpt_type, post_opt,
                                      nn32s=None if nn32s is None else nn32s[v], nan_flags=nan_flags, pool_prep=getattr(vo, "prep", None),
-                                     synth_list=getattr(vo, "synth", None), topk=topk, f0_shift=f0_shift, transpose=transpose)
+                                     synth_list=getattr(vo, "synth", None), topk=topk, f0_shift=f0_shift, transpose=transpose, **tuned)
     lens = [int(q.shape[0]) for q in query_seqs]
     seg = ops.Segments.of_lengths(lens)
     # a voice that was not matched has weight 0 in every row: its pointer is never read, any live voice's stands in
@@ -741,6 +789,8 @@ def match_features_blend(query_seqs, query_f0s, voices, weights, ckpt_type, post
     meds = {v: ops.log_f0_median(voices[v].f0) for v in live}
     pmeds = torch.stack([meds.get(v, meds[live[0]]) for v in range(len(voices))]).contiguous()
     shifted = ops.shift_f0_seg_blend(query_f0, seg, qmed, pmeds, rows, shift_modes, shift_ts)
+    if tuned:
+        shifted = ops.tune_f0_seg(shifted, seg, tunings)
     return list(zip(_split(out_feats, lens), _split(harm, lens), _split(shifted, lens)))
 
 
@@ -751,7 +801,8 @@ def match_bodies(query_of, voices, ckpt_type, post_opt, found, flags, knobs, top
     (``match_features_blend``, on both routes).  ``found``: per voice, ``(nn: item -> neighbour list, ready: item -> event)`` of the
     searches already enqueued (``grouped_knn``); an item not in ``nn`` is searched inside its match.  ``flags``: receives the
     deferred NaN flags.  ``knobs(item)`` -> the item's options.SourceKnobs: its ``f0_shift`` / ``transpose`` and, for a blend, its
-    weight row."""
+    weight row, and its ``tune`` (handed on only when an item of the batch has one that is on: without it the match functions are
+    called as they always were)."""
     dev = voices[0].feats.device
 
     def match(batch, alone):
@@ -762,16 +813,18 @@ def match_bodies(query_of, voices, ckpt_type, post_opt, found, flags, knobs, top
         qs, f0s = (list(t) for t in zip(*(query_of(i) for i in batch)))
         ks = [knobs(i) for i in batch]
         modes, semis = [k.f0_shift for k in ks], [k.transpose for k in ks]
+        tunes = [k.tune for k in ks]
+        tuned = tune_active(tunes)
         if len(voices) > 1:
             return match_features_blend(qs, f0s, voices, [k.blend for k in ks], ckpt_type, post_opt, nn32s=nn32s, nan_flags=flags,
-                                        topk=topk, f0_shift=modes, transpose=semis)
+                                        topk=topk, f0_shift=modes, transpose=semis, **(dict(tune=tunes) if tuned else {}))
         vo = voices[0]
         pool = dict(nan_flags=flags, pool_prep=getattr(vo, "prep", None), synth_list=getattr(vo, "synth", None), topk=topk)
         if alone:              # (through the module global: the CPU tests put their stand-in there)
             return [match_features(qs[0], f0s[0], vo.feats, vo.f0, vo.harm, ckpt_type, post_opt, nn32=nn32s[0][0], f0_shift=modes[0],
-                                   transpose=semis[0], **pool)]
+                                   transpose=semis[0], **(dict(tune=tunes[0]) if tuned else {}), **pool)]
         return match_features_many(qs, f0s, vo.feats, vo.f0, vo.harm, ckpt_type, post_opt, nn32s=nn32s[0], f0_shift=modes,
-                                   transpose=semis, **pool)
+                                   transpose=semis, **(dict(tune=tunes) if tuned else {}), **pool)
     return (lambda item: match([item], True)[0]), (lambda batch: match(batch, False))
 
 
@@ -824,7 +877,7 @@ def match_at_inference_time(src_wav_file, ref_wav_file, wavlm: WavLMEncoder, mat
                             src_dataset_path=None, tgt_dataset_path=None, cache_dir=None, required_subset=None,
                             post_opt="no_post_opt", duration_limit=None, vocode_fn=None, waves_out=None,
                             pool_sharded=None, share_items=False, use_topk=False, use_vad=False, vad_trigger_level=7,
-                            f0_shift="median", transpose=0.0, ext=None, target_duration=None):
+                            f0_shift="median", transpose=0.0, ext=None, target_duration=None, tune=None):
     """Same contract as the reference function (ddsp_prematch_dataset.py:1074).  ``cache_dir`` is ignored (the reference
     force-disables it, :1086-1087).  ``topk`` (k = 32 -> 4 is hard-coded upstream, :1203,1246,1398) / ``use_topk``,
     ``vad_trigger_level`` (upstream passes 7 for the target pool, :1131, to a function that drops it) / ``use_vad``, ``f0_shift``
@@ -833,6 +886,8 @@ def match_at_inference_time(src_wav_file, ref_wav_file, wavlm: WavLMEncoder, mat
     (seconds, None: off; single source file only — with ``src_dataset_path`` a value is refused): the source's features and f0
     are re-timed to that length right behind the encoder (``stretch_queries``), in front of everything of the match stage, so
     the returned tensors have ``duration_plan``'s T_out frames; not to be combined with ``envelope_mix`` > 0.
+    ``tune`` (``resolve_tune``: an options.Tuning, a scale, "off" or None; one value): every source item's shifted f0 is snapped
+    towards that key inside its match (``match_features_many``); the returned f0 is the corrected one.
 
     Build extension (BASELINE cfg 5, many sources against one pool): ``vocode_fn(out_feats, shifted_f0, harm)`` is
     enqueued as the pipeline's tail stage right behind each item's match body and its waveform stored in
@@ -856,6 +911,7 @@ def match_at_inference_time(src_wav_file, ref_wav_file, wavlm: WavLMEncoder, mat
         ext = Extensions.from_reference(topk=topk, use_topk=use_topk, use_vad=use_vad, vad_trigger_level=vad_trigger_level,
                                         f0_shift=f0_shift, transpose=transpose)
     target_duration = resolve_target_duration(target_duration)
+    tune = resolve_tune(tune)
     if target_duration is not None and src_dataset_path is not None:
         raise ValueError("target_duration applies to a single source file: one duration for a dataset of utterances means nothing")
     refuse_duration_with_envelope([target_duration], ext)
@@ -962,7 +1018,7 @@ def match_at_inference_time(src_wav_file, ref_wav_file, wavlm: WavLMEncoder, mat
             g_nn, g_ready = grouped_knn(items, query_pool, matching_list, prep, flags)
             nn.update(g_nn); nn_ready.update(g_ready)
         voice = types.SimpleNamespace(feats=matching_list, f0=matching_f0, harm=harmonics_list, prep=prep, synth=synth_list)
-        own = SourceKnobs(f0_shift=ext.f0_shift, transpose=ext.transpose)          # (checked with the record)
+        own = SourceKnobs(f0_shift=ext.f0_shift, transpose=ext.transpose, tune=tune)          # (checked with the record)
         body, body_many = match_bodies(lambda it: (query_pool[it], query_f0_pool[it]), [voice], ckpt_type, post_opt, [(nn, nn_ready)],
                                        flags, lambda it: own, topk=ext.topk)
         # match bodies in flight at once (each is a chain of single-workgroup recurrences: more lanes = more of them side by side);

@@ -1110,6 +1110,44 @@ def shift_f0_seg_blend(f0, seg, qmed, pmeds, weights, modes=None, transposes=Non
     return _shift_f0_seg("shift_f0_seg_blend", f0, seg, qmed, pmeds, modes, transposes, return_shift, weights)
 
 
+def tune_f0_seg(f0, seg, tunings, return_notes=False):
+    """Pitch correction of the stacked, shifted f0 (knnsvc_tune_f0_seg; include/knnsvc_hip.h "Pitch correction" is the
+    specification).  ``tunings``: one options.Tuning or None (off) per segment -> the corrected f0, a new tensor; with
+    ``return_notes`` -> (f0, int32 notes, -1 where nothing was corrected).  One launch per 64 segments; a run of 64 whose segments
+    are all off is not launched (its rows are copied), and when every segment is off the INPUT TENSOR ITSELF comes back (notes:
+    None) and nothing is launched, loaded or checked beyond the count.  Enqueue only."""
+    n_seg = seg.n if isinstance(seg, Segments) else len(seg) - 1
+    tunings = list(tunings)
+    if len(tunings) != n_seg:
+        raise KnnSvcError(f"tune_f0_seg: {len(tunings)} tunings for {n_seg} segments")
+    live = [t is not None and t.on for t in tunings]
+    if not any(live):
+        return (f0, None) if return_notes else f0
+    _need(f0, name="f0"); seg = _segments(seg, "tune_f0_seg", f0)
+    if f0.dim() != 1:
+        raise KnnSvcError(f"tune_f0_seg: f0 must be [rows], got {tuple(f0.shape)}")
+    f0 = f0.contiguous()
+    out = torch.empty_like(f0)
+    notes = torch.empty(f0.numel(), device=f0.device, dtype=torch.int32) if return_notes else None
+    lib = _lib.load()
+    off = (0, 0.0, 1.0, math.log(440.0))
+    for a, r0, tab in seg.chunks:
+        n = len(tab) - 1
+        r1 = r0 + tab[n]
+        if not any(live[a:a + n]):
+            out[r0:r1].copy_(f0[r0:r1])
+            if return_notes:
+                notes[r0:r1].fill_(-1)
+            continue
+        rows = [(t.mask, t.strength, t.alpha, t.log_ref) if on else off for t, on in zip(tunings[a:a + n], live[a:a + n])]
+        ws_bytes = lib.knnsvc_tune_f0_workspace_bytes(tab[n], n)
+        ws = torch.empty(ws_bytes, device=f0.device, dtype=torch.uint8)
+        check(lib.knnsvc_tune_f0_seg(_p(f0[r0:]), tab, n, (C.c_int32 * n)(*[r[0] for r in rows]), (C.c_double * n)(*[r[1] for r in rows]),
+                                     (C.c_double * n)(*[r[2] for r in rows]), (C.c_double * n)(*[r[3] for r in rows]), _p(out[r0:]),
+                                     _p(notes[r0:]) if return_notes else None, _p(ws), ws_bytes, _stream()), "tune_f0_seg")
+    return (out, notes) if return_notes else out
+
+
 def weighted_gather(idx4, w, pool, mean=False):
     """sum_k w[i, k] * pool[idx4[i, k]].  ``w`` None = uniform weights: each row times 1.0f / k (softmax(ones)), or with ``mean`` the
     sum in order divided by k (torch.mean); the same bits when k is a power of two."""

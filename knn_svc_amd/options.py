@@ -29,6 +29,8 @@ record — the promise above about lengths holds because of that — but in ``So
 """
 from __future__ import annotations
 
+import math
+import numbers
 from dataclasses import dataclass
 
 
@@ -60,6 +62,83 @@ class Extensions:
                                 envelope_mix=envelope_mix, peak_db=peak_db)
 
 
+TUNE_TONICS = {"c": 0, "c#": 1, "db": 1, "d": 2, "d#": 3, "eb": 3, "e": 4, "f": 5, "f#": 6, "gb": 6, "g": 7, "g#": 8, "ab": 8,
+               "a": 9, "a#": 10, "bb": 10, "b": 11}
+# scale name -> the twelve pitch classes from the tonic upwards, '1' = allowed
+TUNE_SCALES = {"major": "101011010101", "minor": "101101011010", "harmonic_minor": "101101011001", "pentatonic": "101010010100",
+               "minor_pentatonic": "100101010010", "blues": "100101110010"}
+TUNE_FRAME_MS = 20.0          # the frame period of the f0 track (hop 320 at 16 kHz)
+
+
+def scale_mask(scale) -> int:
+    """A scale as the library's 12-bit mask (bit k: pitch class k is allowed, C = 0).  Case-insensitive: ``"chromatic"``,
+    ``"<tonic>:<name>"`` (TUNE_TONICS, TUNE_SCALES) or ``"<tonic>:<twelve 0/1 characters>"``, the first of them the tonic, the
+    pattern rotated by the tonic into the C-based mask.  ValueError for anything else, a pattern without a 1 included."""
+    if not isinstance(scale, str):
+        raise ValueError(f"tune: a scale is a string such as 'chromatic', 'A:minor' or 'D:101011010101', got {scale!r}")
+    text = scale.strip().lower()
+    if text == "chromatic":
+        return 0xFFF
+    tonic, sep, name = text.partition(":")
+    if not sep or tonic not in TUNE_TONICS:
+        raise ValueError(f"tune: scale {scale!r} is neither 'chromatic' nor '<tonic>:<name or twelve 0/1>' with a tonic out of "
+                         f"{' '.join(t.capitalize() for t in TUNE_TONICS)}")
+    pattern = TUNE_SCALES.get(name, name)
+    if len(pattern) != 12 or set(pattern) - {"0", "1"}:
+        raise ValueError(f"tune: scale {scale!r}: {name!r} is neither one of {tuple(TUNE_SCALES)} nor twelve 0/1 characters")
+    if "1" not in pattern:
+        raise ValueError(f"tune: scale {scale!r} allows no pitch class")
+    mask = 0
+    for j, ch in enumerate(pattern):
+        if ch == "1":
+            mask |= 1 << ((TUNE_TONICS[tonic] + j) % 12)
+    return mask
+
+
+def _number(value, name, lo, hi):
+    """``value`` as a float in [lo, hi]; no bools or strings where numbers go."""
+    if isinstance(value, bool) or not isinstance(value, numbers.Real) or not lo <= float(value) <= hi:      # (NaN compares false)
+        raise ValueError(f"tune: {name} must be a number in [{lo:g}, {hi:g}], got {value!r}")
+    return float(value)
+
+
+@dataclass(frozen=True)
+class Tuning:
+    """Pitch correction of one source item (include/knnsvc_hip.h "Pitch correction" is the specification): the key and scale the
+    OUTPUT is snapped towards, how far (``strength`` in [0, 1]; 0: off), how fast (``retune_ms`` in [0, 2000]: the time constant
+    of the glide onto a note; 0: a hard snap that also removes vibrato, 80 and more leave vibrato alone) and the frequency of
+    A4 (``tuning_hz`` in [400, 480]).  Checked on construction, so holding one means the values are valid.  ``mask``, ``alpha`` and
+    ``log_ref`` are what the library takes."""
+    scale: str
+    strength: float = 1.0
+    retune_ms: float = 80.0
+    tuning_hz: float = 440.0
+
+    def __post_init__(self):
+        scale_mask(self.scale)
+        for name, lo, hi in (("strength", 0.0, 1.0), ("retune_ms", 0.0, 2000.0), ("tuning_hz", 400.0, 480.0)):
+            object.__setattr__(self, name, _number(getattr(self, name), name, lo, hi))
+
+    @property
+    def mask(self) -> int:
+        return scale_mask(self.scale)
+
+    @property
+    def alpha(self) -> float:
+        return 1.0 if self.retune_ms == 0 else -math.expm1(-TUNE_FRAME_MS / self.retune_ms)
+
+    @property
+    def log_ref(self) -> float:
+        return math.log(self.tuning_hz)
+
+    @property
+    def on(self) -> bool:
+        return self.strength > 0
+
+
+TUNE_OFF = Tuning("chromatic", strength=0.0)      # "off" for an item under a converter whose default is on
+
+
 @dataclass(frozen=True)
 class SourceKnobs:
     """What one source item of a batch carries besides its audio; None: the converter's default, or off.  Built only by the
@@ -76,11 +155,27 @@ class SourceKnobs:
     a sequence of ``TargetVoice`` and a default ``blend``, ``BatchConverter.convert`` and ``RequestQueue.submit`` a ``blend`` per
     source.  Its check is ``matching.resolve_blend``, which also normalises; every knob of ``Extensions`` acts on a blend as on a
     single target (the pitch knobs and ``topk`` inside every voice's match and in the one f0 shift, the tail on the blended
-    frames)."""
+    frames).
+
+    ``tune`` holds the pitch correction (a ``Tuning``; None: the converter's default, or off): a key belongs to a song, that is,
+    to a source item.  ``special_match``, ``bulk_match``, ``many_to_one`` and ``match_at_inference_time`` take ``tune=``,
+    ``BatchConverter(tune=)`` holds the default beside its default blend, ``BatchConverter.convert`` and ``RequestQueue.submit``
+    take one per source ("off" switches a default off).  Its check is ``matching.resolve_tune``.
+
+      field          off (default)       on                                                                    where it acts
+      tune           None                a Tuning, or its scale as a string ("chromatic", "A:minor",           match stage, behind the f0
+                                         "D:101011010101"): the shifted f0 is snapped towards the notes of     shift (ops.tune_f0_seg)
+                                         that key on the GPU; f0 re-rank, pitched re-selection and vocoder
+                                         all see the corrected contour
+    The key is the key of the OUTPUT: correction follows the shift, ``transpose``, a blend's one shift and
+    ``target_duration``'s re-timing, so ``retune_ms`` runs in output time.  With ``f0_shift="median"`` the interval is an
+    arbitrary real number and correction is what puts the result on a grid; with "semitone" / "octave" / "none" plus a whole
+    ``transpose`` the output's key is the source's key moved by that interval."""
     f0_shift: str | None = None
     transpose: float | None = None
     target_duration: float | None = None
     blend: tuple | None = None
+    tune: Tuning | None = None
 
 
 def per_item(value, n, name, one=lambda v: v, default=None, is_list=None, unit="values"):

@@ -95,7 +95,7 @@ class BatchConverter:
                  max_encode_batch: int = 32, match: str | None = None, match_batch: int | None = None,
                  loudness_db: float | None = None, topk: int | None = None, f0_shift: str | None = None,
                  transpose: float | None = None, envelope_mix: float | None = None, peak_db: float | None = None,
-                 ext: Extensions | None = None, blend=None):
+                 ext: Extensions | None = None, blend=None, tune=None):
         # ``target``: one TargetVoice, or a sequence of 2 to 4 of them: the sources are then converted towards a weighted mix of
         # those voices (matching.match_features_blend; include/knnsvc_hip.h "Voice blend"), ``blend`` being the weights a source
         # gets unless a request says otherwise (blend_of; None: equal weights).  Refused before anything else: a sequence of
@@ -108,6 +108,9 @@ class BatchConverter:
         else:
             self.blend = M.resolve_blend(blend, len(self.voices))
             M.refuse_blend_when_sharded()
+        # ``tune``: the pitch correction a source gets unless a request says otherwise (tune_of; an options.Tuning, a scale such as
+        # "A:minor", or None / "off": none; include/knnsvc_hip.h "Pitch correction")
+        self.tune = M.resolve_tune(tune)
         # the extension knobs, checked before anything else (options.py; None: off): ``loudness_db``, ``envelope_mix`` and
         # ``peak_db`` are part of the tail, on the tail's stream, enqueue-only, and apply to every request of a RequestQueue in
         # front of this converter; ``f0_shift`` / ``transpose`` are what a source gets unless a request says otherwise (pitch_of).
@@ -195,12 +198,20 @@ class BatchConverter:
             return self.blend if blend is None else one(blend)
         return per_item(blend, n, "blend", one, default=self.blend, is_list=M.blend_per_item, unit="weight vectors")
 
+    def tune_of(self, tune=None, n=None):
+        """Per-source pitch correction (a value for all sources, or one per source; None entries: this converter's default,
+        "off": none for that source) checked (matching.resolve_tune) -> a list of ``n`` entries (options.Tuning or None);
+        ``n`` None: one checked value."""
+        if n is None:
+            return self.tune if tune is None else M.resolve_tune(tune)
+        return [self.tune if t is None else t for t in M.resolve_tune(tune, n)]
+
     def plan_duration(self, w, target_duration, item=None):
         """matching.duration_plan of a loaded source waveform (its frame count follows from its length: nothing is encoded)."""
         return M.duration_plan(M.frames_of(int(w.shape[0]), self.vc.wavlm), target_duration, item=item)
 
     @torch.inference_mode()
-    def convert(self, sources, loaded=None, f0_shift=None, transpose=None, target_duration=None, blend=None) -> list:
+    def convert(self, sources, loaded=None, f0_shift=None, transpose=None, target_duration=None, blend=None, tune=None) -> list:
         """-> one waveform tensor [T_i * 320] per source, in order.  ``loaded``: the sources already through load_checked.
         ``f0_shift`` / ``transpose``: for all sources or one per source (None: the converter's defaults); one batch may mix
         them on both match routes, each source's interval is chosen on the device.  ``target_duration`` (seconds): for all
@@ -208,11 +219,15 @@ class BatchConverter:
         (matching.stretch_queries, one launch for the batch) and its waveform has matching.duration_plan's T_out * 320
         samples; sources with and without one share a batch.  ``blend`` (a converter with several target voices): the
         weights of the voices, for all sources or one vector per source (None: the converter's default); one batch may mix
-        weight vectors on both match routes ("lanes": one blend per source, "segmented": one blend launch per batch)."""
+        weight vectors on both match routes ("lanes": one blend per source, "segmented": one blend launch per batch).
+        ``tune``: the pitch correction, for all sources or one entry per source (an options.Tuning or a scale; None: the
+        converter's default, "off": none): that source's shifted f0 is snapped towards the key inside its match, on both routes;
+        one batch may mix keys, and sources with and without one share a batch."""
         modes, semis = self.pitch_of(f0_shift, transpose, len(sources))        # refused before a file is read
         durs = self.duration_of(target_duration, len(sources))
         mixes = self.blend_of(blend, len(sources))
-        knobs = [SourceKnobs(*k) for k in zip(modes, semis, durs, mixes or [None] * len(sources))]
+        tunes = self.tune_of(tune, len(sources))
+        knobs = [SourceKnobs(*k) for k in zip(modes, semis, durs, mixes or [None] * len(sources), tunes)]
         if len(sources) == 0:
             return []
         vc, voices = self.vc, self.voices or [self.target]
@@ -255,11 +270,12 @@ class BatchConverter:
             return ys
         return ops.retry_on_overflow(run)
 
-    def convert_files(self, src_files, converted_audio_dir=None, target_duration=None, blend=None) -> list:
+    def convert_files(self, src_files, converted_audio_dir=None, target_duration=None, blend=None, tune=None) -> list:
         """Paths in, files out: ``<dir or the source's folder>/<src>_to_<ref>_knn_<ckpt_type>_<post_opt>.wav`` (the single-file
-        naming, ddsp_matcher.py:1015), PCM_32 16 kHz mono.  -> the written paths.  ``target_duration`` / ``blend``: as ``convert``.
+        naming, ddsp_matcher.py:1015), PCM_32 16 kHz mono.  -> the written paths.  ``target_duration`` / ``blend`` / ``tune``: as ``convert``.
         With several target voices ``<ref>`` is their ids joined by ``+`` (``<idA>+<idB>[+...]``); the weights are not in the name."""
-        ys = self.convert([str(p) for p in src_files], target_duration=target_duration, **({} if blend is None else dict(blend=blend)))
+        ys = self.convert([str(p) for p in src_files], target_duration=target_duration, **({} if blend is None else dict(blend=blend)),
+                          **({} if tune is None else dict(tune=tune)))
         out = []
         for p, y in zip(src_files, ys):
             path = self.output_path(p, converted_audio_dir)
@@ -279,8 +295,10 @@ class RequestQueue:
     ``submit(src, transpose=, f0_shift=)``: the request's own transpose (semitones) / f0 shift mode instead of the converter's;
     ``submit(src, target_duration=)``: the length in seconds the request's conversion is re-timed to (BatchConverter.convert);
     ``submit(src, blend=)`` (a converter with several target voices): the request's own blend weights; a bad vector is refused
-    at the door and fails alone.  Requests with different values share a batch.  The converter's ``loudness_db``, ``envelope_mix``
-    and ``peak_db`` apply to every request (per-request values of those are not supported)."""
+    at the door and fails alone; ``submit(src, tune=)``: the request's own pitch correction (an options.Tuning, a scale, or "off"
+    under a converter whose default is on), refused at the door likewise.  Requests with different values share a batch.
+    The converter's ``loudness_db``, ``envelope_mix`` and ``peak_db`` apply to every request (per-request values of those are
+    not supported)."""
 
     def __init__(self, converter: BatchConverter, max_batch: int = 32, max_wait_ms: float = 5.0):
         self.conv, self.max_batch, self.max_wait = converter, int(max_batch), float(max_wait_ms) / 1e3
@@ -291,7 +309,7 @@ class RequestQueue:
         self._th = threading.Thread(target=self._loop, name="knnsvc-batcher", daemon=True)
         self._th.start()
 
-    def submit(self, src, transpose=None, f0_shift=None, target_duration=None, blend=None) -> Future:
+    def submit(self, src, transpose=None, f0_shift=None, target_duration=None, blend=None, tune=None) -> Future:
         if self._stop:
             raise RuntimeError("RequestQueue is closed")
         fut = Future()
@@ -302,6 +320,8 @@ class RequestQueue:
             own["target_duration"] = self.conv.duration_of(target_duration)
         if blend is not None:
             own["blend"] = self.conv.blend_of(blend)
+        if tune is not None:
+            own["tune"] = self.conv.tune_of(tune)
         self._q.put((src, fut, SourceKnobs(**own)))
         return fut
 
@@ -346,7 +366,7 @@ class RequestQueue:
                 fut.set_exception(e)
         if not good:
             return
-        carried = [names for names in (("f0_shift", "transpose"), ("target_duration",), ("blend",))
+        carried = [names for names in (("f0_shift", "transpose"), ("target_duration",), ("blend",), ("tune",))
                    if any(getattr(own, k) is not None for _s, _f, own in good for k in names)]
         kwargs = lambda gs: {k: [getattr(own, k) for _s, _f, own in gs] for names in carried for k in names}
         try:
