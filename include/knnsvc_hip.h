@@ -236,10 +236,15 @@ int knnsvc_wavlm_gate(const float* xn, int64_t rows, int32_t heads, int32_t head
  * WavLM's key_padding_mask for a chunk that sits zero-padded inside a longer, bucketed sequence (wavlm/WavLM.py:311-321;
  * F.multi_head_attention_forward masks padded keys with -inf).  The table stays indexed with the bucket's T.  Read on the
  * device at launch time, so one captured hipGraph serves every length of its bucket.  Query rows >= kv_len[b] still get
- * (finite, unused) outputs. */
+ * (finite, unused) outputs.  A batch row with ONE visible key (T = 1, kv_len[b] <= 1) gets that key's V row itself, bit for bit,
+ * from every kernel (with kv_f16x2: what its split holds). */
 int knnsvc_wavlm_attention(const float* qkv, const float* gate, const float* table, int32_t batches,
                            int32_t T, int32_t heads, float* out, int32_t out_f16x2, int32_t kv_f16x2, const int32_t* kv_len,
                            void* stream);
+/* Tag of the kernel the calling thread's last knnsvc_wavlm_attention launched: "wavlm_attention2" (f16x2, 128 queries per
+ * workgroup), "wavlm_attention2q" (256), "wavlm_attention2w" (512, eight waves), "wavlm_attention3" (bf16x3), "wavlm_attention"
+ * (fp32); "" before the first launch, unchanged by a refused call.  Measurement and test hook. */
+const char* knnsvc_wavlm_attention_last_kernel(void);
 
 /* x[b, t, :] = 0 for t >= lens[b] on a [batches, T, dim] activation (row pitch ld): WavLM's `x[padding_mask] = 0`
  * (wavlm/WavLM.py:353, 574-575) in front of the positional convolution, for chunks padded up to a bucket length. */

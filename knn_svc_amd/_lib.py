@@ -135,6 +135,7 @@ SIGNATURES = {
     "knnsvc_layernorm": (i32, [vp, i64, i32, i32, vp, vp, i32, vp, i32, vp]),
     "knnsvc_wavlm_conv0": (i32, [vp, i32, i64, vp, i32, i32, i32, vp, vp, vp, i32, vp]),
     "knnsvc_wavlm_gate": (i32, [vp, i64, i32, i32, i32, vp, vp, vp, vp, i32, vp]),
+    "knnsvc_wavlm_attention_last_kernel": (C.c_char_p, []),
     "knnsvc_wavlm_attention": (i32, [vp, vp, vp, i32, i32, i32, vp, i32, i32, vp, vp]),
     "knnsvc_mask_rows": (i32, [vp, i32, i32, i32, i32, vp, vp]),
     "knnsvc_row_norms": (i32, [vp, i64, i32, i32, vp, vp, vp, vp]),

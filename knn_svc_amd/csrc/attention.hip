@@ -197,8 +197,11 @@ __device__ __forceinline__ void att_fill_table(l_f* tb, const float* table, int 
     }
 
 // One query's 64 output channels (row = b T + qi of `out`), o * inv: plain fp32, or (out_split) the f16x2 split layout the output
-// projection stages with plain copies (4 consecutive channels of the row per store)
-__device__ __forceinline__ void att_store(float* out, long row, int E, int head, const f32x16 (&o)[2], float inv, int out_split) {
+// projection stages with plain copies (4 consecutive channels of the row per store).
+// only_v (wave-uniform, usually null): the batch row has ONE visible key, the softmax weight is exactly 1 and the result is that key's
+// V row (64 fp32 channels at only_v) itself, as the fp32 and bf16x3 kernels return it — o * inv would be V through the fp16 split.
+__device__ __forceinline__ void att_store(float* out, long row, int E, int head, const f32x16 (&o)[2], float inv, int out_split,
+                                          const float* only_v = nullptr) {
     const int lh = (threadIdx.x & 63) >> 5;
     float* op = out + row * E + head * HD;
 #pragma unroll
@@ -206,6 +209,7 @@ __device__ __forceinline__ void att_store(float* out, long row, int E, int head,
 #pragma unroll
         for (int r4 = 0; r4 < 4; ++r4) {
             f32x4 v = {o[d][r4 * 4 + 0] * inv, o[d][r4 * 4 + 1] * inv, o[d][r4 * 4 + 2] * inv, o[d][r4 * 4 + 3] * inv};
+            if (only_v) v = *(const f32x4*)(only_v + d * 32 + r4 * 8 + lh * 4);
             if (out_split) {
                 g2_u32x2 hi, lo;
                 f16x2_split4(v, KN_F16X2_A_SCALE, hi, lo);
@@ -609,10 +613,10 @@ struct Att2Wave {
         }
     }
 
-    __device__ __forceinline__ void store(float* out, int b, int T, int E, int head, int out_split) const {
+    __device__ __forceinline__ void store(float* out, int b, int T, int E, int head, int out_split, const float* only_v) const {
 #pragma unroll
         for (int u = 0; u < QB; ++u)
-            if (qvalid[u]) att_store(out, (long)b * T + qi[u], E, head, o[u], 0.0625f / l_run[u], out_split);     // V carried a factor 16
+            if (qvalid[u]) att_store(out, (long)b * T + qi[u], E, head, o[u], 0.0625f / l_run[u], out_split, only_v);     // V carried a factor 16
     }
 };
 
@@ -710,7 +714,8 @@ __global__ __launch_bounds__(256, QB == 1 ? 3 : 2) void attention2q_kernel(const
                (int)blockIdx.z, (double)pf[0] / ntiles, (double)pf[1] / ntiles, (double)pf[2] / ntiles, (double)pf[3] / ntiles, (double)(__builtin_readcyclecounter() - t_begin));
 #endif
 #undef KN_ATICK
-    w.store(out, b, T, E, head, out_split);
+    // one visible key and fp32 V in `qkv`: the result is that V row, exactly (pre-split V is its own fp16 split already)
+    w.store(out, b, T, E, head, out_split, Tk == 1 && !kv_split ? base + 2 * E + head * HD : nullptr);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -943,6 +948,7 @@ __global__ __launch_bounds__(512, 1) void attention2w_kernel(const float* __rest
         if (late) { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); __builtin_amdgcn_s_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup"); }
         bc = bn;
     }
+    const float* only_v = Tk == 1 && !kv_split ? base + 2 * E + head * HD : nullptr;       // as in attention2q_kernel: see att_store
 #pragma unroll
     for (int u = 0; u < QB; ++u) {
         if (!qvalid[u]) continue;
@@ -953,6 +959,7 @@ __global__ __launch_bounds__(512, 1) void attention2w_kernel(const float* __rest
 #pragma unroll
             for (int r4 = 0; r4 < 4; ++r4) {
                 f32x4 v = {o[u][d][r4 * 4 + 0] * inv, o[u][d][r4 * 4 + 1] * inv, o[u][d][r4 * 4 + 2] * inv, o[u][d][r4 * 4 + 3] * inv};
+                if (only_v) v = *(const f32x4*)(only_v + d * 32 + r4 * 8 + lh * 4);
                 if (out_split) {
                     g2_u32x2 hi, lo;
                     f16x2_split4(v, KN_F16X2_A_SCALE, hi, lo);
@@ -970,6 +977,8 @@ __global__ __launch_bounds__(512, 1) void attention2w_kernel(const float* __rest
 #undef KN_ATT2_INIT
 }  // namespace
 
+static thread_local const char* g_last_attention = "";      // tag of the kernel the last knnsvc_wavlm_attention of this thread launched
+
 // One route's launch: the 160 KB LDS limit (t_max: the hint of its message), the kernel's LDS opt-in, a grid of
 // ceil(T / q_per_wg) x heads x batches workgroups, the launch and its check.
 template <auto KERNEL, class... Args>
@@ -979,8 +988,11 @@ static int att_launch(int q_per_wg, int threads, size_t lds_bytes, int t_max, co
     if (const int rc = kn_lds_optin<KERNEL>((int)lds_bytes, "wavlm_attention")) return rc;
     dim3 grid((unsigned)((T + q_per_wg - 1) / q_per_wg), (unsigned)heads, (unsigned)batches);
     hipLaunchKernelGGL(KERNEL, grid, dim3(threads), lds_bytes, (hipStream_t)stream, args...);
+    g_last_attention = tag;
     return knnsvc_check_launch(tag);
 }
+
+extern "C" const char* knnsvc_wavlm_attention_last_kernel(void) { return g_last_attention; }
 
 extern "C" int knnsvc_wavlm_attention(const float* qkv, const float* gate, const float* table, int32_t batches,
                                       int32_t T, int32_t heads, float* out, int32_t out_f16x2, int32_t kv_f16x2, const int32_t* kv_len,

@@ -414,6 +414,12 @@ def wavlm_attention(qkv, gate, table, batches, T, heads, out_split=False, kv_spl
     return out
 
 
+def last_attention_kernel() -> str:
+    """Tag of the kernel the last wavlm_attention of this thread launched ("wavlm_attention2", "wavlm_attention2q",
+    "wavlm_attention2w", "wavlm_attention3", "wavlm_attention"; "" before the first launch): measurement and test hook."""
+    return _lib.load().knnsvc_wavlm_attention_last_kernel().decode()
+
+
 # ------------------------------------------------------------------ kNN
 _SLOT_DBG = os.environ.get("KNNSVC_SLOT_DBG", "")
 

@@ -1,0 +1,160 @@
+"""GPU: every kernel knnsvc_wavlm_attention can dispatch to, reached by name and held to a float64 reference at tile, mask and
+range edges.
+
+The rows, the references and the dispatcher's mirror are in tests/attention_oracle.py.  All GPU work runs in two fresh child
+interpreters, one after the other (tests/attention_child.py, then tests/attention_fp32_child.py for the route that
+KNNSVC_ATTENTION=fp32 selects once per process); they note what they measured, the tests here judge it.  Per row:
+  route         ops.last_attention_kernel() is the tag the row expects; a row that lands on another kernel FAILS;
+  accuracy      err = max |out - ref64| over the query rows below kv_len  <=  F[route] * e32 + floor, e32 = max |float32 evaluation of
+                the same plain formula - ref64|;  rows at and beyond kv_len only have to be finite;
+  stray stores  the output lies between guard rows that still hold the sentinel;
+  determinism   a second launch gives the same bits;
+  schedules     (f16x2) every schedule the length admits — 128, 256 and 512 queries per workgroup — reports its own tag and
+                gives the same bits;
+and next to the rows: a launch at bucket length T with kv_len = n against a launch at exactly n frames, a B = 3 launch against
+three B = 1 launches (same bits, on all five kernels), and the calls every route must refuse without launching.
+
+floor: zero for fp32 and bf16x3, whose splits keep fp32's exponent range.  f16x2 stores V as 16 v = hi + lo in two fp16 values;
+where lo falls below fp16's smallest normal it is rounded to a multiple of 2^-24, so an element of V carries an absolute error
+of up to 2^-25 / 16 (gemm2_core.h) however small v is, and a convex combination of V carries as much: floor = 2^-25 / 16 =
+1.9e-9.  A row read back from the split layout has been split once more at scale 16: + 2^-22 max |ref64| + 2^-25 / 16.
+
+F: twice the worst err / e32 of a route measured on an MI355X, rounded up, under a cap of 16; a ratio above 8 on any row is a
+finding to explain, not a bar to raise.  The full table is in profiles/attention_errors.txt, with the rows that caught each of
+five arithmetic mutations of the kernels.
+
+Measured on an MI355X, err / e32 (e32 was 3.7e-10 .. 0.76 over the rows):
+    f16x2   84 rows; the T-edge, forced, natural, H = 16 and family rows 0.00 (the one-key rows) .. 2.48 (2-cancelling 2.48; 2-small 2.26, all
+            of it inside the floor), 2w-longest-T6240 2.20, 2q-lds-fallback-T6241 3.32, 2-longest-T15712 6.77,
+            limit_kv 6.64, limit_q 7.12 on all three schedules (which give the same bits)                worst 7.12 -> F = 15
+    bf16x3  33 rows; 0.15 .. 2.11 (3-T512), 3-longest-T14112 5.00                                          worst 5.00 -> F = 11
+    fp32    33 rows; 0.67 .. 2.88 (f32-T64), f32-longest-T16256 8.57                                        worst 8.57 -> F = 16 (cap)
+  Two findings:
+    * f32-longest-T16256 is above 8 on the exact-fp32 kernel, and the longest row of every route is that route's second worst.
+      The flash kernels add O and l key step after key step (508 steps of 32 keys at T = 16256), torch's fp32 matmul behind e32
+      sums in blocks: the same 32-key flash recurrence evaluated in fp32 with torch on the CPU is 4.4 x e32 on that row's inputs
+      (2.2e-7 against 4.9e-8).  It is the yardstick that is short there, by the accumulation order; no kernel is beyond it.
+    * 2-T1 was beyond its tolerance when first measured: err 1.19e-07, e32 0, tolerance 1.86e-09.  With one visible key the softmax
+      weight is 1 and fp32 and bf16x3 return V exactly (so e32 = 0 and only the floor is left), while f16x2 returned V through
+      its (hi, lo) split, 2^-23 relative at |v| ~ 2.  The f16x2 kernels now store that key's V row itself when a batch row has one
+      visible key (att_store: only_v): err 0 on 2-T1 and on the one-key rows at T = 129, which hold all five kernels to it.
+"""
+import json
+
+import pytest
+import torch
+
+from tests import attention_oracle as A, gpu_child
+
+pytestmark = pytest.mark.gpu
+CHILD_TIMEOUT_S = 240        # per child; measured: 10 s for the main child, 3 s for the fp32 one, the
+                             # float64 and float32 references on the CPU included; the rest is for a cold torch import and a slower host
+FP32 = "fp32:"               # the second child's notes carry this prefix
+
+# F per route = twice the worst err / e32 measured over the table on an MI355X, rounded up, capped at 16 (see the table above)
+FACTOR = {"fp32": 16, "bf16x3": 11, "f16x2": 15}
+assert all(f <= 16 for f in FACTOR.values())
+V_FLOOR = 2.0 ** -25 / 16
+
+
+def floor(case, omax):
+    if case.route != "f16x2":
+        return 0.0
+    return V_FLOOR + (2.0 ** -22 * omax + V_FLOOR if case.out_split else 0.0)
+
+
+@pytest.fixture(scope="module")
+def report(tmp_path_factory):
+    """The two children, one after the other; the second is not started when the first did not end well."""
+    if torch.cuda.is_initialized():
+        pytest.skip("the children are started from a process that has not initialised the GPU: run this module first / on its own")
+    d = tmp_path_factory.mktemp("attention")
+    rep = gpu_child.run_child("attention_child.py", str(d / "main.json"), CHILD_TIMEOUT_S, stdout_tail=3000)
+    if "__failed__" not in rep:
+        second = gpu_child.run_child("attention_fp32_child.py", str(d / "fp32.json"), CHILD_TIMEOUT_S, stdout_tail=3000)
+        rep.update({k if k == "__failed__" else FP32 + k: v for k, v in second.items()})
+    return rep
+
+
+def _pre(tag):
+    return FP32 if tag == A.TAG_F32 else ""
+
+
+def _record(report, key):
+    assert "__failed__" not in report, report["__failed__"]
+    assert key in report, f"{key}: did not run"
+    return json.loads(report[key]["detail"])
+
+
+def test_children_finished(report):
+    for name in ("rows", "bucket", "batch", "refusals"):
+        gpu_child.check(report, f"{name}/ran", exactly=1)
+        gpu_child.check(report, f"{FP32}{name}/ran", exactly=1)
+
+
+@pytest.mark.parametrize("case", A.CASES, ids=lambda c: c.id)
+def test_row_against_fp64(case, report):
+    rec = _record(report, f"{_pre(case.tag)}row/{case.id}")
+    assert rec["tag"] == case.tag, f"{case.id}: dispatched to {rec['tag']}, the row is about {case.tag}"
+    err, e32 = rec["err"], rec["e32"]
+    tol = FACTOR[case.route] * e32 + floor(case, rec["omax"])
+    ratio = err / e32 if e32 > 0 else float("inf") if err > 0 else 0.0
+    print(f"{case.id}: {rec['tag']} err {err:.3e} e32 {e32:.3e} ratio {ratio:.2f} tolerance {tol:.3e} scale {rec['scale']:.3g}")
+    assert err <= tol, f"{case.id}: err {err:.3e} = {ratio:.1f} x e32, tolerance {tol:.3e}"
+    assert rec["finite"], f"{case.id}: an output row (rows at and beyond kv_len included) is not finite"
+    assert rec["guard"], f"{case.id}: the guard rows around the output were written"
+    assert rec["again"], f"{case.id}: a second launch gives other bits"
+    if case.route == "f16x2":
+        want = [t for _, t in A.schedules(case.T)]
+        assert sorted(rec["sched"]) == sorted(want)
+        for t in want:
+            assert rec["sched"][t] == [t, True], f"{case.id}: schedule {t} reported {rec['sched'][t][0]}, same bits: {rec['sched'][t][1]}"
+
+
+@pytest.mark.parametrize("bucket", A.BUCKETS, ids=lambda b: b[0])
+@pytest.mark.parametrize("n", A.BUCKET_N)
+def test_bucketed_launch_equals_exact_length(bucket, n, report):
+    """What WavLMEncoder.encode_batch relies on: rows below lens[b] of a launch at the bucket's length are, bit for bit, the launch
+    at the exact length (whose table is the bucket's table, columns T - n .. T + n - 2)."""
+    id_, tag = bucket[0], bucket[1]
+    rec = _record(report, f"{_pre(tag)}bucket/{id_}/{n}")
+    assert rec["tag"] == tag
+    assert rec["tag_exact"] == (tag if tag in (A.TAG_3, A.TAG_F32) or n > 128 else A.TAG_2)
+    assert rec["same"], f"{id_}: rows < {n} differ between the bucketed and the exact-length launch"
+    assert rec["guard"]
+
+
+@pytest.mark.parametrize("batch", A.BATCHES, ids=lambda b: b[0])
+def test_batch_equals_single_launches(batch, report):
+    rec = _record(report, f"{_pre(batch[1])}batch/{batch[0]}")
+    assert rec["tag"] == batch[1] and rec["tags"] == [batch[1]] * 3
+    assert rec["same"]
+
+
+_SPLIT = "only implemented by the f16x2 kernel"
+
+
+@pytest.mark.parametrize("child", ("", FP32), ids=("main", "fp32"))
+@pytest.mark.parametrize("id_,text", A.REFUSED)
+def test_bad_arguments_are_refused(id_, text, child, report):
+    _refused(report, f"{child}refuse/{id_}", text)
+
+
+@pytest.mark.parametrize("id_", A.SPLIT_REFUSED + A.F32_SPLIT_REFUSED)
+def test_split_layouts_are_refused_off_the_f16x2_route(id_, report):
+    _refused(report, f"{FP32 if id_ in A.F32_SPLIT_REFUSED else ''}refuse/{id_}", _SPLIT)
+
+
+@pytest.mark.parametrize("tag", sorted(A.TOO_LONG))
+def test_one_frame_too_long_is_refused(tag, report):
+    _refused(report, f"{_pre(tag)}refuse/too-long-{A.SHORT[tag]}", "T too long")
+
+
+def _refused(report, key, text):
+    rec = _record(report, key)
+    assert rec["rc"] != 0 and text in rec["msg"], rec
+    assert rec["tag_kept"] and rec["out_kept"], f"{key}: something was launched ({rec})"
+
+
+def test_parent_process_left_the_gpu_alone(report):
+    assert not torch.cuda.is_initialized()
