@@ -699,6 +699,8 @@ int knnsvc_amp_ratio(const float* spec_q, int32_t ld_q, const float* spec_pool, 
  * (256-byte aligned device memory of at least the size knnsvc_f0_harvest_workspace reports: ~35 MB per second of audio);
  * no host synchronisation.  status (device int32, may be NULL): 0, or a bit mask if a fixed-capacity list overflowed
  * (1: more than 16 candidates in a frame, 2 / 4: section storage) — the track is then incomplete.
+ * Both entries serve 64.59286 <= f0_floor < f0_ceil <= 1600 (below that floor the longest band-pass filter does not fit the
+ * bank kernel's tile: "f0_floor too low"), frame_period >= 1 ms, 1600 <= L < 2^30.
  * Restates the published algorithm, pinned by oracle/f0_ref.py on the reference's two shipped harvest tracks. */
 int knnsvc_f0_harvest_workspace(int64_t L, int32_t sample_rate, float f0_floor, float f0_ceil, float frame_period,
                                 int64_t* n_frames, int64_t* bytes);

@@ -588,11 +588,14 @@ __global__ void hv_sample_kernel(const double* __restrict__ sm, long nfr, double
     out[i] = v < (double)zero_below ? 0.f : (float)v;
 }
 
+constexpr int HV_NARR = 36;              // arrays in the workspace
 struct HvPlan {
     long L, text, ylen, ypad_len, ld, nfr, nout, ecap, chan_cap, scratch_cap; int nch, scap;
     size_t o_t1, o_t2, o_mean, o_ypad, o_bf0, o_hlen, o_filt, o_events, o_ecount, o_raw, o_cand0, o_cand, o_score, o_cand2, o_score2,
            o_base, o_s1, o_s2, o_s3, o_s4, o_sm, o_st, o_ed, o_xst, o_xed, o_keep, o_order, o_gst, o_ged, o_woff, o_soff, o_chan, o_chs, o_ms,
            o_scratch, o_info, total;
+    // every array in the order hv_plan takes it (the order of the o_ fields): byte offset and unpadded byte size
+    int na; size_t at[HV_NARR], size[HV_NARR];
 };
 
 static HvPlan hv_plan(long L, double fs, double f0_floor, double f0_ceil, double frame_period) {
@@ -604,7 +607,12 @@ static HvPlan hv_plan(long L, double fs, double f0_floor, double f0_ceil, double
     p.ecap = p.ylen / 2 + 2;
     p.scap = (int)(p.nfr / 2 + 2);
     size_t o = 0;
-    auto take = [&](size_t bytes) { const size_t at = o; o += (bytes + 255) / 256 * 256; return at; };
+    auto take = [&](size_t bytes) {
+        const size_t at = o; o += (bytes + 255) / 256 * 256;
+        if (p.na < HV_NARR) { p.at[p.na] = at; p.size[p.na] = bytes; }
+        ++p.na;
+        return at;
+    };
     p.o_t1 = take(p.text * 8); p.o_t2 = take(p.text * 8); p.o_mean = take(8); p.o_ypad = take(p.ypad_len * 8);
     p.o_bf0 = take(p.nch * 8); p.o_hlen = take(p.nch * 4);
     p.o_filt = take((size_t)p.nch * p.ld * 8);
@@ -631,7 +639,12 @@ static HvPlan hv_plan(long L, double fs, double f0_floor, double f0_ceil, double
 static int hv_check(int32_t sample_rate, int64_t L, float f0_floor, float f0_ceil, float frame_period) {
     KN_REQUIRE(sample_rate == 16000, "f0_harvest: the path runs at 16 kHz (decimation by 2 to 8 kHz); got %d", sample_rate);
     KN_REQUIRE(L >= 1600 && L < (1L << 30), "f0_harvest: need 0.1 s .. 18 h of audio (got %ld samples)", (long)L);
-    KN_REQUIRE(f0_floor >= 40.f && f0_ceil > f0_floor && f0_ceil <= 1600.f && frame_period >= 1.f, "f0_harvest: bad range / frame period");
+    KN_REQUIRE(f0_floor > 0.f && f0_ceil > f0_floor && f0_ceil <= 1600.f && frame_period >= 1.f, "f0_harvest: bad range / frame period");
+    {   // the longest filter has to fit the bank kernel's LDS tile, the longest refinement window its LDS row: f0_floor > 64.6
+        const double afs = (double)sample_rate / 2.0, b0 = (double)f0_floor * 0.9 * pow(2.0, 1.0 / 40.0);
+        KN_REQUIRE(afs / b0 * 2.0 + 0.5 < (double)(HV_HMAX - 1) && (long)(afs / b0 * 2.0 + 0.5) + 1 <= HV_YPAD, "f0_harvest: f0_floor too low");
+        KN_REQUIRE(1.5 * afs / (double)f0_floor + 1.0 < 192.0, "f0_harvest: f0_floor too low for the refinement window");
+    }
     return KNNSVC_OK;
 }
 
@@ -647,6 +660,26 @@ extern "C" int knnsvc_f0_harvest_workspace(int64_t L, int32_t sample_rate, float
     return KNNSVC_OK;
 }
 
+// For tests only (not in knnsvc_hip.h, like knnsvc_debug_knn_prof): where every array of the run lies in the workspace, from the
+// same hv_check and hv_plan.  Host only, launches nothing.  table[0 .. 2 * 36): byte offset and unpadded byte size of t1, t2,
+// mean, ypad, bf0, hlen, filt, events, ecount, raw, cand0, cand, score, cand2, score2, base, s1, s2, s3, s4, sm, st, ed, xst,
+// xed, keep, order, gst, ged, woff, soff, chan, chs, ms, scratch, info (the order of HvPlan); then total; then nch, ylen, ld,
+// nfr, nout, ecap, scap, chan_cap, scratch_cap; then HV_NC, HV_NS, HV_YPAD, HV_MARG, HV_SMOOTH_MARG: 87 entries.
+extern "C" int knnsvc_debug_f0_harvest_layout(int64_t L, int32_t sample_rate, float f0_floor, float f0_ceil, float frame_period,
+                                              int64_t* table, int32_t n_table) {
+    KN_REQUIRE(table && n_table >= 2 * HV_NARR + 15, "f0_harvest_layout: the table needs %d entries", 2 * HV_NARR + 15);
+    const int rc = hv_check(sample_rate, L, f0_floor, f0_ceil, frame_period);
+    if (rc) return rc;
+    const HvPlan p = hv_plan((long)L, (double)sample_rate, (double)f0_floor, (double)f0_ceil, (double)frame_period);
+    KN_REQUIRE(p.na == HV_NARR, "f0_harvest_layout: %d arrays planned, %d expected", p.na, HV_NARR);
+    int64_t* t = table;
+    for (int i = 0; i < HV_NARR; ++i) { *t++ = (int64_t)p.at[i]; *t++ = (int64_t)p.size[i]; }
+    const int64_t rest[15] = {(int64_t)p.total, p.nch, p.ylen, p.ld, p.nfr, p.nout, p.ecap, p.scap, p.chan_cap, p.scratch_cap,
+                              HV_NC, HV_NS, HV_YPAD, HV_MARG, HV_SMOOTH_MARG};
+    for (int i = 0; i < 15; ++i) *t++ = rest[i];
+    return KNNSVC_OK;
+}
+
 extern "C" int knnsvc_f0_harvest(const float* x, int64_t L, int32_t sample_rate, float f0_floor, float f0_ceil, float frame_period,
                                  float zero_below, float* f0, int64_t n_frames, void* workspace, int64_t workspace_bytes,
                                  int32_t* status, void* stream) {
@@ -658,11 +691,6 @@ extern "C" int knnsvc_f0_harvest(const float* x, int64_t L, int32_t sample_rate,
     KN_REQUIRE(n_frames == p.nout, "f0_harvest: n_frames %ld, expected %ld", (long)n_frames, p.nout);
     KN_REQUIRE(workspace_bytes >= (int64_t)p.total, "f0_harvest: workspace %ld bytes, need %ld", (long)workspace_bytes, (long)p.total);
     KN_REQUIRE(((uintptr_t)workspace & 255) == 0, "f0_harvest: workspace must be 256-byte aligned");
-    {   // the longest filter has to fit the bank kernel's LDS tile
-        const double b0 = (double)f0_floor * 0.9 * pow(2.0, 1.0 / 40.0);
-        KN_REQUIRE((long)(afs / b0 * 2.0 + 0.5) <= HV_HMAX - 2 && (long)(afs / b0 * 2.0 + 0.5) + 1 <= HV_YPAD, "f0_harvest: f0_floor too low");
-        KN_REQUIRE(2 * (int)(1.5 * afs / (double)f0_floor + 1.0) + 1 <= 384, "f0_harvest: f0_floor too low for the refinement window");
-    }
     char* ws = (char*)workspace;
     auto D = [&](size_t off) { return (double*)(ws + off); };
     auto I = [&](size_t off) { return (int*)(ws + off); };

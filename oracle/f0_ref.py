@@ -60,34 +60,48 @@ def _interp1_extrap(x, y, xi):
     return y[k - 1] + s * (y[k] - y[k - 1])
 
 
-def _zero_cross(sig, fs):
-    """Negative-going zero crossings -> (interval centre times, interval f0)."""
+def _events(sig):
+    """1-based sub-sample positions of the negative-going zero crossings of sig."""
     e = np.nonzero((sig[:-1] > 0) & (sig[1:] <= 0))[0] + 1                    # 1-based edge positions
-    if len(e) < 2:
+    return e - sig[e - 1] / (sig[e] - sig[e - 1])
+
+
+def _intervals(fine, fs):
+    """Event positions -> (interval centre times, interval f0); None below two events."""
+    if len(fine) < 2:
         return None
-    fine = e - sig[e - 1] / (sig[e] - sig[e - 1])
     return (fine[:-1] + fine[1:]) / 2.0 / fs, fs / (fine[1:] - fine[:-1])
 
 
-def _raw_candidates(y, y_spec, fft_size, fs, boundary_f0, f0_floor, f0_ceil, tpos):
+def _bank_filter(y, y_spec, fft_size, fs, boundary_f0):
+    """One channel of the band-pass bank: Nuttall-windowed cosine of four periods, applied through the FFT."""
     half = int(_round(np.float64(fs / boundary_f0 * 2.0)))
     bpf = np.zeros(fft_size)
     n = 2 * half + 1
     bpf[:n] = _nuttall(n) * np.cos(2 * np.pi * boundary_f0 * np.arange(-half, half + 1) / fs)
-    filt = np.fft.irfft(np.fft.rfft(bpf) * y_spec, fft_size)[half + 1:half + 1 + len(y)].copy()
-    sets = []
-    z = _zero_cross(filt, fs); sets.append(z)
-    filt = -filt
-    z = _zero_cross(filt, fs); sets.append(z)
-    d = filt[:-1] - filt[1:]
-    z = _zero_cross(d, fs); sets.append(z)
-    z = _zero_cross(-d, fs); sets.append(z)
+    return np.fft.irfft(np.fft.rfft(bpf) * y_spec, fft_size)[half + 1:half + 1 + len(y)].copy()
+
+
+def _event_sets(filt):
+    """The four event lists of one channel: negative- and positive-going zero crossings, peaks, dips."""
+    neg = -filt
+    d = neg[:-1] - neg[1:]
+    return [_events(filt), _events(neg), _events(d), _events(-d)]
+
+
+def _raw_from_events(events, fs, boundary_f0, f0_floor, f0_ceil, tpos):
+    sets = [_intervals(e, fs) for e in events]
     if any(s is None or len(s[0]) < 3 for s in sets):
         return np.zeros(len(tpos))
     f = np.mean([_interp1_extrap(s[0], s[1], tpos) for s in sets], 0)
     bad = (f > boundary_f0 * 1.1) | (f < boundary_f0 * 0.9) | (f > f0_ceil) | (f < f0_floor)
     f[bad] = 0.0
     return f
+
+
+def _raw_candidates(y, y_spec, fft_size, fs, boundary_f0, f0_floor, f0_ceil, tpos):
+    filt = _bank_filter(y, y_spec, fft_size, fs, boundary_f0)
+    return _raw_from_events(_event_sets(filt), fs, boundary_f0, f0_floor, f0_ceil, tpos)
 
 
 def _detect_candidates(raw):
@@ -119,10 +133,11 @@ def _overlap(cand, n=3):
     return out
 
 
-def _refine(y, fs, tpos, cand, f0_floor, f0_ceil):
-    """Instantaneous-frequency refinement of every candidate (GetRefinedF0), batched by window length."""
+def _refine_raw(y, fs, tpos, cand):
+    """Instantaneous-frequency refinement of every candidate (GetRefinedF0), batched by window length, before its gates
+    -> (refined f0, mean harmonic deviation), both zero where there is no candidate."""
     nfr, nc = cand.shape
-    f0 = np.zeros_like(cand); score = np.zeros_like(cand)
+    f0 = np.zeros_like(cand); devs = np.zeros_like(cand)
     fi, ci = np.nonzero(cand > 0)
     cf = cand[fi, ci]
     half = (1.5 * fs / cf + 1.0).astype(np.int64)
@@ -153,13 +168,19 @@ def _refine(y, fs, tpos, cand, f0_floor, f0_ceil):
             p = np.take_along_axis(pw, idx, 1); q = np.take_along_axis(num, idx, 1)
             inst = np.where(p == 0, 0.0, idx * fs / fft_size + q / np.where(p == 0, 1, p) * fs / 2.0 / np.pi)
             amp = np.sqrt(p) * valid
-            rf = (amp * inst).sum(1) / ((amp * k).sum(1) + _EPS)
-            dev = (np.abs((inst / k - f[:, None]) / f[:, None]) * valid).sum(1) / nh
-            sc = 1.0 / (_EPS + dev)
-            bad = (rf < f0_floor) | (rf > f0_ceil) | (sc < 2.5)
-            rf[bad] = 0; sc[bad] = 0
-            f0[fi[s], ci[s]] = rf; score[fi[s], ci[s]] = sc
-    return f0, score
+            f0[fi[s], ci[s]] = (amp * inst).sum(1) / ((amp * k).sum(1) + _EPS)
+            devs[fi[s], ci[s]] = (np.abs((inst / k - f[:, None]) / f[:, None]) * valid).sum(1) / nh
+    return f0, devs
+
+
+def _refine(y, fs, tpos, cand, f0_floor, f0_ceil):
+    """_refine_raw with its gates: the refined f0 inside the range and a score (1 / deviation) of at least 2.5."""
+    rf, devs = _refine_raw(y, fs, tpos, cand)
+    on = cand > 0
+    sc = np.zeros_like(cand)
+    sc[on] = 1.0 / (_EPS + devs[on])
+    ok = on & ~((rf < f0_floor) | (rf > f0_ceil) | (sc < 2.5))
+    return np.where(ok, rf, 0.0), np.where(ok, sc, 0.0)
 
 
 def _select_best(ref, cands, allowed):
@@ -200,10 +221,13 @@ def _sel1(ref, cands, allowed):
     return best
 
 
-def _extend(f0, origin, last, shift, cand, allowed):
+def _extend(f0, origin, last, shift, cand, allowed, log=None):
+    """log, where given, receives (frame, reference value) of every selection made."""
     tmp = f0[origin]; so = origin; count = 0
     for i in range(abs(last - origin) + 1):
         p = origin + shift * i + shift
+        if log is not None:
+            log.append((p, tmp))
         f0[p] = _sel1(tmp, cand[p], allowed)
         if f0[p] == 0:
             count += 1
@@ -219,65 +243,78 @@ def _search_score(f, cands, scores):
     return scores[m].max() if m.any() else 0.0
 
 
-def _fix_contour(cand, score, allowed1=0.008, vmin=6, allowed=0.18, gap=9):
-    """FixF0Contour with WORLD's tuned constants: 0.8 % per-ms jump, 6-frame minimum section, 18 % while extending,
-    gaps shorter than 9 frames bridged."""
+def _contour_base(cand, score, allowed1=0.008):
+    """-> (best-score candidate per frame, the same with 0.8 % per-ms jumps removed)."""
     nfr = len(cand)
     base = np.where(score.max(1) > 0, np.take_along_axis(cand, score.argmax(1)[:, None], 1)[:, 0], 0.0)
-    # step 1: jumps
     s1 = np.zeros(nfr)
     with np.errstate(divide="ignore", invalid="ignore"):
         ref = base[1:-1] * 2 - base[:-2]
         a = np.abs((base[2:] - ref) / ref) > allowed1
         b = np.abs(base[2:] - base[1:-1]) / base[1:-1] > allowed1
     s1[2:] = np.where((base[2:] != 0) & ~(a & b), base[2:], 0.0)
-    # step 2: short sections
+    return base, s1
+
+
+def _drop_short(s1, vmin=6):
     s2 = s1.copy()
     for st, ed in _boundaries(s1):
         if ed - st < vmin:
             s2[st:ed + 1] = 0
-    # step 3: extend / merge
-    secs = _boundaries(s2)
-    out = s2.copy()
-    chans = []
-    for st, ed in secs:
-        ch = np.zeros(nfr); ch[st:ed + 1] = s2[st:ed + 1]
-        ed2 = _extend(ch, ed, min(nfr - 2, ed + 100), 1, cand, allowed)
-        st2 = _extend(ch, st, max(1, st - 100), -1, cand, allowed)
-        m = ch[st2:ed2].mean() if ed2 > st2 else 0.0
-        if m > 0 and 2200.0 / m < ed2 - st2:
-            chans.append((st2, ed2, ch))
-    if chans:
-        # MergeF0 as the library does it, quirks included (the shipped tracks depend on them): the order comes from an
-        # insertion pass that moves a new element at most ONE place forward; the merge starts from channel 0 whatever the
-        # order says; and the running bounds live in channel 0's slots of the boundary list.
-        bl = [[c[0], c[1]] for c in chans]
-        order = list(range(len(chans)))
-        for i in range(1, len(chans)):
-            for j in range(i - 1, -1, -1):
-                if bl[order[j]][0] > bl[order[i]][0]:
-                    order[i], order[j] = order[j], order[i]
-                else:
-                    break
-        merged = chans[0][2].copy()
-        for i in range(1, len(chans)):
-            st, ed = bl[order[i]]
-            ch = chans[order[i]][2]
-            b0, b1 = bl[0]
-            if st - b1 > 0:
-                merged[st:ed + 1] = ch[st:ed + 1]; bl[0] = [st, ed]
-            elif b0 <= st and b1 >= ed:
-                pass
+    return s2
+
+
+def _extend_section(s2, st, ed, cand, allowed=0.18, log=None):
+    """One section in a channel of its own, extended forward then backward -> (start, end, channel, mean, keep?)."""
+    nfr = len(s2)
+    ch = np.zeros(nfr); ch[st:ed + 1] = s2[st:ed + 1]
+    ed2 = _extend(ch, ed, min(nfr - 2, ed + 100), 1, cand, allowed, log)
+    st2 = _extend(ch, st, max(1, st - 100), -1, cand, allowed, log)
+    m = ch[st2:ed2].mean() if ed2 > st2 else 0.0
+    return st2, ed2, ch, m, bool(m > 0 and 2200.0 / m < ed2 - st2)
+
+
+def _merge(chans, cand, score, trace=None):
+    """MergeF0 as the library does it, quirks included (the shipped tracks depend on them): the order comes from an
+    insertion pass that moves a new element at most ONE place forward; the merge starts from channel 0 whatever the
+    order says; and the running bounds live in channel 0's slots of the boundary list.  chans: (start, end, channel)."""
+    bl = [[c[0], c[1]] for c in chans]
+    order = list(range(len(chans)))
+    for i in range(1, len(chans)):
+        for j in range(i - 1, -1, -1):
+            if bl[order[j]][0] > bl[order[i]][0]:
+                order[i], order[j] = order[j], order[i]
             else:
-                sc1 = sum(_search_score(merged[i2], cand[i2], score[i2]) for i2 in range(st, b1 + 1))
-                sc2 = sum(_search_score(ch[i2], cand[i2], score[i2]) for i2 in range(st, b1 + 1))
-                if sc1 > sc2:
-                    merged[b1:ed + 1] = ch[b1:ed + 1]
-                else:
-                    merged[st:ed + 1] = ch[st:ed + 1]
-                bl[0][1] = ed
-        out = merged
-    # step 4: short gaps
+                break
+    if trace is not None:
+        trace["order"] = list(order); trace["steps"] = []
+    merged = chans[0][2].copy()
+    for i in range(1, len(chans)):
+        st, ed = bl[order[i]]
+        ch = chans[order[i]][2]
+        b0, b1 = bl[0]
+        step = {"branch": "inside"}
+        if st - b1 > 0:
+            merged[st:ed + 1] = ch[st:ed + 1]; bl[0] = [st, ed]
+            step["branch"] = "after"
+        elif b0 <= st and b1 >= ed:
+            pass
+        else:
+            t1 = [_search_score(merged[i2], cand[i2], score[i2]) for i2 in range(st, b1 + 1)]
+            t2 = [_search_score(ch[i2], cand[i2], score[i2]) for i2 in range(st, b1 + 1)]
+            sc1 = sum(t1); sc2 = sum(t2)
+            if sc1 > sc2:
+                merged[b1:ed + 1] = ch[b1:ed + 1]
+            else:
+                merged[st:ed + 1] = ch[st:ed + 1]
+            bl[0][1] = ed
+            step = {"branch": "sum", "sc1": sc1, "sc2": sc2, "same_terms": t1 == t2}
+        if trace is not None:
+            trace["steps"].append(step)
+    return merged
+
+
+def _bridge(out, gap=9):
     s4 = out.copy()
     bl = _boundaries(out)
     for (s_a, e_a), (s_b, e_b) in zip(bl[:-1], bl[1:]):
@@ -287,6 +324,21 @@ def _fix_contour(cand, score, allowed1=0.008, vmin=6, allowed=0.18, gap=9):
         t0 = out[e_a] + 1; t1 = out[s_b] - 1
         co = (t1 - t0) / (dist + 1.0)
         s4[e_a + 1:s_b] = t0 + co * np.arange(1, dist + 1)
+    return s4
+
+
+def _fix_contour(cand, score, allowed1=0.008, vmin=6, allowed=0.18, gap=9, trace=None):
+    """FixF0Contour with WORLD's tuned constants: 0.8 % per-ms jump, 6-frame minimum section, 18 % while extending,
+    gaps shorter than 9 frames bridged.  trace, where given, receives the intermediates."""
+    base, s1 = _contour_base(cand, score, allowed1)
+    s2 = _drop_short(s1, vmin)
+    secs = _boundaries(s2)
+    ext = [_extend_section(s2, st, ed, cand, allowed) for st, ed in secs]
+    chans = [(e[0], e[1], e[2]) for e in ext if e[4]]
+    out = _merge(chans, cand, score, trace) if chans else s2.copy()
+    s4 = _bridge(out, gap)
+    if trace is not None:
+        trace.update(base=base, s1=s1, s2=s2, secs=secs, ext=ext, s3=out, s4=s4)
     return s4
 
 
