@@ -31,7 +31,7 @@ extern "C" {
 #define KNNSVC_EHIP      3   /* a HIP runtime call failed                  */
 #define KNNSVC_ENAN      4   /* NaN distance (the reference sys.exit()s)   */
 
-#define KNNSVC_ABI_VERSION 20
+#define KNNSVC_ABI_VERSION 21
 
 int knnsvc_abi_version(void);
 const char* knnsvc_last_error(void);
@@ -39,11 +39,13 @@ const char* knnsvc_last_error(void);
  * measurement hook (bench.py attributes HIP-event times to kernels with it); "" before the first call. */
 const char* knnsvc_conv_gemm_last_kernel(void);
 /* ... and which epilogue that launch took: "patch" (LDS patches, 16-byte stores: conv_epilogue_wide32), "lane" (column per lane) or
- * "" (kernels with an epilogue of their own: the 256x256-tile kernel, fp32, bf16x3).  Test hook. */
+ * "" (kernels with an epilogue of their own: the 256x256-tile kernel, fp32, bf16x3); after a grid of several
+ * descriptors (knnsvc_conv_gemm_multi): the first descriptor's.  Test hook. */
 const char* knnsvc_conv_gemm_last_epilogue(void);
-/* The dispatcher's A/B switches (KNNSVC_QUAD, KNNSVC_QUAD_EPI, KNNSVC_EPILOGUE, KNNSVC_WIN, KNNSVC_WIN_SMALL, KNNSVC_WIN_DEEP,
- * KNNSVC_WIN160, KNNSVC_WIN_WIDE, KNNSVC_GEMM_SMALL) are read from the environment once, at the first launch; this re-reads them (tests and A/B
- * runs that switch a route inside one process). */
+/* The dispatchers' A/B switches (KNNSVC_QUAD, KNNSVC_QUAD_EPI, KNNSVC_EPILOGUE, KNNSVC_WIN, KNNSVC_WIN_SMALL, KNNSVC_WIN_DEEP,
+ * KNNSVC_WIN160, KNNSVC_WIN_WIDE, KNNSVC_GEMM_SMALL of knnsvc_conv_gemm, KNNSVC_ATTENTION of knnsvc_wavlm_attention, KNNSVC_CONV0_RP and
+ * KNNSVC_CONV0_SUBS of knnsvc_wavlm_conv0) are read from the environment once, by the first call that looks at one of them; this
+ * re-reads them all (tests and A/B runs that switch a route inside one process). */
 int knnsvc_reload_knobs(void);
 /* Stream-placement probe: `blocks` one-wave workgroups that spin for `spin` shader-clock ticks each (nothing is read or written).
  * The host side (knn_svc_amd/pipeline.py) times it on two streams at once to MEASURE whether they share a hardware queue or
@@ -135,6 +137,16 @@ int knnsvc_conv_gemm(const knnsvc_conv_desc* d, void* stream);
  * are bit-identical to separate launches either way.  Put the descriptor with the most taps first. */
 int knnsvc_conv_gemm_multi(const knnsvc_conv_desc* descs, int32_t count, void* stream);
 
+/* What the dispatcher decides for `count` (1..4) descriptors, without a launch: host code only, no GPU and no stream; the operand
+ * pointers are looked at (null, alignment) but never followed.  count == 1: the tag knnsvc_conv_gemm_last_kernel() reports after
+ * knnsvc_conv_gemm of the descriptor, and the epilogue tag; both "" for m == 0 (nothing is launched).  count > 1: the tag of the
+ * one grid knnsvc_conv_gemm_multi launches ("W128Dx", ...) and the first descriptor's epilogue, or "" where it launches the
+ * descriptors one by one.  `tag` and `epilogue` hold `cap` >= 16 bytes each.  Returns what the launch entry returns for a
+ * descriptor that does not validate. */
+int knnsvc_conv_gemm_route(const knnsvc_conv_desc* descs, int32_t count, char* tag, char* epilogue, int32_t cap);
+/* Every tag the dispatcher can report, separated by blanks, into `out` (`cap` bytes; 256 are enough). */
+int knnsvc_conv_gemm_tags(char* out, int32_t cap);
+
 /* One ResBlock1 iteration of the generator in one launch (hifigan/ddsp_models.py:13-44):
  *     t1 = lrelu(conv1d(lrelu(x), w1, dilation = dil) + b1);   out = conv1d(t1, w2) + b2 + x
  * x, out: channel-last [t, channels] fp32 (row pitches ldx / ldo), both convolutions `taps` wide with "same" zero padding; the
@@ -213,6 +225,11 @@ int knnsvc_layernorm(const float* x, int64_t rows, int32_t dim, int32_t ldx, con
 int knnsvc_wavlm_conv0(const float* x, int32_t batches, int64_t L, const float* w, int32_t channels, int32_t k,
                        int32_t stride, const float* gamma, const float* beta, float* out, int32_t out_f16x2,
                        void* stream);
+/* The launch shape knnsvc_wavlm_conv0 takes for `batches` inputs of T output frames each, without a launch (host code only):
+ * rows per pass (KNNSVC_CONV0_RP: 2, 4 or 1) and the spans of 64 rows a workgroup walks (KNNSVC_CONV0_SUBS on long inputs, else 1). */
+int knnsvc_wavlm_conv0_route(int32_t batches, int64_t T, int32_t* rows_per_pass, int32_t* spans);
+/* ... and what the calling thread's last knnsvc_wavlm_conv0 launched with (0, 0 before the first launch).  Test hook. */
+void knnsvc_wavlm_conv0_last_route(int32_t* rows_per_pass, int32_t* spans);
 
 /* Gated relative-position multiplier, wavlm/modules.py:523-533:
  *   gate[row, h] = ga*(gb*grep_a[h] - 1) + 2, (ga, gb) = sigmoid(W2 @ xn[row, h*hd:(h+1)*hd] + b2)
@@ -245,6 +262,12 @@ int knnsvc_wavlm_attention(const float* qkv, const float* gate, const float* tab
  * workgroup), "wavlm_attention2q" (256), "wavlm_attention2w" (512, eight waves), "wavlm_attention3" (bf16x3), "wavlm_attention"
  * (fp32); "" before the first launch, unchanged by a refused call.  Measurement and test hook. */
 const char* knnsvc_wavlm_attention_last_kernel(void);
+/* The kernel knnsvc_wavlm_attention launches for these sizes and flags under the knobs as they are (KNNSVC_ATTENTION as last read,
+ * KNNSVC_ATT_QB / KNNSVC_ATT_NW now), without a launch: host code only, no GPU and no stream.  -> its tag (`cap` >= 24 bytes) and
+ * its dynamic LDS in bytes; a call the launch entry refuses for its sizes, its flags or a T too long for the LDS bias table is
+ * refused here with the same code and message. */
+int knnsvc_wavlm_attention_route(int32_t batches, int32_t T, int32_t heads, int32_t out_f16x2, int32_t kv_f16x2, char* tag,
+                                 int32_t cap, int64_t* lds_bytes);
 
 /* x[b, t, :] = 0 for t >= lens[b] on a [batches, T, dim] activation (row pitch ld): WavLM's `x[padding_mask] = 0`
  * (wavlm/WavLM.py:353, 574-575) in front of the positional convolution, for chunks padded up to a bucket length. */

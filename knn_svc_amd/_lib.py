@@ -11,7 +11,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("KNNSVC_LIB") or os.path.join(_HERE, "libknnsvc_hip.so")      # KNNSVC_LIB: an A/B build (csrc/Makefile)
-ABI_VERSION = 20
+ABI_VERSION = 21
 
 vp, i32, i64, f32, f64, sz = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_double, C.c_size_t
 
@@ -115,6 +115,8 @@ SIGNATURES = {
     "knnsvc_conv_gemm_last_epilogue": (C.c_char_p, []),
     "knnsvc_conv_gemm": (i32, [C.POINTER(ConvDesc), vp]),
     "knnsvc_conv_gemm_multi": (i32, [C.POINTER(ConvDesc), i32, vp]),
+    "knnsvc_conv_gemm_route": (i32, [C.POINTER(ConvDesc), i32, C.c_char_p, C.c_char_p, i32]),
+    "knnsvc_conv_gemm_tags": (i32, [C.c_char_p, i32]),
     "knnsvc_mean3": (i32, [vp, vp, vp, i64, f32, vp, vp, vp, i64, vp]),
     "knnsvc_axpy": (i32, [vp, i64, f32, i32, vp, vp]),
     "knnsvc_resblock_pair": (i32, [C.POINTER(PairDesc), vp]),
@@ -134,8 +136,11 @@ SIGNATURES = {
     "knnsvc_generator_forward": (i32, [vp, vp, vp, vp, i64, vp, vp, vp, sz, vp]),
     "knnsvc_layernorm": (i32, [vp, i64, i32, i32, vp, vp, i32, vp, i32, vp]),
     "knnsvc_wavlm_conv0": (i32, [vp, i32, i64, vp, i32, i32, i32, vp, vp, vp, i32, vp]),
+    "knnsvc_wavlm_conv0_route": (i32, [i32, i64, C.POINTER(i32), C.POINTER(i32)]),
+    "knnsvc_wavlm_conv0_last_route": (None, [C.POINTER(i32), C.POINTER(i32)]),
     "knnsvc_wavlm_gate": (i32, [vp, i64, i32, i32, i32, vp, vp, vp, vp, i32, vp]),
     "knnsvc_wavlm_attention_last_kernel": (C.c_char_p, []),
+    "knnsvc_wavlm_attention_route": (i32, [i32, i32, i32, i32, i32, C.c_char_p, i32, C.POINTER(i64)]),
     "knnsvc_wavlm_attention": (i32, [vp, vp, vp, i32, i32, i32, vp, i32, i32, vp, vp]),
     "knnsvc_mask_rows": (i32, [vp, i32, i32, i32, i32, vp, vp]),
     "knnsvc_row_norms": (i32, [vp, i64, i32, i32, vp, vp, vp, vp]),

@@ -979,60 +979,93 @@ __global__ __launch_bounds__(512, 1) void attention2w_kernel(const float* __rest
 
 static thread_local const char* g_last_attention = "";      // tag of the kernel the last knnsvc_wavlm_attention of this thread launched
 
-// One route's launch: the 160 KB LDS limit (t_max: the hint of its message), the kernel's LDS opt-in, a grid of
-// ceil(T / q_per_wg) x heads x batches workgroups, the launch and its check.
+// What a call launches: the kernel, its tag, queries per workgroup, threads and dynamic LDS
+enum AttKernel { ATT_F32, ATT_3, ATT_2, ATT_2Q, ATT_2W };
+struct AttRoute { AttKernel kernel; const char* tag; int q_per_wg, threads; size_t lds_bytes; };
+
+// KNNSVC_ATT_QB (0 = unset, 1, 2) and KNNSVC_ATT_NW (0 = unset, 8, anything else = 4), read per call: the parity test flips them
+static void att_knobs(int& qb, int& nw) {
+    const char* eq = getenv("KNNSVC_ATT_QB");
+    const char* ew = getenv("KNNSVC_ATT_NW");
+    qb = !eq ? 0 : (eq[0] == '1' ? 1 : 2);
+    nw = !ew ? 0 : (ew[0] == '8' ? 8 : 4);
+}
+
+// The dispatch rules: host arithmetic on the sizes, the flags (out_f16x2 with bit 2: the caller's range analysis says Q / K / V may
+// leave the f16x2 kernel's fixed-scale range) and the knobs (mode: KnKnobs::attention); nothing is launched.  A call no kernel
+// takes — a split layout outside the f16x2 route, a T whose bias table does not fit the 160 KB of LDS — is refused here.
+static int att_route(int batches, int T, int heads, int flags, int kv_f16x2, int mode, int qb, int nw, AttRoute& r) {
+    KN_REQUIRE(batches > 0 && T > 0 && heads > 0 && heads <= 65535 && batches <= 65535, "wavlm_attention: bad sizes");
+    if ((flags & 4) && mode == 2) mode = 3;
+    int t_max = 16000;      // the hint of the refusal's message
+    if (mode == 2) {
+        // 64 queries per wave once the 128-query grid is at least two rounds of the 768 resident workgroups (bench batch, 21 x 1500:
+        // 0.86 -> 0.78 ms); below that the larger workgroups leave CUs idle (3 x 777: 0.054 vs 0.063 ms).  Same results either
+        // way, bit for bit.  KNNSVC_ATT_QB=1 / 2 forces one of them.
+        const long blocks128 = (long)((T + 127) / 128) * heads * batches;
+        r = AttRoute{ATT_2, "wavlm_attention2", 128, 256, att2_lds_bytes(1, T)};
+        if ((qb == 2 || (qb == 0 && blocks128 >= 1536)) && T > 128) {
+            // eight waves per workgroup (three K / V buffers, one barrier per tile, SIMD neighbours out of phase) once the 512-query
+            // grid is at least two rounds of one workgroup per CU; KNNSVC_ATT_NW=4 / 8 forces one.  Same results, bit for bit.
+            const long blocks512 = (long)((T + 511) / 512) * heads * batches;
+            if ((nw ? nw == 8 : blocks512 >= 512) && att2_lds_bytes(3, T) <= 160 * 1024)
+                r = AttRoute{ATT_2W, "wavlm_attention2w", 512, 512, att2_lds_bytes(3, T)};
+            else
+                r = AttRoute{ATT_2Q, "wavlm_attention2q", 256, 256, att2_lds_bytes(1, T)};
+        }
+    } else {
+        KN_REQUIRE(!(flags & 1) && !kv_f16x2, "wavlm_attention: split output / pre-split K,V are only implemented by the f16x2 kernel");
+        if (mode == 3) {
+            r = AttRoute{ATT_3, "wavlm_attention3", 128, 256, (size_t)KT * KP3 + (size_t)HD * VP3 + att_table_bytes(T)};
+            t_max = 13000;
+        } else {
+            r = AttRoute{ATT_F32, "wavlm_attention", 128, 256, (size_t)(KT * LDKK + KT * LDV + 2 * T - 1) * 4};
+        }
+    }
+    KN_REQUIRE(r.lds_bytes <= 160 * 1024, "wavlm_attention: T too long for the LDS bias table (T <= ~%d)", t_max);
+    return KNNSVC_OK;
+}
+
+// One route's launch: the kernel's LDS opt-in, a grid of ceil(T / q_per_wg) x heads x batches workgroups, the launch and its check.
 template <auto KERNEL, class... Args>
-static int att_launch(int q_per_wg, int threads, size_t lds_bytes, int t_max, const char* tag, int T, int heads, int batches, void* stream,
-                      Args... args) {
-    KN_REQUIRE(lds_bytes <= 160 * 1024, "wavlm_attention: T too long for the LDS bias table (T <= ~%d)", t_max);
-    if (const int rc = kn_lds_optin<KERNEL>((int)lds_bytes, "wavlm_attention")) return rc;
-    dim3 grid((unsigned)((T + q_per_wg - 1) / q_per_wg), (unsigned)heads, (unsigned)batches);
-    hipLaunchKernelGGL(KERNEL, grid, dim3(threads), lds_bytes, (hipStream_t)stream, args...);
-    g_last_attention = tag;
-    return knnsvc_check_launch(tag);
+static int att_launch(const AttRoute& r, int T, int heads, int batches, void* stream, Args... args) {
+    if (const int rc = kn_lds_optin<KERNEL>((int)r.lds_bytes, "wavlm_attention")) return rc;
+    dim3 grid((unsigned)((T + r.q_per_wg - 1) / r.q_per_wg), (unsigned)heads, (unsigned)batches);
+    hipLaunchKernelGGL(KERNEL, grid, dim3(r.threads), r.lds_bytes, (hipStream_t)stream, args...);
+    g_last_attention = r.tag;
+    return knnsvc_check_launch(r.tag);
 }
 
 extern "C" const char* knnsvc_wavlm_attention_last_kernel(void) { return g_last_attention; }
+
+extern "C" int knnsvc_wavlm_attention_route(int32_t batches, int32_t T, int32_t heads, int32_t out_f16x2, int32_t kv_f16x2, char* tag,
+                                            int32_t cap, int64_t* lds_bytes) {
+    KN_REQUIRE(tag && cap >= 24 && lds_bytes, "wavlm_attention_route: 24 bytes for the tag, and a place for the LDS size");
+    int qb, nw;
+    att_knobs(qb, nw);
+    AttRoute r;
+    if (const int rc = att_route(batches, T, heads, out_f16x2, kv_f16x2, kn_knobs().attention, qb, nw, r)) return rc;
+    snprintf(tag, cap, "%s", r.tag);
+    *lds_bytes = (int64_t)r.lds_bytes;
+    return KNNSVC_OK;
+}
 
 extern "C" int knnsvc_wavlm_attention(const float* qkv, const float* gate, const float* table, int32_t batches,
                                       int32_t T, int32_t heads, float* out, int32_t out_f16x2, int32_t kv_f16x2, const int32_t* kv_len,
                                       void* stream) {
     KN_REQUIRE(qkv && gate && table && out, "wavlm_attention: null pointer");
-    KN_REQUIRE(batches > 0 && T > 0 && heads > 0 && heads <= 65535 && batches <= 65535, "wavlm_attention: bad sizes");
+    int qb, nw;
+    att_knobs(qb, nw);
+    AttRoute r;
+    if (const int rc = att_route(batches, T, heads, out_f16x2, kv_f16x2, kn_knobs().attention, qb, nw, r)) return rc;
     KN_REQUIRE(((uintptr_t)qkv & 15) == 0 && ((uintptr_t)out & 15) == 0, "wavlm_attention: 16-byte alignment");
-    static int env_mode = -1;      // KNNSVC_ATTENTION = f16x2 (default) | bf16x3 | fp32 (exact-f32 MFMA kernel)
-    if (env_mode < 0) {
-        const char* e = getenv("KNNSVC_ATTENTION");
-        env_mode = !e ? 2 : (e[0] == 'b') ? 3 : (e[0] == 'f' && e[1] == 'p') ? 0 : 2;
-    }
-    // bit 2 of the flags: the caller's range analysis says Q / K / V may leave the f16x2 kernel's fixed-scale range
-    const int mode = (out_f16x2 & 4) && env_mode == 2 ? 3 : env_mode;
     out_f16x2 &= 1;
-    if (mode == 2) {
-        // 64 queries per wave once the 128-query grid is at least two rounds of the 768 resident workgroups (bench batch, 21 x 1500:
-        // 0.86 -> 0.78 ms); below that the larger workgroups leave CUs idle (3 x 777: 0.054 vs 0.063 ms).  Same results either
-        // way, bit for bit.  KNNSVC_ATT_QB=1 / 2 forces one of them.
-        const char* eq = getenv("KNNSVC_ATT_QB");          // read per call: the parity test flips it
-        const int qb = !eq ? 0 : (eq[0] == '1' ? 1 : 2);
-        const long blocks128 = (long)((T + 127) / 128) * heads * batches;
-        if ((qb == 2 || (qb == 0 && blocks128 >= 1536)) && T > 128) {
-            // eight waves per workgroup (three K / V buffers, one barrier per tile, SIMD neighbours out of phase) once the 512-query
-            // grid is at least two rounds of one workgroup per CU; KNNSVC_ATT_NW=4 / 8 forces one.  Same results, bit for bit.
-            const char* ew = getenv("KNNSVC_ATT_NW");
-            const long blocks512 = (long)((T + 511) / 512) * heads * batches;
-            if ((ew ? ew[0] == '8' : blocks512 >= 512) && att2_lds_bytes(3, T) <= 160 * 1024)
-                return att_launch<attention2w_kernel<2>>(512, 512, att2_lds_bytes(3, T), 16000, "wavlm_attention2w", T, heads, batches, stream,
-                                                         qkv, gate, table, kv_len, T, heads, out, out_f16x2, kv_f16x2);
-            return att_launch<attention2q_kernel<2>>(256, 256, att2_lds_bytes(1, T), 16000, "wavlm_attention2q", T, heads, batches, stream,
-                                                     qkv, gate, table, kv_len, T, heads, out, out_f16x2, kv_f16x2);
-        }
-        return att_launch<attention2q_kernel<1>>(128, 256, att2_lds_bytes(1, T), 16000, "wavlm_attention2", T, heads, batches, stream,
-                                                 qkv, gate, table, kv_len, T, heads, out, out_f16x2, kv_f16x2);
+    switch (r.kernel) {
+        case ATT_2W: return att_launch<attention2w_kernel<2>>(r, T, heads, batches, stream, qkv, gate, table, kv_len, T, heads, out, out_f16x2, kv_f16x2);
+        case ATT_2Q: return att_launch<attention2q_kernel<2>>(r, T, heads, batches, stream, qkv, gate, table, kv_len, T, heads, out, out_f16x2, kv_f16x2);
+        case ATT_2: return att_launch<attention2q_kernel<1>>(r, T, heads, batches, stream, qkv, gate, table, kv_len, T, heads, out, out_f16x2, kv_f16x2);
+        case ATT_3: return att_launch<attention3_kernel>(r, T, heads, batches, stream, qkv, gate, table, kv_len, T, heads, out);
+        case ATT_F32: break;
     }
-    KN_REQUIRE(!out_f16x2 && !kv_f16x2, "wavlm_attention: split output / pre-split K,V are only implemented by the f16x2 kernel");
-    if (mode == 3)
-        return att_launch<attention3_kernel>(128, 256, (size_t)KT * KP3 + (size_t)HD * VP3 + att_table_bytes(T), 13000, "wavlm_attention3", T, heads,
-                                             batches, stream, qkv, gate, table, kv_len, T, heads, out);
-    return att_launch<attention_kernel>(128, 256, (size_t)(KT * LDKK + KT * LDV + 2 * T - 1) * 4, 16000, "wavlm_attention", T, heads, batches,
-                                        stream, qkv, gate, table, kv_len, T, heads, out);
+    return att_launch<attention_kernel>(r, T, heads, batches, stream, qkv, gate, table, kv_len, T, heads, out);
 }

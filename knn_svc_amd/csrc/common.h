@@ -119,6 +119,25 @@ __device__ __forceinline__ float kn_blend_mix(const KnBlendRow& r, const float (
 // KNNSVC_MATCH_GENERIC_K=1: the match stage at k = 4 skips its fast paths and runs the K kernels as any other k (select.hip)
 bool knnsvc_match_generic_k();
 
+// A/B switches of the three host dispatchers (conv_gemm.hip, attention.hip, elementwise.hip), read from the environment ONCE — by
+// the first call that looks at any of them — into this record; knnsvc_reload_knobs() re-reads them (tests that switch a route
+// inside one process call it through ops.reload_knobs()).  Defaults are the product configuration; none of these changes results
+// beyond what its comment says.  ONE record for the library: the definition, kn_knobs() and the reload are in api.hip.
+struct KnKnobs {
+    int quad = 1;                  // KNNSVC_QUAD: 0 = no 256x256 kernel, 1 = by shape (default), 2 = every qualifying launch
+    bool quad_epi = true;          // KNNSVC_QUAD_EPI=0: generic epilogue behind the quad kernel (bit-identical, slower)
+    bool generic_epilogue = false; // KNNSVC_EPILOGUE=g: the generic (64-bit addressed) epilogue everywhere
+    bool win = true;               // KNNSVC_WIN=0: tap-major kernel instead of the windowed one (other summation order)
+    bool win_wide = true;          // KNNSVC_WIN_WIDE=0: the windowed kernels keep the column-per-lane epilogue
+    bool win_small = true, win_deep = true, win160 = true;      // KNNSVC_WIN_SMALL / _DEEP / WIN160 = 0: tile-shape rules off
+    bool gemm_small = true;        // KNNSVC_GEMM_SMALL=0: no 64x64 tile for launches below one round of 128x128 tiles
+    int attention = 2;             // KNNSVC_ATTENTION = f16x2 (2, default) | bf16x3 (3) | fp32 (0: the exact-f32 MFMA kernel)
+    int conv0_rp = 2;              // KNNSVC_CONV0_RP: conv0's rows per pass, 2 (default), 4, or 1 = the shuffle-sum kernel, for A/B
+    int conv0_subs = 8;            // KNNSVC_CONV0_SUBS: spans of 64 rows a conv0 workgroup walks on long inputs (1..64)
+    bool loaded = false;
+};
+const KnKnobs& kn_knobs();
+
 // Opt-in of KERNEL to `bytes` of dynamic LDS (a launch with more than 64 KiB fails without it).  The attribute is set once per
 // kernel instantiation and process, and again only when a later call needs more.  `entry`: the API entry point, for the message.
 template <auto KERNEL>

@@ -1029,6 +1029,7 @@ __global__ void split_weight_kernel(const float* __restrict__ w, long n, int K, 
 
 template <class G, int VEC>
 int launch(const ConvArgs& a, int batches, hipStream_t st) {
+    if (const int rc = kn_lds_optin<conv_gemm_kernel<G, VEC>>(G::LDS_BYTES, "conv_gemm")) return rc;
     dim3 grid((unsigned)cdiv64(a.m, G::BM), (unsigned)cdiv64(a.n, G::BN), (unsigned)(batches * a.groups));
     hipLaunchKernelGGL((conv_gemm_kernel<G, VEC>), grid, dim3(256), G::LDS_BYTES, st, a);
     return knnsvc_check_launch("conv_gemm");
@@ -1053,47 +1054,7 @@ using W64 = Gemm2Win<256, 64, 4, 1, 2, 2, 64>;        // 320 rows (45 KB) + 9 KB
 using W32 = Gemm2Win<256, 32, 4, 1, 2, 1, 64>;        // 320 rows + 4.5 KB
 using W64P = Gemm2Win<256, 64, 4, 1, 2, 2, 128>;      // k = 128 positional conv: 384 rows (54 KB) + 9 KB
 
-template <class G>
-int prepare() {   // the fp32 kernels' dynamic LDS, all three loader forms, on the first call
-    int rc = kn_lds_optin<conv_gemm_kernel<G, 8>>(G::LDS_BYTES, "conv_gemm");
-    if (!rc) rc = kn_lds_optin<conv_gemm_kernel<G, 4>>(G::LDS_BYTES, "conv_gemm");
-    if (!rc) rc = kn_lds_optin<conv_gemm_kernel<G, 1>>(G::LDS_BYTES, "conv_gemm");
-    return rc;
-}
-
-// A/B switches of the dispatcher, read from the environment ONCE (first launch) into this struct; knnsvc_reload_knobs() re-reads
-// them (tests that switch a route inside one process call it through ops.reload_knobs()).  Round 3 called getenv ~10 times per
-// launch.  Defaults are the product configuration; none of these changes results beyond what its comment says.
-struct Knobs {
-    int quad = 1;                  // KNNSVC_QUAD: 0 = no 256x256 kernel, 1 = by shape (default), 2 = every qualifying launch
-    bool quad_epi = true;          // KNNSVC_QUAD_EPI=0: generic epilogue behind the quad kernel (bit-identical, slower)
-    bool generic_epilogue = false; // KNNSVC_EPILOGUE=g: the generic (64-bit addressed) epilogue everywhere
-    bool win = true;               // KNNSVC_WIN=0: tap-major kernel instead of the windowed one (other summation order)
-    bool win_wide = true;          // KNNSVC_WIN_WIDE=0: the windowed kernels keep the column-per-lane epilogue
-    bool win_small = true, win_deep = true, win160 = true;      // KNNSVC_WIN_SMALL / _DEEP / WIN160 = 0: tile-shape rules off
-    bool gemm_small = true;        // KNNSVC_GEMM_SMALL=0: no 64x64 tile for launches below one round of 128x128 tiles
-    bool loaded = false;
-};
-Knobs g_knobs;
-bool env_off(const char* name) { const char* e = getenv(name); return e && e[0] == '0'; }
-void load_knobs() {
-    Knobs k;
-    const char* q = getenv("KNNSVC_QUAD");
-    k.quad = q ? atoi(q) : 1;
-    k.quad_epi = !env_off("KNNSVC_QUAD_EPI");
-    const char* ep = getenv("KNNSVC_EPILOGUE");
-    k.generic_epilogue = ep && ep[0] == 'g';
-    k.win = !env_off("KNNSVC_WIN"); k.win_small = !env_off("KNNSVC_WIN_SMALL"); k.win_deep = !env_off("KNNSVC_WIN_DEEP");
-    k.win_wide = !env_off("KNNSVC_WIN_WIDE");
-    k.win160 = !env_off("KNNSVC_WIN160"); k.gemm_small = !env_off("KNNSVC_GEMM_SMALL");
-    k.loaded = true;
-    g_knobs = k;
-}
-const Knobs& knobs() { if (!g_knobs.loaded) load_knobs(); return g_knobs; }
-
 }  // namespace
-
-extern "C" int knnsvc_reload_knobs(void) { load_knobs(); return KNNSVC_OK; }
 
 // descriptor -> kernel arguments (validation included); `fast`: the buffer-load fast path applies, `vec4`: 16-byte vectors do
 static int conv_prep(const knnsvc_conv_desc* d, ConvArgs& a, bool& fast, bool& vec4, bool& quad_ok) {
@@ -1137,15 +1098,12 @@ static int conv_prep(const knnsvc_conv_desc* d, ConvArgs& a, bool& fast, bool& v
     KN_REQUIRE(d->out_f16x2 >= 0 && (d->out_f16x2 <= 1 || d->out_f16x2 % 32 == 0), "conv_gemm: out_f16x2 is 0, 1 or the first split column (a multiple of 32)");
     a.wide = 0; a.plain = 0;
     a.lin = !d->convt_u && (long)d->m * d->ldo * 4 < (1L << 31) && (!d->resid || (long)d->m * d->ldr * 4 < (1L << 31)) &&
-            !knobs().generic_epilogue;      // KNNSVC_EPILOGUE=g: generic epilogue (A/B)
+            !kn_knobs().generic_epilogue;      // KNNSVC_EPILOGUE=g: generic epilogue (A/B)
 
     // 16-byte vector path needs every float4 of A and W to be aligned and inside one tap
     vec4 = (d->cin % 4 == 0) && (d->ldx % 4 == 0) && (((uintptr_t)d->x & 15) == 0) &&
                       (((uintptr_t)d->w & 15) == 0) && (d->x_bstride % 4 == 0) && (d->x_gstride % 4 == 0) &&
                       (d->w_gstride % 4 == 0);
-    if (const int rc = prepare<G128>()) return rc;
-    if (const int rc = prepare<G64>()) return rc;
-    if (const int rc = prepare<G32>()) return rc;
     // buffer-load fast path: every slab inside one tap, resources below 1 GiB
     fast = vec4 && (d->cin % 32 == 0) && ((long)d->t_in * d->ldx * 4 < (1L << 30)) &&
                       ((long)d->n * a.K * 4 < (1L << 30)) && ((long)d->m * d->stride * d->ldx * 4 < (1L << 30));
@@ -1175,7 +1133,7 @@ static int conv_prep(const knnsvc_conv_desc* d, ConvArgs& a, bool& fast, bool& v
             d->bias_gstride % 4 == 0;
         const bool plain_t = d->convt_u && !d->resid && d->convt_cout % 4 == 0 && (long)d->t_out * d->ldo * 4 < (1L << 31) &&
                              (long)d->m * d->convt_u < (1L << 30);
-        a.wide = knobs().win_wide && (a.lin || plain_t) && !a.out_split && d->act == KNNSVC_ACT_NONE && !d->accumulate && a.div == 1.0f &&
+        a.wide = kn_knobs().win_wide && (a.lin || plain_t) && !a.out_split && d->act == KNNSVC_ACT_NONE && !d->accumulate && a.div == 1.0f &&
             d->n % 4 == 0 && d->ldo % 4 == 0 && ((uintptr_t)d->out & 15) == 0 && d->o_bstride % 4 == 0 && d->o_gstride % 4 == 0 &&
             (!d->resid || (d->ldr % 4 == 0 && ((uintptr_t)d->resid & 15) == 0 && d->r_bstride % 4 == 0 && d->r_gstride % 4 == 0)) &&
             (!d->bias || (d->bias_period % 4 == 0 && ((uintptr_t)d->bias & 15) == 0 && d->bias_gstride % 4 == 0));
@@ -1184,101 +1142,148 @@ static int conv_prep(const knnsvc_conv_desc* d, ConvArgs& a, bool& fast, bool& v
     return KNNSVC_OK;
 }
 
+// Every kernel the dispatcher can pick, one id per tag; CK_NONE: nothing to launch (m == 0), or no common grid (below)
+enum ConvKernel {
+    CK_NONE, CK_Q256S, CK_W128D, CK_W128S, CK_W160, CK_W128, CK_W64, CK_W32, CK_W64P, CK_F64S, CK_F128, CK_F128A2, CK_F64, CK_F32,
+    CK_H128, CK_H64, CK_H32, CK_G128V8, CK_G128V4, CK_G128V1, CK_G64V8, CK_G64V4, CK_G64V1, CK_G32V8, CK_G32V4, CK_G32V1, CK_COUNT
+};
+// the tag of a kernel (knnsvc_conv_gemm_last_kernel); `merged`: several descriptors in one grid, which only the windowed kernels take
+static const char* conv_tag(int k, bool merged) {
+    static const char* const one[CK_COUNT] = {"", "Q256S", "W128D", "W128S", "W160", "W128", "W64", "W32", "W64P", "F64S", "F128", "F128a2",
+        "F64", "F32", "H128", "H64", "H32", "G128v8", "G128v4", "G128v1", "G64v8", "G64v4", "G64v1", "G32v8", "G32v4", "G32v1"};
+    static const char* const many[] = {"W128Dx", "W128Sx", "W160x", "W128x", "W64x", "W32x", "W64Px"};
+    if (!merged) return one[k];
+    return k >= CK_W128D && k <= CK_W64P ? many[k - CK_W128D] : "";
+}
+
 // the windowed kernel's tile shape for `z` convolutions of [m, n] in one grid (z = batches * groups * descriptors)
-enum WinShape { WS_NONE, WS_128D, WS_128S, WS_160, WS_128, WS_64, WS_32, WS_64P };
-static WinShape win_shape(const knnsvc_conv_desc* d, const ConvArgs& a, long z) {
-    if (a.x_split || d->convt_u || d->stride != 1 || d->taps < 3 || d->dil < 1 || d->ldx % 4 != 0 || !knobs().win) return WS_NONE;
+static ConvKernel win_shape(const knnsvc_conv_desc* d, const ConvArgs& a, long z, const KnKnobs& kb) {
+    if (a.x_split || d->convt_u || d->stride != 1 || d->taps < 3 || d->dil < 1 || d->ldx % 4 != 0 || !kb.win) return CK_NONE;
     const int halo = (d->taps - 1) * d->dil;
     if (halo <= 64) {
         if (d->n > 64) {
             // fewer than ~2/3 of the chip's 768 resident slots at 128-row tiles: halve the tile height
-            if (knobs().win_small && cdiv64(d->m, 128) * cdiv64(d->n, 128) * z < 512) {
+            if (kb.win_small && cdiv64(d->m, 128) * cdiv64(d->n, 128) * z < 512) {
                 // two steps of weight prefetch where a launch leaves at most one workgroup per CU (nothing else hides the L2
                 // round trip: 3750 x 256, k = 11: 70 -> 59 us); with more workgroups per CU the neighbours already do and the
                 // second register set only costs (15 000 x 256, k = 7: 61 -> 66 us).  Same products, same order: same bits.
-                if (knobs().win_deep && cdiv64(d->m, 64) * cdiv64(d->n, 128) * z <= 256) return WS_128D;
-                return WS_128S;
+                if (kb.win_deep && cdiv64(d->m, 64) * cdiv64(d->n, 128) * z <= 256) return CK_W128D;
+                return CK_W128S;
             }
             // Tile-count quantisation: 768 blocks are resident at once (3 per CU); a launch of 938 128-row tiles (the
             // generator's C = 128 stage at 30 s: 120 000 rows) runs two rounds, the second 22 % full.  160-row tiles make
             // it 750 — one round.  Pick the height with the fewer (rounds x rows per round).  KNNSVC_WIN160=0: off.
             const long zz = z * cdiv64(d->n, 128);
             const long r128 = cdiv64(cdiv64(d->m, 128) * zz, 768) * 128, r160 = cdiv64(cdiv64(d->m, 160) * zz, 768) * 160;
-            return (knobs().win160 && r160 < r128) ? WS_160 : WS_128;
+            return (kb.win160 && r160 < r128) ? CK_W160 : CK_W128;
         }
-        return d->n > 32 ? WS_64 : WS_32;
+        return d->n > 32 ? CK_W64 : CK_W32;
     }
-    if (halo <= 128 && d->n > 32 && d->n <= 64) return WS_64P;
-    return WS_NONE;
+    if (halo <= 128 && d->n > 32 && d->n <= 64) return CK_W64P;
+    return CK_NONE;
 }
 
-// the windowed kernel of shape `ws` for one descriptor (over its batches and groups) or for `count` of them in one grid
-static int launch_win(WinShape ws, const ConvArgs* args, int count, int batches, hipStream_t st) {
-    const bool x = count > 1;
-    switch (ws) {
-        case WS_128D: g_last_kernel = x ? "W128Dx" : "W128D"; return launch2win<W128D, 4>(args, count, batches, st);
-        case WS_128S: g_last_kernel = x ? "W128Sx" : "W128S"; return launch2win<W128S, 4>(args, count, batches, st);
-        case WS_160: g_last_kernel = x ? "W160x" : "W160"; return launch2win<W160, 3>(args, count, batches, st);
-        case WS_128: g_last_kernel = x ? "W128x" : "W128"; return launch2win<W128, 3>(args, count, batches, st);
-        case WS_64: g_last_kernel = x ? "W64x" : "W64"; return launch2win<W64, 2>(args, count, batches, st);
-        case WS_32: g_last_kernel = x ? "W32x" : "W32"; return launch2win<W32, 3>(args, count, batches, st);
-        case WS_64P: g_last_kernel = x ? "W64Px" : "W64P"; return launch2win<W64P, 2>(args, count, batches, st);
-        case WS_NONE: break;
+// What a prepared descriptor launches: the kernel, its tag, and the epilogue tag ("patch" / "lane" for the windowed and tap-major
+// f16x2 kernels, "" for kernels with an epilogue of their own).  quad_epi: conv_gemm2quad_kernel's EPI.
+struct ConvRoute { ConvKernel kernel = CK_NONE; int quad_epi = 0; const char* tag = ""; const char* epilogue = ""; };
+
+// The dispatch rules: host arithmetic on the descriptor, what conv_prep derived from it and the knobs; nothing is launched and no
+// operand is read.  count == 1: the descriptor's own launch (over its batches and groups); CK_NONE when m == 0.  count > 1: the
+// descriptor as one of `count` in ONE grid, which only the windowed kernels offer (batches == groups == 1); CK_NONE when it cannot.
+static ConvRoute conv_route(const knnsvc_conv_desc* d, const ConvArgs& a, bool fast, bool vec4, bool quad_ok, int count, const KnKnobs& kb) {
+    ConvRoute r;
+    auto pick = [&](ConvKernel k) { r.kernel = k; r.tag = conv_tag(k, count > 1); return r; };
+    if (d->m == 0) return r;
+    if (count > 1) {
+        if (fast && a.w2 && d->batches == 1 && d->groups == 1 && pick(win_shape(d, a, count, kb)).kernel != CK_NONE)
+            r.epilogue = a.wide ? "patch" : "lane";
+        return r;
     }
-    return knnsvc_fail(KNNSVC_EINVAL, "conv_gemm: no windowed kernel for this shape");
+    if (fast && a.w2) {        // fp32 emulated on the fp16 matrix cores (gemm2_core.h)
+        // 256x256 block, 128x128 wave tiles, hand-pipelined loop (Gemm2QuadS: v_mfma_f32_16x16x32_f16, 32-k slabs): every A2
+        // launch with K >= 1024 and n >= 256 — FFN1 / FFN2 / QKV / out-proj, the conv stack, the kNN's dot matrix.
+        // KNNSVC_QUAD=0 switches it off, =2 forces it for every qualifying launch (tests, A/B runs).
+        // The rule looks at the layer's shape (n, K) only, never at m or the batch: the quad kernel sums over K in another
+        // grouping than the 128x128 kernels, so a rule that counted tiles (round 2) made an utterance's features depend, in
+        // their last bits, on how many chunks were encoded with it — enough to flip near-tied neighbours and to make a source
+        // converted in a batch differ from the same source converted alone (tests/test_gpu_product.py).
+        if (d->fixed_tile != 1 && quad_ok && (d->fixed_tile == 2 || kb.quad == 2 || (kb.quad == 1 && d->n >= 256 && a.K >= 1024))) {
+            // specialised epilogues (conv_epilogue_wide_fast): bias (+ split), GELU (+ split), residual; KNNSVC_QUAD_EPI=0: generic
+            const bool fast_epi = kb.quad_epi && !d->accumulate && a.div == 1.0f && !a.out_absmax &&
+                                  (d->act == KNNSVC_ACT_NONE || d->act == KNNSVC_ACT_GELU) && !(d->resid && d->act != KNNSVC_ACT_NONE);
+            r.quad_epi = !fast_epi ? 0 : d->resid ? 3 : d->act == KNNSVC_ACT_GELU ? 2 : 1;
+            return pick(CK_Q256S);
+        }
+        r.epilogue = a.wide ? "patch" : "lane";
+        // stride-1 multi-tap convolutions on fp32 input: windowed kernel (A staged once per channel slab, not once per tap)
+        const long z = (long)d->batches * d->groups;
+        const ConvKernel ws = win_shape(d, a, z, kb);
+        if (ws != CK_NONE) return pick(ws);
+        if (d->n > 64 && cdiv64(d->m, 128) * cdiv64(d->n, 128) * z < 256 && kb.gemm_small) return pick(CK_F64S);
+        return pick(d->n > 64 ? (a.x_split ? CK_F128A2 : CK_F128) : d->n > 32 ? CK_F64 : CK_F32);
+    }
+    const int size = d->n > 64 ? 0 : d->n > 32 ? 1 : 2;
+    if (fast && a.w3) return pick((ConvKernel)(CK_H128 + size));        // fp32 emulated on the bf16 matrix cores (gemm3_core.h)
+    return pick((ConvKernel)(CK_G128V8 + 3 * size + (fast ? 0 : vec4 ? 1 : 2)));
+}
+
+// prep and route of `count` descriptors.  count > 1: the route of their common grid — one windowed kernel and one output shape
+// for every descriptor — or CK_NONE: one launch each.  A descriptor that does not validate is the error of the whole call.
+static int conv_plan(const knnsvc_conv_desc* descs, int count, ConvArgs* args, ConvRoute& route) {
+    for (int i = 0; i < count; ++i) {
+        bool fast = false, vec4 = false, quad_ok = false;
+        if (const int rc = conv_prep(&descs[i], args[i], fast, vec4, quad_ok)) return rc;
+        const ConvRoute r = conv_route(&descs[i], args[i], fast, vec4, quad_ok, count, kn_knobs());
+        if (i == 0) route = r;
+        else if (r.kernel != route.kernel || descs[i].m != descs[0].m || descs[i].n != descs[0].n) route = ConvRoute();
+    }
+    return KNNSVC_OK;
+}
+
+// the routed kernel for one descriptor (over its batches and groups) or for `count` of them in one grid
+static int conv_launch(const ConvRoute& r, const ConvArgs* args, int count, int batches, hipStream_t st) {
+    const ConvArgs& a = args[0];
+    switch (r.kernel) {
+        case CK_Q256S:
+            if (r.quad_epi == 3) return launch2quad<Q256S, 3>(a, batches, st);
+            if (r.quad_epi == 2) return launch2quad<Q256S, 2>(a, batches, st);
+            if (r.quad_epi == 1) return launch2quad<Q256S, 1>(a, batches, st);
+            return launch2quad<Q256S>(a, batches, st);
+        case CK_W128D: return launch2win<W128D, 4>(args, count, batches, st);
+        case CK_W128S: return launch2win<W128S, 4>(args, count, batches, st);
+        case CK_W160: return launch2win<W160, 3>(args, count, batches, st);
+        case CK_W128: return launch2win<W128, 3>(args, count, batches, st);
+        case CK_W64: return launch2win<W64, 2>(args, count, batches, st);
+        case CK_W32: return launch2win<W32, 3>(args, count, batches, st);
+        case CK_W64P: return launch2win<W64P, 2>(args, count, batches, st);
+        case CK_F64S: return launch2<F64S>(a, batches, st);
+        case CK_F128: case CK_F128A2: return launch2<F128>(a, batches, st);
+        case CK_F64: return launch2<F64>(a, batches, st);
+        case CK_F32: return launch2<F32>(a, batches, st);
+        case CK_H128: return launch3<H128>(a, batches, st);
+        case CK_H64: return launch3<H64>(a, batches, st);
+        case CK_H32: return launch3<H32>(a, batches, st);
+        case CK_G128V8: return launch<G128, 8>(a, batches, st);
+        case CK_G128V4: return launch<G128, 4>(a, batches, st);
+        case CK_G128V1: return launch<G128, 1>(a, batches, st);
+        case CK_G64V8: return launch<G64, 8>(a, batches, st);
+        case CK_G64V4: return launch<G64, 4>(a, batches, st);
+        case CK_G64V1: return launch<G64, 1>(a, batches, st);
+        case CK_G32V8: return launch<G32, 8>(a, batches, st);
+        case CK_G32V4: return launch<G32, 4>(a, batches, st);
+        case CK_G32V1: return launch<G32, 1>(a, batches, st);
+        case CK_NONE: case CK_COUNT: break;
+    }
+    return KNNSVC_OK;
 }
 
 extern "C" int knnsvc_conv_gemm(const knnsvc_conv_desc* d, void* stream) {
     ConvArgs a;
-    bool fast = false, vec4 = false, quad_ok = false;
-    const int rc = conv_prep(d, a, fast, vec4, quad_ok);
-    if (rc) return rc;
-    if (d->m == 0) return KNNSVC_OK;
-    hipStream_t st = (hipStream_t)stream;
-    g_last_epilogue = "";
-    if (fast && a.w2) {        // fp32 emulated on the fp16 matrix cores (gemm2_core.h)
-        if (d->fixed_tile != 1 && quad_ok) {
-            // 256x256 block, 128x128 wave tiles, hand-pipelined loop (Gemm2QuadS: v_mfma_f32_16x16x32_f16, 32-k slabs): every A2
-            // launch with K >= 1024 and n >= 256 — FFN1 / FFN2 / QKV / out-proj, the conv stack, the kNN's dot matrix.
-            // KNNSVC_QUAD=0 switches it off, =2 forces it for every qualifying launch (tests, A/B runs).
-            // The rule looks at the layer's shape (n, K) only, never at m or the batch: the quad kernel sums over K in another
-            // grouping than the 128x128 kernels, so a rule that counted tiles (round 2) made an utterance's features depend, in
-            // their last bits, on how many chunks were encoded with it — enough to flip near-tied neighbours and to make a source
-            // converted in a batch differ from the same source converted alone (tests/test_gpu_product.py).
-            const Knobs& kb = knobs();
-            if (d->fixed_tile == 2 || kb.quad == 2 || (kb.quad == 1 && d->n >= 256 && a.K >= 1024)) {
-                // specialised epilogues (conv_epilogue_wide_fast): bias (+ split), GELU (+ split), residual; KNNSVC_QUAD_EPI=0: generic
-                const bool fast_epi = kb.quad_epi && !d->accumulate && a.div == 1.0f && !a.out_absmax &&
-                                      (d->act == KNNSVC_ACT_NONE || d->act == KNNSVC_ACT_GELU) && !(d->resid && d->act != KNNSVC_ACT_NONE);
-                g_last_kernel = "Q256S";
-                if (fast_epi && d->resid) return launch2quad<Q256S, 3>(a, d->batches, st);
-                if (fast_epi && d->act == KNNSVC_ACT_GELU) return launch2quad<Q256S, 2>(a, d->batches, st);
-                if (fast_epi) return launch2quad<Q256S, 1>(a, d->batches, st);
-                return launch2quad<Q256S>(a, d->batches, st);
-            }
-        }
-        g_last_epilogue = a.wide ? "patch" : "lane";      // the windowed and tap-major f16x2 kernels below
-        // stride-1 multi-tap convolutions on fp32 input: windowed kernel (A staged once per channel slab, not once per tap)
-        const WinShape ws = win_shape(d, a, (long)d->batches * d->groups);
-        if (ws != WS_NONE) return launch_win(ws, &a, 1, d->batches, st);
-        if (d->n > 64 && cdiv64(d->m, 128) * cdiv64(d->n, 128) * d->batches * d->groups < 256) {
-            if (knobs().gemm_small) { g_last_kernel = "F64S"; return launch2<F64S>(a, d->batches, st); }
-        }
-        g_last_kernel = d->n > 64 ? (a.x_split ? "F128a2" : "F128") : d->n > 32 ? "F64" : "F32";
-        if (d->n > 64) return launch2<F128>(a, d->batches, st);
-        if (d->n > 32) return launch2<F64>(a, d->batches, st);
-        return launch2<F32>(a, d->batches, st);
-    }
-    if (fast && a.w3) {        // fp32 emulated on the bf16 matrix cores (gemm3_core.h)
-        g_last_kernel = d->n > 64 ? "H128" : d->n > 32 ? "H64" : "H32";
-        if (d->n > 64) return launch3<H128>(a, d->batches, st);
-        if (d->n > 32) return launch3<H64>(a, d->batches, st);
-        return launch3<H32>(a, d->batches, st);
-    }
-    g_last_kernel = d->n > 64 ? (fast ? "G128v8" : vec4 ? "G128v4" : "G128v1") : d->n > 32 ? (fast ? "G64v8" : vec4 ? "G64v4" : "G64v1") : (fast ? "G32v8" : vec4 ? "G32v4" : "G32v1");
-    if (d->n > 64) return fast ? launch<G128, 8>(a, d->batches, st) : vec4 ? launch<G128, 4>(a, d->batches, st) : launch<G128, 1>(a, d->batches, st);
-    if (d->n > 32) return fast ? launch<G64, 8>(a, d->batches, st) : vec4 ? launch<G64, 4>(a, d->batches, st) : launch<G64, 1>(a, d->batches, st);
-    return fast ? launch<G32, 8>(a, d->batches, st) : vec4 ? launch<G32, 4>(a, d->batches, st) : launch<G32, 1>(a, d->batches, st);
+    ConvRoute r;
+    if (const int rc = conv_plan(d, 1, &a, r)) return rc;
+    if (r.kernel == CK_NONE) return KNNSVC_OK;        // m == 0
+    g_last_kernel = r.tag; g_last_epilogue = r.epilogue;
+    return conv_launch(r, &a, 1, d->batches, (hipStream_t)stream);
 }
 
 extern "C" const char* knnsvc_conv_gemm_last_kernel(void) { return g_last_kernel; }
@@ -1287,21 +1292,38 @@ extern "C" const char* knnsvc_conv_gemm_last_epilogue(void) { return g_last_epil
 extern "C" int knnsvc_conv_gemm_multi(const knnsvc_conv_desc* descs, int32_t count, void* stream) {
     KN_REQUIRE(descs && count >= 1 && count <= KN_MAX_MULTI, "conv_gemm_multi: 1..4 descriptors");
     ConvArgsN an;
-    bool one_grid = true;
-    for (int i = 0; i < count; ++i) {
-        bool fast = false, vec4 = false, quad_ok = false;
-        const int rc = conv_prep(&descs[i], an.b[i], fast, vec4, quad_ok);
-        if (rc) return rc;
-        const knnsvc_conv_desc& d = descs[i];
-        // one grid needs one output shape and the windowed kernel for every descriptor; anything else: one launch each
-        one_grid = one_grid && fast && an.b[i].w2 && d.batches == 1 && d.groups == 1 && d.m == descs[0].m && d.n == descs[0].n && d.m > 0 &&
-                   win_shape(&d, an.b[i], count) != WS_NONE && win_shape(&d, an.b[i], count) == win_shape(&descs[0], an.b[0], count);
-    }
-    if (!one_grid || count == 1) {
+    ConvRoute r;
+    if (const int rc = conv_plan(descs, count, an.b, r)) return rc;
+    if (count == 1 || r.kernel == CK_NONE) {          // no common grid: one launch each
         for (int i = 0; i < count; ++i) { const int rc = knnsvc_conv_gemm(&descs[i], stream); if (rc) return rc; }
         return KNNSVC_OK;
     }
-    return launch_win(win_shape(&descs[0], an.b[0], count), an.b, count, 1, (hipStream_t)stream);      // (not WS_NONE: one_grid)
+    g_last_kernel = r.tag; g_last_epilogue = r.epilogue;
+    return conv_launch(r, an.b, count, 1, (hipStream_t)stream);
+}
+
+extern "C" int knnsvc_conv_gemm_route(const knnsvc_conv_desc* descs, int32_t count, char* tag, char* epilogue, int32_t cap) {
+    KN_REQUIRE(descs && count >= 1 && count <= KN_MAX_MULTI && tag && epilogue && cap >= 16, "conv_gemm_route: 1..4 descriptors, 16 bytes per tag");
+    ConvArgsN an;
+    ConvRoute r;
+    if (const int rc = conv_plan(descs, count, an.b, r)) return rc;
+    snprintf(tag, cap, "%s", r.tag);
+    snprintf(epilogue, cap, "%s", r.epilogue);
+    return KNNSVC_OK;
+}
+
+extern "C" int knnsvc_conv_gemm_tags(char* out, int32_t cap) {
+    KN_REQUIRE(out && cap > 0, "conv_gemm_tags: no buffer");
+    int used = 0;
+    out[0] = 0;
+    for (int merged = 0; merged < 2; ++merged)
+        for (int k = CK_NONE + 1; k < CK_COUNT; ++k) {
+            const char* t = conv_tag(k, merged != 0);
+            if (!t[0]) continue;
+            used += snprintf(out + used, cap - used, used ? " %s" : "%s", t);
+            KN_REQUIRE(used < cap, "conv_gemm_tags: %d bytes are too few", (int)cap);
+        }
+    return KNNSVC_OK;
 }
 
 extern "C" int knnsvc_split_weight_bf16x3(const float* w, int64_t rows, int32_t K, void* out, void* stream) {

@@ -462,6 +462,26 @@ extern "C" int knnsvc_harmonic_amps(const float* spec, const float* f0, int64_t 
     return knnsvc_check_launch("harmonic_amps");
 }
 
+// conv0's launch shape: rows per pass (the kernel's reduction flavour) and the spans of 64 rows a workgroup walks — 8 (21 x 96 063 rows:
+// 1.54 -> 1.34 ms; 4: 1.36, 2: 1.41) where that still leaves several rounds of workgroups (768 are resident), 1 for short inputs.
+// Host arithmetic on the sizes and the knobs (rp: KnKnobs::conv0_rp, subs_env: KnKnobs::conv0_subs).
+struct Conv0Route { int rows_per_pass, spans; };
+static Conv0Route conv0_route(long T, int batches, int rp, int subs_env) {
+    return Conv0Route{rp, cdiv64(T, 64L * subs_env) * batches >= 3072 ? subs_env : 1};
+}
+static thread_local Conv0Route g_last_conv0 = {0, 0};       // what the last knnsvc_wavlm_conv0 of this thread launched with
+
+extern "C" int knnsvc_wavlm_conv0_route(int32_t batches, int64_t T, int32_t* rows_per_pass, int32_t* spans) {
+    KN_REQUIRE(batches > 0 && batches <= 65535 && T >= 1 && rows_per_pass && spans, "wavlm_conv0_route: bad arguments");
+    const Conv0Route r = conv0_route((long)T, batches, kn_knobs().conv0_rp, kn_knobs().conv0_subs);
+    *rows_per_pass = r.rows_per_pass; *spans = r.spans;
+    return KNNSVC_OK;
+}
+extern "C" void knnsvc_wavlm_conv0_last_route(int32_t* rows_per_pass, int32_t* spans) {
+    if (rows_per_pass) *rows_per_pass = g_last_conv0.rows_per_pass;
+    if (spans) *spans = g_last_conv0.spans;
+}
+
 extern "C" int knnsvc_wavlm_conv0(const float* x, int32_t batches, int64_t L, const float* w, int32_t channels, int32_t k,
                                   int32_t stride, const float* gamma, const float* beta, float* out, int32_t out_f16x2, void* stream) {
     KN_REQUIRE(x && w && gamma && beta && out, "wavlm_conv0: null pointer");
@@ -471,11 +491,8 @@ extern "C" int knnsvc_wavlm_conv0(const float* x, int32_t batches, int64_t L, co
     KN_REQUIRE(!out_f16x2 || channels >= 256, "wavlm_conv0: split output needs >= 256 channels");
     const long T = (L - k) / stride + 1;
     hipStream_t st = (hipStream_t)stream;
-    static int rp = -1, subs_env = -1;        // rows per pass and reduction flavour: 2 (default), 4, or 1 = round 2's kernel (shuffle sums), for A/B
-    if (rp < 0) { const char* e = getenv("KNNSVC_CONV0_RP"); rp = e ? atoi(e) : 2; if (rp != 1 && rp != 4) rp = 2; }
-    if (subs_env < 0) { const char* e = getenv("KNNSVC_CONV0_SUBS"); subs_env = e ? atoi(e) : 8; if (subs_env < 1 || subs_env > 64) subs_env = 8; }
-    // spans of 64 rows per workgroup: 8 (21 x 96 063 rows: 1.54 -> 1.34 ms; 4: 1.36, 2: 1.41) where that still leaves several rounds of workgroups (768 are resident), 1 for short inputs
-    const int subs = cdiv64(T, 64L * subs_env) * batches >= 3072 ? subs_env : 1;
+    const Conv0Route r = g_last_conv0 = conv0_route(T, batches, kn_knobs().conv0_rp, kn_knobs().conv0_subs);
+    const int rp = r.rows_per_pass, subs = r.spans;
     dim3 grid((unsigned)cdiv64(T, 64L * subs), (unsigned)batches);
 #define KN_C0R(CPL, KM, RP) hipLaunchKernelGGL((conv0_ln_gelu_kernel<CPL, KM, RP>), grid, dim3(256), 0, st, x, (long)L, T, k, stride, w, gamma, beta, out, out_f16x2, subs)
 #define KN_C0(CPL, KM) { if (rp == 2) KN_C0R(CPL, KM, 2); else if (rp == 4) KN_C0R(CPL, KM, 4); else KN_C0R(CPL, KM, 1); }

@@ -160,6 +160,23 @@ def last_conv_epilogue() -> str:
     return _lib.load().knnsvc_conv_gemm_last_epilogue().decode()
 
 
+def conv_route(descs) -> tuple:
+    """(tag, epilogue) the dispatcher decides for 1..4 descriptors collected with ``conv_gemm(..., defer=descs)``, asked without
+    a launch (knnsvc_conv_gemm_route: host code, CPU tensors' pointers will do).  One descriptor: what last_conv_kernel() /
+    last_conv_epilogue() say after its launch; several: the tag of their one grid, or "" where conv_gemm_multi launches one each."""
+    arr = (ConvDesc * len(descs))(*descs)
+    tag, epi = C.create_string_buffer(32), C.create_string_buffer(32)
+    check(_lib.load().knnsvc_conv_gemm_route(arr, len(descs), tag, epi, 32), "conv_gemm_route")
+    return tag.value.decode(), epi.value.decode()
+
+
+def conv_tags() -> set:
+    """Every tag last_conv_kernel() can report."""
+    buf = C.create_string_buffer(512)
+    check(_lib.load().knnsvc_conv_gemm_tags(buf, 512), "conv_gemm_tags")
+    return set(buf.value.decode().split())
+
+
 def conv_gemm(x, w, out, *, m, n, cin, taps=1, stride=1, dil=1, pad=0, t_in=None, ldx=None, ldo=None,
               bias=None, bias_period=0, act=ACT_NONE, act_slope=0.0, a_slope=1.0, resid=None, ldr=None,
               accumulate=False, div=1.0, batches=1, groups=1, x_bstride=0, x_gstride=0, w_gstride=0,
@@ -380,6 +397,21 @@ def wavlm_conv0(x, w, gamma, beta, k, stride, out_split=False):
     return out
 
 
+def conv0_route(batches, T) -> tuple:
+    """(rows per pass, spans of 64 rows per workgroup) wavlm_conv0 launches with for ``batches`` inputs of T frames, asked
+    without a launch (knnsvc_wavlm_conv0_route)."""
+    rp, spans = C.c_int32(), C.c_int32()
+    check(_lib.load().knnsvc_wavlm_conv0_route(batches, T, C.byref(rp), C.byref(spans)), "wavlm_conv0_route")
+    return rp.value, spans.value
+
+
+def last_conv0_route() -> tuple:
+    """... and what the last wavlm_conv0 of this thread launched with ((0, 0) before the first): test hook."""
+    rp, spans = C.c_int32(), C.c_int32()
+    _lib.load().knnsvc_wavlm_conv0_last_route(C.byref(rp), C.byref(spans))
+    return rp.value, spans.value
+
+
 def wavlm_gate(xn2d, heads, w2, b2, grep_a, x_split=False):
     rows = xn2d.shape[0]
     gate = torch.empty(rows, heads, device=xn2d.device, dtype=torch.float32)
@@ -412,6 +444,15 @@ def wavlm_attention(qkv, gate, table, batches, T, heads, out_split=False, kv_spl
                                              (1 if out_split else 0) | (4 if wide else 0), 1 if kv_split else 0, _p(kv_len),
                                              _stream()), "wavlm_attention")
     return out
+
+
+def attention_route(batches, T, heads, out_split=False, kv_split=False, wide=False) -> tuple:
+    """(tag, bytes of dynamic LDS) of the kernel wavlm_attention launches for these sizes and flags under the knobs as they are,
+    asked without a launch (knnsvc_wavlm_attention_route); raises where wavlm_attention would refuse the call for them."""
+    tag, lds = C.create_string_buffer(32), C.c_int64()
+    check(_lib.load().knnsvc_wavlm_attention_route(batches, T, heads, (1 if out_split else 0) | (4 if wide else 0), 1 if kv_split else 0,
+                                                   tag, 32, C.byref(lds)), "wavlm_attention_route")
+    return tag.value.decode(), lds.value
 
 
 def last_attention_kernel() -> str:
@@ -771,8 +812,9 @@ def raise_if_nan(flag):
 
 
 def reload_knobs() -> None:
-    """Re-read the dispatcher's A/B switches (KNNSVC_QUAD, KNNSVC_QUAD_EPI, KNNSVC_EPILOGUE, KNNSVC_WIN*, KNNSVC_GEMM_SMALL) from
-    the environment: the library reads them once, at its first launch (csrc/conv_gemm.hip: Knobs)."""
+    """Re-read the dispatchers' A/B switches (KNNSVC_QUAD, KNNSVC_QUAD_EPI, KNNSVC_EPILOGUE, KNNSVC_WIN*, KNNSVC_GEMM_SMALL,
+    KNNSVC_ATTENTION, KNNSVC_CONV0_RP, KNNSVC_CONV0_SUBS) from the environment: the library reads them once, when a dispatcher
+    first looks at them (csrc/common.h: KnKnobs)."""
     check(_lib.load().knnsvc_reload_knobs(), "reload_knobs")
 
 

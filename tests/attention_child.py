@@ -11,7 +11,8 @@ Nothing is judged here: every note is `ok` and carries a JSON record in its deta
                  reported and whether it gave the same bits;
   bucket/<id>/n  rows < n of a launch at T with kv_len = n against a launch at exactly n frames (table columns [T-n, T+n-1)): same bits?
   batch/<id>     a B = 3 launch against three B = 1 launches: same bits?
-  refuse/<id>    the return code and message of a call that must be refused, whether the last-kernel tag and the output moved.
+  refuse/<id>    the return code and message of a call that must be refused, whether the last-kernel tag and the output moved;
+  route/asked    how many launches there were, and those whose tag was not what ops.attention_route had answered just before.
 The first exception ends the run (gpu_child.run_cases)."""
 import ctypes
 import json
@@ -59,6 +60,9 @@ def raw(qkv, gate, table, B, T, H, out, flags=0, kv_split=0, kv_len=None):
     return rc, _lib().knnsvc_last_error().decode("utf-8", "replace") if rc else ""
 
 
+ROUTES = [0, []]          # launches, and those that took another kernel than the route entry had answered
+
+
 class Operands:
     """q, k, v, gate, table of the oracle on the device, as the kernel takes them."""
 
@@ -78,12 +82,17 @@ class Operands:
     def launch(self, wide=False, out_split=False):
         """-> (output [B*T, E] inside guard rows (unpacked where split), guard check, tag)"""
         out, untouched = guarded(self.B * self.T, self.E)
+        asked = _ops().attention_route(self.B, self.T, self.H, out_split, self.kv_split, wide)[0]
         rc, msg = raw(self.qkv, self.gate, self.table, self.B, self.T, self.H, out, (1 if out_split else 0) | (4 if wide else 0),
                       1 if self.kv_split else 0, self.kv_len)
         if rc:
             raise RuntimeError(f"wavlm_attention failed ({rc}): {msg}")
         torch.cuda.synchronize()
-        return out, untouched, _ops().last_attention_kernel()
+        tag = _ops().last_attention_kernel()
+        ROUTES[0] += 1
+        if asked != tag:
+            ROUTES[1].append(f"B {self.B} T {self.T} H {self.H}: asked {asked}, launched {tag}")
+        return out, untouched, tag
 
 
 def run_row(case) -> dict:
@@ -199,7 +208,11 @@ def case_refusals():
     set_knobs(())
 
 
-CASES = [("rows", case_rows), ("bucket", case_bucket), ("batch", case_batch), ("refusals", case_refusals)]
+def case_routes():
+    note("route/asked", True, json.dumps(dict(launches=ROUTES[0], differing=ROUTES[1][:8])))
+
+
+CASES = [("rows", case_rows), ("bucket", case_bucket), ("batch", case_batch), ("refusals", case_refusals), ("routes", case_routes)]
 
 if __name__ == "__main__":
     if not FP32:

@@ -3,9 +3,10 @@ dispatcher (knn_svc_amd/csrc/attention.hip) must report through ops.last_attenti
 to: `attention_ref`, a plain evaluation with an explicit score matrix and an ordinary softmax, in float64 (the reference) and in
 float32 (e32, what an fp32 evaluation of the same inputs loses), both with torch on the CPU.
 
-Imports without a GPU.  tests/test_attention_cpu.py checks the reference against torch's SDPA and the oracle's bias path, the
-table against `predict` (a host mirror of the dispatch rules) and the LDS formulas against the kernel source, and that every input
-family reaches the branch it is named for.  tests/attention_child.py / attention_fp32_child.py launch the rows,
+Imports without a GPU.  `route`, `longest_T` and `schedules` are what the dispatcher itself answers through its host-only route
+entry, which launches nothing.  tests/test_attention_cpu.py checks the reference against torch's SDPA and the oracle's bias path,
+the table against `route` at every row and at the dispatch rules' boundaries, and that every input family reaches the branch it
+is named for.  tests/attention_child.py / attention_fp32_child.py launch the rows,
 tests/test_gpu_attention.py judges what they measured.
 
 Layout of the operands (as the kernels read them): q, k, v [B, T, H, 64], gate [B, T, H], table [H, 2T - 1];
@@ -13,6 +14,7 @@ score[b, h, i, j] = q . k / 8 + gate[b, i, h] * table[h, j - i + T - 1]; batch r
 from __future__ import annotations
 
 import functools
+import os
 from dataclasses import dataclass
 
 import torch
@@ -27,7 +29,7 @@ TAGS = (TAG_2, TAG_2Q, TAG_2W, TAG_3, TAG_F32)
 QB2 = (("KNNSVC_ATT_QB", "2"), ("KNNSVC_ATT_NW", "4"))       # the knobs that force a schedule of the f16x2 route
 NW8 = (("KNNSVC_ATT_QB", "2"), ("KNNSVC_ATT_NW", "8"))
 QB1 = (("KNNSVC_ATT_QB", "1"),)
-F32 = (("KNNSVC_ATTENTION", "fp32"),)                        # read once per process: these rows run in attention_fp32_child.py
+F32 = (("KNNSVC_ATTENTION", "fp32"),)                        # read once per process (or reload): these rows run in attention_fp32_child.py
 
 
 # ------------------------------------------------------------------ the reference
@@ -66,65 +68,55 @@ def bucket_table(table, T, n):
     return table[:, T - n:T - n + 2 * n - 1].contiguous()
 
 
-# ------------------------------------------------------------------ the dispatcher's rules, mirrored on the host
-KT, LDKK, LDV, KP2, VP2, KP3, VP3 = 64, 68, 64, 272, 320, 400, 392
-ATT2_TILE = KT * KP2 + KT * VP2
+# ------------------------------------------------------------------ the dispatcher, asked (ops.attention_route launches nothing)
+ROUTE_KNOBS = ("KNNSVC_ATTENTION", "KNNSVC_ATT_QB", "KNNSVC_ATT_NW")
 
 
-def table_bytes(T):
-    return (2 * T - 1 + 64) * 4
+def route(B, T, H, wide=False, env=(), out_split=False, kv_split=False):
+    """-> (tag, bytes of LDS) knnsvc_wavlm_attention takes under the knobs `env` and no other, as the library itself answers;
+    KnnSvcError where it refuses the call.  The environment is put back afterwards."""
+    from knn_svc_amd import ops
+    old = {k: os.environ.pop(k, None) for k in ROUTE_KNOBS}
+    try:
+        os.environ.update(dict(env))
+        ops.reload_knobs()
+        return ops.attention_route(B, T, H, out_split, kv_split, wide)
+    finally:
+        for k, v in old.items():
+            os.environ.pop(k, None)
+            if v is not None:
+                os.environ[k] = v
+        ops.reload_knobs()
 
 
-def lds_bytes(tag, T):
-    if tag in (TAG_2, TAG_2Q):
-        return ATT2_TILE + table_bytes(T)
-    if tag == TAG_2W:
-        return 3 * ATT2_TILE + table_bytes(T)
-    if tag == TAG_3:
-        return KT * KP3 + HD * VP3 + table_bytes(T)
-    return (KT * LDKK + KT * LDV + 2 * T - 1) * 4
-
-
+@functools.lru_cache(maxsize=None)
 def longest_T(tag):
-    """The largest T whose LDS footprint fits 160 KB."""
-    T = 1
-    while lds_bytes(tag, 2 * T) <= LDS_LIMIT:
-        T *= 2
-    step = T
-    while step:
-        if lds_bytes(tag, T + step) <= LDS_LIMIT:
-            T += step
-        step //= 2
-    return T
+    """The largest T (B = H = 1) the dispatcher gives to `tag` under the knobs that force it: one frame more is refused — or,
+    from the eight-wave kernel, handed to the four-wave one."""
+    from knn_svc_amd._lib import KnnSvcError
 
-
-def predict(B, T, H, wide=False, env=()):
-    """The tag knnsvc_wavlm_attention dispatches to."""
-    env = dict(env)
-    mode = env.get("KNNSVC_ATTENTION", "")
-    mode = "bf16x3" if mode[:1] == "b" else "fp32" if mode[:2] == "fp" else "f16x2"
-    if wide and mode == "f16x2":
-        mode = "bf16x3"
-    if mode == "bf16x3":
-        return TAG_3
-    if mode == "fp32":
-        return TAG_F32
-    qb = env.get("KNNSVC_ATT_QB")
-    qb = 0 if qb is None else 1 if qb[0] == "1" else 2
-    if (qb == 2 or (qb == 0 and (T + 127) // 128 * H * B >= 1536)) and T > 128:
-        nw = env.get("KNNSVC_ATT_NW")
-        eight = nw[0] == "8" if nw else (T + 511) // 512 * H * B >= 512
-        return TAG_2W if eight and lds_bytes(TAG_2W, T) <= LDS_LIMIT else TAG_2Q
-    return TAG_2
+    def fits(T):
+        try:
+            return route(1, T, 1, tag == TAG_3, FORCE_ENV[tag])[0] == tag
+        except KnnSvcError:
+            return False
+    lo, hi = 129, 258
+    assert fits(lo)
+    while fits(hi):
+        lo, hi = hi, 2 * hi
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        lo, hi = (mid, hi) if fits(mid) else (lo, mid)
+    return lo
 
 
 def schedules(T):
     """Every f16x2 schedule a length admits: (knobs, tag)."""
-    out = [(QB1, TAG_2)]
-    if T > 128:
-        out.append((QB2, TAG_2Q))
-        if lds_bytes(TAG_2W, T) <= LDS_LIMIT:
-            out.append((NW8, TAG_2W))
+    out = []
+    for env in (QB1, QB2, NW8):
+        tag = route(1, T, 1, env=env)[0]
+        if tag not in [t for _, t in out]:
+            out.append((env, tag))
     return out
 
 
@@ -253,6 +245,9 @@ KV_EDGES = (0, 1, 31, 32, 33, 64, 65, "T-1", "T", "T+5")
 FAMILIES = ("model", "peaked", "rising", "falling", "onelane", "uniform", "cancelling", "small", "limit_kv", "limit_q")
 SHORT = {TAG_2: "2", TAG_2Q: "2q", TAG_2W: "2w", TAG_3: "3", TAG_F32: "f32"}
 ROUTE_ENV = {TAG_2: (), TAG_2Q: QB2, TAG_2W: NW8, TAG_3: (), TAG_F32: F32}
+FORCE_ENV = dict(ROUTE_ENV, **{TAG_2: QB1})                  # the knobs under which a kernel is taken whatever the grid's size
+# the rows at the longest T a kernel takes: what longest_T(tag) answers (tests/test_attention_cpu.py holds the two together)
+LONGEST = {TAG_2: 15712, TAG_2Q: 15712, TAG_2W: 6240, TAG_3: 14112, TAG_F32: 16256}
 
 
 def _kv(T, i, B):
@@ -290,13 +285,13 @@ def _table():
         f16 = tag in (TAG_2, TAG_2Q, TAG_2W)
         add(f"{SHORT[tag]}-H16", tag, 2, 333, 16, (333 - 31, 65), wide=tag == TAG_3, env=ROUTE_ENV[tag], kv_split=f16, out_split=f16)
     # the LDS fallback of the eight-wave kernel, and the longest T every kernel accepts
-    t2w = longest_T(TAG_2W)
+    t2w = LONGEST[TAG_2W]
     add(f"2w-longest-T{t2w}", TAG_2W, 1, t2w, 1, env=NW8, sample=True)
     add(f"2q-lds-fallback-T{t2w + 1}", TAG_2Q, 1, t2w + 1, 1, env=NW8, sample=True)
-    add(f"2-longest-T{longest_T(TAG_2)}", TAG_2, 1, longest_T(TAG_2), 1, env=QB1, sample=True)
-    add(f"2q-longest-T{longest_T(TAG_2Q)}", TAG_2Q, 1, longest_T(TAG_2Q), 1, env=QB2, sample=True)
-    add(f"3-longest-T{longest_T(TAG_3)}", TAG_3, 1, longest_T(TAG_3), 1, wide=True, sample=True)
-    add(f"f32-longest-T{longest_T(TAG_F32)}", TAG_F32, 1, longest_T(TAG_F32), 1, env=F32, sample=True)
+    add(f"2-longest-T{LONGEST[TAG_2]}", TAG_2, 1, LONGEST[TAG_2], 1, env=QB1, sample=True)
+    add(f"2q-longest-T{LONGEST[TAG_2Q]}", TAG_2Q, 1, LONGEST[TAG_2Q], 1, env=QB2, sample=True)
+    add(f"3-longest-T{LONGEST[TAG_3]}", TAG_3, 1, LONGEST[TAG_3], 1, wide=True, sample=True)
+    add(f"f32-longest-T{LONGEST[TAG_F32]}", TAG_F32, 1, LONGEST[TAG_F32], 1, env=F32, sample=True)
     # input families: T = 333 (eleven 32-key steps, the last tile has one; three ragged 128-query blocks), B = 2, the second batch
     # row one step short
     for tag in TAGS:
@@ -323,4 +318,4 @@ SPLIT_REFUSED = ("wide-kv_split", "wide-out_split")              # flag bit 2 wi
 F32_SPLIT_REFUSED = ("fp32-kv_split", "fp32-out_split")          # the fp32 route with a split layout (fp32 child)
 # one frame more than longest_T(tag) is refused ("T too long"), under the knobs that reach the kernel; the eight-wave kernel falls
 # back to the four-wave one instead (the 2q-lds-fallback row)
-TOO_LONG = {TAG_2: QB1, TAG_2Q: QB2, TAG_3: (), TAG_F32: F32}
+TOO_LONG = {t: e for t, e in FORCE_ENV.items() if t != TAG_2W}

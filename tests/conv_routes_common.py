@@ -2,14 +2,16 @@
 ops.last_conv_kernel(), with the descriptor that reaches it, plus the yardsticks every row is held to: the same operation in fp64
 (F.conv1d / F.conv_transpose1d and the epilogue chain in the kernel's order) and in fp32, both with torch on the CPU.
 
-Imports without a GPU.  tests/test_conv_routes_cpu.py checks the table against the dispatcher's source and against `predict`, a
-host mirror of the dispatch rules; tests/conv_routes_child.py launches every row, tests/test_gpu_conv_routes.py judges what it measured.
+Imports without a GPU.  tests/test_conv_routes_cpu.py checks the table against what the dispatcher itself answers (`route`: the
+row's descriptors handed to ops.conv_route, which launches nothing); tests/conv_routes_child.py launches every row,
+tests/test_gpu_conv_routes.py judges what it measured.
 
 Shapes are ragged on purpose: m is a whole number of tiles plus an odd remainder (or less than one tile), n is no multiple of the
 tile width, every output has `COL_SLACK` columns behind n and `ROW_GAP` rows around every batch item that no launch may touch."""
 from __future__ import annotations
 
 import functools
+import os
 from dataclasses import dataclass, replace
 
 import torch
@@ -256,67 +258,130 @@ def tolerance(factor: float, e32: float, scale: float) -> float:
     return factor * e32 + 1e-6 * scale
 
 
-# ------------------------------------------------------------------ host mirror of the dispatch rules (conv_gemm.hip)
-def _cdiv(a, b):
-    return -(-a // b)
+# ------------------------------------------------------------------ a row's descriptors, and what the dispatcher says to them
+def _ops():
+    from knn_svc_amd import ops
+    return ops
 
 
-def _win_shape(c: Case, z: int, knobs: dict) -> str | None:
-    if c.x_split or c.convt or c.stride != 1 or c.k < 3 or c.dil < 1 or (c.groups * c.cin) % 4 or knobs.get("KNNSVC_WIN") == "0":
-        return None
-    halo = (c.k - 1) * c.dil
-    if halo <= 64:
-        if c.n > 64:
-            if _cdiv(c.m, 128) * _cdiv(c.n, 128) * z < 512:
-                return "W128D" if _cdiv(c.m, 64) * _cdiv(c.n, 128) * z <= 256 else "W128S"
-            zz = z * _cdiv(c.n, 128)
-            r128 = _cdiv(_cdiv(c.m, 128) * zz, 768) * 128
-            r160 = _cdiv(_cdiv(c.m, 160) * zz, 768) * 160
-            return "W160" if r160 < r128 else "W128"
-        return "W64" if c.n > 32 else "W32"
-    if halo <= 128 and 32 < c.n <= 64:
-        return "W64P"
-    return None
+class Knobs:
+    """The row's dispatcher knobs and weight split in the environment for the length of a `with`, then what was there before."""
+
+    def __init__(self, case):
+        self.env = dict(case.env)
+        if case.split:
+            self.env["KNNSVC_GEMM"] = case.split
+
+    def __enter__(self):
+        self.old = {k: os.environ.get(k) for k in self.env}
+        os.environ.update(self.env)
+        _ops().reload_knobs()
+
+    def __exit__(self, *exc):
+        for k, v in self.old.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+        _ops().reload_knobs()
 
 
-def wide_ok(c: Case, knobs: dict) -> bool:
-    """The preconditions of the 16-byte LDS-patch epilogue that depend on the descriptor (the buffers here are 16-byte aligned)."""
-    generic = knobs.get("KNNSVC_EPILOGUE") == "g"
-    lin = not c.convt and not generic
-    plain_t = bool(c.convt) and not c.resid and c.convt[1] % 4 == 0
-    n, ldo = c.n, c.ldo
-    return ((lin or plain_t) and c.act == ACT_NONE and not c.accumulate and c.div == 1.0 and n % 4 == 0 and ldo % 4 == 0 and
-            (not c.resid or c.ldr % 4 == 0) and (not c.bias or (c.convt[1] if c.convt else 0) % 4 == 0) and
-            (c.groups == 1 or n % 4 == 0))
+class Launch:
+    """One descriptor of a row on `dev`: operands, the sentinel-framed output buffer and the conv_gemm call.  On "cpu" nothing can
+    be launched, but `launch(defer=descs)` builds the same descriptor (ops.conv_route takes it): attach_split needs a GPU, so a
+    few zero bytes stand in for the split planes there — the dispatcher looks at their address, never behind it."""
+
+    def __init__(self, case, inp, rows_alloc=None, x_rows_alloc=None, dev="cuda"):
+        ops = _ops()
+        self.case, c = case, case
+        B, G = c.batches, c.groups
+        self.rows_alloc = rows_alloc or c.rows                      # a bucketed launch is laid out for more rows than are valid
+        x = inp["x"]
+        if x_rows_alloc:                                            # rows behind the valid input: finite junk the kernel must not read
+            x = torch.cat([x, torch.full((B, x_rows_alloc - x.shape[1], x.shape[2]), 7.0)], 1)
+        self.t_alloc = x.shape[1]
+        x2d = x.reshape(-1, G * c.cin)
+        self.x = (ops.split_pack(x2d) if c.x_split else x2d.contiguous()).to(dev)
+        if c.convt:
+            wp = ops.pack_convT_weight(inp["w"], c.convt[0])
+        elif G > 1:
+            wp = ops.pack_grouped_conv_weight(inp["w"], G)
+        else:
+            wp = ops.pack_conv_weight(inp["w"])
+        self.w = wp.to(dev)
+        if c.split and dev == "cpu":
+            planes = torch.zeros(8, dtype=torch.int16)
+            if c.split == "bf16x3":
+                self.w._w3 = planes
+            else:
+                self.w._w2, self.w._w2_scale = planes, 1.0
+        elif c.split:
+            self.w = ops.attach_split(self.w)
+            assert hasattr(self.w, "_w3" if c.split == "bf16x3" else "_w2"), "the weights did not take the split this row is about"
+        self.bias = inp["bias"].to(dev) if inp["bias"] is not None else None
+        self.resid = None
+        if inp["resid"] is not None:
+            r = torch.zeros(B, c.rows, c.ldr)
+            r[:, :, :c.width] = inp["resid"]
+            self.resid = r.to(dev)
+        self.prev = inp["prev"]
+        self.pitch = self.rows_alloc + ROW_GAP                      # rows from one batch item's block to the next
+        self.buf = torch.empty(ROW_GAP + B * self.pitch, c.ldo, device=dev)
+        self.slot = ops.new_slot(dev) if c.slot else None
+        self.reset()
+
+    def reset(self):
+        c = self.case
+        self.buf.fill_(SENTINEL)
+        if self.prev is not None:
+            self._blocks()[:, :c.rows, :c.width] = self.prev.to(self.buf.device)
+        if self.slot is not None:
+            self.slot.zero_()
+
+    def _blocks(self):
+        return self.buf[ROW_GAP:].view(self.case.batches, self.pitch, self.case.ldo)
+
+    def valid(self, rows=None):
+        return self._blocks()[:, :rows or self.case.rows, :self.case.width]
+
+    def outside_is_untouched(self, rows=None):
+        """Every float outside the [rows, width] blocks still holds the sentinel's bits."""
+        mask = torch.ones_like(self.buf, dtype=torch.bool)
+        mask[ROW_GAP:].view(self.case.batches, self.pitch, self.case.ldo)[:, :rows or self.case.rows, :self.case.width] = False
+        return bool((self.buf[mask] == SENTINEL).all()), int((self.buf[mask] != SENTINEL).sum())
+
+    def launch(self, defer=None, dyn=None, m_alloc=None):
+        """conv_gemm of this descriptor (defer: appended to the list instead).  dyn = (count, bucket) with m_alloc: this
+        (exact-length) descriptor's data through a launch laid out for the bucket's m_alloc rows."""
+        ops, c = _ops(), self.case
+        B, G = c.batches, c.groups
+        ldx = G * c.cin
+        kw = dict(m=c.m if dyn is None else m_alloc, n=c.n, cin=c.cin, taps=c.k, stride=c.stride, dil=c.dil, pad=c.pad_,
+                  t_in=self.t_alloc if dyn is not None else c.t_in_, ldx=ldx, ldo=c.ldo, bias=self.bias, a_slope=c.a_slope, act=c.act,
+                  act_slope=c.act_slope, accumulate=c.accumulate, div=c.div, batches=B, groups=G, x_bstride=self.t_alloc * ldx,
+                  o_bstride=self.pitch * c.ldo, x_split=c.x_split, out_absmax=self.slot, defer=defer, dyn=dyn)
+        if G > 1:
+            kw.update(x_gstride=c.cin, w_gstride=c.n * c.cin * c.k, bias_gstride=c.n, o_gstride=c.n, r_gstride=c.n)
+        if self.resid is not None:
+            kw.update(resid=self.resid, ldr=c.ldr, r_bstride=c.rows * c.ldr)
+        if c.convt:
+            u, cout = c.convt
+            kw.update(bias_period=cout if self.bias is not None else 0, convt_u=u, convt_cout=cout, convt_pad=(c.k * u - u) // 2,
+                      t_out=self.rows_alloc)
+        ops.conv_gemm(self.x, self.w, self.buf[ROW_GAP:], **kw)
+
+    def route(self, **kw):
+        """What the dispatcher says to this descriptor alone, without a launch."""
+        descs = []
+        self.launch(defer=descs, **kw)
+        return _ops().conv_route(descs)
 
 
-def predict(case: Case) -> tuple:
-    """-> (tag, epilogue) the dispatcher picks for this row under the row's knobs (epilogue None for a merged grid: the hook
-    reports single launches)."""
-    knobs = dict(case.env)
-    ds = case.descs()
-    c = ds[0]
-    ldx = c.groups * c.cin
-    vec4 = c.cin % 4 == 0 and ldx % 4 == 0
-    fast = vec4 and c.cin % 32 == 0
-    if fast and c.split == "f16x2":
-        K = c.cin * c.k
-        quad_ok = c.x_split and not c.convt and knobs.get("KNNSVC_EPILOGUE") != "g" and c.n % 4 == 0 and c.ldo % 4 == 0 and (not c.resid or c.ldr % 4 == 0)
-        if quad_ok and c.n >= 256 and K >= 1024:
-            return "Q256S", ""
-        epi = "patch" if wide_ok(c, knobs) else "lane"
-        if len(ds) > 1:
-            shapes = {_win_shape(d, len(ds), knobs) for d in ds}
-            assert len(shapes) == 1 and None not in shapes and c.batches == 1 and c.groups == 1, (case.id, shapes)
-            return shapes.pop() + "x", None
-        ws = _win_shape(c, c.batches * c.groups, knobs)
-        if ws:
-            return ws, epi
-        if c.n > 64 and _cdiv(c.m, 128) * _cdiv(c.n, 128) * c.batches * c.groups < 256:
-            return "F64S", epi
-        return ("F128a2" if c.x_split else "F128") if c.n > 64 else "F64" if c.n > 32 else "F32", epi
-    assert len(ds) == 1 and not c.x_split
-    size = "128" if c.n > 64 else "64" if c.n > 32 else "32"
-    if fast and c.split == "bf16x3":
-        return "H" + size, ""
-    return "G" + size + ("v8" if fast else "v4" if vec4 else "v1"), ""
+def route(case: Case) -> tuple:
+    """-> (tag, epilogue) the library picks for this row under the row's knobs, asked on the CPU: the descriptors are the ones
+    the GPU child launches (Launch), one per branch for a merged grid."""
+    with Knobs(case):
+        descs = []
+        for d in case.descs():
+            Launch(d, make_inputs(d), dev="cpu").launch(defer=descs)
+        return _ops().conv_route(descs)

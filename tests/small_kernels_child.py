@@ -157,12 +157,19 @@ def case_layernorm():
 
 
 # ------------------------------------------------------------------ wavlm_conv0
+C0_ROUTES = [0, []]          # launches, and those whose shape was not what the route entry had answered
+
+
 def run_conv0(x, w, ga, be, k, stride, split=False):
     B, L = x.shape
     C_ = ga.numel()
     T = (L - k) // stride + 1
     out, clean = guarded(B * T, C_)
+    asked = ops.conv0_route(B, T)
     lib_call("knnsvc_wavlm_conv0", _p(x), B, L, _p(w), C_, k, stride, _p(ga), _p(be), _p(out), 1 if split else 0)
+    C0_ROUTES[0] += 1
+    if ops.last_conv0_route() != asked:
+        C0_ROUTES[1].append(f"B {B} T {T}: asked {asked}, launched {ops.last_conv0_route()}")
     return out, clean
 
 
@@ -198,6 +205,8 @@ def case_wavlm_conv0():
     guards(f"{key}/guards", clean)
     single = torch.cat([run_conv0(dx[b:b + 64].contiguous(), dw, dg, db, k, stride)[0] for b in range(0, B, 64)])
     bits(f"{key}/equals-single-span-launches/bits", out, single, "the same batches in launches of 64 (one span per workgroup)")
+    note("wavlm_conv0/route-entry-equals-every-launch", C0_ROUTES[0] > 0 and not C0_ROUTES[1],
+         f"ops.conv0_route before against ops.last_conv0_route() after each of {C0_ROUTES[0]} launches; differing: {C0_ROUTES[1][:5]}")
 
 
 # ------------------------------------------------------------------ wavlm_gate

@@ -1,6 +1,6 @@
 """References and case generators for the small kernels between the stages (csrc/elementwise.hip, csrc/synth.hip and absmax /
 mean3 / axpy of csrc/conv_gemm.hip): what tests/small_kernels_child.py compares the GPU with and tests/test_small_kernels_cpu.py
-checks on the CPU.  numpy and torch on the CPU only: this module imports neither knn_svc_amd.ops nor anything that opens the GPU.
+checks on the CPU.  numpy and torch on the CPU only: nothing here opens the GPU (conv0_subs asks the library's host-only route entry).
 
 Every reference is written over its arguments' dtype: float64 arguments give the fp64 reference, float32 arguments the "plain
 fp32 evaluation" whose error against the fp64 reference is the yardstick of the child's third comparison rule.  Where oracle/
@@ -8,14 +8,10 @@ has the operation (synth_ref.additive_synth, sine_excitation, harmonic_amps, pre
 restated; sine_excitation64 is the one exception: the oracle casts the wrapped phase to fp32 before the sine (as the model
 does), so a reference that is fp64 to the end needs the cast left out."""
 import math
-import os
-import re
 
 import numpy as np
 import torch
 import torch.nn.functional as F
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def rng(*key):
@@ -204,20 +200,18 @@ def conv0_inputs(batches, channels, k, stride, T):
     return x, w, torch.randn(channels, generator=g), torch.randn(channels, generator=g)
 
 
-def conv0_dispatch_rule():
-    """(the spans a workgroup walks on the multi-span route, the workgroup count from which the dispatcher takes it), as the
-    source of knnsvc_wavlm_conv0 states them."""
-    with open(os.path.join(ROOT, "knn_svc_amd", "csrc", "elementwise.hip")) as f:
-        src = f.read()
-    subs = re.search(r'getenv\("KNNSVC_CONV0_SUBS"\);\s*subs_env = e \? atoi\(e\) : (\d+);', src)
-    rule = re.search(r"const int subs = cdiv64\(T, 64L \* subs_env\) \* batches >= (\d+) \? subs_env : 1;", src)
-    assert subs and rule, "the dispatcher of knnsvc_wavlm_conv0 no longer reads as this test expects"
-    return int(subs.group(1)), int(rule.group(1))
-
-
 def conv0_subs(T, batches):
-    subs, least = conv0_dispatch_rule()
-    return subs if -(-T // (64 * subs)) * batches >= least else 1
+    """The spans of 64 rows a workgroup of knnsvc_wavlm_conv0 walks for this launch, as the dispatcher itself answers
+    (ops.conv0_route: host code, nothing is launched)."""
+    from knn_svc_amd import ops
+    return ops.conv0_route(batches, T)[1]
+
+
+def conv0_dispatch_rule():
+    """(the spans a workgroup walks on the multi-span route, the workgroup count from which the dispatcher takes it), found by
+    asking it about inputs of 64 frames: one workgroup per batch item on either route, so the workgroup count is the batch."""
+    subs = conv0_subs(64, 65535)
+    return subs, next(b for b in range(1, 65536) if conv0_subs(64, b) > 1)
 
 
 def gate_weights():

@@ -1,17 +1,13 @@
 """CPU: the yardsticks and the route table of the attention tests (tests/attention_oracle.py) — the reference against torch's SDPA
-and against the oracle's bias path, the host mirror of the dispatcher and of the LDS formulas against attention.hip, and every
-input family against the branch of the flash step it is named for."""
+and against the oracle's bias path, the table against the dispatcher itself (asked through its host-only route entry, at every
+row and on both sides of every boundary of its rules), and every input family against the branch of the flash step it is named for."""
 import os
-import re
 
 import pytest
 import torch
 import torch.nn.functional as F
 
 from tests import attention_oracle as A
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = open(os.path.join(ROOT, "knn_svc_amd", "csrc", "attention.hip")).read()
 
 
 def _sdpa64(q, k, v, gate, table, kv_len):
@@ -103,29 +99,70 @@ def test_rows_cover_what_the_issue_lists():
     assert all(c.env == () for c in A.CASES if c.id.startswith("natural"))
 
 
-def test_predict_agrees_with_the_table_and_the_source():
+def test_the_dispatcher_agrees_with_the_table():
     for c in A.CASES:
-        assert A.predict(c.B, c.T, c.H, c.wide, c.env) == c.tag, c.id
-        assert A.lds_bytes(c.tag, c.T) <= A.LDS_LIMIT, c.id
-    for tag, val in (("KT", A.KT), ("LDKK", A.LDKK), ("LDV", A.LDV), ("KP2", A.KP2), ("VP2", A.VP2), ("KP3", A.KP3), ("VP3", A.VP3), ("HD", A.HD)):
-        assert re.search(rf"constexpr int {tag} = {val};", SRC), tag
-    for text in ("blocks128 >= 1536", "T > 128", "blocks512 >= 512", "att2_lds_bytes(3, T) <= 160 * 1024", "lds_bytes <= 160 * 1024",
-                 "(size_t)(2 * T - 1 + 64) * 4", "(size_t)nbuf * ATT2_TILE + att_table_bytes(T)", "ATT2_TILE = KT * KP2 + KT * VP2",
-                 "(size_t)KT * KP3 + (size_t)HD * VP3 + att_table_bytes(T)", "(size_t)(KT * LDKK + KT * LDV + 2 * T - 1) * 4"):
-        assert text in SRC, text
-    for tag in A.TAGS:
-        assert f'"{tag}"' in SRC
+        tag, lds = A.route(c.B, c.T, c.H, c.wide, c.env, c.out_split, c.kv_split)
+        assert tag == c.tag, c.id
+        assert 0 < lds <= A.LDS_LIMIT, c.id
+
+
+NW4 = (("KNNSVC_ATT_NW", "4"),)
+QB2_ONLY = (("KNNSVC_ATT_QB", "2"),)
+
+
+@pytest.mark.parametrize("B,T,H,env,tag", [
+    # ceil(T / 128) H B = 1535 / 1536: 64 queries per wave from two rounds of the resident workgroups on
+    (1, 640, 307, NW4, A.TAG_2), (1, 768, 256, NW4, A.TAG_2Q), (1, 640, 307, (), A.TAG_2), (1, 768, 256, (), A.TAG_2W),
+    # ... and never at T <= 128, whatever forces it
+    (2, 128, 2, A.QB2, A.TAG_2), (2, 129, 2, A.QB2, A.TAG_2Q), (2, 128, 2, A.NW8, A.TAG_2), (2, 129, 2, A.NW8, A.TAG_2W),
+    (1536, 128, 1, (), A.TAG_2), (768, 129, 1, (), A.TAG_2W),
+    # ceil(T / 512) H B = 511 / 512 with KNNSVC_ATT_NW unset: eight waves from two rounds of one workgroup per CU on
+    (73, 3584, 1, (), A.TAG_2Q), (256, 1024, 1, (), A.TAG_2W), (73, 3584, 1, QB2_ONLY, A.TAG_2Q), (256, 1024, 1, QB2_ONLY, A.TAG_2W),
+])
+def test_the_dispatch_rules_at_their_boundaries(B, T, H, env, tag):
+    assert A.route(B, T, H, env=env)[0] == tag
+    if not env:
+        assert ((T + 127) // 128 * H * B, (T + 511) // 512 * H * B) in ((1535, 614), (1536, 512), (1536, 1536), (1536, 768), (2044, 511), (2048, 512))
+
+
+def test_flags_and_modes():
+    from knn_svc_amd._lib import KnnSvcError
+    assert A.route(2, 333, 2, wide=True)[0] == A.TAG_3                           # flag bit 2 on the f16x2 default
+    assert A.route(2, 333, 2, env=(("KNNSVC_ATTENTION", "bf16x3"),))[0] == A.TAG_3
+    assert A.route(2, 333, 2, wide=True, env=A.F32)[0] == A.TAG_F32              # the fp32 route has the range anyway
+    for kw in (dict(wide=True), dict(env=A.F32)):
+        for split in (dict(out_split=True), dict(kv_split=True)):
+            with pytest.raises(KnnSvcError, match="only implemented by the f16x2 kernel"):
+                A.route(2, 333, 2, **kw, **split)
+    for B, T, H in ((0, 8, 2), (4, 0, 2), (4, 8, 0), (65536, 8, 2), (4, 8, 65536)):
+        with pytest.raises(KnnSvcError, match="bad sizes"):
+            A.route(B, T, H)
+    assert {A.route(1, 129, 1, t == A.TAG_3, A.FORCE_ENV[t])[0] for t in A.TAGS} == set(A.TAGS)
 
 
 def test_longest_lengths():
-    assert A.longest_T(A.TAG_2W) == 6240
+    from knn_svc_amd._lib import KnnSvcError
+    assert A.longest_T(A.TAG_2W) == 6240 and {t: A.longest_T(t) for t in A.TAGS} == A.LONGEST
     for tag in A.TAGS:
-        T = A.longest_T(tag)
-        assert A.lds_bytes(tag, T) <= A.LDS_LIMIT < A.lds_bytes(tag, T + 1)
+        T, wide, env = A.longest_T(tag), tag == A.TAG_3, A.FORCE_ENV[tag]
+        got, lds = A.route(1, T, 1, wide, env)
+        assert got == tag and lds <= A.LDS_LIMIT < lds + 8                   # a frame more is two more entries of the bias table
+        if tag == A.TAG_2W:
+            assert A.route(1, T + 1, 1, wide, env)[0] == A.TAG_2Q            # falls back to the four-wave kernel
+        else:
+            with pytest.raises(KnnSvcError, match="T too long for the LDS bias table"):
+                A.route(1, T + 1, 1, wide, env)
         assert any(c.tag == tag and c.T == T and c.B == c.H == 1 for c in A.CASES), tag
     t = A.longest_T(A.TAG_2W)
-    assert A.predict(1, t, 1, env=A.NW8) == A.TAG_2W and A.predict(1, t + 1, 1, env=A.NW8) == A.TAG_2Q
     assert A.schedules(t + 1) == [(A.QB1, A.TAG_2), (A.QB2, A.TAG_2Q)] and len(A.schedules(129)) == 3 and len(A.schedules(128)) == 1
+    assert A.schedules(t) == [(A.QB1, A.TAG_2), (A.QB2, A.TAG_2Q), (A.NW8, A.TAG_2W)]
+
+
+def test_asking_leaves_the_environment_as_it_was(monkeypatch):
+    monkeypatch.setenv("KNNSVC_ATT_QB", "1")
+    monkeypatch.delenv("KNNSVC_ATT_NW", raising=False)
+    assert A.route(2, 333, 2, env=A.NW8)[0] == A.TAG_2W
+    assert os.environ["KNNSVC_ATT_QB"] == "1" and "KNNSVC_ATT_NW" not in os.environ
 
 
 # ------------------------------------------------------------------ the families reach their branches

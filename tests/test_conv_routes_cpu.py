@@ -1,30 +1,17 @@
-"""CPU: the route table of tests/conv_routes_common.py against the dispatcher's source.  A kernel tag the dispatcher can report
-without a row — a new route nobody compares with fp64 — fails here, before any GPU run; so does a row whose shape does not
-satisfy the preconditions of the route it is about."""
-import re
-from pathlib import Path
-
+"""CPU: the route table of tests/conv_routes_common.py against the dispatcher itself, asked through its host-only route entry
+(ops.conv_route / ops.conv_tags: nothing is launched).  A kernel tag the dispatcher can report without a row — a new route
+nobody compares with fp64 — fails here, before any GPU run; so does a row the dispatcher sends elsewhere than it says, or whose
+shape does not have the properties the row is about."""
 import pytest
 import torch
 
+from knn_svc_amd import ops
 from tests import conv_routes_common as R
-
-SRC = Path(__file__).resolve().parents[1] / "knn_svc_amd" / "csrc" / "conv_gemm.hip"
-
-
-def _dispatcher_tags():
-    """Every string literal on the right-hand side of an assignment to g_last_kernel."""
-    text = SRC.read_text()
-    tags = set()
-    for stmt in re.findall(r"\bg_last_kernel\s*=([^;]*);", text):
-        tags.update(re.findall(r'"([^"]*)"', stmt))
-    tags.discard("")          # the initial value, before the first launch
-    return tags
 
 
 def test_every_tag_the_dispatcher_can_report_has_a_row():
-    tags = _dispatcher_tags()
-    assert len(tags) >= 30, sorted(tags)            # the parse itself still finds the families
+    tags = ops.conv_tags()
+    assert len(tags) >= 30, sorted(tags)            # every family is there
     table = {c.tag for c in R.CASES}
     assert table == tags, f"without a row: {sorted(tags - table)}; rows for no kernel: {sorted(table - tags)}"
 
@@ -33,17 +20,18 @@ def test_bucketed_rows_name_kernels_of_the_table():
     assert {c.tag for c, *_ in R.DYN_CASES} <= {c.tag for c in R.CASES}
     for c, per, count, bucket in R.DYN_CASES:
         assert c.batches == 1 and 0 < count < bucket and c.m // bucket == per
-        assert R.predict(R.dyn_exact(c, per, count, bucket))[0] == c.tag        # the exact-length launch takes the same kernel
+        assert R.route(R.dyn_exact(c, per, count, bucket))[0] == c.tag          # the exact-length launch takes the same kernel
 
 
 @pytest.mark.parametrize("case", R.CASES + [c for c, *_ in R.DYN_CASES], ids=lambda c: c.id)
 def test_row_reaches_its_route_by_the_dispatch_rules(case):
-    """The host mirror of the dispatch rules sends the row where it says, and the row's shape has the properties it relies on."""
-    tag, epi = R.predict(case)
+    """The dispatcher sends the row's descriptors where the row says, and the row's shape has the properties it relies on."""
+    tag, epi = R.route(case)
     assert tag == case.tag
     if case.branches:
         assert case.epi is None and 2 <= len(case.branches) <= 4
         assert len({k for k, _ in case.branches}) == len(case.branches)     # different taps per descriptor
+        assert epi in ("patch", "lane")                                     # the windowed kernels' epilogues
     else:
         assert case.epi == epi
     for c in case.descs():
@@ -58,9 +46,6 @@ def test_row_reaches_its_route_by_the_dispatch_rules(case):
             assert (c.cin * c.k) % 32 == 0                      # attach_split takes the weights
         if c.epi == "patch":
             assert c.n % 4 == 0 and c.ldo % 4 == 0 and c.act == R.ACT_NONE and not c.accumulate and c.div == 1.0
-            assert R.wide_ok(c, dict(c.env))
-        if c.epi == "lane":
-            assert not R.wide_ok(c, dict(c.env))
         if c.x_split:
             assert c.a_slope == 1.0 and c.split == "f16x2"
         if c.convt:

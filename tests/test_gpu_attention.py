@@ -87,7 +87,7 @@ def _record(report, key):
 
 
 def test_children_finished(report):
-    for name in ("rows", "bucket", "batch", "refusals"):
+    for name in ("rows", "bucket", "batch", "refusals", "routes"):
         gpu_child.check(report, f"{name}/ran", exactly=1)
         gpu_child.check(report, f"{FP32}{name}/ran", exactly=1)
 
@@ -154,6 +154,13 @@ def _refused(report, key, text):
     rec = _record(report, key)
     assert rec["rc"] != 0 and text in rec["msg"], rec
     assert rec["tag_kept"] and rec["out_kept"], f"{key}: something was launched ({rec})"
+
+
+@pytest.mark.parametrize("child", ("", FP32), ids=("main", "fp32"))
+def test_route_entry_answers_what_every_launch_takes(child, report):
+    """ops.attention_route, asked right before each launch of the child, named the kernel the launch then reported."""
+    rec = _record(report, f"{child}route/asked")
+    assert rec["launches"] > 50 and rec["differing"] == [], rec
 
 
 def test_parent_process_left_the_gpu_alone(report):

@@ -6,7 +6,7 @@ front of test_gpu_dist2, which must find the interpreter without an initialised 
 process — unless something else already has: then the same rows run in this process, no child is started and nothing is skipped.
 Per row:
   route         ops.last_conv_kernel() (and last_conv_epilogue() where the row names one) is what the row expects; a row that lands
-                on another kernel FAILS — it is not skipped;
+                on another kernel FAILS — it is not skipped; and it is what ops.conv_route answered before the launch;
   accuracy      max |out - ref64| <= F * e32 + 1e-6 * max |ref64|, e32 = max |torch fp32 on the CPU - ref64| on the same inputs, one
                 F per family of kernels;
   stray stores  the output lies in a sentinel-filled buffer: ROW_GAP rows in front of and behind every batch item, COL_SLACK
@@ -74,6 +74,7 @@ def test_route_against_fp64(case, report):
     assert tag == case.tag, f"{case.id}: dispatched to {tag}, the row is about {case.tag}"
     if case.epi is not None:
         assert epi == case.epi, f"{case.id}: epilogue {epi!r}, expected {case.epi!r}"
+    assert rec["route"] == [tag, epi], f"{case.id}: the route entry answered {rec['route']}, the launch took {tag}/{epi}"
     assert len(rec["descs"]) == len(case.descs())
     for d in rec["descs"]:
         err, e32 = d["err"], d["e32"]
@@ -92,9 +93,9 @@ def test_bucketed_launch_equals_exact_length(row, report):
     exact-length launch, and leaves the rows behind them alone (the input rows behind the valid ones hold junk)."""
     bucket_case = row[0]
     rec = _record(report, bucket_case.id)
-    assert rec["exact_tag"] == bucket_case.tag
+    assert rec["exact_tag"] == bucket_case.tag == rec["exact_route"]
     assert rec["err"] <= R.tolerance(FACTOR[bucket_case.family], rec["e32"], rec["scale"]), (rec["err"], rec["e32"])
-    assert (rec["tag"], rec["epi"]) == (bucket_case.tag, bucket_case.epi)
+    assert (rec["tag"], rec["epi"]) == (bucket_case.tag, bucket_case.epi) == tuple(rec["route"])
     assert rec["same_bits"]
     assert rec["stray"] == 0, f"{rec['stray']} floats behind the valid rows or outside the blocks were written"
     assert rec["slots"][0] == rec["slots"][1] == rec["slots"][2], rec["slots"]

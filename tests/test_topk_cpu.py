@@ -70,7 +70,7 @@ def test_new_symbols_are_exported_and_typed():
     from knn_svc_amd import _lib as L
     for name in NEW:
         assert name in L.SIGNATURES and hasattr(lib, name), name
-    assert L.ABI_VERSION == 20 == lib.knnsvc_abi_version()
+    assert L.ABI_VERSION == lib.knnsvc_abi_version() >= 20          # (20 brought these names; later versions keep them)
 
 
 def test_workspace_size_by_k():
