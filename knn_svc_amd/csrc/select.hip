@@ -134,7 +134,8 @@ __global__ void shift_f0_kernel(const float* __restrict__ f0, const KnSegTable s
     out[o + i] = r;
 }
 
-// half a wave (32 lanes) per query row; rank by counting gives torch.sort(stable=True) order
+// one wave (64 lanes, one per neighbour: k <= 64) per query row, four rows per block; rank by counting gives
+// torch.sort(stable=True) order
 __global__ __launch_bounds__(256) void f0_rerank_kernel(const long* __restrict__ nn, long nq, int k,
                                                        const float* __restrict__ sf0, const float* __restrict__ pf0,
                                                        long* __restrict__ out) {

@@ -7,7 +7,7 @@ import torch
 
 
 def smooth_weights(idx: torch.Tensor, pool: torch.Tensor, scale: float, max_iter: int = 100000,
-                   return_iters: bool = False, row_scale: torch.Tensor | None = None):
+                   return_iters: bool = False, row_scale: torch.Tensor | None = None, dtype: torch.dtype = torch.float32):
     """theta in R^{N x k} from 0; w = softmax(theta); E_s[t] = sum_k w[t,k] pool[clamp(idx[t,k]+s)]
     for s in {-1,0,+1}; loss = mean_t scale*MSE(E_-1[t+1], E_0[t]) + mean_t scale*MSE(E_0[t+1], E_+1[t]).
     Adam(lr .1, betas .9/.999, eps 1e-8, amsgrad).  Every iteration: remember the best theta;
@@ -20,15 +20,21 @@ def smooth_weights(idx: torch.Tensor, pool: torch.Tensor, scale: float, max_iter
 
     ``row_scale`` [N,k] is compute_weight_with_amp's amp_ratio (:684-713): every gathered row
     (shift -1, 0, +1) of candidate k of frame t is multiplied by row_scale[t,k] first; that
-    function uses phase_mae, i.e. scale = 1000 (:744-754)."""
+    function uses phase_mae, i.e. scale = 1000 (:744-754).
+
+    ``dtype``: the precision of the whole loop — theta, the pool and ``row_scale`` are cast to it.  float32 is the reference's
+    own; float64 is the yardstick of the tests that stop before any stopping rule can fire (max_iter <= 100)."""
     n_pool = len(pool)
+    pool = pool.to(dtype)
+    if row_scale is not None:
+        row_scale = row_scale.to(dtype)
     gathered = {}
     for s in (-1, 0, 1):
         j = torch.clamp(idx + s, 0, n_pool - 1)
         gathered[s] = pool[j.reshape(-1)].reshape(idx.shape[0], idx.shape[1], pool.shape[-1])
         if row_scale is not None:
             gathered[s] = gathered[s] * row_scale[:, :, None]
-    theta = torch.zeros(idx.shape, dtype=torch.float32, requires_grad=True)
+    theta = torch.zeros(idx.shape, dtype=dtype, requires_grad=True)
     opt = torch.optim.Adam([theta], lr=1e-1, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, amsgrad=True)
     min_loss = 20000
     conv_min = 20000
