@@ -696,6 +696,45 @@ int knnsvc_tune_f0_seg(const float* f0, const int64_t* host_seg, int32_t n_seg, 
                        const double* host_sigma, const double* host_alpha, const double* host_log_ref, float* out,
                        int32_t* notes, void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Harmony voice (an extension; upstream has none): the f0 contour of a harmony PART derived from the lead's, for n_seg
+ * stacked segments: every note of the lead moved by a number of scale DEGREES (a third above in C major is 4 semitones
+ * over C and 3 over D), the lead's own deviation from its note (vibrato, drift, phrasing) carried over unchanged.  It
+ * stands behind knnsvc_shift_f0_seg* and, when on, knnsvc_tune_f0_seg, and in front of everything that reads the f0 (f0
+ * re-rank, pitched concat re-selection, vocoder), so a part's pool frames are chosen at the part's pitch.  This
+ * restatement is the specification.
+ * Per segment s:  x[i] fp32, the lead's final f0;  mask (int) 12 bits as in "Pitch correction";  steps (int) scale degrees,
+ * -KNNSVC_HARMONY_MAX_STEPS..KNNSVC_HARMONY_MAX_STEPS;  a (fp64) in (0, 1], the glide coefficient per frame;  log_ref
+ * (fp64), the natural log of the tuning frequency of A4.  mask == 0 or steps == 0: the segment is OFF, its output is the
+ * input bit for bit, its notes are -1 and nothing else of it is read.  Constants S, H, HYST as there.  All arithmetic is
+ * fp64 with contraction off, every step rounded on its own; the output is rounded once.
+ *   1-4. Steps 1 to 4 of "Pitch correction", word for word: pitched frames and runs, l[i] and m[i], the centre c[i], the
+ *      note n[i] with its hysteresis.  (One copy of the device code serves both kernels.)
+ *   5. Degree move.  p_0 < ... < p_{d-1}: the allowed pitch classes, d = popcount(mask).  n[i] is allowed by construction;
+ *      j: the index of its pitch class, o = (n[i] - p_j) / 12 (exact), J = j + steps.
+ *      t[i] = 12 * (o + floordiv(J, d)) + p_{floormod(J, d)}: floor division and the non-negative remainder, for negative
+ *      J and negative notes (below 8.18 Hz at 440) too.  D[i] = t[i] - n[i], a whole number of semitones.
+ *   6. Glide, sequential along the run.  h[b] = (double)D[b];  h[i] = h[i-1] + a * ((double)D[i] - h[i-1]).  A part's
+ *      interval changes where the lead changes note; a = 1 makes that a jump, a smaller a a short portamento.
+ *   7. Output.  y[i] = (float)exp(l[i] + h[i] * S);  notes[i] = t[i] (int32), -1 for an unpitched frame, which keeps its
+ *      bits.  (A part's note may itself be -1, below 8.18 Hz; the lead's frame is then pitched.)
+ * With the chromatic mask D == steps: a parallel part, y = (float)exp(l + steps * S).  steps = +-d gives D == +-12.  The
+ * part keeps the lead's deviation from its note to the cent.  A caller that thinks in milliseconds uses
+ * a = -expm1(-20 / glide_ms) (glide_ms = 0: a = 1).
+ * knnsvc_harmony_f0_seg: host_mask, host_steps (int32), host_alpha, host_log_ref (double), each [n_seg], are HOST tables
+ * handed to the kernel by value.  Workspace (knnsvc_tune_f0_workspace_bytes), launch shape (one workgroup per segment,
+ * phases A / B / C) and promises are those of knnsvc_tune_f0_seg: one launch, no allocation, no synchronisation, no
+ * floating-point atomics, hipGraph-capturable; a segment's output is bit-identical whether it is launched alone or
+ * stacked, and from call to call; rows outside the table are not written.
+ * Refused before the first HIP call, with a message that names the segment: what knnsvc_tune_f0_seg refuses (steps in
+ * the place of sigma: outside -24..24).
+ * ------------------------------------------------------------------------------------------ */
+#define KNNSVC_HARMONY_MAX_STEPS 24
+#define KNNSVC_HARMONY_MAX_PARTS 3
+int knnsvc_harmony_f0_seg(const float* f0, const int64_t* host_seg, int32_t n_seg, const int32_t* host_mask,
+                          const int32_t* host_steps, const double* host_alpha, const double* host_log_ref, float* out,
+                          int32_t* notes, void* ws, size_t ws_bytes, void* stream);
+
 /* out[i,:] = sum_k w[i,k] * pool[idx[i,k], :]   (ddsp_prematch_dataset.py:1358, 1444).  w NULL = uniform weights:
  * mean_mode 0 multiplies every row by 1.0f / k (softmax(ones), :1361-1364), mean_mode 1 sums in order and divides by k
  * (torch.mean, harmonics :1446); any k >= 1, the two are bit-identical when k is a power of two. */
@@ -902,6 +941,17 @@ int knnsvc_envelope_mix(const float* y, int64_t n, const float* x, int64_t nx, i
 int knnsvc_peak_limit(const float* y, int64_t n, int32_t sample_rate, double peak_db, float* out, void* stats, void* stream);
 /* HOST: samples per workgroup tile and L at 16 kHz; tests take their edge lengths from here; either pointer may be NULL. */
 void knnsvc_peak_limit_layout(int32_t* tile, int32_t* lookahead_at_16k);
+/* Mix of the voices of one output (the lead and its harmony parts; "Harmony voice"), between the per-voice half of the tail
+ * (generator, envelope mix) and the per-output half (loudness, ceiling):
+ *     out[i] = (float)( sum_v g_v * (double)y_v[i] )
+ * over the voices in order.  Every product and every sum is an fp64 operation of its own (no contraction), the sum starts
+ * with the first product that is read, the result is rounded once.  A voice whose gain is exactly 0 is NOT READ: a NaN in
+ * it does not reach the output.  host_y: a HOST array of n_voices device pointers to n samples each; host_gains: HOST
+ * double [n_voices], finite and >= 0, at least one > 0 (a caller in dB uses 10^(dB / 20)); both reach the kernel by value.
+ * n_voices 1..KNNSVC_HARMONY_MAX_PARTS + 1.  out may be one of the inputs and may not overlap one otherwise.  One launch on
+ * `stream` (four samples per thread; 16-byte accesses when out and every voice that is read are 16-byte aligned, else
+ * scalar), enqueue only: no allocation, no synchronisation, capturable.  Anything else is KNNSVC_EINVAL before a launch. */
+int knnsvc_mix_waves(const float* const* host_y, int32_t n_voices, const double* host_gains, int64_t n, float* out, void* stream);
 
 #ifdef __cplusplus
 }

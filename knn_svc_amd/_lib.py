@@ -173,6 +173,7 @@ SIGNATURES = {
     "knnsvc_shift_f0_seg_blend": (i32, [vp, vp, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp]),
     "knnsvc_tune_f0_workspace_bytes": (sz, [i64, i32]),
     "knnsvc_tune_f0_seg": (i32, [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+    "knnsvc_harmony_f0_seg": (i32, [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
     "knnsvc_weighted_gather": (i32, [vp, vp, i64, i32, vp, i32, i32, i32, vp, vp]),
     "knnsvc_round_f16": (i32, [vp, i64, vp, vp]),
     "knnsvc_amp_ratio": (i32, [vp, i32, vp, i32, i64, vp, i64, i32, i32, vp, vp]),
@@ -197,6 +198,7 @@ SIGNATURES = {
     "knnsvc_envelope_mix": (i32, [vp, i64, vp, i64, i32, f64, vp, vp, vp, sz, vp]),
     "knnsvc_peak_limit": (i32, [vp, i64, i32, f64, vp, vp, vp]),
     "knnsvc_peak_limit_layout": (None, [C.POINTER(i32), C.POINTER(i32)]),
+    "knnsvc_mix_waves": (i32, [vp, i32, vp, i64, vp, vp]),
 }
 
 _lib = None

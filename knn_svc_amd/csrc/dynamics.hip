@@ -241,7 +241,89 @@ __global__ __launch_bounds__(PK_T) void pk_limit_kernel(const float* y, long n, 
     }
 }
 
+// ---------------------------------------------------------------------------------------------- mix of the voices
+// The voices of a mix: host tables of device pointers and gains, handed over by value.
+constexpr int MX_VOICES = KNNSVC_HARMONY_MAX_PARTS + 1;
+constexpr int MX_T = 256;                            // four samples per thread
+struct KnMixTable { const float* y[MX_VOICES]; double g[MX_VOICES]; };
+
+// (float)(sum_v g[v] * (double)x[v]) over the voices whose gain is not 0, in order, every operation on its own; the sum starts with
+// the first product.  (Unlike a blend's one-hot row, a single live voice is still multiplied: its gain need not be 1.)
+__device__ __forceinline__ float mx_sum(const KnMixTable& mt, const float (&x)[MX_VOICES]) {
+#pragma clang fp contract(off)
+    double acc = 0.0;
+    bool first = true;
+#pragma unroll
+    for (int v = 0; v < MX_VOICES; ++v) {
+        if (mt.g[v] != 0.0) {
+            const double p = mt.g[v] * (double)x[v];
+            acc = first ? p : acc + p;
+            first = false;
+        }
+    }
+    return (float)acc;
+}
+
+// A thread reads its four samples of every live voice and then writes them: out may be one of the voices.  The gains are uniform,
+// so a silent voice costs a scalar branch and no load.  VEC: every live pointer and out are 16-byte aligned; the last thread's
+// quad may be short and is then done sample by sample.
+template <bool VEC>
+__global__ __launch_bounds__(MX_T) void mix_kernel(const KnMixTable mt, long n, float* out) {
+#pragma clang fp contract(off)
+    const long n0 = 4 * ((long)blockIdx.x * MX_T + threadIdx.x);
+    if (n0 >= n) return;
+    if (VEC && n0 + 4 <= n) {
+        f32x4 xv[MX_VOICES];
+#pragma unroll
+        for (int v = 0; v < MX_VOICES; ++v) xv[v] = mt.g[v] != 0.0 ? *reinterpret_cast<const f32x4*>(mt.y[v] + n0) : (f32x4)(0.f);
+        f32x4 vo;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const float x[MX_VOICES] = {xv[0][e], xv[1][e], xv[2][e], xv[3][e]};
+            vo[e] = mx_sum(mt, x);
+        }
+        *reinterpret_cast<f32x4*>(out + n0) = vo;
+    } else {
+        const int len = n - n0 < 4 ? (int)(n - n0) : 4;
+        float r[4];
+        for (int e = 0; e < len; ++e) {
+            float x[MX_VOICES];
+#pragma unroll
+            for (int v = 0; v < MX_VOICES; ++v) x[v] = mt.g[v] != 0.0 ? mt.y[v][n0 + e] : 0.f;
+            r[e] = mx_sum(mt, x);
+        }
+        for (int e = 0; e < len; ++e) out[n0 + e] = r[e];
+    }
+}
+static_assert(MX_VOICES == 4, "mix_kernel spells out four voices");
+
 }  // namespace
+
+extern "C" int knnsvc_mix_waves(const float* const* host_y, int32_t n_voices, const double* host_gains, int64_t n, float* out,
+                                void* stream) {
+    KN_REQUIRE(n_voices >= 1 && n_voices <= MX_VOICES, "mix_waves: n_voices %d outside 1..%d", (int)n_voices, MX_VOICES);
+    KN_REQUIRE(n >= 0 && n <= DY_MAX_N, "mix_waves: bad length %lld (0 .. 2^36)", (long long)n);
+    KN_REQUIRE(host_y && host_gains && (out || n == 0), "mix_waves: null pointer");
+    KnMixTable mt;
+    bool vec = ((uintptr_t)out & 15) == 0, positive = false;
+    for (int v = 0; v < MX_VOICES; ++v) {
+        mt.y[v] = v < n_voices ? host_y[v] : nullptr;
+        mt.g[v] = v < n_voices ? host_gains[v] + 0.0 : 0.0;
+        if (v >= n_voices) continue;
+        KN_REQUIRE(mt.g[v] >= 0.0 && mt.g[v] <= 1.79769313486231570815e308, "mix_waves: gain %d is %g, not finite and >= 0", v, mt.g[v]);
+        KN_REQUIRE(mt.y[v] || n == 0, "mix_waves: null pointer for voice %d", v);
+        KN_REQUIRE(n == 0 || out == mt.y[v] || out + n <= mt.y[v] || mt.y[v] + n <= out, "mix_waves: out overlaps voice %d without being it", v);
+        if (mt.g[v] != 0.0) { positive = true; vec = vec && ((uintptr_t)mt.y[v] & 15) == 0; }
+    }
+    KN_REQUIRE(positive, "mix_waves: no positive gain");
+    if (n == 0) return KNNSVC_OK;
+    const dim3 grid((unsigned)cdiv64(n, 4 * MX_T));
+    if (vec)
+        hipLaunchKernelGGL(mix_kernel<true>, grid, dim3(MX_T), 0, (hipStream_t)stream, mt, (long)n, out);
+    else
+        hipLaunchKernelGGL(mix_kernel<false>, grid, dim3(MX_T), 0, (hipStream_t)stream, mt, (long)n, out);
+    return knnsvc_check_launch("mix_waves");
+}
 
 extern "C" size_t knnsvc_envelope_workspace_bytes(int64_t n, int32_t hop) {
     if (!ev_hop_ok(hop)) { knnsvc_fail(KNNSVC_EINVAL, "envelope: hop %d is not a positive multiple of 64 up to %d", (int)hop, EV_MAX_HOP); return 0; }

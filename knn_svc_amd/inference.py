@@ -18,13 +18,18 @@ three times) adds target voices and --blend W0,W1[,...] weighs TGT and them: the
 (matcher.KNeighborsVC.blend_voices; the output is named <src>_to_<tgt>+<blend_tgt>..., without the weights).  --tune SCALE
 ("chromatic", "A:minor", "D:101011010101"; options.Tuning) snaps the converted f0 towards the notes of that key — the key of the
 OUTPUT —, with --tune_strength S (0..1), --retune_ms MS (0..2000; 0: hard snap) and --tuning_hz HZ (400..480) as its
-refinements, refused without --tune; no file name changes.  --dur_limit is
+refinements, refused without --tune; no file name changes.  --harmony_steps 2,-3 (file mode only; options.Harmony) adds
+harmony parts, each the lead's contour moved by that many scale degrees, sung by the same target voice and mixed under the lead:
+--harmony_scale S (default: --tune's scale), --harmony_gain_db -6,-9 (one per part, default -6), --harmony_lead_db 0 and
+--harmony_glide_ms 40 refine it and are refused without --harmony_steps; the mix is written, no file name changes (stems and a
+different target voice per part are not offered).  --dur_limit is
 compared in seconds, as upstream (ddsp_prematch_dataset.py:408-411).
 """
 from __future__ import annotations
 
 import argparse
 import os
+import re
 
 FLAGS = [
     ("--ckpt_dir", dict(type=str, default="/home/ken/Downloads/knn_vc_data/ckpt_saved")),
@@ -47,6 +52,13 @@ def _bool(v: str) -> bool:
     raise argparse.ArgumentTypeError("boolean value expected")
 
 
+def _steps(v: str) -> list:
+    try:
+        return [int(w) for w in v.split(",")]
+    except ValueError:
+        raise argparse.ArgumentTypeError("comma-separated whole numbers expected, e.g. 2,-3")
+
+
 def _weights(v: str) -> list:
     try:
         return [float(w) for w in v.split(",")]
@@ -56,6 +68,8 @@ def _weights(v: str) -> list:
 
 def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description="kNN-SVC inference (MI355X build): file or folder mode")
+    # a comma-separated list that starts with a negative number ("--harmony_gain_db -6,-9") is a value, not an option
+    ap._negative_number_matcher = re.compile(r"^-\d[\d.,eE+-]*$|^-\.\d[\d.,eE+-]*$")
     ap.add_argument("src")
     ap.add_argument("tgt")
     for flag, kw in FLAGS:
@@ -96,6 +110,18 @@ def build_parser() -> argparse.ArgumentParser:
                     help="(extension, with --tune) time constant of the glide onto a note, 0..2000, default 80; 0 is a hard snap")
     ap.add_argument("--tuning_hz", type=float, default=None, metavar="HZ",
                     help="(extension, with --tune) the frequency of A4, 400..480, default 440")
+    ap.add_argument("--harmony_steps", type=_steps, default=None, metavar="N[,N[,N]]",
+                    help="(extension, file mode only) one to three harmony parts, each that many scale degrees above (> 0) or below "
+                         "(< 0) the lead, e.g. 2,-3: a third above and a fourth below")
+    ap.add_argument("--harmony_scale", type=str, default=None, metavar="S",
+                    help="(extension, with --harmony_steps) the key the parts move in, as --tune takes it; default: --tune's scale")
+    ap.add_argument("--harmony_gain_db", type=_weights, default=None, metavar="DB[,DB[,DB]]",
+                    help="(extension, with --harmony_steps) the level of each part in the mix, -60..12, default -6")
+    ap.add_argument("--harmony_lead_db", type=float, default=None, metavar="DB",
+                    help="(extension, with --harmony_steps) the level of the lead in the mix, -60..12, default 0")
+    ap.add_argument("--harmony_glide_ms", type=float, default=None, metavar="MS",
+                    help="(extension, with --harmony_steps) how fast a part's interval changes where the lead changes note, "
+                         "0..2000, default 40; 0 is a jump")
     ap.add_argument("--weights", default="auto", choices=["auto", "checkpoint", "seeded"],
                     help="(extension) 'seeded' runs with random weights when the released checkpoints are unavailable")
     return ap
@@ -121,6 +147,24 @@ def tuning_of(a):
     return Tuning(scale=a.tune, **more)
 
 
+def harmony_of_flags(a, tune=None):
+    """The command line's --harmony flags as an options.Harmony (None without --harmony_steps), checked against ``tune`` (the
+    --tune flags' Tuning): ValueError for a bad value, a refinement without --harmony_steps, gains that are not one per part, or
+    no scale in either."""
+    from .options import Harmony, HarmonyPart
+    more = {k: v for k, v in (("scale", a.harmony_scale), ("lead_db", a.harmony_lead_db), ("glide_ms", a.harmony_glide_ms)) if v is not None}
+    if a.harmony_steps is None:
+        if more or a.harmony_gain_db is not None:
+            raise ValueError("--harmony_scale / --harmony_gain_db / --harmony_lead_db / --harmony_glide_ms refine --harmony_steps: give the steps")
+        return None
+    gains = a.harmony_gain_db if a.harmony_gain_db is not None else [-6.0] * len(a.harmony_steps)
+    if len(gains) != len(a.harmony_steps):
+        raise ValueError(f"--harmony_gain_db: {len(gains)} gains for {len(a.harmony_steps)} parts")
+    h = Harmony(tuple(HarmonyPart(s, g) for s, g in zip(a.harmony_steps, gains)), **more)
+    h.shifts(tune)
+    return h
+
+
 def main(argv=None) -> int:
     ap = build_parser()
     a = ap.parse_args(argv)
@@ -133,8 +177,11 @@ def main(argv=None) -> int:
         from .matching import refuse_duration_with_envelope, resolve_target_duration
         refuse_duration_with_envelope([resolve_target_duration(a.target_duration)], ext)
         tune = tuning_of(a)
+        harmony = harmony_of_flags(a, tune)
     except ValueError as e:
         ap.error(str(e))
+    if harmony is not None and os.path.isdir(a.src):
+        ap.error("--harmony_steps applies to a single conversion: a dataset run returns one feature set per utterance")
     if (a.blend_tgt is not None or a.blend is not None) and os.path.isdir(a.src):
         ap.error("--blend_tgt / --blend apply to a single conversion: a dataset run pairs speakers, a blend has no meaning there")
     try:                                                   # the count of voices and of weights, before the models are loaded
@@ -151,7 +198,7 @@ def main(argv=None) -> int:
                   **({} if tune is None else dict(tune=tune)))
     if os.path.isfile(a.src) and os.path.isfile(a.tgt):
         knn.special_match(src_wav_file=a.src, ref_wav_file=a.tgt, target_duration=a.target_duration, blend_with=a.blend_tgt,
-                          blend=a.blend, **common)
+                          blend=a.blend, **({} if harmony is None else dict(harmony=harmony)), **common)
         return 0
     if os.path.isdir(a.src) and os.path.isdir(a.tgt):
         knn.bulk_match(src_dataset_path=a.src, tgt_dataset_path=a.tgt,

@@ -21,7 +21,8 @@ from pathlib import Path
 import torch
 
 from . import audio_io, config as C, dist as kdist, ops
-from .matching import load_utterance, match_at_inference_time, refuse_duration_with_envelope, resolve_target_duration, resolve_tune
+from .matching import (harmony_of, load_utterance, match_at_inference_time, refuse_duration_with_envelope, resolve_harmony,
+                       resolve_target_duration, resolve_tune)
 from .options import Extensions
 from .vocoder import Vocoder
 from .wavlm import WavLMEncoder
@@ -43,15 +44,36 @@ class Tail:
         self.needs_source = ext.envelope_mix > 0
 
     def __call__(self, out_feats, shifted_f0, harm, src_wav=None):
+        return self.per_output(self.per_voice(out_feats, shifted_f0, harm, src_wav))
+
+    def per_voice(self, out_feats, shifted_f0, harm, src_wav=None):
+        """The half that runs once per voice of an output (the lead, and every harmony part): generator, envelope mix."""
         vc, ext = self.vc, self.ext
         y = vc.hifigan.forward(out_feats.float(), shifted_f0.reshape(-1).float(), None if self.f0only or harm is None else harm.float())
         if self.needs_source:
             ops.envelope_mix(y, src_wav, ext.envelope_mix, hop=vc.hop_length, out=y)
+        return y
+
+    def per_output(self, y):
+        """The half that runs once per output, on one voice or on the mix of several (ops.mix_waves): loudness, ceiling.  The
+        loudness in place."""
+        vc, ext = self.vc, self.ext
         if ext.loudness_db is not None:
             ops.normalize_loudness(y, ext.loudness_db, vc.sr, out=y)
         if ext.peak_db is not None:
             y = ops.limit_peak(y, ext.peak_db, vc.sr)          # out of place: the parallel launch
         return y
+
+
+class VoiceTail:
+    """The per-voice half of a ``Tail`` as a ``vocode_fn`` of its own: what a voice that is going to be mixed with others (a lead
+    and its harmony parts) runs behind its match body."""
+
+    def __init__(self, tail: Tail):
+        self.tail, self.needs_source = tail, tail.needs_source
+
+    def __call__(self, out_feats, shifted_f0, harm, src_wav=None):
+        return self.tail.per_voice(out_feats, shifted_f0, harm, src_wav)
 
 
 class KNeighborsVC:
@@ -115,8 +137,13 @@ class KNeighborsVC:
     def special_match(self, src_wav_file, ref_wav_file, topk: int = 4, device=None, prioritize_f0=True,
                       ckpt_type="wavlm_only", tgt_loudness_db=-16, post_opt="no_post_opt", save=True, normalize_loudness=False,
                       use_topk=False, use_vad=False, vad_trigger_level=7, f0_shift="median", transpose=0.0, envelope_mix=0.0,
-                      peak_db=None, target_duration=None, blend_with=None, blend=None, tune=None):
-        """``tune`` (an options.Tuning, a scale such as "A:minor" or "chromatic", None: off): pitch correction — the shifted f0
+                      peak_db=None, target_duration=None, blend_with=None, blend=None, tune=None, harmony=None):
+        """``harmony`` (an options.Harmony, None: off): 1 to 3 harmony parts — the lead's contour moved by scale degrees, sung by
+        the same target voice from the source's one encoder pass and neighbour search, and mixed under the lead on the GPU
+        (options.py has the semantics; its scale, or else ``tune``'s, names the key); through serving.TargetVoice and
+        serving.BatchConverter, as a blend; the mix is returned and written, the file name does not change.  ``bulk_match``,
+        ``match_at_inference_time`` and ``vocode`` do not take it: they return one feature set per source.
+        ``tune`` (an options.Tuning, a scale such as "A:minor" or "chromatic", None: off): pitch correction — the shifted f0
         is snapped towards the notes of that key, the OUTPUT's key, on the GPU inside the match stage (matching.resolve_tune;
         options.py has the semantics); the file name does not change.  ``vocode`` does not take it: it starts behind the match
         stage, where ops.tune_f0_seg serves such callers.
@@ -129,14 +156,19 @@ class KNeighborsVC:
                                         transpose, envelope_mix, peak_db)          # refused before a file is read
         refuse_duration_with_envelope([resolve_target_duration(target_duration)], ext)
         tune = resolve_tune(tune)
+        harmony = resolve_harmony(harmony)
+        parts = harmony_of(harmony, tune)          # a harmony without a scale, its own or the tune's, is refused here
         refs = self.blend_voices(ref_wav_file, blend_with, blend)
+        if refs is None and parts is not None:
+            refs = [ref_wav_file]
         f0only = "wavlm_only" in ckpt_type or "no_harm_no_amp" in ckpt_type
         if "wavlm_only_original" in ckpt_type:
             raise NotImplementedError("wavlm_only_original needs hifigan/models.py, absent upstream")
         if refs is not None:
             from . import serving
             voices = [serving.TargetVoice(self, r, vad_trigger_level=ext.vad_level) for r in refs]
-            conv = serving.BatchConverter(self, voices, ckpt_type, post_opt, ext=ext, blend=blend, tune=tune)
+            conv = serving.BatchConverter(self, voices if len(voices) > 1 else voices[0], ckpt_type, post_opt, ext=ext, blend=blend,
+                                          tune=tune, harmony=harmony)
             pred = conv.convert([str(src_wav_file)], target_duration=target_duration)[0]
             if save:
                 out_file = conv.output_path(src_wav_file)
@@ -163,7 +195,7 @@ class KNeighborsVC:
     def many_to_one(self, src_files, ref_wav_file, converted_audio_dir=None, ckpt_type="mix", post_opt="post_opt_0.2",
                     duration_limit=None, target=None, match=None, loudness_db=None, topk=None, vad_trigger_level=None,
                     f0_shift=None, transpose=None, envelope_mix=None, peak_db=None, target_duration=None, blend_with=None,
-                    blend=None, tune=None):
+                    blend=None, tune=None, harmony=None):
         """BASELINE cfg 5 (no counterpart upstream: the reference would call ``special_match`` once per source and rebuild the
         target pool each time, ddsp_matcher.py:937-1023): MANY sources against ONE target pool that is built once and stays
         resident, all sources through the stream pipeline as one batch (knn_svc_amd/serving.py).  Under a process group the
@@ -176,11 +208,14 @@ class KNeighborsVC:
         converted towards that weighted mix of voices (``blend_voices``; each voice's pool is trimmed when ``vad_trigger_level``
         is given); ``target`` is then a sequence of TargetVoice to reuse, and the outputs are named ``<src>_to_<idA>+<idB>[+...]``.
         ``tune``: the pitch correction, one value for all sources or a list with one entry per source (an options.Tuning, a
-        scale, None / "off": none; serving.BatchConverter.convert)."""
+        scale, None / "off": none; serving.BatchConverter.convert).  ``harmony``: harmony parts, one value for all sources or a list
+        with one entry per source (an options.Harmony, None / "off": none; serving.BatchConverter.convert): the mix is written."""
         from . import serving
         ext = Extensions.from_serving(loudness_db, topk, vad_trigger_level, f0_shift, transpose, envelope_mix, peak_db)   # before a file is read
         refuse_duration_with_envelope(resolve_target_duration(target_duration, len(src_files)), ext)
-        resolve_tune(tune, len(src_files))
+        tunes = resolve_tune(tune, len(src_files))
+        for h, t in zip(resolve_harmony(harmony, len(src_files)), tunes):
+            harmony_of(h, t)
         # (voices handed in as ``target``: the converter checks the weights against them)
         refs = None if isinstance(target, (list, tuple)) else self.blend_voices(ref_wav_file, blend_with, blend)
         if target is None:
@@ -191,8 +226,10 @@ class KNeighborsVC:
             target_duration = kdist.my_share(list(target_duration))
         if isinstance(tune, (list, tuple)):
             tune = kdist.my_share(list(tune))
+        if isinstance(harmony, (list, tuple)):
+            harmony = kdist.my_share(list(harmony))
         written = serving.BatchConverter(self, target, ckpt_type, post_opt, match=match, ext=ext, blend=blend).convert_files(
-            mine, converted_audio_dir, target_duration=target_duration, tune=tune)
+            mine, converted_audio_dir, target_duration=target_duration, tune=tune, harmony=harmony)
         return kdist.gather_paths(written)
 
     @torch.inference_mode()

@@ -23,7 +23,7 @@ import numpy as np
 import torch
 
 from . import audio_io, config as C, dist as kdist, features, ops, pipeline, pool_cache
-from .options import TUNE_OFF, Extensions, SourceKnobs, Tuning, per_item
+from .options import TUNE_OFF, Extensions, Harmony, HarmonyShift, SourceKnobs, Tuning, per_item
 from .wavlm import WavLMEncoder, chunk_plan
 
 AUDIO_EXT = {".flac", ".wav", ".mp3"}
@@ -588,6 +588,60 @@ def tune_active(tunings) -> bool:
     return any(t is not None and t.on for t in tunings)
 
 
+# Harmony voices (an extension; include/knnsvc_hip.h "Harmony voice" is the specification): a source item sung in 1 + P parts by the
+# same target voice.  A part is a further ITEM of the match stage whose f0 is the lead's final f0 (shifted and, when on, corrected)
+# moved by scale degrees (ops.harmony_f0_seg), right behind ops.tune_f0_seg and in front of the f0 re-rank, so that a part's pool
+# frames are the ones sung at the part's pitch.  The parts share the lead's encoder output and neighbour lists (``nn32s``); the
+# converter mixes their waveforms (ops.mix_waves).  The match stage takes, per item, the part's options.HarmonyShift or None; the
+# user's options.Harmony is resolved by the converter, which knows the item's ``tune``.
+HARMONY_OFF = "off"           # what resolve_harmony returns for "off": an item under a converter whose default is on
+
+
+def _one_harmony(value):
+    if value is None or isinstance(value, Harmony):       # (a Harmony is checked when it is built)
+        return value
+    if isinstance(value, str) and value.strip().lower() == "off":
+        return HARMONY_OFF
+    raise ValueError(f"harmony must be an options.Harmony, 'off' or None, got {value!r}")
+
+
+def resolve_harmony(value, n_items=None):
+    """``harmony`` checked, refused (ValueError) before any file or device work when it is not valid.  None -> None (nothing of
+    its own: the converter's default, or off); "off" -> HARMONY_OFF, an explicit off for that item; an options.Harmony ->
+    itself.  ``n_items`` None: one value.  ``n_items`` = the number of items of a batch: one value for all items or a list /
+    tuple with one entry per item -> a list of n_items entries."""
+    if n_items is None:
+        if isinstance(value, (list, tuple)):
+            raise ValueError("harmony: a single value expected here, not a list")
+        return _one_harmony(value)
+    return per_item(value, n_items, "harmony", _one_harmony)
+
+
+def harmony_of(value, tune=None):
+    """A resolved ``harmony`` entry and the item's resolved ``tune`` -> (the options.Harmony, its HarmonyShift per part), or None
+    when the item has no harmony.  ValueError when neither names a scale."""
+    if value is None or value == HARMONY_OFF:
+        return None
+    return value, value.shifts(tune)
+
+
+def _one_shift(value):
+    if value is None or isinstance(value, HarmonyShift):
+        return value
+    raise ValueError(f"harmony: the match stage takes an options.HarmonyShift per item (Harmony.shifts) or None, got {value!r}")
+
+
+def resolve_harmony_shifts(value, n_items):
+    """The match stage's ``harmony`` argument: one options.HarmonyShift (or None) for all items, or a list with one per item
+    -> a list of n_items entries."""
+    return per_item(value, n_items, "harmony", _one_shift)
+
+
+def harmony_active(shifts) -> bool:
+    """Whether any entry of a resolved list of part records moves its item (None or an off record does not)."""
+    return any(p is not None and p.on for p in shifts)
+
+
 def resolve_dynamics(envelope_mix, peak_db):
     """The two output-dynamics switches as the library takes them, refused before any device or file work when they are not
     valid -> (a, p).  ``envelope_mix``: a number in [0, 1], None = 0 (off): how much of the source's volume envelope the tail
@@ -604,16 +658,17 @@ def resolve_dynamics(envelope_mix, peak_db):
 
 def match_features(query_seq, query_f0, matching_list, matching_f0, harmonics_list, ckpt_type, post_opt,
                    return_debug=False, nn32=None, nan_flags=None, pool_prep=None, synth_list=None, topk=None,
-                   f0_shift=None, transpose=None, tune=None):
+                   f0_shift=None, transpose=None, tune=None, harmony=None):
     """The per-query body (ddsp_prematch_dataset.py:1189-1450) on device tensors: ``match_features_many`` (below, where the
     arguments are described) of one utterance.  ``nn32`` may carry neighbours already found by the pool-sharded search
     (knn_svc_amd.dist.sharded_knn); in the debug dict ``iters_*`` are one-element tensors, or 0 without the Adam stage."""
     resolve_f0_shift(f0_shift, transpose)     # one value each
     resolve_tune(tune)
+    part = {} if harmony is None else dict(harmony=[_one_shift(harmony)])
     return match_features_many([query_seq], [query_f0], matching_list, matching_f0, harmonics_list, ckpt_type, post_opt,
                                nn32s=None if nn32 is None else [nn32], nan_flags=nan_flags, pool_prep=pool_prep,
                                synth_list=synth_list, return_debug=return_debug, topk=topk, f0_shift=f0_shift,
-                               transpose=transpose, tune=tune)[0]
+                               transpose=transpose, tune=tune, **part)[0]
 
 
 # How the match stage of SEVERAL items is put on the chip: "lanes" (one match_features per item on the lane streams, the default) or
@@ -652,7 +707,7 @@ def _split(t, lens):
 
 def match_features_many(query_seqs, query_f0s, matching_list, matching_f0, harmonics_list, ckpt_type, post_opt, nn32s=None,
                         nan_flags=None, pool_prep=None, synth_list=None, return_debug=False, topk=None, f0_shift=None,
-                        transpose=None, tune=None):
+                        transpose=None, tune=None, harmony=None):
     """The per-query body (ddsp_prematch_dataset.py:1189-1450) for several query utterances against one pool, run ONCE over their
     stacked frames -> a list of per-item tuples (out_feats, harm or None, shifted_f0[, debug dict]) (views of the stacked outputs).
     The row-wise stages (row norms, f0 re-rank, weighted sums) take the stacked rows as they are; the per-sequence stages (median,
@@ -671,10 +726,15 @@ def match_features_many(query_seqs, query_f0s, matching_list, matching_f0, harmo
     none).  When any item has one, the shifted f0 goes through ops.tune_f0_seg right behind the shift, on the side stream, so the
     re-rank, the pitched concat re-selection and the returned f0 (the vocoder's) all see the corrected contour; otherwise nothing
     is launched.  The debug dict carries ``tuned_notes``: the item's int32 note per frame (-1: not corrected), None when off;
-    ``shift_semitones`` stays the shift's interval."""
+    ``shift_semitones`` stays the shift's interval.
+    ``harmony``: per item the options.HarmonyShift of a harmony part (``resolve_harmony_shifts``: one for all items or one per
+    item; None: the item is a lead).  When any item has one, the shifted (and corrected) f0 goes through ops.harmony_f0_seg right
+    behind the correction, on the side stream: re-rank, pitched re-selection and the returned f0 see the part's contour;
+    otherwise nothing is launched.  The debug dict carries ``harmony_notes``: the part's int32 note per frame, None when off."""
     topk = resolve_topk(topk)                 # before any device work
     shift_modes, shift_ts = resolve_f0_shift(f0_shift, transpose, len(query_seqs))
     tunings = resolve_tune(tune, len(query_seqs))
+    parts = resolve_harmony_shifts(harmony, len(query_seqs))
     lens = [int(q.shape[0]) for q in query_seqs]
     seg = ops.Segments.of_lengths(lens)       # the host tables once for the six segmented calls
     q = _stacked(query_seqs)
@@ -707,6 +767,10 @@ def match_features_many(query_seqs, query_f0s, matching_list, matching_f0, harmo
         if tune_active(tunings):
             shifted = ops.tune_f0_seg(shifted, seg, tunings, return_notes=return_debug)
             shifted, notes = shifted if return_debug else (shifted, None)
+        hnotes = None
+        if harmony_active(parts):
+            shifted = ops.harmony_f0_seg(shifted, seg, parts, return_notes=return_debug)
+            shifted, hnotes = shifted if return_debug else (shifted, None)
         ranked = ops.f0_rerank(nn32, shifted, matching_f0)
         idx2 = ranked[:, :topk].contiguous()
         if cw != -1:
@@ -723,7 +787,7 @@ def match_features_many(query_seqs, query_f0s, matching_list, matching_f0, harmo
         w, it1 = ops.smooth_weights_seg(idx, seg, Ps, 0.1, return_iters=True)
     out_feats = ops.weighted_gather(idx, w, Ps)                                      # without Adam: softmax(ones) (:1361-1364)
     main.wait_stream(side)
-    for t in (shifted, semis, notes, idx2, harm_w, w2, it2):
+    for t in (shifted, semis, notes, hnotes, idx2, harm_w, w2, it2):
         if t is not None:
             t.record_stream(main)
     if nan_flag is not None:
@@ -736,22 +800,22 @@ def match_features_many(query_seqs, query_f0s, matching_list, matching_f0, harmo
                 with ops.fused_off():
                     return match_features_many(query_seqs, query_f0s, matching_list, matching_f0, harmonics_list, ckpt_type, post_opt,
                                                pool_prep=pool_prep, synth_list=synth_list, return_debug=return_debug, topk=topk,
-                                               f0_shift=f0_shift, transpose=transpose, tune=tune)
+                                               f0_shift=f0_shift, transpose=transpose, tune=tune, harmony=harmony)
     out = []
-    dbg = [_split(t, lens) for t in (nn32, idx, w, idx2, w2, notes)]
+    dbg = [_split(t, lens) for t in (nn32, idx, w, idx2, w2, notes, hnotes)]
     for i, (of, hw, sf) in enumerate(zip(_split(out_feats, lens), _split(harm_w, lens), _split(shifted, lens))):
         if return_debug:
             out.append((of, hw, sf, dict(nn32=dbg[0][i], idx_wavlm=dbg[1][i], w_wavlm=dbg[2][i], idx_harm=dbg[3][i], w_harm=dbg[4][i],
                                          iters_wavlm=it1[i:i + 1] if it1 is not None else 0,
                                          iters_harm=it2[i:i + 1] if it2 is not None else 0,
-                                         shift_semitones=semis[i:i + 1], tuned_notes=dbg[5][i])))
+                                         shift_semitones=semis[i:i + 1], tuned_notes=dbg[5][i], harmony_notes=dbg[6][i])))
         else:
             out.append((of, hw, sf))
     return out
 
 
 def match_features_blend(query_seqs, query_f0s, voices, weights, ckpt_type, post_opt, nn32s=None, nan_flags=None, topk=None,
-                         f0_shift=None, transpose=None, tune=None):
+                         f0_shift=None, transpose=None, tune=None, harmony=None):
     """``match_features_many`` towards a weighted mix of 2..BLEND_MAX_VOICES ``voices`` (serving.TargetVoice, or anything with
     ``feats`` / ``f0`` / ``harm`` and optionally ``prep`` / ``synth``: ``match_bodies``) -> the same list of
     per-item tuples (out_feats, harm or None, shifted_f0).  ``weights``: ``resolve_blend``'s argument (one vector for all items or
@@ -762,11 +826,15 @@ def match_features_blend(query_seqs, query_f0s, voices, weights, ckpt_type, post
     voices' log medians (the per-voice shifted tracks are used inside each voice's match only).  A voice whose weight is 0 for
     every item is not matched.  ``nn32s``: per voice, the per-item neighbour lists of ``match_features_many`` (or None).  NaN
     flags and the overflow retry work per voice, as there.  ``tune``: as there, inside every voice's match (each on that voice's
-    shifted track) and, through one more ops.tune_f0_seg, on the returned f0: the blend's one shift, corrected."""
+    shifted track) and, through one more ops.tune_f0_seg, on the returned f0: the blend's one shift, corrected.  ``harmony``: as
+    there too: inside every voice's match and once more, behind that correction, on the returned f0."""
     rows = resolve_blend(weights, len(voices), len(query_seqs))      # before any device work
     resolve_topk(topk)
     tunings = resolve_tune(tune, len(query_seqs))
     tuned = dict(tune=tunings) if tune_active(tunings) else {}
+    parts = resolve_harmony_shifts(harmony, len(query_seqs))
+    if harmony_active(parts):
+        tuned["harmony"] = parts
     shift_modes, shift_ts = resolve_f0_shift(f0_shift, transpose, len(query_seqs))
     live = [v for v in range(len(voices)) if any(r[v] != 0.0 for r in rows)]
     per = {}
@@ -789,12 +857,14 @@ def match_features_blend(query_seqs, query_f0s, voices, weights, ckpt_type, post
     meds = {v: ops.log_f0_median(voices[v].f0) for v in live}
     pmeds = torch.stack([meds.get(v, meds[live[0]]) for v in range(len(voices))]).contiguous()
     shifted = ops.shift_f0_seg_blend(query_f0, seg, qmed, pmeds, rows, shift_modes, shift_ts)
-    if tuned:
+    if "tune" in tuned:
         shifted = ops.tune_f0_seg(shifted, seg, tunings)
+    if "harmony" in tuned:
+        shifted = ops.harmony_f0_seg(shifted, seg, parts)
     return list(zip(_split(out_feats, lens), _split(harm, lens), _split(shifted, lens)))
 
 
-def match_bodies(query_of, voices, ckpt_type, post_opt, found, flags, knobs, topk=None):
+def match_bodies(query_of, voices, ckpt_type, post_opt, found, flags, knobs, topk=None, parts=None):
     """-> the ``(body, body_many)`` pair of ``run_match_bodies``: the match of one item, and of a batch of items stacked.
     ``query_of(item)`` -> (features, f0) of the item's query.  ``voices``: a list of one voice (serving.TargetVoice, or anything
     with ``feats`` / ``f0`` / ``harm`` and optionally ``prep`` / ``synth``), or of 2..BLEND_MAX_VOICES for a blend
@@ -802,7 +872,8 @@ def match_bodies(query_of, voices, ckpt_type, post_opt, found, flags, knobs, top
     searches already enqueued (``grouped_knn``); an item not in ``nn`` is searched inside its match.  ``flags``: receives the
     deferred NaN flags.  ``knobs(item)`` -> the item's options.SourceKnobs: its ``f0_shift`` / ``transpose`` and, for a blend, its
     weight row, and its ``tune`` (handed on only when an item of the batch has one that is on: without it the match functions are
-    called as they always were)."""
+    called as they always were).  ``parts(item)`` -> the options.HarmonyShift of an item that is a harmony part, or None (a record
+    of its own beside the knobs); ``parts`` None: no item is one.  Handed on by the same rule as ``tune``."""
     dev = voices[0].feats.device
 
     def match(batch, alone):
@@ -815,16 +886,20 @@ def match_bodies(query_of, voices, ckpt_type, post_opt, found, flags, knobs, top
         modes, semis = [k.f0_shift for k in ks], [k.transpose for k in ks]
         tunes = [k.tune for k in ks]
         tuned = tune_active(tunes)
+        moves = [None] * len(batch) if parts is None else [parts(i) for i in batch]
+        part = harmony_active(moves)
         if len(voices) > 1:
             return match_features_blend(qs, f0s, voices, [k.blend for k in ks], ckpt_type, post_opt, nn32s=nn32s, nan_flags=flags,
-                                        topk=topk, f0_shift=modes, transpose=semis, **(dict(tune=tunes) if tuned else {}))
+                                        topk=topk, f0_shift=modes, transpose=semis, **(dict(tune=tunes) if tuned else {}),
+                                        **(dict(harmony=moves) if part else {}))
         vo = voices[0]
         pool = dict(nan_flags=flags, pool_prep=getattr(vo, "prep", None), synth_list=getattr(vo, "synth", None), topk=topk)
         if alone:              # (through the module global: the CPU tests put their stand-in there)
             return [match_features(qs[0], f0s[0], vo.feats, vo.f0, vo.harm, ckpt_type, post_opt, nn32=nn32s[0][0], f0_shift=modes[0],
-                                   transpose=semis[0], **(dict(tune=tunes[0]) if tuned else {}), **pool)]
+                                   transpose=semis[0], **(dict(tune=tunes[0]) if tuned else {}),
+                                   **(dict(harmony=moves[0]) if part else {}), **pool)]
         return match_features_many(qs, f0s, vo.feats, vo.f0, vo.harm, ckpt_type, post_opt, nn32s=nn32s[0], f0_shift=modes,
-                                   transpose=semis, **(dict(tune=tunes) if tuned else {}), **pool)
+                                   transpose=semis, **(dict(tune=tunes) if tuned else {}), **(dict(harmony=moves) if part else {}), **pool)
     return (lambda item: match([item], True)[0]), (lambda batch: match(batch, False))
 
 

@@ -1196,6 +1196,74 @@ def tune_f0_seg(f0, seg, tunings, return_notes=False):
     return (out, notes) if return_notes else out
 
 
+HARMONY_MAX_PARTS = 3        # KNNSVC_HARMONY_MAX_PARTS
+
+
+def harmony_f0_seg(f0, seg, parts, return_notes=False):
+    """The f0 contour of a harmony part from the lead's stacked final f0 (knnsvc_harmony_f0_seg; include/knnsvc_hip.h "Harmony
+    voice" is the specification).  ``parts``: per segment None (off: the segment keeps its bits) or anything with ``mask`` /
+    ``steps`` / ``alpha`` / ``log_ref`` (options.HarmonyShift) -> the part's f0, a new tensor; with ``return_notes`` -> (f0, int32
+    notes of the part, -1 where nothing was moved).  One launch per 64 segments; a run of 64 whose segments are all off is not
+    launched (its rows are copied), and when every segment is off the INPUT TENSOR ITSELF comes back (notes: None) and nothing is
+    launched, loaded or checked beyond the count.  Enqueue only."""
+    n_seg = seg.n if isinstance(seg, Segments) else len(seg) - 1
+    parts = list(parts)
+    if len(parts) != n_seg:
+        raise KnnSvcError(f"harmony_f0_seg: {len(parts)} parts for {n_seg} segments")
+    live = [p is not None and p.mask != 0 and p.steps != 0 for p in parts]
+    if not any(live):
+        return (f0, None) if return_notes else f0
+    _need(f0, name="f0"); seg = _segments(seg, "harmony_f0_seg", f0)
+    if f0.dim() != 1:
+        raise KnnSvcError(f"harmony_f0_seg: f0 must be [rows], got {tuple(f0.shape)}")
+    f0 = f0.contiguous()
+    out = torch.empty_like(f0)
+    notes = torch.empty(f0.numel(), device=f0.device, dtype=torch.int32) if return_notes else None
+    lib = _lib.load()
+    off = (0, 0, 1.0, math.log(440.0))
+    for a, r0, tab in seg.chunks:
+        n = len(tab) - 1
+        r1 = r0 + tab[n]
+        if not any(live[a:a + n]):
+            out[r0:r1].copy_(f0[r0:r1])
+            if return_notes:
+                notes[r0:r1].fill_(-1)
+            continue
+        rows = [(int(p.mask), int(p.steps), float(p.alpha), float(p.log_ref)) if on else off for p, on in zip(parts[a:a + n], live[a:a + n])]
+        ws_bytes = lib.knnsvc_tune_f0_workspace_bytes(tab[n], n)
+        ws = torch.empty(ws_bytes, device=f0.device, dtype=torch.uint8)
+        check(lib.knnsvc_harmony_f0_seg(_p(f0[r0:]), tab, n, (C.c_int32 * n)(*[r[0] for r in rows]), (C.c_int32 * n)(*[r[1] for r in rows]),
+                                        (C.c_double * n)(*[r[2] for r in rows]), (C.c_double * n)(*[r[3] for r in rows]), _p(out[r0:]),
+                                        _p(notes[r0:]) if return_notes else None, _p(ws), ws_bytes, _stream()), "harmony_f0_seg")
+    return (out, notes) if return_notes else out
+
+
+def mix_waves(ys, gains, out=None):
+    """out[i] = (float)(sum_v gains[v] * (double)ys[v][i]) over 1..4 voices in order (knnsvc_mix_waves; include/knnsvc_hip.h: fp64
+    products and sums of their own, one rounding, a voice with gain 0 not read).  ``ys``: contiguous 1-D fp32 tensors of one
+    length; ``gains``: linear, finite and >= 0, at least one > 0; ``out``: a buffer to write into, which may be one of ``ys``.
+    One launch; enqueue only."""
+    ys = list(ys)
+    if not 1 <= len(ys) <= HARMONY_MAX_PARTS + 1:
+        raise KnnSvcError(f"mix_waves: {len(ys)} voices, expected 1..{HARMONY_MAX_PARTS + 1}")
+    for v, y in enumerate(ys):
+        _need(y, name=f"ys[{v}]")
+        if y.dim() != 1 or not y.is_contiguous() or y.shape != ys[0].shape:
+            raise KnnSvcError(f"mix_waves: ys[{v}] must be a contiguous [n] tensor of the voices' common length, got {tuple(y.shape)}")
+    gains = [float(g) for g in gains]
+    if len(gains) != len(ys):
+        raise KnnSvcError(f"mix_waves: {len(gains)} gains for {len(ys)} voices")
+    if out is None:
+        out = torch.empty_like(ys[0])
+    _need(out, name="out")
+    if out.shape != ys[0].shape or not out.is_contiguous():
+        raise KnnSvcError(f"mix_waves: out must be a contiguous {tuple(ys[0].shape)} tensor, got {tuple(out.shape)}")
+    nv = len(ys)
+    check(_lib.load().knnsvc_mix_waves((C.c_void_p * nv)(*[y.data_ptr() for y in ys]), nv, (C.c_double * nv)(*gains), ys[0].numel(),
+                                       _p(out), _stream()), "mix_waves")
+    return out
+
+
 def weighted_gather(idx4, w, pool, mean=False):
     """sum_k w[i, k] * pool[idx4[i, k]].  ``w`` None = uniform weights: each row times 1.0f / k (softmax(ones)), or with ``mean`` the
     sum in order divided by k (torch.mean); the same bits when k is a power of two."""

@@ -26,6 +26,17 @@ takes the "None = off" arguments of ``many_to_one``, ``TargetVoice`` and ``Batch
 
 What belongs to a *source item* (a request's own pitch values, its ``target_duration``, its blend weights) is NOT in this
 record — the promise above about lengths holds because of that — but in ``SourceKnobs`` below, one per source.
+
+Harmony parts (``Harmony`` / ``HarmonyPart`` below; include/knnsvc_hip.h "Harmony voice") belong to a source item too, but they are
+not a field of ``SourceKnobs``: a source with P parts becomes 1 + P items of the match stage that share its knobs, and what tells
+a part from its lead, the ``HarmonyShift`` (mask, steps, alpha, log_ref), travels in a record of its own beside the item's knobs
+(matching.match_bodies ``parts=``; the match functions' ``harmony=``).
+
+  argument       off (default)       on                                                                    where it acts
+  harmony        None                an options.Harmony: 1..3 parts, each the lead's final f0 moved by      match stage, behind the
+                                     scale degrees with the lead's deviation kept, matched as an item of    correction (ops.harmony_f0_seg);
+                                     its own from the lead's encoder output and neighbour list, and mixed   tail, between its per-voice and
+                                     under the lead on the GPU                                              per-output halves (ops.mix_waves)
 """
 from __future__ import annotations
 
@@ -176,6 +187,118 @@ class SourceKnobs:
     target_duration: float | None = None
     blend: tuple | None = None
     tune: Tuning | None = None
+
+
+HARMONY_MAX_PARTS = 3        # KNNSVC_HARMONY_MAX_PARTS
+HARMONY_MAX_STEPS = 24       # KNNSVC_HARMONY_MAX_STEPS
+
+
+def _harmony_number(value, name, lo, hi):
+    if isinstance(value, bool) or not isinstance(value, numbers.Real) or not lo <= float(value) <= hi:      # (NaN compares false)
+        raise ValueError(f"harmony: {name} must be a number in [{lo:g}, {hi:g}], got {value!r}")
+    return float(value)
+
+
+@dataclass(frozen=True)
+class HarmonyPart:
+    """One harmony part: ``steps`` scale degrees above (> 0) or below (< 0) the lead, a non-zero int in -24..24 (2: a third
+    above, -5: a sixth below, +-7 in a seven-note scale: an octave), and its level in the mix, ``gain_db`` in [-60, 12].
+    Checked on construction."""
+    steps: int
+    gain_db: float = -6.0
+
+    def __post_init__(self):
+        s = self.steps
+        if isinstance(s, bool) or not isinstance(s, numbers.Integral) or int(s) == 0 or abs(int(s)) > HARMONY_MAX_STEPS:
+            raise ValueError(f"harmony: steps must be a non-zero int in -{HARMONY_MAX_STEPS}..{HARMONY_MAX_STEPS} (scale degrees), got {s!r}")
+        object.__setattr__(self, "steps", int(s))
+        object.__setattr__(self, "gain_db", _harmony_number(self.gain_db, "gain_db", -60.0, 12.0))
+
+    @property
+    def gain(self) -> float:
+        return 10.0 ** (self.gain_db / 20.0)
+
+
+@dataclass(frozen=True)
+class HarmonyShift:
+    """What the library takes for one part (include/knnsvc_hip.h "Harmony voice"): ``(mask, steps, alpha, log_ref)``.  It travels
+    in a record of its own beside the item's ``SourceKnobs``; built only by ``Harmony.shifts``, so holding one means the values
+    are valid."""
+    mask: int
+    steps: int
+    alpha: float
+    log_ref: float
+
+    @property
+    def on(self) -> bool:
+        return self.mask != 0 and self.steps != 0
+
+
+@dataclass(frozen=True)
+class Harmony:
+    """Harmony parts of one source item (include/knnsvc_hip.h "Harmony voice" is the specification): 1 to 3 ``parts``
+    (``HarmonyPart``, or bare ints for their steps), each the lead's contour moved by scale degrees in ``scale``, sung by the
+    same target voice and mixed under the lead on the GPU.  Checked on construction.
+
+      field       default             meaning
+      parts       (required)          1..3 HarmonyPart or ints: degrees above / below the lead, each with its gain_db (-6)
+      scale       None: the item's    the key the parts move in ("chromatic": parallel parts of ``steps`` semitones; "A:minor";
+                  ``tune`` scale      "D:101011010101"); without a scale here and without a ``tune`` on the item: ValueError
+      lead_db     0.0                 the lead's level in the mix, [-60, 12] dB
+      glide_ms    40.0                [0, 2000]: where the lead changes note a part's interval changes too; the time constant of
+                                      that change (0: a jump), a = -expm1(-20 / glide_ms)
+      tuning_hz   None: the item's    the frequency of A4, [400, 480]; None without a ``tune``: 440
+                  ``tune`` tuning
+    A different target voice per part and stems from the command line are out of scope."""
+    parts: tuple
+    scale: str | None = None
+    lead_db: float = 0.0
+    glide_ms: float = 40.0
+    tuning_hz: float | None = None
+
+    def __post_init__(self):
+        parts = self.parts
+        if isinstance(parts, (HarmonyPart, numbers.Integral)) and not isinstance(parts, bool):
+            parts = (parts,)
+        if isinstance(parts, (str, bytes)) or not isinstance(parts, (list, tuple)):
+            raise ValueError(f"harmony: parts must be a sequence of 1..{HARMONY_MAX_PARTS} HarmonyPart or ints, got {self.parts!r}")
+        if not 1 <= len(parts) <= HARMONY_MAX_PARTS:
+            raise ValueError(f"harmony: {len(parts)} parts, expected 1..{HARMONY_MAX_PARTS}")
+        object.__setattr__(self, "parts", tuple(p if isinstance(p, HarmonyPart) else HarmonyPart(p) for p in parts))
+        if self.scale is not None:
+            scale_mask_for_harmony(self.scale)
+        object.__setattr__(self, "lead_db", _harmony_number(self.lead_db, "lead_db", -60.0, 12.0))
+        object.__setattr__(self, "glide_ms", _harmony_number(self.glide_ms, "glide_ms", 0.0, 2000.0))
+        if self.tuning_hz is not None:
+            object.__setattr__(self, "tuning_hz", _harmony_number(self.tuning_hz, "tuning_hz", 400.0, 480.0))
+
+    @property
+    def alpha(self) -> float:
+        return 1.0 if self.glide_ms == 0 else -math.expm1(-TUNE_FRAME_MS / self.glide_ms)
+
+    @property
+    def gains(self) -> tuple:
+        """The linear gains of the mix, lead first."""
+        return (10.0 ** (self.lead_db / 20.0),) + tuple(p.gain for p in self.parts)
+
+    def shifts(self, tune=None) -> tuple:
+        """-> one ``HarmonyShift`` per part, with the scale and tuning frequency taken from ``tune`` (the item's Tuning; one that
+        is off counts as none) where this record leaves them open.  ValueError without a scale."""
+        tune = tune if tune is not None and tune.on else None
+        scale = self.scale if self.scale is not None else (tune.scale if tune is not None else None)
+        if scale is None:
+            raise ValueError("harmony: no scale: give Harmony(scale=...) or a tune= with the key of the song")
+        hz = self.tuning_hz if self.tuning_hz is not None else (tune.tuning_hz if tune is not None else 440.0)
+        mask, a, lr = scale_mask_for_harmony(scale), self.alpha, math.log(hz)
+        return tuple(HarmonyShift(mask, p.steps, a, lr) for p in self.parts)
+
+
+def scale_mask_for_harmony(scale) -> int:
+    """``scale_mask`` with the message of a harmony."""
+    try:
+        return scale_mask(scale)
+    except ValueError as e:
+        raise ValueError(str(e).replace("tune:", "harmony:", 1)) from None
 
 
 def per_item(value, n, name, one=lambda v: v, default=None, is_list=None, unit="values"):

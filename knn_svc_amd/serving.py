@@ -36,7 +36,7 @@ import torch
 
 from . import audio_io, config as C, ops
 from . import matching as M
-from .matcher import Tail
+from .matcher import Tail, VoiceTail
 from .options import Extensions, SourceKnobs, per_item
 
 
@@ -95,7 +95,7 @@ class BatchConverter:
                  max_encode_batch: int = 32, match: str | None = None, match_batch: int | None = None,
                  loudness_db: float | None = None, topk: int | None = None, f0_shift: str | None = None,
                  transpose: float | None = None, envelope_mix: float | None = None, peak_db: float | None = None,
-                 ext: Extensions | None = None, blend=None, tune=None):
+                 ext: Extensions | None = None, blend=None, tune=None, harmony=None):
         # ``target``: one TargetVoice, or a sequence of 2 to 4 of them: the sources are then converted towards a weighted mix of
         # those voices (matching.match_features_blend; include/knnsvc_hip.h "Voice blend"), ``blend`` being the weights a source
         # gets unless a request says otherwise (blend_of; None: equal weights).  Refused before anything else: a sequence of
@@ -111,6 +111,10 @@ class BatchConverter:
         # ``tune``: the pitch correction a source gets unless a request says otherwise (tune_of; an options.Tuning, a scale such as
         # "A:minor", or None / "off": none; include/knnsvc_hip.h "Pitch correction")
         self.tune = M.resolve_tune(tune)
+        # ``harmony``: the harmony parts a source gets unless a request says otherwise (harmony_of; an options.Harmony, or None /
+        # "off": none; include/knnsvc_hip.h "Harmony voice").  Whether it names a scale, or the source's ``tune`` does, is checked
+        # per source at the door of ``convert``.
+        self.harmony = M.resolve_harmony(harmony)
         # the extension knobs, checked before anything else (options.py; None: off): ``loudness_db``, ``envelope_mix`` and
         # ``peak_db`` are part of the tail, on the tail's stream, enqueue-only, and apply to every request of a RequestQueue in
         # front of this converter; ``f0_shift`` / ``transpose`` are what a source gets unless a request says otherwise (pitch_of).
@@ -206,12 +210,23 @@ class BatchConverter:
             return self.tune if tune is None else M.resolve_tune(tune)
         return [self.tune if t is None else t for t in M.resolve_tune(tune, n)]
 
+    def harmony_of(self, harmony=None, tunes=None, n=None):
+        """Per-source harmony (a value for all sources, or one per source; None entries: this converter's default, "off": none
+        for that source) checked (matching.resolve_harmony) against the source's resolved ``tunes`` entry, which names the scale
+        and tuning frequency where the harmony leaves them open -> a list of ``n`` entries, each None or (the options.Harmony,
+        its options.HarmonyShift per part); ``n`` None: one entry for the single ``tunes`` value."""
+        if n is None:
+            return M.harmony_of(self.harmony if harmony is None else M.resolve_harmony(harmony), tunes)
+        own = [self.harmony if h is None else h for h in M.resolve_harmony(harmony, n)]
+        return [M.harmony_of(h, t) for h, t in zip(own, tunes)]
+
     def plan_duration(self, w, target_duration, item=None):
         """matching.duration_plan of a loaded source waveform (its frame count follows from its length: nothing is encoded)."""
         return M.duration_plan(M.frames_of(int(w.shape[0]), self.vc.wavlm), target_duration, item=item)
 
     @torch.inference_mode()
-    def convert(self, sources, loaded=None, f0_shift=None, transpose=None, target_duration=None, blend=None, tune=None) -> list:
+    def convert(self, sources, loaded=None, f0_shift=None, transpose=None, target_duration=None, blend=None, tune=None,
+                harmony=None, stems=False) -> list:
         """-> one waveform tensor [T_i * 320] per source, in order.  ``loaded``: the sources already through load_checked.
         ``f0_shift`` / ``transpose``: for all sources or one per source (None: the converter's defaults); one batch may mix
         them on both match routes, each source's interval is chosen on the device.  ``target_duration`` (seconds): for all
@@ -222,12 +237,21 @@ class BatchConverter:
         weight vectors on both match routes ("lanes": one blend per source, "segmented": one blend launch per batch).
         ``tune``: the pitch correction, for all sources or one entry per source (an options.Tuning or a scale; None: the
         converter's default, "off": none): that source's shifted f0 is snapped towards the key inside its match, on both routes;
-        one batch may mix keys, and sources with and without one share a batch."""
+        one batch may mix keys, and sources with and without one share a batch.
+        ``harmony``: harmony parts, for all sources or one entry per source (an options.Harmony; None: the converter's default,
+        "off": none).  A source with P parts becomes 1 + P items of the match stage that share its encoder output, its re-timed
+        query and, per target voice, its ONE neighbour search; every part runs its own match body with the source's knobs and
+        its own options.HarmonyShift (on the segmented route the parts are further segments), then the per-voice half of the
+        tail (generator, envelope mix).  The voices are mixed (ops.mix_waves, gains 10^(dB / 20), lead first) and the per-output
+        half (loudness, ceiling) and the finiteness check run on the mix.  The lead is bit-identical to the source's conversion
+        without a harmony.  ``stems``: -> per source the list [mix, lead, part_1, ...] of waveforms instead of the mix alone
+        (the stems are the outputs of the per-voice half; a source without a harmony: [output, lead])."""
         modes, semis = self.pitch_of(f0_shift, transpose, len(sources))        # refused before a file is read
         durs = self.duration_of(target_duration, len(sources))
         mixes = self.blend_of(blend, len(sources))
         tunes = self.tune_of(tune, len(sources))
         knobs = [SourceKnobs(*k) for k in zip(modes, semis, durs, mixes or [None] * len(sources), tunes)]
+        harms = self.harmony_of(harmony, tunes, len(sources))
         if len(sources) == 0:
             return []
         vc, voices = self.vc, self.voices or [self.target]
@@ -247,35 +271,64 @@ class BatchConverter:
             f0s.append(f0[:T].contiguous().to(dev) if isinstance(f0, torch.Tensor)
                        else torch.from_numpy(np.ascontiguousarray(f0[:T])).to(dev, non_blocking=True))
         feats, f0s = M.stretch_queries(feats, f0s, durs)               # in front of everything of the match stage
-        items = list(range(len(sources)))
-        qpool = dict(enumerate(feats))
+        # items of the match stage: source i is item i (its lead); the parts of the harmonised sources follow behind the leads
+        n_src = len(sources)
+        src_of, part_of, members = list(range(n_src)), [None] * n_src, [[i] for i in range(n_src)]
+        for i, h in enumerate(harms):
+            for shift in (h[1] if h is not None else ()):
+                members[i].append(len(src_of)); src_of.append(i); part_of.append(shift)
+        items = list(range(len(src_of)))
+        leads = items[:n_src]
+        qpool = {it: feats[src_of[it]] for it in items}
         # the reference does not forward post_opt to the f0-only generators (ddsp_matcher.py:970, 1102-1110)
         post_opt = "no_post_opt" if self.f0only else self.post_opt
-        tail = M.vocoding_tail(Tail(vc, self.f0only, self.ext), items, wavs.__getitem__)
+        whole = Tail(vc, self.f0only, self.ext)
+        source_of = lambda it: wavs[src_of[it]]
+        tail = M.vocoding_tail(whole, items, source_of)
+        # the items whose output is mixed (or handed out as a stem) stop behind the per-voice half of the tail
+        halved = {it for it in items if stems or len(members[src_of[it]]) > 1}
+        if halved:
+            tail_whole, tail_voice = tail, M.vocoding_tail(VoiceTail(whole), items, source_of)
+            tail = lambda item, r: (tail_voice if item in halved else tail_whole)(item, r)
 
         def run():
             # every voice that some source of the batch gives weight to (a single target: that one) is searched over the frames
             # of several sources at a time (grouped_knn) and matched on its own; a blend sits between the match bodies and the tail
             flags = []
             used = [len(items) > 1 and (mixes is None or any(m[v] != 0.0 for m in mixes)) for v in range(len(voices))]
-            found = [M.grouped_knn(items, qpool, vo.feats, vo.prep, flags) if u else ({}, {}) for vo, u in zip(voices, used)]
-            body, body_many = M.match_bodies(lambda i: (qpool[i], f0s[i]), voices, self.ckpt_type, post_opt, found, flags,
-                                             knobs.__getitem__, topk=self.ext.topk)
+            found = [M.grouped_knn(leads, qpool, vo.feats, vo.prep, flags) if u else ({}, {}) for vo, u in zip(voices, used)]
+            for nn, ready in found:                          # a part reuses its lead's list: it is not searched again
+                for it in items[n_src:]:
+                    if src_of[it] in nn:
+                        nn[it] = nn[src_of[it]]
+                        if src_of[it] in ready:
+                            ready[it] = ready[src_of[it]]
+            body, body_many = M.match_bodies(lambda i: (qpool[i], f0s[src_of[i]]), voices, self.ckpt_type, post_opt, found, flags,
+                                             lambda i: knobs[src_of[i]], topk=self.ext.topk,
+                                             **(dict(parts=part_of.__getitem__) if len(items) > n_src else {}))
             ys = M.run_match_bodies(items, body, body_many, tail, device=dev, lanes=max(1, min(self.lanes, len(items))),
                                     match=self.match, match_batch=self.match_batch)
-            peak = torch.stack([y.abs().max() for y in ys])
+            outs = ys[:n_src]
+            for i in range(n_src if halved else 0):
+                if len(members[i]) > 1:
+                    mix = ops.mix_waves([ys[it] for it in members[i]], harms[i][0].gains)
+                    outs[i] = whole.per_output(mix)
+                elif i in halved:                            # (stems of a source without parts: the lead stays as it is)
+                    outs[i] = whole.per_output(ys[i].clone())
+            peak = torch.stack([y.abs().max() for y in outs])
             for f in flags:
                 ops.raise_if_nan(f)                          # one host read per search, after everything is enqueued
             vc._check_finite(peak)
-            return ys
+            return [[outs[i]] + [ys[it] for it in members[i]] for i in range(n_src)] if stems else outs
         return ops.retry_on_overflow(run)
 
-    def convert_files(self, src_files, converted_audio_dir=None, target_duration=None, blend=None, tune=None) -> list:
+    def convert_files(self, src_files, converted_audio_dir=None, target_duration=None, blend=None, tune=None, harmony=None) -> list:
         """Paths in, files out: ``<dir or the source's folder>/<src>_to_<ref>_knn_<ckpt_type>_<post_opt>.wav`` (the single-file
-        naming, ddsp_matcher.py:1015), PCM_32 16 kHz mono.  -> the written paths.  ``target_duration`` / ``blend`` / ``tune``: as ``convert``.
+        naming, ddsp_matcher.py:1015), PCM_32 16 kHz mono.  -> the written paths.  ``target_duration`` / ``blend`` / ``tune`` / ``harmony``: as ``convert``
+        (the mix is written; the file name does not change).
         With several target voices ``<ref>`` is their ids joined by ``+`` (``<idA>+<idB>[+...]``); the weights are not in the name."""
         ys = self.convert([str(p) for p in src_files], target_duration=target_duration, **({} if blend is None else dict(blend=blend)),
-                          **({} if tune is None else dict(tune=tune)))
+                          **({} if tune is None else dict(tune=tune)), **({} if harmony is None else dict(harmony=harmony)))
         out = []
         for p, y in zip(src_files, ys):
             path = self.output_path(p, converted_audio_dir)
@@ -296,7 +349,8 @@ class RequestQueue:
     ``submit(src, target_duration=)``: the length in seconds the request's conversion is re-timed to (BatchConverter.convert);
     ``submit(src, blend=)`` (a converter with several target voices): the request's own blend weights; a bad vector is refused
     at the door and fails alone; ``submit(src, tune=)``: the request's own pitch correction (an options.Tuning, a scale, or "off"
-    under a converter whose default is on), refused at the door likewise.  Requests with different values share a batch.
+    under a converter whose default is on), refused at the door likewise; ``submit(src, harmony=)``: the request's own harmony
+    parts (an options.Harmony, or "off"), refused at the door likewise.  Requests with different values share a batch.
     The converter's ``loudness_db``, ``envelope_mix`` and ``peak_db`` apply to every request (per-request values of those are
     not supported)."""
 
@@ -309,7 +363,7 @@ class RequestQueue:
         self._th = threading.Thread(target=self._loop, name="knnsvc-batcher", daemon=True)
         self._th.start()
 
-    def submit(self, src, transpose=None, f0_shift=None, target_duration=None, blend=None, tune=None) -> Future:
+    def submit(self, src, transpose=None, f0_shift=None, target_duration=None, blend=None, tune=None, harmony=None) -> Future:
         if self._stop:
             raise RuntimeError("RequestQueue is closed")
         fut = Future()
@@ -322,7 +376,13 @@ class RequestQueue:
             own["blend"] = self.conv.blend_of(blend)
         if tune is not None:
             own["tune"] = self.conv.tune_of(tune)
-        self._q.put((src, fut, SourceKnobs(**own)))
+        if harmony is None:
+            self._q.put((src, fut, SourceKnobs(**own)))
+            return fut
+        # a harmony travels beside the knobs, in an entry of its own; checked against the tune the request will be converted with
+        harmony = M.resolve_harmony(harmony)
+        self.conv.harmony_of(harmony, own.get("tune", self.conv.tune))
+        self._q.put((src, fut, SourceKnobs(**own), harmony))
         return fut
 
     def _loop(self):
@@ -351,27 +411,30 @@ class RequestQueue:
     def _run(self, batch):
         """One batch; a request that cannot be loaded, or whose data makes the conversion fail (a NaN source, an f0 track of the
         wrong length, a target duration out of proportion to its length), fails ALONE: the others of its batch are converted
-        without it.  An entry is (source, Future, SourceKnobs: the request's own values, None where it has none); a knob is
+        without it.  An entry is (source, Future, SourceKnobs: the request's own values, None where it has none[, the request's own
+        harmony]); a knob is
         passed on to ``convert`` only when a request of the batch carries it (``f0_shift`` and ``transpose`` together), so a batch
         in which no request carries values of its own is converted as it always was."""
         good, loaded = [], []
-        for s, fut, own in batch:
+        for s, fut, own, *harm in batch:
             try:
                 ld = self.conv.load_checked(s)
                 if own.target_duration is not None:          # needs the loaded source: refused here, before the batch is formed
                     self.conv.plan_duration(ld[0], own.target_duration, item="request")
                 loaded.append(ld)
-                good.append((s, fut, own))
+                good.append((s, fut, own, harm[0] if harm else None))
             except BaseException as e:
                 fut.set_exception(e)
         if not good:
             return
         carried = [names for names in (("f0_shift", "transpose"), ("target_duration",), ("blend",), ("tune",))
-                   if any(getattr(own, k) is not None for _s, _f, own in good for k in names)]
-        kwargs = lambda gs: {k: [getattr(own, k) for _s, _f, own in gs] for names in carried for k in names}
+                   if any(getattr(own, k) is not None for _s, _f, own, _h in good for k in names)]
+        harmonised = any(h is not None for _s, _f, _own, h in good)
+        kwargs = lambda gs: dict({k: [getattr(own, k) for _s, _f, own, _h in gs] for names in carried for k in names},
+                                 **(dict(harmony=[h for _s, _f, _own, h in gs]) if harmonised else {}))
         try:
             ys = self.conv.convert([g[0] for g in good], loaded=loaded, **kwargs(good))
-            for (_s, fut, _own), y in zip(good, ys):
+            for (_s, fut, _own, _h), y in zip(good, ys):
                 fut.set_result(y.detach().cpu())
             return
         except BaseException as e:
